@@ -15,6 +15,13 @@ Launching: with WORLD_SIZE set (torch.distributed.run) this process is one rank 
 --gpus.  With WORLD_SIZE unset and --gpus N > 1 this process starts the N ranks itself as child processes
 (python -m torch.distributed.run ... bench.py ...) BEFORE anything touches the GPU, waits, and relays their
 output and exit code -- it never re-executes a process that has initialised the GPU.
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line (metric, value, unit, ms_per_step,
+config); the validity bitmap of the last timed step is checked against the closed-form expectation.  --full adds the
+side measurements: the pre-timing correctness step, per-kernel times, the roofline of the dominant kernel (with its
+VALU probe run), the exact and RLC paths on the same batch and the CPU baseline.  --dump-outputs DIR writes the
+bitmap the last timed step returned as DIR/valid.npy (float32, one value per tuple, 1 = the signature verifies);
+inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -30,6 +37,8 @@ N_PER_GPU_MULTI = 1048576  # BASELINE configs[3]: 8 M tuples over 8 GPUs
 UNIQ = 64                 # cpu_baseline sample only: distinct tuples signed by the CPU oracle, tiled
 INVALID_EVERY = 64        # 1/64 of the tuples are corrupted
 FP_MUL_MADS = 136         # 32x32->64 MADs of one 8x32-bit-limb Montgomery multiplication (2n^2 + n)
+DUMP_BYTES = 64000000     # --dump-outputs: at most this many bytes in all
+DUMP_SAMPLE = 4000000     # tuples kept (seeded sample) when the whole bitmap as float32 would exceed DUMP_BYTES
 
 
 def main():
@@ -39,9 +48,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--tuples-per-gpu", dest="n", type=int, default=0,
                     help="tuples per GPU (default: 262144 at --gpus 1 = configs[1], 1048576 at --gpus N > 1 = configs[3])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: per-kernel times, roofline, exact_path / rlc_path legs, cpu_baseline")
+    ap.add_argument("--dump-outputs", dest="dump", metavar="DIR", default=None,
+                    help="write the validity bitmap of the last timed step as DIR/valid.npy (float32 per tuple)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-side-paths", action="store_true",
-                    help="skip the untimed exact_path / rlc_path legs (profiling runs: keeps rocprofv3's per-kernel averages to the timed path)")
+                    help="with --full: skip the untimed exact_path / rlc_path legs (profiling runs: keeps rocprofv3's per-kernel averages to the timed path)")
     ap.add_argument("--key-pool", dest="pool", type=int, default=1024,
                     help="distinct public keys in the batch (SURVEY.md 8d: 1024); 0 = every tuple has its own key (the all-distinct case)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
@@ -144,15 +157,15 @@ def run_rank(args):
 
     for _ in range(args.warmup):
         step()
-    # correctness of what is being timed: bitmap equals the closed-form expectation
-    step()
-    torch.cuda.synchronize()
-    ok = bytes(t_bm.cpu().numpy()) == synth.bitmap_of(exp)
-    if not ok:
-        raise SystemExit("bench: GPU bitmap differs from the expected pattern")
-
-    eng.profile_enable(True)
-    eng.profile_reset()
+    if args.full:
+        # correctness of what is being timed: bitmap equals the closed-form expectation
+        step()
+        torch.cuda.synchronize()
+        ok = bytes(t_bm.cpu().numpy()) == synth.bitmap_of(exp)
+        if not ok:
+            raise SystemExit("bench: GPU bitmap differs from the expected pattern")
+        eng.profile_enable(True)
+        eng.profile_reset()
     barrier()
     t0 = time.perf_counter()
     words = None
@@ -162,8 +175,9 @@ def run_rank(args):
     dt_own = time.perf_counter() - t0         # this rank's own K steps, before it waits for the others
     barrier()
     dt = time.perf_counter() - t0
-    prof = eng.profile_read()
-    eng.profile_enable(False)
+    if args.full:
+        prof = eng.profile_read()
+        eng.profile_enable(False)
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -180,13 +194,38 @@ def run_rank(args):
                        "note": "per rank: its own K steps before the closing barrier (verify + bitmap exchange), and the exchange alone "
                                "(all_reduce of %d int32 words + synchronize); datagen is outside the timed region" % ((n_total + 31) // 32)}
         # every rank holds the same full bitmap: check it against the closed-form expectation over all global indices
-        full = sharded.words_to_bitmap_bytes(words.cpu().numpy(), n_total)
-        if full != synth.bitmap_of(synth.expected_bits(n_total, INVALID_EVERY)):
+        got = sharded.words_to_bitmap_bytes(words.cpu().numpy(), n_total)
+        if got != synth.bitmap_of(synth.expected_bits(n_total, INVALID_EVERY)):
             raise SystemExit("bench: all-reduced bitmap differs from the expected pattern")
+    else:
+        # what the last timed step returned (the side paths of --full below overwrite t_bm)
+        got = bytes(t_bm.cpu().numpy())
+        if got != synth.bitmap_of(exp):
+            raise SystemExit("bench: GPU bitmap of the last timed step differs from the expected pattern")
+    if rank == 0 and args.dump:
+        dump_outputs(args.dump, got, n_total)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = n_total * args.steps / dt
+        if world == 1:
+            wl = "BASELINE configs[1]"
+        else:
+            wl = "BASELINE configs[3] shape: %d tuples sharded over %d ranks, bitmap all-reduce (%s)" % (
+                n_total, world, "RCCL over xGMI" if args.backend == "nccl" else args.backend)
+        out = {
+            "metric": "BN254 pairings/sec (= BLS verifies/sec)", "value": round(value, 1), "unit": "verifies/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+            "config": {"workload": "%d batched single-sig BLS verifies per GPU (%s), unique 32-byte messages, "
+                                   "%s, 1/64 invalid tuples; key de-duplication + hash-to-G1 + per-key G2 checks and line tables "
+                                   "+ 2-pair Miller loop + final exp" % (n, wl, ("%d-key pool" % pool) if args.pool > 0 else "every tuple its own public key"),
+                       "tuples_per_gpu": n, "tuples_total": n_total, "key_pool": pool, "datagen_s": round(t_gen, 1)},
+        }
+        if world > 1:
+            out["ranks"] = rank_spread
+
+    if rank == 0 and args.full:
         core = O.verify_core_counts()         # exact Fp-mul counts of the algorithmic unit (instrumented oracle)
         # dominant kernel: the 2-pair Miller loop.  Which one ran depends on the batch: few distinct public keys (this
         # workload: a 1024-key pool) -> every key is prepared once and the table-only loop k_miller_prepared runs
@@ -223,21 +262,9 @@ def run_rank(args):
             for pname, pe in json.load(open(epath)).get("phases", {}).items():
                 if "(k_" + dom + ")" in pname:
                     exec_mads, exec_ratio = pe["executed_mads"], pe.get("executed_over_algorithmic")
-        if world == 1:
-            wl = "BASELINE configs[1]"
-        else:
-            wl = "BASELINE configs[3] shape: %d tuples sharded over %d ranks, bitmap all-reduce (%s)" % (
-                n_total, world, "RCCL over xGMI" if args.backend == "nccl" else args.backend)
-        out = {
-            "metric": "BN254 pairings/sec (= BLS verifies/sec)", "value": round(value, 1), "unit": "verifies/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-            "config": {"workload": "%d batched single-sig BLS verifies per GPU (%s), unique 32-byte messages, "
-                                   "%s, 1/64 invalid tuples; key de-duplication + hash-to-G1 + per-key G2 checks and line tables "
-                                   "+ 2-pair Miller loop + final exp" % (n, wl, ("%d-key pool" % pool) if args.pool > 0 else "every tuple its own public key"),
-                       "tuples_per_gpu": n, "tuples_total": n_total, "key_pool": pool, "datagen_s": round(t_gen, 1),
-                       "path": "prepared-keys (distinct public keys validated and turned into line tables once per batch, inside the timed step)"
-                               if prepared else "exact per-tuple"},
+        out["config"]["path"] = ("prepared-keys (distinct public keys validated and turned into line tables once per batch, inside the timed step)"
+                                 if prepared else "exact per-tuple")
+        out.update({
             "roofline": {"bound": "valu", "kernel": "k_" + dom, "achieved": round(achieved, 4), "peak": round(peak, 3),
                          "unit": "T int-MAD/s", "frac": round(achieved / peak, 4),
                          "peak_issue_ceiling": round(ceiling, 3), "frac_issue_ceiling": round(achieved / ceiling, 4),
@@ -260,9 +287,7 @@ def run_rank(args):
             "kernel_ms": kern,
             "algorithmic_fp_mul_per_verify": {"miller_variable_pair": core[0], "miller_fixed_pair_lines": core[1], "final_exp": core[2],
                                               "miller_shared_squarings": core[4], "dominant_kernel": alg_fp_mul},
-        }
-        if world > 1:
-            out["ranks"] = rank_spread
+        })
         if world == 1 and prepared and not args.no_side_paths:
             # the same batch through the exact per-tuple path (what a batch of all-distinct keys takes), reported beside the
             # headline so that the number does not hinge on the workload's key pool; outside the timed region above
@@ -315,10 +340,24 @@ def run_rank(args):
                                        "fall on 16 of the 1024 keys, which keeps the fallback small; profiles/r02_rlc.json has the spread-out cases"}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(O, synth, dst)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, bitmap, n):
+    """DIR/valid.npy: the validity bitmap as one float32 per tuple (1 = verifies).  Above DUMP_BYTES, a seeded sample of
+    DUMP_SAMPLE tuples, with their indices in DIR/valid_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    valid = np.unpackbits(np.frombuffer(bitmap, dtype=np.uint8), bitorder="little")[:n].astype(np.float32)
+    if valid.nbytes > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(d, "valid_index.npy"), idx.astype(np.float64))
+        valid = valid[idx]
+    np.save(os.path.join(d, "valid.npy"), valid)
 
 
 def cpu_baseline(O, synth, dst):

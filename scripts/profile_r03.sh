@@ -19,14 +19,14 @@ export BLSBN254_AUTO_PREPARE=0 &&
 step exact_sq && timeout -k 10 300 rocprofv3 --pmc $SQ --kernel-trace --output-format csv -d $O/exact_sq -o sq -- $B > $O/exact_sq.log 2>&1 &&
 step exact_fetch && timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/exact_fetch -o fetch -- $B > $O/exact_fetch.log 2>&1 &&
 step exact_write && timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/exact_write -o write -- $B > $O/exact_write.log 2>&1 &&
-step exact_bench && timeout -k 10 400 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_exact.json 2> $O/bench_exact.err &&
+step exact_bench && timeout -k 10 400 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_exact.json 2> $O/bench_exact.err &&
 unset BLSBN254_AUTO_PREPARE &&
 step rlc_stats && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rlc_stats -o rlc -- python3 scripts/run_rlc_once.py 5 > $O/rlc_stats.log 2>&1 &&
 step rlc_sq && timeout -k 10 300 rocprofv3 --pmc $SQ --kernel-trace --output-format csv -d $O/rlc_sq -o sq -- python3 scripts/run_rlc_once.py 1 > $O/rlc_sq.log 2>&1 &&
 step rlc_fetch && timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/rlc_fetch -o fetch -- python3 scripts/run_rlc_once.py 1 > $O/rlc_fetch.log 2>&1 &&
 step rlc_write && timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/rlc_write -o write -- python3 scripts/run_rlc_once.py 1 > $O/rlc_write.log 2>&1 &&
-step bench && timeout -k 10 400 python3 bench.py --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err &&
-step distinct && timeout -k 10 400 python3 bench.py --key-pool 0 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_distinct.json 2> $O/bench_distinct.err &&
+step bench && timeout -k 10 400 python3 bench.py --full --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err &&
+step distinct && timeout -k 10 400 python3 bench.py --full --key-pool 0 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_distinct.json 2> $O/bench_distinct.err &&
 step configs && timeout -k 10 300 python3 scripts/bench_configs.py > $O/configs.json 2> $O/configs.err &&
 step rlc && timeout -k 10 300 python3 scripts/bench_rlc.py 262144 0 2,3 > $O/rlc.json 2> $O/rlc.err &&
 step rlc_1m && timeout -k 10 300 python3 scripts/bench_rlc.py 1048576 0 > $O/rlc_1m.json 2> $O/rlc_1m.err &&

@@ -1,11 +1,15 @@
-"""CPU-only: bench.py's launch contract (the parts that run without a GPU) and the shape of the bench line and
-rocprof summary committed under profiles/ (fields and internal consistency only -- no performance numbers are asserted)."""
+"""bench.py's launch contract (the parts that run without a GPU) and the shape of the bench line and rocprof summary
+committed under profiles/ (fields and internal consistency only -- no performance numbers are asserted); on the GPU
+(`-m gpu`), a plain run and a --full run at a reduced batch size."""
 import csv
 import glob
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLEAN = ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE", "GROUP_RANK")
@@ -33,6 +37,51 @@ def test_bench_parent_spawns_n_ranks_and_relays_their_exit_code():
     assert out.returncode != 0
     text = out.stderr + out.stdout
     assert "torch.distributed" in text or "ChildFailedError" in text or "rank" in text.lower()
+
+
+def test_bench_options():
+    """--full (the side measurements) and --dump-outputs DIR are parsed before anything touches the GPU"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config")
+SIDE = ("roofline", "kernel_ms", "algorithmic_fp_mul_per_verify", "exact_path", "rlc_path", "cpu_baseline")
+
+
+def _bench_line(args):
+    env = {k: v for k, v in os.environ.items() if k not in CLEAN}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args,
+                         env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(tmp_path):
+    """a plain run reports the headline only, and --dump-outputs writes the validity of every tuple of the last timed
+    step (float32): the closed-form pattern of the synthetic batch, every 64th tuple invalid"""
+    n = 32768
+    j = _bench_line(["--steps", "3", "--warmup", "1", "--tuples-per-gpu", str(n), "--dump-outputs", str(tmp_path)])
+    assert all(k in j for k in HEADLINE) and not any(k in j for k in SIDE)
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert abs(n * 1e3 / j["ms_per_step"] / j["value"] - 1) < 0.01
+    assert sorted(os.listdir(tmp_path)) == ["valid.npy"]
+    v = np.load(str(tmp_path / "valid.npy"))
+    assert v.dtype == np.float32 and v.shape == (n,)
+    assert np.array_equal(v, np.array([0.0 if i % 64 == 63 else 1.0 for i in range(n)], dtype=np.float32))
+
+
+@pytest.mark.gpu
+def test_bench_full_run_keeps_the_side_measurements():
+    """--full: per-kernel times, the roofline of the dominant kernel, the exact and RLC paths on the same batch and the
+    CPU baseline beside the headline"""
+    j = _bench_line(["--full", "--steps", "2", "--warmup", "1", "--tuples-per-gpu", "32768"])
+    assert all(k in j for k in HEADLINE + SIDE)
+    assert j["config"]["path"].startswith("prepared-keys") and j["roofline"]["kernel"] == "k_miller_prepared"
+    assert j["roofline"]["achieved"] > 0 and j["exact_path"]["value"] > 0 and j["rlc_path"]["value"] > 0 and j["cpu_baseline"]["value"] > 0
 
 
 def _latest(pattern):
