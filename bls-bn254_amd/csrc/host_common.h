@@ -33,6 +33,12 @@ struct DevBuf {
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+// multi-scalar multiplication (host_msm.hip, k_msm_bucket.hip): point rows, bucket entries, sorted entries, bucket counts and ends,
+// the levels' partial sums (ping-pong), the bucket sums, the window segments, the device-side counters; reserved for the largest call
+struct MsmWs {
+  DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, stat;
+  void release() { DevBuf* b[] = {&pts, &key, &val, &sorted, &hist, &end, &part[0], &part[1], &bsum, &seg, &stat}; for (DevBuf* x : b) x->release(); }
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -92,6 +98,9 @@ struct blsbn254_ctx {
   uint8_t dst_host[256];  // the (pre-hashed if oversize) DST currently resident in `dst`, and its length; -1 = none
   int dst_host_len = -1;
   size_t chunk = (size_t)1 << 22;   // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
+  MsmWs msm;
+  int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
+  uint64_t stat_msm[4] = {0, 0, 0, 0};   // bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
   bool profiling = false;
   std::map<std::string, ProfEntry> prof;
   std::string last_error;

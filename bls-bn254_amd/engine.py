@@ -396,6 +396,28 @@ class Engine:
         self._chk(self._lib.blsbn254_g2_mul_batch(self._ctx, pa, pk, ctypes.c_size_t(n), po))
         return o[:128 * n].tobytes()
 
+    def g1_msm(self, points, scalars, n):
+        """LinearCombination for G1Projective (g1.rs:559), n-term form: sum_i [k_i] P_i as 64 uncompressed bytes (bucket method)."""
+        a, pa = _inbuf(points, 64 * n); k, pk = _inbuf(scalars, 32 * n); o, po = _outbuf(64)
+        self._chk(self._lib.blsbn254_g1_msm(self._ctx, pa, pk, ctypes.c_size_t(n), po))
+        return o[:64].tobytes()
+
+    def g2_msm(self, points, scalars, n):
+        """LinearCombination for G2Projective (g2.rs:577), n-term form: sum_i [k_i] Q_i as 128 uncompressed bytes."""
+        a, pa = _inbuf(points, 128 * n); k, pk = _inbuf(scalars, 32 * n); o, po = _outbuf(128)
+        self._chk(self._lib.blsbn254_g2_msm(self._ctx, pa, pk, ctypes.c_size_t(n), po))
+        return o[:128].tobytes()
+
+    def set_msm_window(self, c):
+        """window width of the bucket method: 0 = chosen from n, 2..16 = forced"""
+        self._chk(self._lib.blsbn254_set_msm_window(self._ctx, ctypes.c_int(c)))
+
+    def msm_stats(self):
+        """dict: calls on the bucket path, calls on the small-n path, bucket entries accumulated, level-0 chunks summed"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_msm_stats(self._ctx, o))
+        return {"bucket_calls": int(o[0]), "small_calls": int(o[1]), "entries": int(o[2]), "chunks": int(o[3])}
+
     def threshold_combine(self, ids, partial_sigs, t):
         a, pa = _inbuf(ids, 32 * t); s, ps = _inbuf(partial_sigs, 64 * t); o, po = _outbuf(64)
         self._chk(self._lib.blsbn254_threshold_combine(self._ctx, pa, ps, ctypes.c_size_t(t), po))

@@ -229,6 +229,19 @@ int blsbn254_fast_aggregate_verify_batch(blsbn254_ctx* ctx, const uint8_t* pks, 
  * double-and-add, computed with 4-bit windows over the complete RCB formulas.  Not constant time. */
 int blsbn254_g1_mul_batch(blsbn254_ctx* ctx, const uint8_t* g1 /* n*64 */, const uint8_t* scalars /* n*32 */, size_t n, uint8_t* out /* n*64 */);
 int blsbn254_g2_mul_batch(blsbn254_ctx* ctx, const uint8_t* g2 /* n*128 */, const uint8_t* scalars /* n*32 */, size_t n, uint8_t* out /* n*128 */);
+/* out = sum_i [k_i] P_i  (LinearCombination for G1Projective g1.rs:559 / G2Projective g2.rs:577, n-term form;
+ * = Mul<Scalar> g1.rs:518-534 + Sum g1.rs:561-565).  Points uncompressed, scalars 32 B big-endian < r.  Errors as
+ * blsbn254_g1_mul_batch: a point that does not decode or is off the curve -> BLSBN254_ERR_G1 / _G2 (the first such
+ * index in last_error), a scalar >= r -> BLSBN254_ERR_SCALAR.  n == 0 -> the identity encoding.  n <= 2^23 per call
+ * (BLSBN254_E_ARG beyond).  G2 points need not lie in the r-torsion: the result is the integer combination.
+ * Bucket (Pippenger) method: G1 over the GLV halves, G2 over the full scalar; signed c-bit windows. */
+int blsbn254_g1_msm(blsbn254_ctx* ctx, const uint8_t* g1 /* n*64 */, const uint8_t* scalars /* n*32 */, size_t n, uint8_t out[64]);
+int blsbn254_g2_msm(blsbn254_ctx* ctx, const uint8_t* g2 /* n*128 */, const uint8_t* scalars /* n*32 */, size_t n, uint8_t out[128]);
+/* window width of the bucket method: 0 = chosen from n (default), 2..16 = forced (tests, tuning); else BLSBN254_E_ARG */
+int blsbn254_set_msm_window(blsbn254_ctx* ctx, int c);
+/* since context creation: out[0] calls on the bucket path, out[1] calls on the small-n path, out[2] bucket entries
+ * accumulated, out[3] chunks of bucket entries summed */
+int blsbn254_msm_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* sum_i lambda_i * sig_i with Lagrange coefficients at 0 for the t distinct non-zero ids
  * (Mul<Scalar> g1.rs:518-534 + Sum; Fr arithmetic scalar.rs:523-548) */
 int blsbn254_threshold_combine(blsbn254_ctx* ctx, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]);
