@@ -1,7 +1,8 @@
 // host.hip -- C-ABI host side (include/blsbn254.h), core unit: contexts, profiling, the VALU probe, staging helpers, the final-
 // exponentiation pipeline, and the primitive entry points (pairing, Miller loop, hash to curve, point checks).
 // The other pipelines: host_verify.hip (verify + G2Prepared), host_rlc.hip (RLC batch verification), host_aggregate.hip
-// (aggregate verify, sums, threshold), host_groupops.hip (group operations, FastAggregateVerify), host_misc.hip.
+// (aggregate verify, sums, threshold), host_groupops.hip (group operations, FastAggregateVerify), host_pairing_check.hip
+// (pairing-product equations over groups of pairs), host_misc.hip.
 #include "host_common.h"
 
 extern "C" {
@@ -81,6 +82,7 @@ void blsbn254_ctx_destroy(blsbn254_ctx* c) {
   for (DevBuf& b : c->gs_ok) b.release();
   c->gs_start.release(); c->gs_len.release(); c->gs_pk.release(); c->tri_vals.release();
   c->msm.release();
+  c->pc.release();
   { DevBuf* tb[] = {&c->th_x, &c->th_num, &c->th_den, &c->th_glv, &c->th_part, &c->th_part2, &c->q_ws}; for (DevBuf* b : tb) b->release(); }
   { DevBuf* rb[] = {&c->rlc_a2, &c->rlc_a, &c->rlc_b, &c->rlc_elig, &c->rlc_f2, &c->rlc_bytes, &c->rlc_neg, &c->rlc_ok, &c->rlc_idx, &c->rlc_cpk, &c->rlc_csig, &c->rlc_ch, &c->rlc_csub, &c->rlc_cbm};
     for (DevBuf* b : rb) b->release(); }

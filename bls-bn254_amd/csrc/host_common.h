@@ -39,6 +39,14 @@ struct MsmWs {
   DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, stat;
   void release() { DevBuf* b[] = {&pts, &key, &val, &sorted, &hist, &end, &part[0], &part[1], &bsum, &seg, &stat}; for (DevBuf* x : b) x->release(); }
 };
+// pairing-product equations (host_pairing_check.hip, k_pairing_check.hip): per-equation products (limb-major, stride n_eq) and
+// validity, per-pair validity of a launch, the product levels (ping-pong) with their flags, the chunk descriptors (device and
+// the host copies they are uploaded from)
+struct PcWs {
+  DevBuf prod, ok, pair_ok, seg[2], seg_ok[2], start, len;
+  std::vector<uint32_t> h_start, h_len;
+  void release() { DevBuf* b[] = {&prod, &ok, &pair_ok, &seg[0], &seg[1], &seg_ok[0], &seg_ok[1], &start, &len}; for (DevBuf* x : b) x->release(); }
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -99,6 +107,7 @@ struct blsbn254_ctx {
   int dst_host_len = -1;
   size_t chunk = (size_t)1 << 22;   // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
   MsmWs msm;
+  PcWs pc;
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
   uint64_t stat_msm[4] = {0, 0, 0, 0};   // bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
   bool profiling = false;

@@ -67,6 +67,9 @@ BN_KERNEL k_g2_mul(const uint8_t* g2, const uint8_t* scalars, size_t n, uint8_t*
 BN_KERNEL k_g2_load(const uint8_t* g2, size_t n, int32_t* ws, uint8_t* ok);
 BN_KERNEL k_g2_seg_sum(const int32_t* in_ws, size_t in_stride, const uint8_t* ok_in, const uint32_t* chunk_start, const uint32_t* chunk_len, size_t m,
                        int32_t* out_ws, size_t out_stride, uint8_t* ok_out);
+BN_KERNEL k_pair_ok(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* ok);
+BN_KERNEL k_fp12_seg_prod(const int32_t* in_ws, size_t in_stride, const uint8_t* ok_in, const uint32_t* chunk_start, const uint32_t* chunk_len,
+                          size_t m, int32_t* out_ws, size_t out_stride, uint8_t* ok_out, int carry);
 BN_KERNEL k_g2p_to_bytes(const int32_t* ws, size_t stride, const uint8_t* ok, size_t m, uint8_t* out, int poison);
 BN_KERNEL k_keygen(const uint8_t* ikm, size_t ikm_len, size_t n, const uint8_t* key_info, size_t key_info_len,
                    uint8_t* sks, uint8_t* status);

@@ -170,6 +170,29 @@ class Engine:
         self._chk(self._lib.blsbn254_multi_miller_loop(self._ctx, pa, pb, ctypes.c_size_t(n), po))
         return o.tobytes()
 
+    @staticmethod
+    def _eq_offsets(off):
+        o = np.ascontiguousarray(np.asarray(off, dtype=np.uint64).reshape(-1))
+        if o.size == 0:
+            raise ValueError("equation offsets need n_eq + 1 entries")
+        return o, o.size - 1, int(o.max())
+
+    def multi_miller_loop_batch(self, g1, g2, off):
+        """n_eq multi_miller_loop products (pairings.rs:808-857): equation g owns the pairs off[g] .. off[g + 1] of the
+        concatenated points g1 (64 B each) / g2 (128 B each).  Returns n_eq x 384 bytes."""
+        o, n_eq, npairs = self._eq_offsets(off)
+        a, pa = _inbuf(g1, 64 * npairs); b, pb = _inbuf(g2, 128 * npairs); r, pr = _outbuf(384 * n_eq)
+        self._chk(self._lib.blsbn254_multi_miller_loop_batch(self._ctx, pa, pb, o.ctypes.data_as(_u64p), ctypes.c_size_t(n_eq), pr))
+        return r[:384 * n_eq].tobytes()
+
+    def pairing_check_batch(self, g1, g2, off):
+        """Bit g (LSB-first) = prod_{j in equation g} e(P_j, Q_j) == 1 with every member a valid point (P on the curve, Q on the
+        curve and in the r-torsion; identities allowed).  Same arguments as multi_miller_loop_batch; returns the bitmap bytes."""
+        o, n_eq, npairs = self._eq_offsets(off)
+        a, pa = _inbuf(g1, 64 * npairs); b, pb = _inbuf(g2, 128 * npairs); r, pr = _outbuf((n_eq + 7) // 8)
+        self._chk(self._lib.blsbn254_pairing_check_batch(self._ctx, pa, pb, o.ctypes.data_as(_u64p), ctypes.c_size_t(n_eq), pr))
+        return r[:(n_eq + 7) // 8].tobytes()
+
     def final_exponentiation(self, ml, n=1):
         a, pa = _inbuf(ml, 384 * n); o, po = _outbuf(384 * n)
         self._chk(self._lib.blsbn254_final_exponentiation(self._ctx, pa, ctypes.c_size_t(n), po))

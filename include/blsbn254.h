@@ -70,6 +70,20 @@ int blsbn254_pairing_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* 
  * (pairing::MultiMillerLoop :706-713).  Pairs with an identity member are skipped.  Output = the
  * 384-byte Fp12 Miller-loop value (before final exponentiation). */
 int blsbn254_multi_miller_loop(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t ml_out[384]);
+/* n_eq independent multi_miller_loop products (pairings.rs:808-857): equation g owns the pairs
+ * g1[64*off[g] .. 64*off[g+1]) / g2[128*off[g] .. 128*off[g+1]) (off: n_eq + 1 non-decreasing element offsets, host array).
+ * ml_out[384*g ..] = the product of its Miller values, byte-identical to blsbn254_multi_miller_loop on those pairs.
+ * Identity pairs are skipped; an empty group gives Fp12::ONE.  Errors as blsbn254_multi_miller_loop: a pair that does not
+ * decode returns BLSBN254_ERR_G1 / _G2 (first bad pair index in last_error).  off[n_eq] - off[0] <= 2^23 pairs and
+ * n_eq <= 2^23, else BLSBN254_E_ARG.  n_eq == 0 returns 0. */
+int blsbn254_multi_miller_loop_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint64_t* off,
+                                     size_t n_eq, uint8_t* ml_out /* n_eq*384 */);
+/* Bit g (LSB-first) = prod_{j in g} e(P_j, Q_j) == 1, i.e. the product above .final_exponentiation() == Gt::IDENTITY
+ * (pairing::MillerLoopResult pairings.rs:698-704, MultiMillerLoop :706-713), AND every P_j decodes and is on the curve
+ * (identity allowed), AND every Q_j decodes, is on the curve and lies in the r-torsion (identity allowed).  A bad point
+ * clears its equation's bit; it is never an error.  An empty group holds.  Same size limits. */
+int blsbn254_pairing_check_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint64_t* off,
+                                 size_t n_eq, uint8_t* valid_bitmap /* ceil(n_eq/8) */);
 /* per-pair Miller loops (no product): n outputs of 384 B */
 int blsbn254_miller_loop_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* ml_out);
 /* MillerLoopResult::final_exponentiation, pairings.rs:50-178 (pairing::MillerLoopResult :698-704) */
