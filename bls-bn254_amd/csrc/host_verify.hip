@@ -126,6 +126,18 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
   c->u_hint = 0;                                      // keys did not repeat: the next call counts them first again
   return verify_exact_dev(c, d_pks, d_msgs, d_off, d_sigs, n, dl, d_bitmap);
 }
+// The key capacity a chunk of n tuples would be enqueued with, or 0 when it has to take the counting path.  Host state only: the
+// caller decides with it BEFORE it stages its tag (see verify_batch_dev_impl).
+static size_t async_capacity(const blsbn254_ctx* c, size_t n, size_t dst_len) {
+  const bool small = (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && c->tri_fe && n <= c->tri_max);
+  if (!c->async_verify || !c->auto_prepare || c->u_hint == 0 || !(n >= 1024 || small) || dst_len > 255) return 0;
+  size_t cap = 2 * c->u_hint < 1024 ? 1024 : 2 * c->u_hint;
+  if (cap < c->u_max_seen) cap = c->u_max_seen;
+  if (cap > PREP_MAX_KEYS) cap = PREP_MAX_KEYS;
+  if (cap > n) cap = n;
+  if (!small && cap > n / 2) cap = n / 2;
+  return cap;
+}
 // ---- asynchronous variant: no read-back before the pipeline is enqueued.
 // A steady caller's batches repeat their key set: after a chunk has taken the prepared-key path, the NEXT chunk is enqueued on the
 // assumption that it does too, with tables reserved for twice the last key count -- de-duplication, a one-lane decision kernel
@@ -136,18 +148,11 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
 // not valid yet: it is re-run on the counting path right there, before the caller can see it -- key ids beyond the capacity were
 // clamped by k_kd_propagate, so the discarded run indexed nothing out of bounds.  The caller's device buffers must stay untouched
 // until blsbn254_ctx_synchronize returns, as the header has always required of the device entry points.
+// The caller has made room in the queue (fewer than four calls pending) and staged the tag; nothing in here settles a pending call.
 static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n,
-                              uint32_t dl, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap, bool* took) {
-  *took = false;
+                              size_t cap, uint32_t dl, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap) {
   const bool small = (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && c->tri_fe && n <= c->tri_max);
-  if (!c->async_verify || !c->auto_prepare || c->u_hint == 0 || !(n >= 1024 || small) || dst_len > 255) return 0;
-  size_t cap = 2 * c->u_hint < 1024 ? 1024 : 2 * c->u_hint;
-  if (cap < c->u_max_seen) cap = c->u_max_seen;
-  if (cap > PREP_MAX_KEYS) cap = PREP_MAX_KEYS;
-  if (cap > n) cap = n;
-  if (!small && cap > n / 2) cap = n / 2;
-  if (cap == 0) return 0;
-  if (c->pend_count == 4) { int rc = resolve_pending(c, true); if (rc) return rc; }
+  if (cap == 0 || c->pend_count >= 4) { c->last_error = "verify_chunk_async: not eligible or queue full"; return BLSBN254_E_ARG; }
   if (!c->pend_host) {
     HIPCHK(c, hipHostMalloc((void**)&c->pend_host, 4 * 2 * sizeof(uint32_t), hipHostMallocDefault));
     HIPCHK(c, c->pend_dev.reserve(4 * 2 * sizeof(uint32_t)));
@@ -176,7 +181,6 @@ static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8
   if (dst_len) std::memcpy(pv.dst, dst, dst_len);
   ++c->pend_count;
   ++c->stat_async_chunks;
-  *took = true;
   return 0;
 }
 // Read back the checks of the asynchronously enqueued chunks, oldest first (blocking: all of them; else only those whose event has
@@ -207,14 +211,15 @@ static int verify_batch_dev_impl(blsbn254_ctx* c, const uint8_t* d_pks, const ui
   HIPCHK(c, hipSetDevice(c->device));
   int rc = resolve_pending(c, !allow_async);           // settle what has already come back (everything, for a caller that reads the result right away)
   if (rc) return rc;
+  // Everything that can still re-run an older call is settled BEFORE this call's tag is staged: a re-run stages the older
+  // call's tag, and one that ran between stage_dst and the kernels below would leave them hashing under the wrong tag.  The
+  // path is chosen from host state alone (no read-back); the queue is drained when it is full or when this call takes the
+  // counting path, which reads back anyway.
+  const size_t cap = (allow_async && n <= c->chunk) ? async_capacity(c, n, dst_len) : 0;
+  if (c->pend_count && (cap == 0 || c->pend_count == 4)) { rc = resolve_pending(c, true); if (rc) return rc; }
   uint32_t dl; rc = stage_dst(c, dst, dst_len, &dl);   // (a new tag waits for the kernels that still read the old one)
   if (rc) return rc;
-  if (allow_async && n <= c->chunk) {
-    bool took = false;
-    rc = verify_chunk_async(c, d_pks, d_msgs, d_off, d_sigs, n, dl, dst, dst_len, d_bitmap, &took);
-    if (rc || took) return rc;
-  }
-  if (c->pend_count) { rc = resolve_pending(c, true); if (rc) return rc; }     // the counting path reads back: settle the queue first
+  if (cap) return verify_chunk_async(c, d_pks, d_msgs, d_off, d_sigs, n, cap, dl, dst, dst_len, d_bitmap);
   for (size_t lo = 0; lo < n; lo += c->chunk) {        // chunk starts are multiples of 8: bitmap bytes do not straddle
     size_t m = n - lo < c->chunk ? n - lo : c->chunk;
     rc = verify_chunk_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, d_bitmap + lo / 8);

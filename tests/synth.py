@@ -51,14 +51,15 @@ def make_batch(oracle, n, dst, pool=8, invalid_every=0, uniq=None):
     return b"".join(pks), msgs, b"".join(sigs), exp
 
 
-def make_batch_gpu(engine, oracle, n, dst, pool=1024, invalid_every=0, spot=1000, seed=1, base=0):
+def make_batch_gpu(engine, oracle, n, dst, pool=1024, invalid_every=0, spot=1000, seed=1, base=0, key0=0):
     """n UNIQUE signed tuples: key pool of `pool` keys, 32-byte messages msg_g, signatures
     sig_g = [sk_(g mod pool)] H(msg_g) made by the engine's own GPU signing kernels and spot-checked at `spot`
     random indices against the CPU oracle.  g = base + i is the tuple's GLOBAL index (rank r of a sharded run
-    passes base = r * n, so every rank holds different messages); corruption pattern as in make_batch, keyed on g."""
+    passes base = r * n, so every rank holds different messages); corruption pattern as in make_batch, keyed on g.
+    The pool is keys key0 .. key0 + pool - 1 of the seeded key sequence (another key0: a disjoint key set of the same size)."""
     import random
     pool = min(pool, max(n, 1))
-    sks = [sk_of(k) for k in range(pool)]
+    sks = [sk_of(key0 + k) for k in range(pool)]
     skb = b"".join(s.to_bytes(32, "big") for s in sks)
     pk_pool = engine.sk_to_pk_batch(skb, pool)
     msgs = [msg_of(base + i) for i in range(n)]
@@ -94,6 +95,18 @@ def make_batch_gpu(engine, oracle, n, dst, pool=1024, invalid_every=0, spot=1000
             else:
                 pks[128 * i:128 * i + 128] = NON_SUBGROUP_PK
     return bytes(pks), msgs, bytes(sigs), exp
+
+
+def dev_batch(M, torch, pks, msgs, sigs):
+    """The arguments of the device-pointer entry points as torch tensors on cuda:0: [pks, message bytes, offsets, sigs, bitmap];
+    the bitmap is pre-filled with 0x5a so that bytes a call did not write show."""
+    data, off = M.engine.pack_messages(msgs)
+    dev = torch.device("cuda", 0)
+    t = [torch.frombuffer(bytearray(pks), dtype=torch.uint8).to(dev), torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev),
+         torch.from_numpy(off.astype(np.int64)).to(dev), torch.frombuffer(bytearray(sigs), dtype=torch.uint8).to(dev),
+         torch.full(((len(msgs) + 7) // 8,), 0x5a, dtype=torch.uint8, device=dev)]
+    torch.cuda.synchronize()
+    return t
 
 
 def expected_bits(n_total, invalid_every):
