@@ -69,37 +69,15 @@ int blsbn254_ctx_create(int device, blsbn254_ctx** out) {
 void blsbn254_ctx_destroy(blsbn254_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
+  (void)hipStreamSynchronize(c->stream);               // nothing is freed while either stream may still run work that touches it
+  (void)hipStreamSynchronize(c->stream2);
   for (auto& pv : c->pend) if (pv.ev) (void)hipEventDestroy(pv.ev);       // pending checks are dropped: the caller did not ask for their results
   if (c->pend_host) (void)hipHostFree(c->pend_host);
-  c->pend_dev.release();
   for (auto& kv : c->prof) for (auto& pr : kv.second.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  DevBuf* bufs[] = {&c->in_a, &c->in_b, &c->in_c, &c->in_off, &c->dst, &c->h_ws, &c->f_ws, &c->f_ws2, &c->flags, &c->sub_ok, &c->status, &c->status_all, &c->bitmap, &c->out, &c->scalars, &c->misc};
-  for (DevBuf* b : bufs) b->release();
-  for (DevBuf& b : c->fe) b.release();
-  c->fe_slots.release(); c->fe_wide_one.release();
-  for (DevBuf& b : c->gs_ws) b.release();
-  for (DevBuf& b : c->gs_ok) b.release();
-  c->gs_start.release(); c->gs_len.release(); c->gs_pk.release(); c->tri_vals.release();
-  c->msm.release();
-  c->pc.release();
-  { DevBuf* tb[] = {&c->th_x, &c->th_num, &c->th_den, &c->th_glv, &c->th_part, &c->th_part2, &c->q_ws}; for (DevBuf* b : tb) b->release(); }
-  { DevBuf* rb[] = {&c->rlc_a2, &c->rlc_a, &c->rlc_b, &c->rlc_elig, &c->rlc_f2, &c->rlc_bytes, &c->rlc_neg, &c->rlc_ok, &c->rlc_idx, &c->rlc_cpk, &c->rlc_csig, &c->rlc_ch, &c->rlc_csub, &c->rlc_cbm};
-    for (DevBuf* b : rb) b->release(); }
-  { DevBuf* kb[] = {&c->kd_slots, &c->kd_rep, &c->kd_kid, &c->kd_keys, &c->kd_hist, &c->kd_cursor, &c->kd_perm, &c->kd_cnt, &c->prep_table, &c->prep_raw, &c->prep_ok,
-                    &c->prep_isone, &c->prep_valid};
-    for (DevBuf* b : kb) b->release(); }
-  { DevBuf* rb[] = {&c->r2_seed, &c->r2_a, &c->r2_b, &c->r2_sigok, &c->r2_tchunk, &c->r2_ccnt, &c->r2_cbase, &c->r2_ckid, &c->r2_cstart, &c->r2_clen, &c->r2_csig,
-                    &c->r2_ch, &c->r2_cstate, &c->r2_iota, &c->r2_cisone, &c->r2_need, &c->r2_bcnt, &c->r2_bbase, &c->r2_list, &c->r2_valid,
-                    &c->ks_cnt[0], &c->ks_cnt[1], &c->ks_base[0], &c->ks_base[1], &c->ks_kid[0], &c->ks_kid[1], &c->ks_start, &c->ks_len, &c->ks_tchunk, &c->ks_iota,
-                    &c->ks_out[0], &c->ks_out[1], &c->ks_out2[0], &c->ks_out2[1], &c->r2_sa, &c->r2_sb, &c->r2_celig, &c->r2_kelig, &c->r2_ksig, &c->r2_kh, &c->r2_kstate, &c->r2_kisone,
-                    &c->r2_kpass, &c->r2_cpass, &c->r2_clist, &c->r2_cneed, &c->r2_cbcnt, &c->r2_cbbase};
-    for (DevBuf* b : rb) b->release(); }
-  (void)hipStreamSynchronize(c->stream2);
   (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join);
   (void)hipStreamDestroy(c->stream2);
   (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;                                            // every DevBuf frees itself
 }
 int blsbn254_ctx_synchronize(blsbn254_ctx* c) {
   if (!c) return BLSBN254_E_ARG;
@@ -158,7 +136,7 @@ int blsbn254_valu_probe(blsbn254_ctx* c, double out[6]) {
     double best = 0, best_clk = 0;
     for (int rep = 0; rep < 4; ++rep) {
       HIPCHK(c, hipEventRecord(ev.e0, c->stream));
-      hipLaunchKernelGGL(k_valu_peak, dim3(blocks), dim3(256), 0, c->stream, (uint32_t*)c->misc.p, 1u + rep, iters, kind, d_stamps);
+      TRY(launch(c, c->stream, nullptr, Shape{dim3(blocks), dim3(256)}, k_valu_peak, (uint32_t*)c->misc.p, 1u + rep, iters, kind, d_stamps));
       HIPCHK(c, hipEventRecord(ev.e1, c->stream));
       HIPCHK(c, hipEventSynchronize(ev.e1));
       float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
@@ -212,23 +190,25 @@ int check_offsets(const uint64_t* off, size_t n) {
   for (size_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return BLSBN254_E_ARG;
   return 0;
 }
+int min_index_arm(blsbn254_ctx* c, int* d, size_t words) {
+  static const int none[2] = {NO_INDEX, NO_INDEX};          // static: outlives the asynchronous copy
+  HIPCHK(c, hipMemcpyAsync(d, none, 4 * words, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+int min_index_read(blsbn254_ctx* c, const int* d, int* out) {
+  TRY(download(c, out, d, 4));
+  if (*out == NO_INDEX) *out = -1;
+  return 0;
+}
 // first index whose status differs from the wanted value, or -1
 int first_bad(blsbn254_ctx* c, const uint8_t* d_status, size_t n, uint8_t mask, uint8_t val, int* out) {
   HIPCHK(c, c->misc.reserve(64));
-  int init = 0x7fffffff;
-  HIPCHK(c, hipMemcpyAsync(c->misc.p, &init, 4, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "status_reduce", k_status_reduce, n, d_status, n, mask, val, (int*)c->misc.p);
-  HIPCHK(c, hipMemcpyAsync(out, c->misc.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (*out == 0x7fffffff) *out = -1;
-  return 0;
+  TRY(min_index_arm(c, (int*)c->misc.p, 1));
+  TRY(launch(c, c->stream, "status_reduce", grid_lanes(n), k_status_reduce, d_status, n, mask, val, (int*)c->misc.p));
+  return min_index_read(c, (const int*)c->misc.p, out);
 }
 // status byte of the tuple at index idx (host read)
-int read_status(blsbn254_ctx* c, const uint8_t* d_status, int idx, uint8_t* st) {
-  HIPCHK(c, hipMemcpyAsync(st, d_status + idx, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
+int read_status(blsbn254_ctx* c, const uint8_t* d_status, int idx, uint8_t* st) { return download(c, st, d_status + idx, 1); }
 
 
 // Final exponentiation of the n Fp12 values at f (limb-major, `stride`), in place for the easy part.
@@ -244,19 +224,19 @@ int run_final_exp(blsbn254_ctx* c, int32_t* f, size_t n, size_t stride, int mode
   // t = f^((p^6-1)(p^2+1)), in place.  From a round of waves up, the ONE Fp inversion of the easy part is shared by four tuples
   // per lane (head / inv4 / tail, k_fe_easy.hip; the pieces wait in the phase buffers A and B, which the hard part only fills later)
   if (n >= c->lanes_per_round / 2 && c->split_easy) {
-    LAUNCH(c, "fe_easy_head", k_fe_easy_head, n, (const int32_t*)f, n, stride, A, B);
-    LAUNCH(c, "fe_inv4", k_fe_inv4, (n + 3) / 4, B, n, stride);
-    LAUNCH(c, "fe_easy_tail", k_fe_easy_tail, n, (const int32_t*)f, f, n, stride, (const int32_t*)A, (const int32_t*)B);
+    TRY(launch(c, c->stream, "fe_easy_head", grid_lanes(n), k_fe_easy_head, (const int32_t*)f, n, stride, A, B));
+    TRY(launch(c, c->stream, "fe_inv4", grid_lanes((n + 3) / 4), k_fe_inv4, B, n, stride));
+    TRY(launch(c, c->stream, "fe_easy_tail", grid_lanes(n), k_fe_easy_tail, (const int32_t*)f, f, n, stride, (const int32_t*)A, (const int32_t*)B));
   } else {
-    LAUNCH(c, "fe_easy", k_fe_easy, n, (const int32_t*)f, f, n, stride);
+    TRY(launch(c, c->stream, "fe_easy", grid_lanes(n), k_fe_easy, (const int32_t*)f, f, n, stride));
   }
   // Few tuples: the lane-per-tuple kernels below would be the latency of one lane's chain (4.5 ms for any n <= 65536); the hard
   // part runs with one WAVE per tuple instead (k_fe_wide.hip): ~0.6 ms per round of CUs x 16 tuples.  Same values.
   if (c->wide_fe && n <= c->wide_fe_max) {
     uint8_t* one = nullptr;
     if (mode == 0) { HIPCHK(c, c->fe_wide_one.reserve(n)); one = (uint8_t*)c->fe_wide_one.p; }
-    LAUNCH_WIDE(c, "fe_hard_wide", k_fe_hard_wide, n, (const int32_t*)f, n, stride, flags, sub_ok, one, d_gt, d_is_one, mode);
-    if (mode == 0) { LAUNCH(c, "pack_bitmap", k_pack_bitmap, n, (const uint8_t*)one, n, d_bitmap); }
+    TRY(launch(c, c->stream, "fe_hard_wide", grid_wide(n), k_fe_hard_wide, (const int32_t*)f, n, stride, flags, sub_ok, one, d_gt, d_is_one, mode));
+    if (mode == 0) TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)one, n, d_bitmap));
     return 0;
   }
   // Between the wave-per-tuple limit and a quarter of a round of lanes: three lanes per tuple (k_tri.hip) -- the lane-per-tuple
@@ -265,16 +245,16 @@ int run_final_exp(blsbn254_ctx* c, int32_t* f, size_t n, size_t stride, int mode
     HIPCHK(c, c->tri_vals.reserve(n * TRI_VALUE_LIMBS * 4));
     uint8_t* one = nullptr;
     if (mode == 0) { HIPCHK(c, c->fe_wide_one.reserve(n)); one = (uint8_t*)c->fe_wide_one.p; }
-    LAUNCH_TRI(c, "fe_tri_hard", k_fe_tri_hard, n, (const int32_t*)f, n, stride, (int32_t*)c->tri_vals.p, flags, sub_ok, one, d_gt, d_is_one, mode);
-    if (mode == 0) { LAUNCH(c, "pack_bitmap", k_pack_bitmap, n, (const uint8_t*)one, n, d_bitmap); }
+    TRY(launch(c, c->stream, "fe_tri_hard", grid_tri(n), k_fe_tri_hard, (const int32_t*)f, n, stride, (int32_t*)c->tri_vals.p, flags, sub_ok, one, d_gt, d_is_one, mode));
+    if (mode == 0) TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)one, n, d_bitmap));
     return 0;
   }
   // t^x three times; the glue steps fe_h1 / fe_h2 are computed by the first two launches themselves (k_fe_expx_tail.hip)
-  LAUNCH(c, "fe_expx_h1", k_fe_expx_h1, n, (const int32_t*)f, S, n, stride, A, B);
-  LAUNCH(c, "fe_expx_h2", k_fe_expx_h2, n, (const int32_t*)B, S, n, stride, B, C, B2, D);
-  LAUNCH(c, "fe_expx", k_fe_expx, n, (const int32_t*)D, X, S, n, stride);
-  LAUNCH(c, "fe_h3", k_fe_h3, n, (const int32_t*)f, (const int32_t*)A, (const int32_t*)C, (const int32_t*)B2, (const int32_t*)X, S, n, stride,
-         flags, sub_ok, d_bitmap, d_gt, d_is_one, mode);
+  TRY(launch(c, c->stream, "fe_expx_h1", grid_lanes(n), k_fe_expx_h1, (const int32_t*)f, S, n, stride, A, B));
+  TRY(launch(c, c->stream, "fe_expx_h2", grid_lanes(n), k_fe_expx_h2, (const int32_t*)B, S, n, stride, B, C, B2, D));
+  TRY(launch(c, c->stream, "fe_expx", grid_lanes(n), k_fe_expx, (const int32_t*)D, X, S, n, stride));
+  TRY(launch(c, c->stream, "fe_h3", grid_lanes(n), k_fe_h3, (const int32_t*)f, (const int32_t*)A, (const int32_t*)C, (const int32_t*)B2, (const int32_t*)X, S, n, stride,
+             flags, sub_ok, d_bitmap, d_gt, d_is_one, mode));
   return 0;
 }
 
@@ -284,11 +264,11 @@ int miller_to_ws(blsbn254_ctx* c, const uint8_t* d_g1, const uint8_t* d_g2, size
   HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
   HIPCHK(c, c->status.reserve(n));
   if (c->wide_fe && n <= c->wide_fe_max / 2) {        // few pairs: one wave per pair (lane 0 runs the G2 point arithmetic); the serial part makes the chain ~2 x a prepared one
-    LAUNCH_WIDE(c, "miller_wide_1", k_miller_wide_1, n, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p);
+    TRY(launch(c, c->stream, "miller_wide_1", grid_wide(n), k_miller_wide_1, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p));
   } else if (n <= c->tri_max && c->tri_miller) {      // mid-size: a quad of lanes per pair (k_tri.hip: line steps four lanes per point, f three lanes per value)
-    LAUNCH_TRI(c, "miller_tri_1", k_miller_tri_1, n, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p);
+    TRY(launch(c, c->stream, "miller_tri_1", grid_tri(n), k_miller_tri_1, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p));
   } else {
-    LAUNCH(c, "miller_1", k_miller_1, n, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p);
+    TRY(launch(c, c->stream, "miller_1", grid_lanes(n), k_miller_1, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p));
   }
   return 0;
 }
@@ -306,14 +286,12 @@ int blsbn254_pairing_batch_dev(blsbn254_ctx* c, const uint8_t* d_g1, const uint8
   if (n == 0) return 0;
   ENTER(c);
   HIPCHK(c, c->status_all.reserve(n));
-  for (size_t lo = 0; lo < n; lo += c->chunk) {
-    size_t m = n - lo < c->chunk ? n - lo : c->chunk;
-    int rc = miller_to_ws(c, d_g1 + 64 * lo, d_g2 + 128 * lo, m);
-    if (rc) return rc;
-    rc = run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 1, nullptr, nullptr, nullptr, d_gt + 384 * lo, nullptr);
-    if (rc) return rc;
+  TRY(for_chunks(c, n, [&](size_t lo, size_t m) -> int {
+    TRY(miller_to_ws(c, d_g1 + 64 * lo, d_g2 + 128 * lo, m));
+    TRY(run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 1, nullptr, nullptr, nullptr, d_gt + 384 * lo, nullptr));
     HIPCHK(c, hipMemcpyAsync((uint8_t*)c->status_all.p + lo, c->status.p, m, hipMemcpyDeviceToDevice, c->stream));
-  }
+    return 0;
+  }));
   if (d_status) HIPCHK(c, hipMemcpyAsync(d_status, c->status_all.p, n, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
@@ -321,88 +299,62 @@ int blsbn254_pairing_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2
   if (!c || (n && (!g1 || !g2 || !gt))) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(64 * n)); HIPCHK(c, c->in_b.reserve(128 * n)); HIPCHK(c, c->out.reserve(384 * n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, g1, 64 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, g2, 128 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->out.reserve(384 * n));
+  TRY(upload(c, c->in_a, g1, 64 * n));
+  TRY(upload(c, c->in_b, g2, 128 * n));
   int rc = blsbn254_pairing_batch_dev(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, n, (uint8_t*)c->out.p, nullptr);
   if (rc) return rc;
   rc = decode_status_rc(c, (const uint8_t*)c->status_all.p, n);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(gt, c->out.p, 384 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, gt, c->out.p, 384 * n);
 }
 int blsbn254_miller_loop_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* ml_out) {
   if (!c || (n && (!g1 || !g2 || !ml_out))) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(64 * n)); HIPCHK(c, c->in_b.reserve(128 * n)); HIPCHK(c, c->out.reserve(384 * n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, g1, 64 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, g2, 128 * n, hipMemcpyHostToDevice, c->stream));
-  for (size_t lo = 0; lo < n; lo += c->chunk) {
-    size_t m = n - lo < c->chunk ? n - lo : c->chunk;
-    int rc = miller_to_ws(c, (const uint8_t*)c->in_a.p + 64 * lo, (const uint8_t*)c->in_b.p + 128 * lo, m);
-    if (rc) return rc;
-    rc = decode_status_rc(c, (const uint8_t*)c->status.p, m);
-    if (rc) return rc;
-    LAUNCH(c, "fp12_to_bytes", k_fp12_to_bytes, m, (const int32_t*)c->f_ws.p, m, m, (uint8_t*)c->out.p + 384 * lo);
-  }
-  HIPCHK(c, hipMemcpyAsync(ml_out, c->out.p, 384 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
-// product of the n Fp12 values in f_ws (stride n) -> left in *result (pointer into f_ws or f_ws2), stride *rs
-int product_tree(blsbn254_ctx* c, size_t n, const int32_t** result, size_t* rs) {
-  HIPCHK(c, c->f_ws2.reserve(((n + 1) / 2) * 108 * 4));
-  int32_t* a = (int32_t*)c->f_ws.p; int32_t* b = (int32_t*)c->f_ws2.p;
-  size_t sa = n, m = n;
-  while (m > 1) {
-    size_t mo = (m + 1) / 2;
-    LAUNCH(c, "fp12_mul_pairs", k_fp12_mul_pairs, mo, (const int32_t*)a, m, sa, b, mo);
-    std::swap(a, b); sa = mo; m = mo;
-  }
-  *result = a; *rs = sa;
-  return 0;
+  HIPCHK(c, c->out.reserve(384 * n));
+  TRY(upload(c, c->in_a, g1, 64 * n));
+  TRY(upload(c, c->in_b, g2, 128 * n));
+  TRY(for_chunks(c, n, [&](size_t lo, size_t m) -> int {
+    TRY(miller_to_ws(c, (const uint8_t*)c->in_a.p + 64 * lo, (const uint8_t*)c->in_b.p + 128 * lo, m));
+    TRY(decode_status_rc(c, (const uint8_t*)c->status.p, m));
+    return launch(c, c->stream, "fp12_to_bytes", grid_lanes(m), k_fp12_to_bytes, (const int32_t*)c->f_ws.p, m, m, (uint8_t*)c->out.p + 384 * lo);
+  }));
+  return download(c, ml_out, c->out.p, 384 * n);
 }
 int blsbn254_multi_miller_loop(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t ml_out[384]) {
   if (!c || !ml_out || (n && (!g1 || !g2))) return BLSBN254_E_ARG;
   if (n == 0) { std::memset(ml_out, 0, 384); ml_out[31] = 1; return 0; }       // empty product = Fp12::ONE
   CHECK_LANES(c, n);
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(64 * n)); HIPCHK(c, c->in_b.reserve(128 * n)); HIPCHK(c, c->out.reserve(384));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, g1, 64 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, g2, 128 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->out.reserve(384));
+  TRY(upload(c, c->in_a, g1, 64 * n));
+  TRY(upload(c, c->in_b, g2, 128 * n));
   int rc = miller_to_ws(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, n);
   if (rc) return rc;
   rc = decode_status_rc(c, (const uint8_t*)c->status.p, n);
   if (rc) return rc;
-  const int32_t* res; size_t rs;
-  rc = product_tree(c, n, &res, &rs);
+  int32_t* res; size_t rs;
+  rc = fp12_tree(c, (int32_t*)c->f_ws.p, n, n, &res, &rs);
   if (rc) return rc;
-  LAUNCH(c, "fp12_to_bytes", k_fp12_to_bytes, 1, res, (size_t)1, rs, (uint8_t*)c->out.p);
-  HIPCHK(c, hipMemcpyAsync(ml_out, c->out.p, 384, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(1), k_fp12_to_bytes, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p));
+  return download(c, ml_out, c->out.p, 384);
 }
 int blsbn254_final_exponentiation(blsbn254_ctx* c, const uint8_t* ml, size_t n, uint8_t* gt) {
   if (!c || (n && (!ml || !gt))) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(384 * n)); HIPCHK(c, c->out.reserve(384 * n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, ml, 384 * n, hipMemcpyHostToDevice, c->stream));
-  for (size_t lo = 0; lo < n; lo += c->chunk) {
-    size_t m = n - lo < c->chunk ? n - lo : c->chunk;
+  HIPCHK(c, c->out.reserve(384 * n));
+  TRY(upload(c, c->in_a, ml, 384 * n));
+  TRY(for_chunks(c, n, [&](size_t lo, size_t m) -> int {
     HIPCHK(c, c->f_ws.reserve(m * 108 * 4)); HIPCHK(c, c->status.reserve(m));
-    LAUNCH(c, "fp12_from_bytes", k_fp12_from_bytes, m, (const uint8_t*)c->in_a.p + 384 * lo, m, (int32_t*)c->f_ws.p, m, (uint8_t*)c->status.p);
-    int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, m, 1, 1, &bad);
-    if (rc) return rc;
+    TRY(launch(c, c->stream, "fp12_from_bytes", grid_lanes(m), k_fp12_from_bytes, (const uint8_t*)c->in_a.p + 384 * lo, m, (int32_t*)c->f_ws.p, m, (uint8_t*)c->status.p));
+    int bad;
+    TRY(first_bad(c, (const uint8_t*)c->status.p, m, 1, 1, &bad));
     if (bad >= 0) return BLSBN254_ERR_GT;
-    rc = run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 1, nullptr, nullptr, nullptr, (uint8_t*)c->out.p + 384 * lo, nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipMemcpyAsync(gt, c->out.p, 384 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+    return run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 1, nullptr, nullptr, nullptr, (uint8_t*)c->out.p + 384 * lo, nullptr);
+  }));
+  return download(c, gt, c->out.p, 384 * n);
 }
 
 // ---------------- hash to curve
@@ -430,11 +382,11 @@ static int h2c_common(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off,
   if (rc) return rc;
   size_t sz = g2 ? 128 : 64;
   HIPCHK(c, c->out.reserve(sz * n));
-  if (g2) { LAUNCH(c, "hash_to_g2", k_hash_to_g2, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (uint8_t*)c->out.p, ro); }
-  else { LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)nullptr, n, (uint8_t*)c->out.p, ro ? 1 : 2); }
-  HIPCHK(c, hipMemcpyAsync(out, c->out.p, sz * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  if (g2) TRY(launch(c, c->stream, "hash_to_g2", grid_lanes(n), k_hash_to_g2, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
+                     (uint8_t*)c->out.p, ro));
+  else TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)nullptr,
+                  n, (uint8_t*)c->out.p, ro ? 1 : 2));
+  return download(c, out, c->out.p, sz * n);
 }
 int blsbn254_hash_to_g1_batch(blsbn254_ctx* c, const uint8_t* m, const uint64_t* o, size_t n, const uint8_t* d, size_t dl, uint8_t* out) { return h2c_common(c, m, o, n, d, dl, out, 0, 1); }
 int blsbn254_encode_to_g1_batch(blsbn254_ctx* c, const uint8_t* m, const uint64_t* o, size_t n, const uint8_t* d, size_t dl, uint8_t* out) { return h2c_common(c, m, o, n, d, dl, out, 0, 0); }
@@ -447,13 +399,11 @@ static int check_common(blsbn254_ctx* c, const uint8_t* pts, size_t n, uint8_t* 
   if (n == 0) return 0;
   ENTER(c);
   size_t sz = g2 ? 128 : 64, nb = (n + 7) / 8;
-  HIPCHK(c, c->in_a.reserve(sz * n)); HIPCHK(c, c->bitmap.reserve(nb + 8));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pts, sz * n, hipMemcpyHostToDevice, c->stream));
-  if (g2) { LAUNCH(c, "g2_check", k_g2_check, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)nullptr, (uint8_t*)c->bitmap.p); }
-  else { LAUNCH(c, "g1_check", k_g1_check, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->bitmap.p); }
-  HIPCHK(c, hipMemcpyAsync(bm, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  HIPCHK(c, c->bitmap.reserve(nb + 8));
+  TRY(upload(c, c->in_a, pts, sz * n));
+  if (g2) TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, (const uint8_t*)c->in_a.p, n, (uint8_t*)nullptr, (uint8_t*)c->bitmap.p));
+  else TRY(launch(c, c->stream, "g1_check", grid_lanes(n), k_g1_check, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->bitmap.p));
+  return download(c, bm, c->bitmap.p, nb);
 }
 int blsbn254_g1_check_batch(blsbn254_ctx* c, const uint8_t* g1, size_t n, uint8_t* bm) { return check_common(c, g1, n, bm, 0); }
 int blsbn254_g2_check_batch(blsbn254_ctx* c, const uint8_t* g2, size_t n, uint8_t* bm) { return check_common(c, g2, n, bm, 1); }

@@ -10,7 +10,7 @@ int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res,
   int32_t* b = (int32_t*)c->f_ws2.p;
   while (cnt > 1) {
     size_t mo = (cnt + 1) / 2;
-    LAUNCH(c, "fp12_mul_pairs", k_fp12_mul_pairs, mo, (const int32_t*)a, cnt, sa, b, mo);
+    TRY(launch(c, c->stream, "fp12_mul_pairs", grid_lanes(mo), k_fp12_mul_pairs, (const int32_t*)a, cnt, sa, b, mo));
     std::swap(a, b); sa = mo; cnt = mo;
   }
   *res = a; *rs = sa;
@@ -62,37 +62,39 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
     if (u * 2 <= np && u <= PREP_MAX_KEYS) {
       HIPCHK(c, c->prep_table.reserve(64)); HIPCHK(c, c->prep_ok.reserve(u)); HIPCHK(c, c->prep_raw.reserve(u * PREP_RAW_LIMBS * 4));
       HIPCHK(c, fork_stream2(c));
-      LAUNCH_G2_PREPARE(c, LAUNCH2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, (const uint32_t*)nullptr);
+      TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
       HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-      LAUNCH(c, "kd_propagate", k_kd_propagate, np, (const uint32_t*)c->kd_rep.p, (uint32_t)np, (uint32_t)u, (uint32_t*)c->kd_kid.p, (uint32_t*)nullptr);   // no sorting here: no histogram
+      TRY(launch(c, c->stream, "kd_propagate", grid_lanes(np), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)np, (uint32_t)u, (uint32_t*)c->kd_kid.p,
+                 (uint32_t*)nullptr));   // no sorting here: no histogram
       prepared = true;
     }
   }
   // hash (and, on the exact path, key checks) over the caller's n pairs; their H points land in slots 0..n-1 of a stride-np workspace
   if (n) {
-    LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, np, (uint8_t*)nullptr, 0);
-    if (!prepared) { LAUNCH(c, "g2_check", k_g2_check, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr); }
+    TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p,
+               np, (uint8_t*)nullptr, 0));
+    if (!prepared) TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
   }
-  if (extra_sig) { LAUNCH(c, "g1_to_ws", k_g1_to_ws, 1, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 1)); }
+  if (extra_sig) TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 1)));
   if (prepared) {
     // few distinct keys: every key (and -G2gen, when the signature's pair is carried) was validated and turned into its line
     // table once, beside hash-to-G1; the pairs read their lines from those tables
     HIPCHK(c, join_stream2(c));
-    LAUNCH(c, "miller_hpk2p", k_miller_hpk2p, n_lanes, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)c->prep_raw.p,
-           (const uint8_t*)c->prep_ok.p, np, f, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)nullptr);
-    if (n) { LAUNCH(c, "and_reduce", k_and_reduce, n, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok); }
+    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)c->prep_raw.p,
+               (const uint8_t*)c->prep_ok.p, np, f, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)nullptr));
+    if (n) TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok));
   } else {
-    LAUNCH(c, "miller_hpk2", k_miller_hpk2, n_lanes, (const int32_t*)c->h_ws.p, (const uint8_t*)c->in_a.p, np, (int32_t*)c->q_ws.p, f, n_lanes, (uint8_t*)c->flags.p);
-    if (n) { LAUNCH(c, "and_reduce", k_and_reduce, n, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p, n, d_ok); }
+    TRY(launch(c, c->stream, "miller_hpk2", grid_lanes(n_lanes), k_miller_hpk2, (const int32_t*)c->h_ws.p, (const uint8_t*)c->in_a.p, np, (int32_t*)c->q_ws.p, f, n_lanes,
+               (uint8_t*)c->flags.p));
+    if (n) TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p, n, d_ok));
   }
   int32_t* res; size_t rs;
   rc = fp12_tree(c, f, n_lanes, n_lanes, &res, &rs);
   if (rc) return rc;
-  LAUNCH(c, "fp12_to_bytes", k_fp12_to_bytes, 1, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p);
+  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(1), k_fp12_to_bytes, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p));
   int h_ok[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(ml_out, c->out.p, 384, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_ok, d_ok, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, h_ok, d_ok, 8));
   *all_pks_ok = h_ok[0];
   if (sig_ok) *sig_ok = (h_ok[1] & 0xff) == 1;
   return 0;
@@ -127,14 +129,14 @@ int blsbn254_aggregate_finish(blsbn254_ctx* c, const uint8_t* partials, size_t k
   if (k) {
     HIPCHK(c, hipMemcpyAsync(c->in_a.p, partials, 384 * k, hipMemcpyHostToDevice, c->stream));
     // partials arrive as bytes: decode into slots 0..k-1 of the stride-m array
-    LAUNCH(c, "fp12_from_bytes", k_fp12_from_bytes, k, (const uint8_t*)c->in_a.p, k, f, m, (uint8_t*)c->status.p);
+    TRY(launch(c, c->stream, "fp12_from_bytes", grid_lanes(k), k_fp12_from_bytes, (const uint8_t*)c->in_a.p, k, f, m, (uint8_t*)c->status.p));
     int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, k, 1, 1, &bad);
     if (rc) return rc;
     if (bad >= 0) return BLSBN254_ERR_GT;
   }
   if (with_sig) {
-    LAUNCH(c, "miller_1", k_miller_1, 1, (const uint8_t*)c->in_b.p, (const uint8_t*)c->in_b.p + 64, (size_t)1, f + k, m, (uint8_t*)c->status.p);
-    LAUNCH(c, "g1_check", k_g1_check, 1, (const uint8_t*)c->in_b.p, (size_t)1, (uint8_t*)c->bitmap.p);
+    TRY(launch(c, c->stream, "miller_1", grid_lanes(1), k_miller_1, (const uint8_t*)c->in_b.p, (const uint8_t*)c->in_b.p + 64, (size_t)1, f + k, m, (uint8_t*)c->status.p));
+    TRY(launch(c, c->stream, "g1_check", grid_lanes(1), k_g1_check, (const uint8_t*)c->in_b.p, (size_t)1, (uint8_t*)c->bitmap.p));
   }
   int32_t* res; size_t rs;
   int rc = fp12_tree(c, f, m, m, &res, &rs);
@@ -170,15 +172,15 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   if (rc) return rc;
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
-  HIPCHK(c, c->in_a.reserve(128 * (n + 1))); HIPCHK(c, c->in_b.reserve(64));
+  HIPCHK(c, c->in_a.reserve(128 * (n + 1)));
   HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * n, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));   // "tuple n": the key of the signature's pair
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sig, 64, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->in_b, agg_sig, 64));
   size_t u = 0;
   rc = dedup_keys(c, (const uint8_t*)c->in_a.p, n, &u);
   if (rc) return rc;
   // few pairs: from tables, one wave per pair (or, up to tri_max pairs, a quad of lanes per pair: k_miller_tri_1p), whatever the keys
-  const bool small = (c->wide_fe && n + 1 <= c->wide_fe_max) || (c->tri_miller && n + 1 <= c->tri_max);
+  const bool small = small_for_prepared(c, n + 1, false);      // n + 1: the signature's pair joins the launch; one final exponentiation in all
   if (!((u * 2 <= n || small) && u + 1 <= PREP_MAX_KEYS)) return 0;
   *took = true;
   const size_t np = u + 1, n_lanes = (np + 1) / 2;
@@ -189,7 +191,7 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   HIPCHK(c, hipStreamSynchronize(c->stream));                                   // last_key and the staged copies are consumed
   HIPCHK(c, c->prep_ok.reserve(np)); HIPCHK(c, c->prep_raw.reserve(np * PREP_RAW_LIMBS * 4));
   HIPCHK(c, fork_stream2(c));
-  LAUNCH_G2_PREPARE(c, LAUNCH2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, np, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, (const uint32_t*)nullptr);
+  TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, np, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   // key ids, key-sorted order
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
@@ -197,11 +199,11 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   HIPCHK(c, c->rlc_b.reserve(np * 18 * 4)); HIPCHK(c, c->rlc_idx.reserve(4 * np));
   uint32_t *hist = (uint32_t*)c->kd_hist.p, *cursor = (uint32_t*)c->kd_cursor.p, *perm = (uint32_t*)c->kd_perm.p, *kid = (uint32_t*)c->kd_kid.p;
   HIPCHK(c, hipMemsetAsync(hist, 0, 4 * u, c->stream));
-  LAUNCH(c, "kd_propagate", k_kd_propagate, n, (const uint32_t*)c->kd_rep.p, n32, u32, kid, hist);
-  { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)hist, u32, cursor); }
-  HIPCHK(c, hipGetLastError());
-  LAUNCH(c, "kd_scatter", k_kd_scatter, n, (const uint32_t*)kid, n32, u32, cursor, perm);          // cursor[k] is now the END of run k
-  LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 3);
+  TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, n32, u32, kid, hist));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, u32, cursor));
+  TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, (const uint32_t*)kid, n32, u32, cursor, perm));          // cursor[k] is now the END of run k
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n,
+             (uint8_t*)nullptr, 3));
   // sums per key: the tuples in sorted order (columns perm[s] of h_ws) -> one sum per key (key_sums)
   const int32_t* pts = nullptr; size_t pts_stride = u;
   rc = key_sums(c, (const int32_t*)c->h_ws.p, nullptr, n, perm, perm, kid, hist, cursor, n, u, &pts, nullptr);
@@ -211,37 +213,38 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   int* d_ok = (int*)c->misc.p;                                                  // [0] all keys valid, [1] (byte) signature valid, [4] is_one
   static const int ones[2] = {1, 1};
   HIPCHK(c, hipMemcpyAsync(d_ok, ones, 8, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "g1p_to_h", k_g1p_to_h_affine, u, pts, pts_stride, u, h2, np, st);
+  TRY(launch(c, c->stream, "g1p_to_h", grid_lanes(u), k_g1p_to_h_affine, pts, pts_stride, u, h2, np, st));
   HIPCHK(c, hipMemsetAsync(st + u, 1, 1, c->stream));
-  LAUNCH(c, "g1_to_ws", k_g1_to_ws, 1, (const uint8_t*)c->in_b.p, h2, u, np, (uint8_t*)(d_ok + 1));
-  LAUNCH(c, "iota", k_iota_u32, np, kid2, (uint32_t)np);
+  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, h2, u, np, (uint8_t*)(d_ok + 1)));
+  TRY(launch(c, c->stream, "iota", grid_lanes(np), k_iota_u32, kid2, (uint32_t)np));
   HIPCHK(c, join_stream2(c));
   // few pairs: the launch is the latency of one wave, so one pair per lane (no shared f^2, shorter chain); else two per lane
   const bool one_per_lane = np * 2 <= c->lanes_per_round;
   const size_t f_cnt = one_per_lane ? np : n_lanes;
   HIPCHK(c, c->f_ws.reserve(f_cnt * 108 * 4));
   if (c->wide_fe && np <= c->wide_fe_max) {           // a handful of keys: one WAVE per pair
-    LAUNCH_WIDE(c, "miller_wide_1p", k_miller_wide_1p, np, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
-                (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st);
+    TRY(launch(c, c->stream, "miller_wide_1p", grid_wide(np), k_miller_wide_1p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p,
+               (const uint8_t*)c->prep_ok.p, np,
+               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st));
   } else if (c->tri_miller && np <= c->tri_max) {     // a few thousand pairs: a quad of lanes per pair
-    LAUNCH_TRI(c, "miller_tri_1p", k_miller_tri_1p, np, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
-               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st);
+    TRY(launch(c, c->stream, "miller_tri_1p", grid_tri(np), k_miller_tri_1p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
+               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st));
   } else if (one_per_lane) {
-    LAUNCH(c, "miller_hpk1p", k_miller_hpk1p, np, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
-           (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st);
+    TRY(launch(c, c->stream, "miller_hpk1p", grid_lanes(np), k_miller_hpk1p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
+               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st));
   } else {
-    LAUNCH(c, "miller_hpk2p", k_miller_hpk2p, n_lanes, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
-           (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)st);
+    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p,
+               (const uint8_t*)c->prep_ok.p, np,
+               (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)st));
   }
-  LAUNCH(c, "and_reduce", k_and_reduce, u, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, u, d_ok);
+  TRY(launch(c, c->stream, "and_reduce", grid_lanes(u), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, u, d_ok));
   int32_t* res; size_t rs;
   rc = fp12_tree(c, (int32_t*)c->f_ws.p, f_cnt, f_cnt, &res, &rs);
   if (rc) return rc;
   rc = run_final_exp(c, res, 1, rs, 3, nullptr, nullptr, nullptr, nullptr, d_ok + 4);
   if (rc) return rc;
   int h[5] = {0, 0, 0, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(h, d_ok, 20, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, h, d_ok, 20));
   *valid = (h[0] == 1 && (h[1] & 0xff) == 1 && h[4] == 1) ? 1 : 0;
   ++c->stat_grouped_aggregates;
   return 0;
@@ -276,25 +279,48 @@ int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]) {
   size_t sa = n, cnt = n;
   while (cnt > 1) {
     size_t mo = (cnt + 1) / 2;
-    LAUNCH(c, "g1_add_pairs", k_g1_add_pairs, mo, (const int32_t*)a, cnt, sa, b, mo);
+    TRY(launch(c, c->stream, "g1_add_pairs", grid_lanes(mo), k_g1_add_pairs, (const int32_t*)a, cnt, sa, b, mo));
     std::swap(a, b); sa = mo; cnt = mo;
   }
-  LAUNCH(c, "g1_to_bytes", k_g1_to_bytes, 1, (const int32_t*)a, sa, (uint8_t*)c->out.p);
-  HIPCHK(c, hipMemcpyAsync(out, c->out.p, 64, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  TRY(launch(c, c->stream, "g1_to_bytes", grid_lanes(1), k_g1_to_bytes, (const int32_t*)a, sa, (uint8_t*)c->out.p));
+  return download(c, out, c->out.p, 64);
 }
 int blsbn254_aggregate_sigs(blsbn254_ctx* c, const uint8_t* sigs, size_t n, uint8_t out[64]) {
   if (!c || !out || (n && !sigs)) return BLSBN254_E_ARG;
   if (n == 0) { std::memset(out, 0, 64); out[63] = 1; return 0; }            // empty sum = identity (0, 1)
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(64 * n)); HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, sigs, 64 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "g1_load", k_g1_load, n, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p);
+  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->status.reserve(n));
+  TRY(upload(c, c->in_a, sigs, 64 * n));
+  TRY(launch(c, c->stream, "g1_load", grid_lanes(n), k_g1_load, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_G1;
   return g1_sum_to_bytes(c, n, out);
+}
+// The first half of threshold_combine and lagrange_at_zero: t ids (32 bytes each, the caller's) -> their Lagrange coefficients at
+// zero in c->scalars (t x 32 bytes big-endian) and as GLV halves in c->th_glv, over t x S lanes (S ~ sqrt(t) slices: critical
+// path 2 (t / S + S) products).  Left for the caller: the ids' decode status in c->status[0 .. t) (room for t more bytes behind
+// them), their duplicate marks in c->flags, and two armed "first bad index" words at c->misc.
+static int lagrange_enqueue(blsbn254_ctx* c, const uint8_t* ids, size_t t) {
+  size_t S = 1;
+  while (S < 64 && S * S < t) ++S;
+  const size_t J = (t + S - 1) / S;
+  HIPCHK(c, c->scalars.reserve(32 * t)); HIPCHK(c, c->status.reserve(2 * t)); HIPCHK(c, c->flags.reserve(t)); HIPCHK(c, c->misc.reserve(64));
+  HIPCHK(c, c->th_x.reserve(9 * t * 4)); HIPCHK(c, c->th_num.reserve(9 * t * S * 4)); HIPCHK(c, c->th_den.reserve(9 * t * S * 4)); HIPCHK(c, c->th_glv.reserve(9 * t * 4));
+  uint8_t* dup = (uint8_t*)c->flags.p;
+  TRY(upload(c, c->in_b, ids, 32 * t));
+  TRY(min_index_arm(c, (int*)c->misc.p, 2));
+  HIPCHK(c, hipMemsetAsync(dup, 0, t, c->stream));
+  TRY(launch(c, c->stream, "fr_decode", grid_lanes(t), k_fr_decode, (const uint8_t*)c->in_b.p, t, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
+  TRY(launch(c, c->stream, "lagrange_partial", Shape{dim3(nblocks(t), (unsigned)S), dim3(256)}, k_lagrange_partial, (const int32_t*)c->th_x.p, t, J,
+             (int32_t*)c->th_num.p, (int32_t*)c->th_den.p, dup));
+  return launch(c, c->stream, "lagrange_finish", grid_lanes(t), k_lagrange_finish, (const int32_t*)c->th_num.p, (const int32_t*)c->th_den.p, t, S, (uint8_t*)c->scalars.p,
+                (uint32_t*)c->th_glv.p);
+}
+// ... and the ids' checks, folded into misc[0]: decoded, non-zero (status 1) and pairwise distinct (dup 0)
+static int lagrange_ids_reduce(blsbn254_ctx* c, size_t t) {
+  TRY(launch(c, c->stream, "status_reduce", grid_lanes(t), k_status_reduce, (const uint8_t*)c->status.p, t, (uint8_t)1, (uint8_t)1, (int*)c->misc.p));
+  return launch(c, c->stream, "status_reduce", grid_lanes(t), k_status_reduce, (const uint8_t*)c->flags.p, t, (uint8_t)1, (uint8_t)0, (int*)c->misc.p);
 }
 // Threshold combine (k_threshold.hip): Lagrange coefficients over t x sqrt(t) lanes, GLV-split 4-bit-window MSM over
 // 2t x 32 lanes with in-workgroup sums, one short finishing kernel.  One host synchronisation at the end.
@@ -303,50 +329,28 @@ int blsbn254_threshold_combine(blsbn254_ctx* c, const uint8_t* ids, const uint8_
   if (t == 0) { std::memset(out_sig, 0, 64); out_sig[63] = 1; return 0; }
   CHECK_LANES(c, t);
   ENTER(c);
-  size_t S = 1;
-  while (S < 64 && S * S < t) ++S;                       // ~sqrt(t) slices: t x S lanes, critical path 2 (t / S + S) products
-  const size_t J = (t + S - 1) / S;
   size_t n_chunks = (2 * t + 255) / 256;
-  HIPCHK(c, c->in_a.reserve(64 * t)); HIPCHK(c, c->in_b.reserve(32 * t)); HIPCHK(c, c->scalars.reserve(32 * t));
-  HIPCHK(c, c->status.reserve(2 * t)); HIPCHK(c, c->flags.reserve(t)); HIPCHK(c, c->misc.reserve(64)); HIPCHK(c, c->out.reserve(64));
-  HIPCHK(c, c->th_x.reserve(9 * t * 4)); HIPCHK(c, c->th_num.reserve(9 * t * S * 4)); HIPCHK(c, c->th_den.reserve(9 * t * S * 4));
-  HIPCHK(c, c->th_glv.reserve(9 * t * 4)); HIPCHK(c, c->th_part.reserve(27 * 32 * n_chunks * 4)); HIPCHK(c, c->th_part2.reserve(27 * 32 * ((n_chunks + 1) / 2) * 4));
-  uint8_t* st_ids = (uint8_t*)c->status.p; uint8_t* st_pts = st_ids + t; uint8_t* dup = (uint8_t*)c->flags.p;
+  HIPCHK(c, c->out.reserve(64)); HIPCHK(c, c->th_part.reserve(27 * 32 * n_chunks * 4)); HIPCHK(c, c->th_part2.reserve(27 * 32 * ((n_chunks + 1) / 2) * 4));
+  TRY(upload(c, c->in_a, partial_sigs, 64 * t));
+  TRY(lagrange_enqueue(c, ids, t));
+  uint8_t* st_pts = (uint8_t*)c->status.p + t;
   int* d_bad = (int*)c->misc.p;
-  static const int init[2] = {0x7fffffff, 0x7fffffff};      // static: outlives the asynchronous copy
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, partial_sigs, 64 * t, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, ids, 32 * t, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_bad, init, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(dup, 0, t, c->stream));
-  LAUNCH(c, "fr_decode", k_fr_decode, t, (const uint8_t*)c->in_b.p, t, (int32_t*)c->th_x.p, st_ids);
-  { ProfScope ps_(c, "lagrange_partial");
-    hipLaunchKernelGGL(k_lagrange_partial, dim3(nblocks(t), (unsigned)S), dim3(256), 0, c->stream, (const int32_t*)c->th_x.p, t, J,
-                       (int32_t*)c->th_num.p, (int32_t*)c->th_den.p, dup); }
-  HIPCHK(c, hipGetLastError());
-  LAUNCH(c, "lagrange_finish", k_lagrange_finish, t, (const int32_t*)c->th_num.p, (const int32_t*)c->th_den.p, t, S, (uint8_t*)c->scalars.p, (uint32_t*)c->th_glv.p);
-  { ProfScope ps_(c, "msm_window");
-    hipLaunchKernelGGL(k_msm_window, dim3((unsigned)n_chunks, 32), dim3(256), 0, c->stream, (const uint8_t*)c->in_a.p, (const uint32_t*)c->th_glv.p, t,
-                       (int32_t*)c->th_part.p, st_pts); }
-  HIPCHK(c, hipGetLastError());
+  TRY(launch(c, c->stream, "msm_window", Shape{dim3((unsigned)n_chunks, 32), dim3(256)}, k_msm_window, (const uint8_t*)c->in_a.p, (const uint32_t*)c->th_glv.p, t,
+             (int32_t*)c->th_part.p, st_pts));
   int32_t* pa = (int32_t*)c->th_part.p; int32_t* pb = (int32_t*)c->th_part2.p;
   while (n_chunks > 16) {                                  // large t only: fold the chunk axis pairwise
     const size_t no = (n_chunks + 1) / 2;
-    LAUNCH(c, "msm_fold", k_msm_fold, no * 32, (const int32_t*)pa, n_chunks, pb);
+    TRY(launch(c, c->stream, "msm_fold", grid_lanes(no * 32), k_msm_fold, (const int32_t*)pa, n_chunks, pb));
     std::swap(pa, pb); n_chunks = no;
   }
-  { ProfScope ps_(c, "msm_finish");
-    hipLaunchKernelGGL(k_msm_finish, dim3(1), dim3(64), 0, c->stream, (const int32_t*)pa, n_chunks, (uint8_t*)c->out.p); }
-  HIPCHK(c, hipGetLastError());
-  // ids: decoded, non-zero (status 1) and pairwise distinct (dup 0); points: decoded
-  LAUNCH(c, "status_reduce", k_status_reduce, t, (const uint8_t*)st_ids, t, (uint8_t)1, (uint8_t)1, d_bad);
-  LAUNCH(c, "status_reduce", k_status_reduce, t, (const uint8_t*)dup, t, (uint8_t)1, (uint8_t)0, d_bad);
-  LAUNCH(c, "status_reduce", k_status_reduce, t, (const uint8_t*)st_pts, t, (uint8_t)1, (uint8_t)1, d_bad + 1);
+  TRY(launch(c, c->stream, "msm_finish", Shape{dim3(1), dim3(64)}, k_msm_finish, (const int32_t*)pa, n_chunks, (uint8_t*)c->out.p));
+  TRY(lagrange_ids_reduce(c, t));
+  TRY(launch(c, c->stream, "status_reduce", grid_lanes(t), k_status_reduce, (const uint8_t*)st_pts, t, (uint8_t)1, (uint8_t)1, d_bad + 1));   // points: decoded
   int bad[2];
   HIPCHK(c, hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out_sig, c->out.p, 64, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (bad[0] != 0x7fffffff) return BLSBN254_ERR_SCALAR;
-  if (bad[1] != 0x7fffffff) return BLSBN254_ERR_G1;
+  TRY(download(c, out_sig, c->out.p, 64));
+  if (bad[0] != NO_INDEX) return BLSBN254_ERR_SCALAR;
+  if (bad[1] != NO_INDEX) return BLSBN254_ERR_G1;
   return 0;
 }
 // The Lagrange coefficients at zero alone (t x 32 bytes big-endian), for callers that combine elsewhere and for tests.
@@ -355,32 +359,12 @@ int blsbn254_lagrange_at_zero(blsbn254_ctx* c, const uint8_t* ids, size_t t, uin
   if (t == 0) return 0;
   CHECK_LANES(c, t);
   ENTER(c);
-  size_t S = 1;
-  while (S < 64 && S * S < t) ++S;
-  const size_t J = (t + S - 1) / S;
-  HIPCHK(c, c->in_b.reserve(32 * t)); HIPCHK(c, c->scalars.reserve(32 * t)); HIPCHK(c, c->status.reserve(t)); HIPCHK(c, c->flags.reserve(t));
-  HIPCHK(c, c->misc.reserve(64));
-  HIPCHK(c, c->th_x.reserve(9 * t * 4)); HIPCHK(c, c->th_num.reserve(9 * t * S * 4)); HIPCHK(c, c->th_den.reserve(9 * t * S * 4)); HIPCHK(c, c->th_glv.reserve(9 * t * 4));
-  uint8_t* st_ids = (uint8_t*)c->status.p; uint8_t* dup = (uint8_t*)c->flags.p;
-  int* d_bad = (int*)c->misc.p;
-  const int init = 0x7fffffff;
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, ids, 32 * t, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_bad, &init, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(dup, 0, t, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));             // `init` is on the stack
-  LAUNCH(c, "fr_decode", k_fr_decode, t, (const uint8_t*)c->in_b.p, t, (int32_t*)c->th_x.p, st_ids);
-  { ProfScope ps_(c, "lagrange_partial");
-    hipLaunchKernelGGL(k_lagrange_partial, dim3(nblocks(t), (unsigned)S), dim3(256), 0, c->stream, (const int32_t*)c->th_x.p, t, J,
-                       (int32_t*)c->th_num.p, (int32_t*)c->th_den.p, dup); }
-  HIPCHK(c, hipGetLastError());
-  LAUNCH(c, "lagrange_finish", k_lagrange_finish, t, (const int32_t*)c->th_num.p, (const int32_t*)c->th_den.p, t, S, (uint8_t*)c->scalars.p, (uint32_t*)c->th_glv.p);
-  LAUNCH(c, "status_reduce", k_status_reduce, t, (const uint8_t*)st_ids, t, (uint8_t)1, (uint8_t)1, d_bad);
-  LAUNCH(c, "status_reduce", k_status_reduce, t, (const uint8_t*)dup, t, (uint8_t)1, (uint8_t)0, d_bad);
+  TRY(lagrange_enqueue(c, ids, t));
+  TRY(lagrange_ids_reduce(c, t));
   int bad;
-  HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out, c->scalars.p, 32 * t, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return bad != 0x7fffffff ? BLSBN254_ERR_SCALAR : 0;
+  HIPCHK(c, hipMemcpyAsync(&bad, c->misc.p, 4, hipMemcpyDeviceToHost, c->stream));
+  TRY(download(c, out, c->scalars.p, 32 * t));
+  return bad != NO_INDEX ? BLSBN254_ERR_SCALAR : 0;
 }
 
 

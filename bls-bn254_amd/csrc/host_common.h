@@ -1,4 +1,4 @@
-// host_common.h -- shared by the host-side translation units (host*.hip): the context, device buffers, launch macros and the
+// host_common.h -- shared by the host-side translation units (host*.hip): the context, device buffers, the launch helper and the
 // internal helpers one pipeline borrows from another.  Nothing here is exported (BNH = hidden visibility); the C ABI is
 // include/blsbn254.h.  There is no CPU fallback anywhere on the host side: every entry point launches kernels or fails.
 #pragma once
@@ -19,9 +19,17 @@
 
 using namespace bn;
 
+#define BNH __attribute__((visibility("hidden")))     // nothing of the host side is exported but the C ABI
+
 // ------------------------------------------------------------------ host side
-struct DevBuf {
+// A device allocation that grows on demand and frees itself: a DevBuf member of the context (or of a prepared-key table) needs
+// no entry in any release list.  Not copyable.  Whoever destroys the owner first makes sure no stream still runs work on it.
+struct BNH DevBuf {
   void* p = nullptr; size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -31,21 +39,16 @@ struct DevBuf {
     if (e == hipSuccess) cap = want;
     return e;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 // multi-scalar multiplication (host_msm.hip, k_msm_bucket.hip): point rows, bucket entries, sorted entries, bucket counts and ends,
 // the levels' partial sums (ping-pong), the bucket sums, the window segments, the device-side counters; reserved for the largest call
-struct MsmWs {
-  DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, stat;
-  void release() { DevBuf* b[] = {&pts, &key, &val, &sorted, &hist, &end, &part[0], &part[1], &bsum, &seg, &stat}; for (DevBuf* x : b) x->release(); }
-};
+struct BNH MsmWs { DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, stat; };
 // pairing-product equations (host_pairing_check.hip, k_pairing_check.hip): per-equation products (limb-major, stride n_eq) and
 // validity, per-pair validity of a launch, the product levels (ping-pong) with their flags, the chunk descriptors (device and
 // the host copies they are uploaded from)
-struct PcWs {
+struct BNH PcWs {
   DevBuf prod, ok, pair_ok, seg[2], seg_ok[2], start, len;
   std::vector<uint32_t> h_start, h_len;
-  void release() { DevBuf* b[] = {&prod, &ok, &pair_ok, &seg[0], &seg[1], &seg_ok[0], &seg_ok[1], &start, &len}; for (DevBuf* x : b) x->release(); }
 };
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
@@ -118,46 +121,53 @@ struct blsbn254_ctx {
 #define HIPCHK(ctx, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { (ctx)->last_error = std::string(#x) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? BLSBN254_E_NOMEM : BLSBN254_E_HIP; } } while (0)
 
-static inline unsigned nblocks(size_t n) { return (unsigned)((n + 255) / 256); }
+// TRY(f(...)): a non-zero return code of f leaves the calling function, as ONE statement
+#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
-struct ProfScope {
-  blsbn254_ctx* c; const char* name; hipEvent_t e0 = nullptr, e1 = nullptr;
-  ProfScope(blsbn254_ctx* c_, const char* n) : c(c_), name(n) {
-    if (c->profiling) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, c->stream); }
+static inline unsigned nblocks(size_t n) { return (unsigned)((n + 255) / 256); }
+// Launch shapes, named where they are decided (a 2-D grid is written out as Shape{dim3(x, y), dim3(256)}):
+struct Shape { dim3 grid, block; };
+static inline Shape grid_lanes(size_t n) { return {dim3(nblocks(n)), dim3(256)}; }                   // one lane per element
+static inline Shape grid_tri(size_t n) { return {dim3((unsigned)((n + 63) / 64)), dim3(256)}; }      // four lanes per element (tri.h): 256-lane workgroups of 64 elements
+static inline Shape grid_wide(size_t n) { return {dim3((unsigned)n), dim3(128)}; }                   // two waves (wide.h: WIDE_LANES = 128) per element: the wave-per-tuple kernels
+static const size_t TRI_VALUE_LIMBS = 20 * 108;      // tri.h TRI_VALUES x 108
+
+// One timed launch of the profile (blsbn254_profile_read): an event pair around it on the stream it runs on.  name == nullptr: not profiled.
+struct BNH ProfScope {
+  blsbn254_ctx* c; hipStream_t s; const char* name; hipEvent_t e0 = nullptr, e1 = nullptr;
+  ProfScope(blsbn254_ctx* c_, hipStream_t s_, const char* n) : c(c_), s(s_), name(c_->profiling ? n : nullptr) {
+    if (name) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, s); }
   }
   ~ProfScope() {
-    if (c->profiling) { (void)hipEventRecord(e1, c->stream); ProfEntry& p = c->prof[name]; ++p.launches; p.pending.emplace_back(e0, e1); }
+    if (name) { (void)hipEventRecord(e1, s); ProfEntry& p = c->prof[name]; ++p.launches; p.pending.emplace_back(e0, e1); }
   }
 };
-#define LAUNCH(ctx, name, kernel, n, ...) do { ProfScope ps_(ctx, name); \
-    hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, (ctx)->stream, __VA_ARGS__); } while (0); HIPCHK(ctx, hipGetLastError())
-
-// four lanes per element (tri.h): 256-lane workgroups of 64 elements
-#define LAUNCH_TRI(ctx, name, kernel, n, ...) do { ProfScope ps_(ctx, name); \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(((n) + 63) / 64)), dim3(256), 0, (ctx)->stream, __VA_ARGS__); } while (0); HIPCHK(ctx, hipGetLastError())
-static const size_t TRI_VALUE_LIMBS = 20 * 108;      // tri.h TRI_VALUES x 108
-// G2Prepared::from for u keys (decode, on-curve, psi subgroup test, 88 line triples): four lanes per key (k_keyprep_quad.hip, half
-// the latency) while the 8 u lanes fit one round of waves, else one lane per key (k_keyprep.hip).  L = LAUNCH or LAUNCH2.
-#define LAUNCH_G2_PREPARE(ctx, L, pks, keys, u, raw, ok, d_u) do { \
-    if ((ctx)->quad_prep && 8 * (size_t)(u) <= (ctx)->lanes_per_round) { L(ctx, "g2_prepare", k_g2_prepare_quad, 2 * 256 * (size_t)nblocks(4 * (size_t)(u)), pks, keys, (uint32_t)(u), raw, ok, d_u); } \
-    else { L(ctx, "g2_prepare", k_g2_prepare, 2 * 256 * (size_t)nblocks(u), pks, keys, (uint32_t)(u), raw, ok, d_u); } } while (0)
-
-// one workgroup of 128 lanes (two waves) per element: the wave-per-tuple kernels (wide.h)
-#define LAUNCH_WIDE(ctx, name, kernel, n, ...) do { ProfScope ps_(ctx, name); \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(n)), dim3(128), 0, (ctx)->stream, __VA_ARGS__); } while (0); HIPCHK(ctx, hipGetLastError())      /* wide.h: WIDE_LANES */
-
-// the same on the context's second stream (events recorded there)
-struct ProfScope2 {
-  blsbn254_ctx* c; const char* name; hipEvent_t e0 = nullptr, e1 = nullptr;
-  ProfScope2(blsbn254_ctx* c_, const char* n) : c(c_), name(n) {
-    if (c->profiling) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, c->stream2); }
-  }
-  ~ProfScope2() {
-    if (c->profiling) { (void)hipEventRecord(e1, c->stream2); ProfEntry& p = c->prof[name]; ++p.launches; p.pending.emplace_back(e0, e1); }
-  }
-};
-#define LAUNCH2(ctx, name, kernel, n, ...) do { ProfScope2 ps_(ctx, name); \
-    hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, (ctx)->stream2, __VA_ARGS__); } while (0); HIPCHK(ctx, hipGetLastError())
+// THE way a kernel is launched on the host side: on stream s of the context, counted under `name`; 0 or the project's error code
+template <typename... P, typename... A>
+static inline int launch(blsbn254_ctx* c, hipStream_t s, const char* name, Shape g, void (*kernel)(P...), A... args) {
+  { ProfScope ps(c, s, name); hipLaunchKernelGGL(kernel, g.grid, g.block, 0, s, args...); }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// reserve, then copy host -> device on the main stream (the source must outlive the copy: the caller's, or ctx-owned / static)
+static inline int upload(blsbn254_ctx* c, DevBuf& b, const void* src, size_t bytes) {
+  HIPCHK(c, b.reserve(bytes));
+  HIPCHK(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+// copy device -> host behind everything enqueued on the main stream, and wait for it
+static inline int download(blsbn254_ctx* c, void* dst, const void* src, size_t bytes) {
+  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+// body(lo, m) for every launch chunk [lo, lo + m) of n independent elements (ctx->chunk each, the last one shorter); stops at the
+// first non-zero return code.  Chunk starts are multiples of 8: bitmap bytes do not straddle chunks.
+template <typename F>
+static inline int for_chunks(const blsbn254_ctx* c, size_t n, F body) {
+  for (size_t lo = 0; lo < n; lo += c->chunk) TRY(body(lo, std::min(n - lo, c->chunk)));
+  return 0;
+}
 
 // Work forked onto stream2 must never outlive a failing call: a function that forks holds one of these, and an early
 // error return (before the main stream has waited for ev_join) then waits for stream2 on the way out, so nothing is
@@ -179,14 +189,13 @@ static inline hipError_t join_stream2(blsbn254_ctx* c) {
   return e;
 }
 
-#define BNH __attribute__((visibility("hidden")))
 extern "C" {
 // every entry point: select the device, then settle what the asynchronous verify path left open (read back its checks, re-run a
 // batch whose optimistic choice did not hold) -- results of earlier calls are final before this call touches the context
 BNH int resolve_pending(blsbn254_ctx* c, bool blocking);   // host_verify.hip
 BNH int blsbn254_internal_verify_batch_dev_sync(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                                                 const uint8_t* d_sigs, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap);   // host_verify.hip
-#define ENTER(c) do { HIPCHK(c, hipSetDevice((c)->device)); if ((c)->pend_count) { int rc_ = resolve_pending(c, true); if (rc_) return rc_; } } while (0)
+#define ENTER(c) do { HIPCHK(c, hipSetDevice((c)->device)); if ((c)->pend_count) TRY(resolve_pending(c, true)); } while (0)
 extern BNH const uint8_t NEG_G2_BYTES[128];     // -G2gen = (x, p - y) of the generator fp2.rs:305-333, as bytes (host.hip)
 
 // The kernels address limb-major workspaces through a buffer descriptor with a 32-bit scalar byte offset
@@ -203,17 +212,26 @@ struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok;
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip
 BNH int check_offsets(const uint64_t* off, size_t n);   // host.hip
+// "The minimum index that fails, or none": k_status_reduce / k_kd_hist fold failing indices with atomicMin into an int that starts
+// at NO_INDEX.  min_index_arm enqueues that start value for `words` (<= 2) ints at d, from a static source; min_index_read copies
+// one back, waits, and reports -1 for none.
+static const int NO_INDEX = 0x7fffffff;
+BNH int min_index_arm(blsbn254_ctx* c, int* d, size_t words);   // host.hip
+BNH int min_index_read(blsbn254_ctx* c, const int* d, int* out);   // host.hip
 BNH int first_bad(blsbn254_ctx* c, const uint8_t* d_status, size_t n, uint8_t mask, uint8_t val, int* out);   // host.hip
 BNH int read_status(blsbn254_ctx* c, const uint8_t* d_status, int idx, uint8_t* st);   // host.hip
 BNH int run_final_exp(blsbn254_ctx* c, int32_t* f, size_t n, size_t stride, int mode, const uint8_t* flags, const uint8_t* sub_ok,
                          uint8_t* d_bitmap, uint8_t* d_gt, int* d_is_one);   // host.hip
 BNH int miller_to_ws(blsbn254_ctx* c, const uint8_t* d_g1, const uint8_t* d_g2, size_t n);   // host.hip
 BNH int decode_status_rc(blsbn254_ctx* c, const uint8_t* d_status, size_t n);   // host.hip
-BNH int product_tree(blsbn254_ctx* c, size_t n, const int32_t** result, size_t* rs);   // host.hip
 BNH int stage_msgs(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off, size_t n);   // host.hip
+BNH int launch_g2_prepare(blsbn254_ctx* c, hipStream_t s, const uint8_t* pks, const uint32_t* keys, size_t u, int32_t* raw, uint8_t* ok, const uint32_t* d_u);   // host_verify.hip
 BNH int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_keys, size_t u, int32_t* table, uint8_t* key_ok, const uint32_t* d_u);   // host_verify.hip
 BNH int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* key_ok, size_t u, const uint32_t* d_kid, bool hist_done,
                                const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join);   // host_verify.hip
+BNH int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u, uint32_t* hist, const char* what, bool armed);   // host_verify.hip
+BNH int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
+                               const int32_t* table, const uint8_t* key_ok, size_t n);   // host_verify.hip
 BNH int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out);   // host_verify.hip
 BNH int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
@@ -226,4 +244,20 @@ BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* ki
                           size_t cnt, uint8_t* d_isone);   // host_rlc.hip
 BNH int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res, size_t* rs);   // host_aggregate.hip
 BNH int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]);   // host_aggregate.hip
+
+// A launch of n tuples is small enough that the prepared-key path wins whatever its keys: with line tables the Miller loop (and
+// the final exponentiation) can run one WAVE per tuple (wide.h) or, up to tri_max, three lanes per tuple (k_tri.hip) instead of
+// at the latency of one lane.  per_tuple_fe: the launch also runs a final exponentiation per tuple, so the three-lane form only
+// pays when that half is enabled too (the grouped aggregate verify runs ONE final exponentiation and passes false).
+static inline bool small_for_prepared(const blsbn254_ctx* c, size_t n, bool per_tuple_fe) {
+  return (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && (c->tri_fe || !per_tuple_fe) && n <= c->tri_max);
+}
+
+// Level planner of the segmented reductions (k_g2_seg_sum, k_fp12_seg_prod).  cur[0..ne] are the boundaries of ne segments of
+// items: every segment is cut into runs of at most G items, one (start, len) descriptor per run (an empty segment: ONE empty run),
+// the runs are the next level's items, and so on until there is one run per segment.  Descriptors are appended to start / len,
+// one {first descriptor, count} per level to `levels`; `cur` is consumed.  `what` names the reduction in the (internal) error.
+struct SegLevel { size_t first, count; };
+BNH int plan_seg_levels(blsbn254_ctx* c, std::vector<uint64_t>& cur, size_t G, std::vector<uint32_t>& start, std::vector<uint32_t>& len,
+                        std::vector<SegLevel>& levels, const char* what);   // host_groupops.hip
 }  // extern "C"

@@ -11,30 +11,46 @@ static int mul_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalar
   if (n == 0) return 0;
   ENTER(c);
   const size_t sz = g2 ? 128 : 64;
-  for (size_t lo = 0; lo < n; lo += c->chunk) {
-    const size_t m = n - lo < c->chunk ? n - lo : c->chunk;
-    HIPCHK(c, c->in_a.reserve(sz * m)); HIPCHK(c, c->scalars.reserve(32 * m)); HIPCHK(c, c->out.reserve(sz * m)); HIPCHK(c, c->status.reserve(m));
-    HIPCHK(c, hipMemcpyAsync(c->in_a.p, pts + sz * lo, sz * m, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->scalars.p, scalars + 32 * lo, 32 * m, hipMemcpyHostToDevice, c->stream));
-    if (g2) { LAUNCH(c, "g2_mul", k_g2_mul, m, (const uint8_t*)c->in_a.p, (const uint8_t*)c->scalars.p, m, (uint8_t*)c->out.p, (uint8_t*)c->status.p); }
-    else { LAUNCH(c, "g1_mul", k_g1_mul, m, (const uint8_t*)c->in_a.p, (const uint8_t*)c->scalars.p, m, (uint8_t*)c->out.p, (uint8_t*)c->status.p); }
+  return for_chunks(c, n, [&](size_t lo, size_t m) -> int {
+    HIPCHK(c, c->out.reserve(sz * m)); HIPCHK(c, c->status.reserve(m));
+    TRY(upload(c, c->in_a, pts + sz * lo, sz * m));
+    TRY(upload(c, c->scalars, scalars + 32 * lo, 32 * m));
+    if (g2) TRY(launch(c, c->stream, "g2_mul", grid_lanes(m), k_g2_mul, (const uint8_t*)c->in_a.p, (const uint8_t*)c->scalars.p, m, (uint8_t*)c->out.p, (uint8_t*)c->status.p));
+    else TRY(launch(c, c->stream, "g1_mul", grid_lanes(m), k_g1_mul, (const uint8_t*)c->in_a.p, (const uint8_t*)c->scalars.p, m, (uint8_t*)c->out.p, (uint8_t*)c->status.p));
     int bad;
-    int rc = first_bad(c, (const uint8_t*)c->status.p, m, 3, 3, &bad);
-    if (rc) return rc;
+    TRY(first_bad(c, (const uint8_t*)c->status.p, m, 3, 3, &bad));
     if (bad >= 0) {
       uint8_t st = 0;
-      rc = read_status(c, (const uint8_t*)c->status.p, bad, &st);
-      if (rc) return rc;
+      TRY(read_status(c, (const uint8_t*)c->status.p, bad, &st));
       c->last_error = std::string(st & 1 ? "scalar not canonical" : "point does not decode or is off the curve") + " at element " + std::to_string(lo + (size_t)bad);
       return (st & 1) ? BLSBN254_ERR_SCALAR : (g2 ? BLSBN254_ERR_G2 : BLSBN254_ERR_G1);
     }
-    HIPCHK(c, hipMemcpyAsync(out + sz * lo, c->out.p, sz * m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return 0;
+    return download(c, out + sz * lo, c->out.p, sz * m);
+  });
 }
 int blsbn254_g1_mul_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* scalars, size_t n, uint8_t* out) { return mul_common(c, g1, scalars, n, out, 0); }
 int blsbn254_g2_mul_batch(blsbn254_ctx* c, const uint8_t* g2, const uint8_t* scalars, size_t n, uint8_t* out) { return mul_common(c, g2, scalars, n, out, 1); }
+
+int plan_seg_levels(blsbn254_ctx* c, std::vector<uint64_t>& cur, size_t G, std::vector<uint32_t>& start, std::vector<uint32_t>& len,
+                    std::vector<SegLevel>& levels, const char* what) {
+  const size_t ne = cur.size() - 1;
+  std::vector<uint64_t> nxt(ne + 1);
+  for (int level = 0; ; ++level) {
+    if (level > 40) { c->last_error = what; return BLSBN254_E_HIP; }
+    const size_t first = start.size();
+    for (size_t e = 0; e < ne; ++e) {
+      const uint64_t a = cur[e], b = cur[e + 1];
+      nxt[e] = start.size() - first;
+      if (a == b) { start.push_back((uint32_t)a); len.push_back(0); }            // empty segment: one empty run (identity, flag 0)
+      for (uint64_t s = a; s < b; s += G) { start.push_back((uint32_t)s); len.push_back((uint32_t)std::min<uint64_t>(b - s, G)); }
+    }
+    const size_t m = start.size() - first;
+    nxt[ne] = m;
+    levels.push_back({first, m});
+    if (m == ne) return 0;
+    cur.swap(nxt);
+  }
+}
 
 // Segmented sums of G2 points: n points already staged at d_pks, groups [goff[g], goff[g + 1]).  Level by level every group is
 // cut into chunks of at most G2_SUM_GROUP items, one lane sums a chunk, and the chunk sums (group-major order) are the next
@@ -44,41 +60,26 @@ static const size_t G2_SUM_GROUP = 16;
 static int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups, const int32_t** sum_ws, const uint8_t** sum_ok) {
   const size_t G = G2_SUM_GROUP;
   // chunk descriptors of ALL levels first (host arithmetic on the offsets), uploaded in one copy: no synchronisation between levels
-  std::vector<uint64_t> cur(goff, goff + n_groups + 1), nxt(n_groups + 1);
+  std::vector<uint64_t> cur(goff, goff + n_groups + 1);
   for (size_t g = 0; g <= n_groups; ++g) cur[g] -= goff[0];
   std::vector<uint32_t> start, len;
-  std::vector<size_t> level_first, level_count;
-  for (int level = 0; ; ++level) {
-    if (level > 40) { c->last_error = "internal: group sums do not converge"; return BLSBN254_E_HIP; }
-    const size_t first = start.size();
-    for (size_t g = 0; g < n_groups; ++g) {
-      const uint64_t a = cur[g], b = cur[g + 1];
-      nxt[g] = start.size() - first;
-      if (a == b) { start.push_back((uint32_t)a); len.push_back(0); }          // empty group: one empty chunk (identity, flag 0)
-      for (uint64_t s = a; s < b; s += G) { start.push_back((uint32_t)s); len.push_back((uint32_t)(b - s < G ? b - s : G)); }
-    }
-    const size_t m = start.size() - first;
-    nxt[n_groups] = m;
-    level_first.push_back(first); level_count.push_back(m);
-    cur.swap(nxt);
-    if (m == n_groups) break;
-  }
-  const size_t total = start.size(), m_max = level_count[0];
+  std::vector<SegLevel> levels;
+  TRY(plan_seg_levels(c, cur, G, start, len, levels, "internal: group sums do not converge"));
+  const size_t total = start.size(), m_max = levels[0].count;
   // ping-pong workspaces: the level-0 items (n) and the largest chunk array (the first level's)
   HIPCHK(c, c->gs_ws[0].reserve((n ? n : 1) * 54 * 4)); HIPCHK(c, c->gs_ok[0].reserve(n ? n : 1));
   HIPCHK(c, c->gs_ws[1].reserve(m_max * 54 * 4)); HIPCHK(c, c->gs_ok[1].reserve(m_max));
   HIPCHK(c, c->gs_ws[2].reserve(m_max * 54 * 4)); HIPCHK(c, c->gs_ok[2].reserve(m_max));
-  HIPCHK(c, c->gs_start.reserve(4 * total)); HIPCHK(c, c->gs_len.reserve(4 * total));
-  HIPCHK(c, hipMemcpyAsync(c->gs_start.p, start.data(), 4 * total, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->gs_len.p, len.data(), 4 * total, hipMemcpyHostToDevice, c->stream));
-  if (n) { LAUNCH(c, "g2_load", k_g2_load, n, d_pks, n, (int32_t*)c->gs_ws[0].p, (uint8_t*)c->gs_ok[0].p); }
+  TRY(upload(c, c->gs_start, start.data(), 4 * total));
+  TRY(upload(c, c->gs_len, len.data(), 4 * total));
+  if (n) TRY(launch(c, c->stream, "g2_load", grid_lanes(n), k_g2_load, d_pks, n, (int32_t*)c->gs_ws[0].p, (uint8_t*)c->gs_ok[0].p));
   int src = 0;
   size_t items = n;
-  for (size_t lv = 0; lv < level_count.size(); ++lv) {
-    const size_t m = level_count[lv];
+  for (const SegLevel& L : levels) {
+    const size_t m = L.count;
     const int dst = src == 1 ? 2 : 1;
-    LAUNCH(c, "g2_seg_sum", k_g2_seg_sum, m, (const int32_t*)c->gs_ws[src].p, items ? items : 1, (const uint8_t*)c->gs_ok[src].p,
-           (const uint32_t*)c->gs_start.p + level_first[lv], (const uint32_t*)c->gs_len.p + level_first[lv], m, (int32_t*)c->gs_ws[dst].p, m, (uint8_t*)c->gs_ok[dst].p);
+    TRY(launch(c, c->stream, "g2_seg_sum", grid_lanes(m), k_g2_seg_sum, (const int32_t*)c->gs_ws[src].p, items ? items : 1, (const uint8_t*)c->gs_ok[src].p,
+               (const uint32_t*)c->gs_start.p + L.first, (const uint32_t*)c->gs_len.p + L.first, m, (int32_t*)c->gs_ws[dst].p, m, (uint8_t*)c->gs_ok[dst].p));
     src = dst; items = m;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));                                   // `start` / `len` go out of scope
@@ -92,17 +93,16 @@ int blsbn254_aggregate_pks(blsbn254_ctx* c, const uint8_t* pks, size_t n, uint8_
   if (n == 0) { std::memset(out, 0, 128); out[127] = 1; return 0; }             // G2Affine::identity: x = 0, y = 1
   if (n > ((size_t)1 << 26)) { c->last_error = "more than 2^26 points in one sum"; return BLSBN254_E_ARG; }
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(128 * n)); HIPCHK(c, c->out.reserve(128));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->out.reserve(128));
+  TRY(upload(c, c->in_a, pks, 128 * n));
   const uint64_t goff[2] = {0, (uint64_t)n};
   const int32_t* ws; const uint8_t* ok;
   int rc = g2_group_sums(c, (const uint8_t*)c->in_a.p, n, goff, 1, &ws, &ok);
   if (rc) return rc;
   uint8_t good = 0;
-  LAUNCH(c, "g2p_to_bytes", k_g2p_to_bytes, 1, ws, (size_t)1, ok, (size_t)1, (uint8_t*)c->out.p, 0);
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(1), k_g2p_to_bytes, ws, (size_t)1, ok, (size_t)1, (uint8_t*)c->out.p, 0));
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, 128, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&good, ok, 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, &good, ok, 1));
   if (!good) { c->last_error = "a point does not decode or is off the curve"; return BLSBN254_ERR_G2; }
   return 0;
 }
@@ -125,20 +125,18 @@ int blsbn254_fast_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, co
   rc = stage_msgs(c, msgs, off, n_groups);
   if (rc) return rc;
   const size_t nb = (n_groups + 7) / 8;
-  HIPCHK(c, c->in_a.reserve(128 * (n_keys ? n_keys : 1))); HIPCHK(c, c->in_b.reserve(64 * n_groups)); HIPCHK(c, c->gs_pk.reserve(128 * n_groups));
+  HIPCHK(c, c->in_a.reserve(128 * (n_keys ? n_keys : 1))); HIPCHK(c, c->gs_pk.reserve(128 * n_groups));
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   if (n_keys) HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks + 128 * (size_t)key_off[0], 128 * n_keys, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, sigs, 64 * n_groups, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->in_b, sigs, 64 * n_groups));
   const int32_t* ws; const uint8_t* ok;
   rc = g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, key_off, n_groups, &ws, &ok);
   if (rc) return rc;
-  LAUNCH(c, "g2p_to_bytes", k_g2p_to_bytes, n_groups, ws, n_groups, ok, n_groups, (uint8_t*)c->gs_pk.p, 1);
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, ws, n_groups, ok, n_groups, (uint8_t*)c->gs_pk.p, 1));
   rc = verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
                         (uint8_t*)c->bitmap.p);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, valid_bitmap, c->bitmap.p, nb);
 }
 int blsbn254_fast_aggregate_verify(blsbn254_ctx* c, const uint8_t* pks, size_t n, const uint8_t* msg, size_t msg_len, const uint8_t sig[64],
                                    const uint8_t* dst, size_t dst_len, int* valid) {

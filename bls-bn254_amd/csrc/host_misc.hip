@@ -13,18 +13,16 @@ int blsbn254_field_op_batch(blsbn254_ctx* c, int op, const uint8_t* a, const uin
   if (n == 0) return 0;
   ENTER(c);
   const bool bin = field_op_binary(op);
-  HIPCHK(c, c->in_a.reserve(w * n)); HIPCHK(c, c->out.reserve(w * n)); HIPCHK(c, c->status.reserve(n));
+  HIPCHK(c, c->out.reserve(w * n)); HIPCHK(c, c->status.reserve(n));
   if (bin) HIPCHK(c, c->in_b.reserve(w * n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, a, w * n, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->in_a, a, w * n));
   if (bin) HIPCHK(c, hipMemcpyAsync(c->in_b.p, b, w * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "field_op", k_field_op, n, op, (const uint8_t*)c->in_a.p, bin ? (const uint8_t*)c->in_b.p : (const uint8_t*)nullptr, n,
-         (uint8_t*)c->out.p, (uint8_t*)c->status.p);
+  TRY(launch(c, c->stream, "field_op", grid_lanes(n), k_field_op, op, (const uint8_t*)c->in_a.p, bin ? (const uint8_t*)c->in_b.p : (const uint8_t*)nullptr, n,
+             (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_GT;
-  HIPCHK(c, hipMemcpyAsync(out, c->out.p, w * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->out.p, w * n);
 }
 int blsbn254_gt_mul_batch(blsbn254_ctx* c, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
   return blsbn254_field_op_batch(c, BLSBN254_OP_FP12_MUL, a, b, n, out);
@@ -33,16 +31,14 @@ int blsbn254_gt_pow_batch(blsbn254_ctx* c, const uint8_t* gt, const uint8_t* sca
   if (!c || (n && (!gt || !scalars || !out))) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(384 * n)); HIPCHK(c, c->in_b.reserve(32 * n)); HIPCHK(c, c->out.reserve(384 * n)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, gt, 384 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, scalars, 32 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "gt_pow", k_gt_pow, n, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p);
+  HIPCHK(c, c->out.reserve(384 * n)); HIPCHK(c, c->status.reserve(n));
+  TRY(upload(c, c->in_a, gt, 384 * n));
+  TRY(upload(c, c->in_b, scalars, 32 * n));
+  TRY(launch(c, c->stream, "gt_pow", grid_lanes(n), k_gt_pow, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_GT;
-  HIPCHK(c, hipMemcpyAsync(out, c->out.p, 384 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->out.p, 384 * n);
 }
 
 // ---------------- compressed codecs
@@ -52,16 +48,14 @@ static int codec_common(blsbn254_ctx* c, const uint8_t* in, size_t n, uint8_t* o
   ENTER(c);
   size_t full = g2 ? 128 : 64, comp = full / 2;
   size_t isz = mode == 0 ? full : comp, osz = mode == 0 ? comp : full;
-  HIPCHK(c, c->in_a.reserve(isz * n)); HIPCHK(c, c->out.reserve(osz * n)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, in, isz * n, hipMemcpyHostToDevice, c->stream));
-  if (g2) { LAUNCH(c, "g2_codec", k_g2_codec, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p, mode); }
-  else { LAUNCH(c, "g1_codec", k_g1_codec, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p, mode); }
+  HIPCHK(c, c->out.reserve(osz * n)); HIPCHK(c, c->status.reserve(n));
+  TRY(upload(c, c->in_a, in, isz * n));
+  if (g2) TRY(launch(c, c->stream, "g2_codec", grid_lanes(n), k_g2_codec, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p, mode));
+  else TRY(launch(c, c->stream, "g1_codec", grid_lanes(n), k_g1_codec, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p, mode));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return g2 ? BLSBN254_ERR_G2 : BLSBN254_ERR_G1;
-  HIPCHK(c, hipMemcpyAsync(out, c->out.p, osz * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, out, c->out.p, osz * n);
 }
 int blsbn254_g1_compress_batch(blsbn254_ctx* c, const uint8_t* g1, size_t n, uint8_t* out) { return codec_common(c, g1, n, out, 0, 0); }
 int blsbn254_g1_decompress_batch(blsbn254_ctx* c, const uint8_t* in, size_t n, uint8_t* g1) { return codec_common(c, in, n, g1, 0, 1); }
@@ -78,10 +72,10 @@ int blsbn254_sign_batch(blsbn254_ctx* c, const uint8_t* sks, const uint8_t* msgs
   if (rc) return rc;
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
-  HIPCHK(c, c->in_a.reserve(32 * n)); HIPCHK(c, c->out.reserve(64 * n)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, sks, 32 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "sign", k_sign, n, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-         (uint8_t*)c->out.p, (uint8_t*)c->status.p);
+  HIPCHK(c, c->out.reserve(64 * n)); HIPCHK(c, c->status.reserve(n));
+  TRY(upload(c, c->in_a, sks, 32 * n));
+  TRY(launch(c, c->stream, "sign", grid_lanes(n), k_sign, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
+             (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_SCALAR;
@@ -94,9 +88,9 @@ int blsbn254_sk_to_pk_batch(blsbn254_ctx* c, const uint8_t* sks, size_t n, uint8
   if (!c || (n && (!sks || !pks_out))) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(32 * n)); HIPCHK(c, c->out.reserve(128 * n)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, sks, 32 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "sk_to_pk", k_sk_to_pk, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p);
+  HIPCHK(c, c->out.reserve(128 * n)); HIPCHK(c, c->status.reserve(n));
+  TRY(upload(c, c->in_a, sks, 32 * n));
+  TRY(launch(c, c->stream, "sk_to_pk", grid_lanes(n), k_sk_to_pk, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_SCALAR;
@@ -112,12 +106,12 @@ int blsbn254_keygen_batch(blsbn254_ctx* c, const uint8_t* ikm, size_t ikm_len, s
   if (!c || ikm_len < 32 || (n && (!ikm || !sks_out)) || (key_info_len && !key_info)) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  HIPCHK(c, c->in_a.reserve(ikm_len * n)); HIPCHK(c, c->in_c.reserve(key_info_len + 1));
+  HIPCHK(c, c->in_c.reserve(key_info_len + 1));
   HIPCHK(c, c->out.reserve(32 * n)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, ikm, ikm_len * n, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->in_a, ikm, ikm_len * n));
   if (key_info_len) HIPCHK(c, hipMemcpyAsync(c->in_c.p, key_info, key_info_len, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "keygen", k_keygen, n, (const uint8_t*)c->in_a.p, ikm_len, n, (const uint8_t*)c->in_c.p, key_info_len,
-         (uint8_t*)c->out.p, (uint8_t*)c->status.p);
+  TRY(launch(c, c->stream, "keygen", grid_lanes(n), k_keygen, (const uint8_t*)c->in_a.p, ikm_len, n, (const uint8_t*)c->in_c.p, key_info_len,
+             (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_SCALAR;
@@ -137,11 +131,9 @@ int blsbn254_hash_to_scalar_batch(blsbn254_ctx* c, const uint8_t* msgs, const ui
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   HIPCHK(c, c->out.reserve(32 * n));
-  LAUNCH(c, "hash_to_scalar", k_hash_to_scalar, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-         (uint8_t*)c->out.p);
-  HIPCHK(c, hipMemcpyAsync(out, c->out.p, 32 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  TRY(launch(c, c->stream, "hash_to_scalar", grid_lanes(n), k_hash_to_scalar, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
+             (uint8_t*)c->out.p));
+  return download(c, out, c->out.p, 32 * n);
 }
 int blsbn254_pop_prove_batch(blsbn254_ctx* c, const uint8_t* sks, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* proofs_out) {
   if (!c || (n && (!sks || !proofs_out)) || (dst_len && !dst)) return BLSBN254_E_ARG;
@@ -149,13 +141,13 @@ int blsbn254_pop_prove_batch(blsbn254_ctx* c, const uint8_t* sks, size_t n, cons
   ENTER(c);
   uint32_t dl; int rc = stage_dst(c, dst, dst_len, &dl);
   if (rc) return rc;
-  HIPCHK(c, c->in_a.reserve(32 * n)); HIPCHK(c, c->in_c.reserve(128 * n)); HIPCHK(c, c->in_off.reserve(8 * (n + 1)));
+  HIPCHK(c, c->in_c.reserve(128 * n)); HIPCHK(c, c->in_off.reserve(8 * (n + 1)));
   HIPCHK(c, c->out.reserve(64 * n)); HIPCHK(c, c->status.reserve(n));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, sks, 32 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "sk_to_pk", k_sk_to_pk, n, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->in_c.p, (uint8_t*)c->status.p);
-  LAUNCH(c, "iota_off", k_iota_off, n + 1, (uint64_t*)c->in_off.p, n, (uint64_t)128);
-  LAUNCH(c, "sign", k_sign, n, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-         (uint8_t*)c->out.p, (uint8_t*)c->status.p);
+  TRY(upload(c, c->in_a, sks, 32 * n));
+  TRY(launch(c, c->stream, "sk_to_pk", grid_lanes(n), k_sk_to_pk, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->in_c.p, (uint8_t*)c->status.p));
+  TRY(launch(c, c->stream, "iota_off", grid_lanes(n + 1), k_iota_off, (uint64_t*)c->in_off.p, n, (uint64_t)128));
+  TRY(launch(c, c->stream, "sign", grid_lanes(n), k_sign, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
+             (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_SCALAR;
@@ -170,17 +162,15 @@ int blsbn254_pop_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   if (n == 0) return 0;
   ENTER(c);
   size_t nb = (n + 7) / 8;
-  HIPCHK(c, c->in_a.reserve(128 * n)); HIPCHK(c, c->in_b.reserve(64 * n)); HIPCHK(c, c->in_off.reserve(8 * (n + 1)));
+  HIPCHK(c, c->in_off.reserve(8 * (n + 1)));
   HIPCHK(c, c->bitmap.reserve(nb + 8));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, proofs, 64 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "iota_off", k_iota_off, n + 1, (uint64_t*)c->in_off.p, n, (uint64_t)128);
+  TRY(upload(c, c->in_a, pks, 128 * n));
+  TRY(upload(c, c->in_b, proofs, 64 * n));
+  TRY(launch(c, c->stream, "iota_off", grid_lanes(n + 1), k_iota_off, (uint64_t*)c->in_off.p, n, (uint64_t)128));
   int rc = blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_a.p, (const uint64_t*)c->in_off.p,
                                      (const uint8_t*)c->in_b.p, n, dst, dst_len, (uint8_t*)c->bitmap.p);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(bm, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, bm, c->bitmap.p, nb);
 }
 
 

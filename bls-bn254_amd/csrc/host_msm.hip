@@ -46,45 +46,42 @@ int msm_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalars, size
   while (((size_t)1 << (MSM_LG_CHUNK * (levels + 1))) < S) ++levels;
   const size_t slots0 = (E >> MSM_LG_CHUNK) + u + 1;                               // level-0 output slots (msm.h: off_0 bound)
   MsmWs& m = c->msm;
-  HIPCHK(c, c->in_a.reserve(psz * n)); HIPCHK(c, c->scalars.reserve(32 * n)); HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->out.reserve(psz));
+  HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->out.reserve(psz));
   HIPCHK(c, m.pts.reserve(S * 2 * K * 4)); HIPCHK(c, m.key.reserve(E * 4)); HIPCHK(c, m.val.reserve(E * 4)); HIPCHK(c, m.sorted.reserve(E * 4));
   HIPCHK(c, m.hist.reserve((size_t)u * 4)); HIPCHK(c, m.end.reserve((size_t)u * 4));
   HIPCHK(c, m.part[0].reserve(slots0 * 3 * K * 4)); HIPCHK(c, m.part[1].reserve(slots0 * 3 * K * 4));
   HIPCHK(c, m.bsum.reserve((size_t)u * 3 * K * 4)); HIPCHK(c, m.seg.reserve((size_t)W * G * 3 * K * 4)); HIPCHK(c, m.stat.reserve(8));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pts, psz * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->scalars.p, scalars, 32 * n, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->in_a, pts, psz * n));
+  TRY(upload(c, c->scalars, scalars, 32 * n));
   const uint8_t* d_pts = (const uint8_t*)c->in_a.p; const uint8_t* d_sc = (const uint8_t*)c->scalars.p;
   int32_t* rows = (int32_t*)m.pts.p; uint32_t* key = (uint32_t*)m.key.p; uint32_t* val = (uint32_t*)m.val.p; uint32_t* sorted = (uint32_t*)m.sorted.p;
   uint32_t* hist = (uint32_t*)m.hist.p; uint32_t* end = (uint32_t*)m.end.p;
   uint8_t* status = (uint8_t*)c->status.p;
-  if (g2) { LAUNCH(c, "msm_prep", k_msm_g2_prep, n, d_pts, d_sc, n, cw, (int)W, rows, key, val, status); }
-  else { LAUNCH(c, "msm_prep", k_msm_g1_prep, n, d_pts, d_sc, n, cw, (int)W, rows, key, val, status); }
+  if (g2) TRY(launch(c, c->stream, "msm_prep", grid_lanes(n), k_msm_g2_prep, d_pts, d_sc, n, cw, (int)W, rows, key, val, status));
+  else TRY(launch(c, c->stream, "msm_prep", grid_lanes(n), k_msm_g1_prep, d_pts, d_sc, n, cw, (int)W, rows, key, val, status));
   // counting sort by (window, bucket)
   const dim3 sort_grid((unsigned)((S + MSM_SORT_TILE - 1) / MSM_SORT_TILE), W);
   HIPCHK(c, hipMemsetAsync(hist, 0, (size_t)u * 4, c->stream));
-  { ProfScope ps_(c, "msm_hist"); hipLaunchKernelGGL(k_kd_msm_hist, sort_grid, dim3(256), 0, c->stream, (const uint32_t*)key, S, B, hist); }
-  HIPCHK(c, hipGetLastError());
-  { ProfScope ps_(c, "msm_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)hist, u, end); }
-  HIPCHK(c, hipGetLastError());
-  { ProfScope ps_(c, "msm_scatter"); hipLaunchKernelGGL(k_kd_msm_scatter, sort_grid, dim3(256), 0, c->stream, (const uint32_t*)key, (const uint32_t*)val, S, B, end, sorted); }
-  HIPCHK(c, hipGetLastError());
+  TRY(launch(c, c->stream, "msm_hist", Shape{sort_grid, dim3(256)}, k_kd_msm_hist, (const uint32_t*)key, S, B, hist));
+  TRY(launch(c, c->stream, "msm_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, u, end));
+  TRY(launch(c, c->stream, "msm_scatter", Shape{sort_grid, dim3(256)}, k_kd_msm_scatter, (const uint32_t*)key, (const uint32_t*)val, S, B, end, sorted));
   // bucket sums: levels 0 .. levels-1 into the ping-pong slots, the last level into bsum (slot = bucket)
   const int32_t* in_ws = nullptr; size_t in_st = 1;
   for (int lv = 0; lv <= levels; ++lv) {
     const bool fin = lv == levels;
     const size_t nslots = fin ? (size_t)u : (E >> (MSM_LG_CHUNK * (lv + 1))) + u + 1;
     int32_t* out_ws = fin ? (int32_t*)m.bsum.p : (int32_t*)m.part[lv & 1].p;
-    if (g2) { LAUNCH(c, "msm_bucket", k_msm_g2_bucket, nslots, (uint32_t)nslots, lv, fin ? 1 : 0, (const uint32_t*)hist, (const uint32_t*)end, u,
-                     (const uint32_t*)sorted, (const int32_t*)rows, S, in_ws, in_st, out_ws, nslots); }
-    else { LAUNCH(c, "msm_bucket", k_msm_g1_bucket, nslots, (uint32_t)nslots, lv, fin ? 1 : 0, (const uint32_t*)hist, (const uint32_t*)end, u,
-                  (const uint32_t*)sorted, (const int32_t*)rows, S, in_ws, in_st, out_ws, nslots); }
+    if (g2) TRY(launch(c, c->stream, "msm_bucket", grid_lanes(nslots), k_msm_g2_bucket, (uint32_t)nslots, lv, fin ? 1 : 0, (const uint32_t*)hist, (const uint32_t*)end, u,
+                       (const uint32_t*)sorted, (const int32_t*)rows, S, in_ws, in_st, out_ws, nslots));
+    else TRY(launch(c, c->stream, "msm_bucket", grid_lanes(nslots), k_msm_g1_bucket, (uint32_t)nslots, lv, fin ? 1 : 0, (const uint32_t*)hist, (const uint32_t*)end, u,
+                    (const uint32_t*)sorted, (const int32_t*)rows, S, in_ws, in_st, out_ws, nslots));
     in_ws = out_ws; in_st = nslots;
   }
   const size_t lanes = (size_t)W * G;
-  if (g2) { LAUNCH(c, "msm_reduce", k_msm_g2_reduce, lanes, W, B, G, cw, (const int32_t*)m.bsum.p, (size_t)u, (int32_t*)m.seg.p); }
-  else { LAUNCH(c, "msm_reduce", k_msm_g1_reduce, lanes, W, B, G, cw, (const int32_t*)m.bsum.p, (size_t)u, (int32_t*)m.seg.p); }
-  if (g2) { LAUNCH(c, "msm_final", k_msm_g2_final, 1, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.stat.p); }
-  else { LAUNCH(c, "msm_final", k_msm_g1_final, 1, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.stat.p); }
+  if (g2) TRY(launch(c, c->stream, "msm_reduce", grid_lanes(lanes), k_msm_g2_reduce, W, B, G, cw, (const int32_t*)m.bsum.p, (size_t)u, (int32_t*)m.seg.p));
+  else TRY(launch(c, c->stream, "msm_reduce", grid_lanes(lanes), k_msm_g1_reduce, W, B, G, cw, (const int32_t*)m.bsum.p, (size_t)u, (int32_t*)m.seg.p));
+  if (g2) TRY(launch(c, c->stream, "msm_final", grid_lanes(1), k_msm_g2_final, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.stat.p));
+  else TRY(launch(c, c->stream, "msm_final", grid_lanes(1), k_msm_g1_final, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.stat.p));
   // the validity of every term (first bad index, as blsbn254_g1_mul_batch)
   int bad;
   int rc = first_bad(c, status, n, 3, 3, &bad);
@@ -98,8 +95,7 @@ int msm_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalars, size
   }
   uint32_t cnt[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, psz, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cnt, m.stat.p, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, cnt, m.stat.p, 8));
   c->stat_msm[0] += 1; c->stat_msm[2] += cnt[0]; c->stat_msm[3] += cnt[1];
   return 0;
 }

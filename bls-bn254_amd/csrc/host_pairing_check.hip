@@ -15,8 +15,7 @@ extern "C" {
 static const size_t FP12_SEG_GROUP = 8;     // Miller values per lane of the segmented product
 
 namespace {
-struct PcLevel { size_t first, count; };
-struct PcLaunch { size_t lo, hi, ga, gb; bool carry; std::vector<PcLevel> levels; };
+struct PcLaunch { size_t lo, hi, ga, gb; bool carry; std::vector<SegLevel> levels; };
 }
 
 // Launches and their product levels for equations rel[0..n_eq] (offsets rebased to 0); descriptors appended to start / len.
@@ -35,24 +34,10 @@ static int plan_launches(blsbn254_ctx* c, const std::vector<uint64_t>& rel, size
     const size_t gb = hi == N ? n_eq : (size_t)(std::lower_bound(rel.begin(), rel.end(), (uint64_t)hi) - rel.begin());
     L.lo = lo; L.hi = hi; L.ga = g; L.gb = gb; L.carry = rel[g] < lo;
     const size_t ne = gb - g;
-    std::vector<uint64_t> cur(ne + 1), nxt(ne + 1);
+    std::vector<uint64_t> cur(ne + 1);
     for (size_t e = 0; e <= ne; ++e) cur[e] = std::min<uint64_t>(std::max<uint64_t>(rel[g + e], lo), hi) - lo;   // launch-local boundaries
-    for (int level = 0; ; ++level) {
-      if (level > 40) { c->last_error = "internal: segmented products do not converge"; return BLSBN254_E_HIP; }
-      const size_t first = start.size();
-      for (size_t e = 0; e < ne; ++e) {
-        const uint64_t a = cur[e], b = cur[e + 1];
-        nxt[e] = start.size() - first;
-        if (a == b) { start.push_back((uint32_t)a); len.push_back(0); }             // empty (part of an) equation: ONE
-        for (uint64_t s = a; s < b; s += FP12_SEG_GROUP) { start.push_back((uint32_t)s); len.push_back((uint32_t)std::min<uint64_t>(b - s, FP12_SEG_GROUP)); }
-      }
-      const size_t m = start.size() - first;
-      nxt[ne] = m;
-      L.levels.push_back({first, m});
-      if (m == ne) break;
-      *items_max = std::max(*items_max, m);
-      cur.swap(nxt);
-    }
+    TRY(plan_seg_levels(c, cur, FP12_SEG_GROUP, start, len, L.levels, "internal: segmented products do not converge"));
+    for (size_t lv = 0; lv + 1 < L.levels.size(); ++lv) *items_max = std::max(*items_max, L.levels[lv].count);   // (the last level writes into the products)
     out.push_back(std::move(L));
     g = (gb > g && rel[gb] > hi) ? gb - 1 : gb;      // an equation cut at hi continues in the next launch
     lo = hi;
@@ -96,7 +81,7 @@ static int pc_products(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, co
       if (rc) return rc;
       src = (const int32_t*)c->f_ws.p;
       if (check) {
-        LAUNCH(c, "pair_ok", k_pair_ok, m, d_g1 + 64 * L.lo, d_g2 + 128 * L.lo, m, (uint8_t*)w.pair_ok.p);
+        TRY(launch(c, c->stream, "pair_ok", grid_lanes(m), k_pair_ok, d_g1 + 64 * L.lo, d_g2 + 128 * L.lo, m, (uint8_t*)w.pair_ok.p));
       } else {                                        // the errors of multi_miller_loop: the first pair that does not decode
         int bad;
         rc = first_bad(c, (const uint8_t*)c->status.p, m, 3, 3, &bad);
@@ -112,12 +97,12 @@ static int pc_products(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, co
     }
     int dst = 0;
     for (size_t lv = 0; lv < L.levels.size(); ++lv) {
-      const PcLevel& P = L.levels[lv];
+      const SegLevel& P = L.levels[lv];
       const bool last = lv + 1 == L.levels.size();
       int32_t* out = last ? (int32_t*)w.prod.p + L.ga : (int32_t*)w.seg[dst].p;
       uint8_t* out_ok = check ? (last ? (uint8_t*)w.ok.p + L.ga : (uint8_t*)w.seg_ok[dst].p) : nullptr;
-      LAUNCH(c, "fp12_seg_prod", k_fp12_seg_prod, P.count, src, src_stride, src_ok, (const uint32_t*)w.start.p + P.first,
-             (const uint32_t*)w.len.p + P.first, P.count, out, last ? n_eq : P.count, out_ok, (last && L.carry) ? 1 : 0);
+      TRY(launch(c, c->stream, "fp12_seg_prod", grid_lanes(P.count), k_fp12_seg_prod, src, src_stride, src_ok, (const uint32_t*)w.start.p + P.first,
+                 (const uint32_t*)w.len.p + P.first, P.count, out, last ? n_eq : P.count, out_ok, (last && L.carry) ? 1 : 0));
       src = out; src_ok = out_ok; src_stride = P.count; dst ^= 1;
     }
   }
@@ -143,10 +128,8 @@ int blsbn254_multi_miller_loop_batch(blsbn254_ctx* c, const uint8_t* g1, const u
   rc = pc_products(c, g1, g2, off, n_eq, false);
   if (rc) return rc;
   HIPCHK(c, c->out.reserve(384 * n_eq));
-  LAUNCH(c, "fp12_to_bytes", k_fp12_to_bytes, n_eq, (const int32_t*)c->pc.prod.p, n_eq, n_eq, (uint8_t*)c->out.p);
-  HIPCHK(c, hipMemcpyAsync(ml_out, c->out.p, 384 * n_eq, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(n_eq), k_fp12_to_bytes, (const int32_t*)c->pc.prod.p, n_eq, n_eq, (uint8_t*)c->out.p));
+  return download(c, ml_out, c->out.p, 384 * n_eq);
 }
 
 int blsbn254_pairing_check_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint64_t* off, size_t n_eq, uint8_t* valid_bitmap) {
@@ -163,20 +146,16 @@ int blsbn254_pairing_check_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8
   const uint8_t* ok = (const uint8_t*)c->pc.ok.p;
   // chunks of ctx->chunk equations (a multiple of 8: whole bitmap bytes); beyond one chunk each is first gathered into f_ws
   // (the Miller values are consumed) so that the final exponentiation keeps stride == n
-  for (size_t e0 = 0; e0 < n_eq; e0 += c->chunk) {
-    const size_t m = std::min(n_eq - e0, c->chunk);
+  TRY(for_chunks(c, n_eq, [&](size_t e0, size_t m) -> int {
     int32_t* f = prod;
     if (m != n_eq) {
       HIPCHK(c, c->f_ws.reserve(m * 108 * 4));
       f = (int32_t*)c->f_ws.p;
       HIPCHK(c, hipMemcpy2DAsync(f, m * 4, prod + e0, n_eq * 4, m * 4, 108, hipMemcpyDeviceToDevice, c->stream));
     }
-    rc = run_final_exp(c, f, m, m, 0, ok + e0, ok + e0, (uint8_t*)c->bitmap.p + e0 / 8, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+    return run_final_exp(c, f, m, m, 0, ok + e0, ok + e0, (uint8_t*)c->bitmap.p + e0 / 8, nullptr, nullptr);
+  }));
+  return download(c, valid_bitmap, c->bitmap.p, nb);
 }
 
 }  // extern "C"

@@ -21,23 +21,23 @@ int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pt
     if (pts2) HIPCHK(c, c->ks_out2[t].reserve(27 * 4 * m_max));
   }
   HIPCHK(c, c->ks_start.reserve(4 * m_max)); HIPCHK(c, c->ks_len.reserve(4 * m_max)); HIPCHK(c, c->ks_tchunk.reserve(4 * items)); HIPCHK(c, c->ks_iota.reserve(4 * m_max));
-  LAUNCH(c, "iota", k_iota_u32, m_max, (uint32_t*)c->ks_iota.p, (uint32_t)m_max);
+  TRY(launch(c, c->stream, "iota", grid_lanes(m_max), k_iota_u32, (uint32_t*)c->ks_iota.p, (uint32_t)m_max));
   int a = 0;
   for (int level = 0; ; ++level) {
     if (level > 8) { c->last_error = "internal: key sums do not converge"; return BLSBN254_E_HIP; }
     uint32_t *cnt = (uint32_t*)c->ks_cnt[a].p, *base = (uint32_t*)c->ks_base[a].p, *ckid = (uint32_t*)c->ks_kid[a].p;
-    LAUNCH(c, "rlc2_counts", k_rlc2_chunk_counts, u + 1, hist, u32, G32, cnt);
-    { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)cnt, u32 + 1, base); }
-    HIPCHK(c, hipGetLastError());
+    TRY(launch(c, c->stream, "rlc2_counts", grid_lanes(u + 1), k_rlc2_chunk_counts, hist, u32, G32, cnt));
+    TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)cnt, u32 + 1, base));
     uint32_t m32 = 0;
-    HIPCHK(c, hipMemcpyAsync(&m32, base + u, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(download(c, &m32, base + u, 4));
     const size_t m = m32;
     if (m < u || m > m_max || m > items) { c->last_error = "internal: chunk count out of range"; return BLSBN254_E_HIP; }
-    LAUNCH(c, "rlc2_mark", k_rlc2_mark, items, mark_perm, kid, hist, run_end, (const uint32_t*)base, (uint32_t)items, G32,
-           (uint32_t*)c->ks_tchunk.p, ckid, (uint32_t*)c->ks_start.p, (uint32_t*)c->ks_len.p);
-    LAUNCH(c, "g1_seg_sum", k_g1_seg_sum, m, pts, pts_stride, pt_perm, (const uint32_t*)c->ks_start.p, (const uint32_t*)c->ks_len.p, m, (int32_t*)c->ks_out[a].p, m);
-    if (pts2) { LAUNCH(c, "g1_seg_sum", k_g1_seg_sum, m, pts2, pts_stride, pt_perm, (const uint32_t*)c->ks_start.p, (const uint32_t*)c->ks_len.p, m, (int32_t*)c->ks_out2[a].p, m); }
+    TRY(launch(c, c->stream, "rlc2_mark", grid_lanes(items), k_rlc2_mark, mark_perm, kid, hist, run_end, (const uint32_t*)base, (uint32_t)items, G32,
+               (uint32_t*)c->ks_tchunk.p, ckid, (uint32_t*)c->ks_start.p, (uint32_t*)c->ks_len.p));
+    TRY(launch(c, c->stream, "g1_seg_sum", grid_lanes(m), k_g1_seg_sum, pts, pts_stride, pt_perm, (const uint32_t*)c->ks_start.p, (const uint32_t*)c->ks_len.p, m,
+               (int32_t*)c->ks_out[a].p, m));
+    if (pts2) TRY(launch(c, c->stream, "g1_seg_sum", grid_lanes(m), k_g1_seg_sum, pts2, pts_stride, pt_perm, (const uint32_t*)c->ks_start.p, (const uint32_t*)c->ks_len.p, m,
+                         (int32_t*)c->ks_out2[a].p, m));
     pts = (const int32_t*)c->ks_out[a].p; pts2 = pts2 ? (const int32_t*)c->ks_out2[a].p : nullptr; pts_stride = m; items = m;
     if (m == u) break;                                                          // one chunk per key: chunk index == key id
     // next level: item j has key ckid[j]; key k owns items base[k] .. base[k + 1]
@@ -63,16 +63,7 @@ int draw_seed(blsbn254_ctx* c, uint8_t out[32]) {
 int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
                           size_t cnt, uint8_t* d_isone) {
   HIPCHK(c, c->f_ws.reserve(cnt * 108 * 4)); HIPCHK(c, c->flags.reserve(cnt));
-  if (c->wide_fe && cnt <= c->wide_fe_max) {
-    LAUNCH_WIDE(c, "miller_wide_prepared", k_miller_wide_prepared, cnt, perm, kid, sigs, h_ws, h_stride, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, cnt,
-                (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
-  } else if (cnt <= c->tri_max && c->tri_miller) {     // the chunk / fallback rounds: three lanes per (virtual) tuple (k_tri.hip)
-    LAUNCH_TRI(c, "miller_tri_prepared", k_miller_tri_prepared, cnt, perm, kid, sigs, h_ws, h_stride, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, cnt,
-               (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
-  } else {
-    LAUNCH(c, "miller_prepared", k_miller_prepared, cnt, perm, kid, sigs, h_ws, h_stride, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, cnt,
-           (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
-  }
+  TRY(launch_miller_prepared(c, perm, kid, sigs, h_ws, h_stride, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, cnt));
   return run_final_exp(c, (int32_t*)c->f_ws.p, cnt, cnt, 4, nullptr, nullptr, nullptr, d_isone, nullptr);
 }
 // n <= ctx->chunk tuples, everything device-resident; d_seed = 32 bytes in device memory.  *took = 0 when the keys do not repeat
@@ -117,29 +108,28 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   uint32_t *ccnt = (uint32_t*)c->r2_ccnt.p, *cbase = (uint32_t*)c->r2_cbase.p;
   // key ids, key-sorted order, chunk numbering
   HIPCHK(c, hipMemsetAsync(hist, 0, 4 * u, c->stream));
-  LAUNCH(c, "kd_propagate", k_kd_propagate, n, (const uint32_t*)c->kd_rep.p, n32, u32, kid, hist);
-  { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)hist, u32, cursor); }
-  HIPCHK(c, hipGetLastError());
-  LAUNCH(c, "kd_scatter", k_kd_scatter, n, (const uint32_t*)kid, n32, u32, cursor, perm);          // cursor[k] is now the END of run k
-  LAUNCH(c, "rlc2_counts", k_rlc2_chunk_counts, u + 1, (const uint32_t*)hist, u32, G32, ccnt);
-  { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)ccnt, u32 + 1, cbase); }
-  HIPCHK(c, hipGetLastError());
+  TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, n32, u32, kid, hist));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, u32, cursor));
+  TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, (const uint32_t*)kid, n32, u32, cursor, perm));          // cursor[k] is now the END of run k
+  TRY(launch(c, c->stream, "rlc2_counts", grid_lanes(u + 1), k_rlc2_chunk_counts, (const uint32_t*)hist, u32, G32, ccnt));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)ccnt, u32 + 1, cbase));
   uint32_t m32 = 0;
   HIPCHK(c, hipMemcpyAsync(&m32, cbase + u, 4, hipMemcpyDeviceToHost, c->stream));
   // the hash points and the weighted points r_i sig_i, r_i H_i (the host learns the chunk count while these run)
-  LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 3);
-  LAUNCH(c, "rlc2_prep", k_rlc2_prep, n, (const uint32_t*)perm, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, d_seed, (int32_t*)c->r2_a.p, (int32_t*)c->r2_b.p,
-         (uint8_t*)c->r2_sigok.p);
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 3));
+  TRY(launch(c, c->stream, "rlc2_prep", grid_lanes(n), k_rlc2_prep, (const uint32_t*)perm, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, d_seed, (int32_t*)c->r2_a.p, (int32_t*)c->r2_b.p,
+             (uint8_t*)c->r2_sigok.p));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t m = m32;
   if (m == 0 || m > n) { c->last_error = "internal: chunk count out of range"; return BLSBN254_E_HIP; }
   HIPCHK(c, c->r2_ckid.reserve(4 * m)); HIPCHK(c, c->r2_cstart.reserve(4 * m)); HIPCHK(c, c->r2_clen.reserve(4 * m)); HIPCHK(c, c->r2_csig.reserve(64 * m));
   HIPCHK(c, c->r2_ch.reserve(27 * 4 * m)); HIPCHK(c, c->r2_cstate.reserve(m)); HIPCHK(c, c->r2_iota.reserve(4 * m)); HIPCHK(c, c->r2_cisone.reserve(m));
-  LAUNCH(c, "rlc2_mark", k_rlc2_mark, n, (const uint32_t*)perm, (const uint32_t*)kid, (const uint32_t*)hist, (const uint32_t*)cursor, (const uint32_t*)cbase, n32, G32,
-         (uint32_t*)c->r2_tchunk.p, (uint32_t*)c->r2_ckid.p, (uint32_t*)c->r2_cstart.p, (uint32_t*)c->r2_clen.p);
+  TRY(launch(c, c->stream, "rlc2_mark", grid_lanes(n), k_rlc2_mark, (const uint32_t*)perm, (const uint32_t*)kid, (const uint32_t*)hist, (const uint32_t*)cursor, (const uint32_t*)cbase,
+             n32, G32,
+             (uint32_t*)c->r2_tchunk.p, (uint32_t*)c->r2_ckid.p, (uint32_t*)c->r2_cstart.p, (uint32_t*)c->r2_clen.p));
   HIPCHK(c, c->r2_sa.reserve(27 * 4 * m)); HIPCHK(c, c->r2_sb.reserve(27 * 4 * m)); HIPCHK(c, c->r2_celig.reserve(4 * m));
-  LAUNCH(c, "rlc2_sum", k_rlc2_sum, m, (const int32_t*)c->r2_a.p, (const int32_t*)c->r2_b.p, n, (const uint8_t*)c->r2_sigok.p, (const uint32_t*)c->r2_cstart.p,
-         (const uint32_t*)c->r2_clen.p, m, (int32_t*)c->r2_sa.p, (int32_t*)c->r2_sb.p, (uint32_t*)c->r2_celig.p);
+  TRY(launch(c, c->stream, "rlc2_sum", grid_lanes(m), k_rlc2_sum, (const int32_t*)c->r2_a.p, (const int32_t*)c->r2_b.p, n, (const uint8_t*)c->r2_sigok.p, (const uint32_t*)c->r2_cstart.p,
+             (const uint32_t*)c->r2_clen.p, m, (int32_t*)c->r2_sa.p, (int32_t*)c->r2_sb.p, (uint32_t*)c->r2_celig.p));
   HIPCHK(c, join_stream2(c));                      // the key tables are ready
   // The key round: ALL tuples of a key as one virtual tuple (the chunk sums of the key, summed) -- u checks, few enough for the
   // wave-per-tuple kernels.  A batch without invalid signatures (the usual case) is decided here, in a fraction of a chunk round;
@@ -149,7 +139,7 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   HIPCHK(c, c->r2_cbbase.reserve(4 * (mblk + 2)));
   const uint32_t* clist = nullptr;                     // chunks of the chunk round (NULL: all of them, in order)
   size_t mc = m;
-  LAUNCH(c, "iota", k_iota_u32, m, (uint32_t*)c->r2_iota.p, (uint32_t)m);
+  TRY(launch(c, c->stream, "iota", grid_lanes(m), k_iota_u32, (uint32_t*)c->r2_iota.p, (uint32_t)m));
   // Batches that keep failing it (a stream with invalid signatures spread over all keys) would pay for the key round every time:
   // after a failure the next 2 (then 4, 8, 16) batches skip it; a pass resets the back-off.
   const bool key_round = c->rlc_key_round && c->rlc_key_skip == 0;
@@ -162,65 +152,68 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
                   (const uint32_t*)ccnt, (const uint32_t*)cbase + 1, m, u, &ksa, &ksb);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(c->r2_kelig.p, 0, 4 * u, c->stream));
-    LAUNCH(c, "rlc2_key_elig", k_rlc2_key_elig, m, (const uint32_t*)c->r2_ckid.p, (const uint32_t*)c->r2_celig.p, (uint32_t)m, (uint32_t*)c->r2_kelig.p);
-    LAUNCH(c, "rlc2_virtual", k_rlc2_virtual, u, ksa, ksb, u, (const uint32_t*)c->r2_kelig.p, (const uint32_t*)nullptr, u, (uint8_t*)c->r2_ksig.p, (int32_t*)c->r2_kh.p,
-           (uint8_t*)c->r2_kstate.p);
+    TRY(launch(c, c->stream, "rlc2_key_elig", grid_lanes(m), k_rlc2_key_elig, (const uint32_t*)c->r2_ckid.p, (const uint32_t*)c->r2_celig.p, (uint32_t)m, (uint32_t*)c->r2_kelig.p));
+    TRY(launch(c, c->stream, "rlc2_virtual", grid_lanes(u), k_rlc2_virtual, ksa, ksb, u, (const uint32_t*)c->r2_kelig.p, (const uint32_t*)nullptr, u, (uint8_t*)c->r2_ksig.p,
+               (int32_t*)c->r2_kh.p,
+               (uint8_t*)c->r2_kstate.p));
     rc = prepared_round(c, (const uint32_t*)c->r2_iota.p, (const uint32_t*)c->r2_iota.p, (const uint8_t*)c->r2_ksig.p, (const int32_t*)c->r2_kh.p, u, u, (uint8_t*)c->r2_kisone.p);
     if (rc) return rc;
     int* d_all = (int*)c->misc.p;
     static const int one_i = 1;
     HIPCHK(c, hipMemcpyAsync(d_all, &one_i, 4, hipMemcpyHostToDevice, c->stream));
-    LAUNCH(c, "rlc2_keys_pass", k_rlc2_keys_pass, u, (const uint8_t*)c->prep_ok.p, (const uint8_t*)c->r2_kstate.p, (const uint8_t*)c->r2_kisone.p, u32, (uint8_t*)c->r2_kpass.p, d_all);
+    TRY(launch(c, c->stream, "rlc2_keys_pass", grid_lanes(u), k_rlc2_keys_pass, (const uint8_t*)c->prep_ok.p, (const uint8_t*)c->r2_kstate.p, (const uint8_t*)c->r2_kisone.p, u32,
+               (uint8_t*)c->r2_kpass.p, d_all));
     // the chunks of the keys that failed, as an ordered list (counted while the host waits for the verdict)
-    LAUNCH(c, "rlc2_chunk_need", k_rlc2_chunk_need, m, (const uint32_t*)c->r2_ckid.p, (const uint8_t*)c->r2_kpass.p, (uint32_t)m, (uint8_t*)c->r2_cneed.p, (uint32_t*)c->r2_cbcnt.p);
-    { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)c->r2_cbcnt.p, (uint32_t)mblk + 1, (uint32_t*)c->r2_cbbase.p); }
-    HIPCHK(c, hipGetLastError());
+    TRY(launch(c, c->stream, "rlc2_chunk_need", grid_lanes(m), k_rlc2_chunk_need, (const uint32_t*)c->r2_ckid.p, (const uint8_t*)c->r2_kpass.p, (uint32_t)m, (uint8_t*)c->r2_cneed.p,
+               (uint32_t*)c->r2_cbcnt.p));
+    TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)c->r2_cbcnt.p, (uint32_t)mblk + 1, (uint32_t*)c->r2_cbbase.p));
     int all_pass = 0; uint32_t mc32 = 0;
     HIPCHK(c, hipMemcpyAsync(&all_pass, d_all, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&mc32, (uint32_t*)c->r2_cbbase.p + mblk, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(download(c, &mc32, (uint32_t*)c->r2_cbbase.p + mblk, 4));
     c->stat_rlc[0] += n; ++c->stat_rlc_key_rounds;
     if (all_pass == 1) {
       ++c->stat_rlc_key_rounds_passed;
       c->rlc_key_streak = 0;
-      LAUNCH(c, "rlc2_valid_fast", k_rlc2_valid_fast, n, (const uint32_t*)perm, (const uint32_t*)kid, (const uint8_t*)c->r2_sigok.p, (const uint8_t*)c->prep_ok.p, n32, (uint8_t*)c->r2_valid.p);
-      LAUNCH(c, "pack_bitmap", k_pack_bitmap, n, (const uint8_t*)c->r2_valid.p, n, d_bitmap);
-      return 0;
+      TRY(launch(c, c->stream, "rlc2_valid_fast", grid_lanes(n), k_rlc2_valid_fast, (const uint32_t*)perm, (const uint32_t*)kid, (const uint8_t*)c->r2_sigok.p,
+                 (const uint8_t*)c->prep_ok.p, n32, (uint8_t*)c->r2_valid.p));
+      return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->r2_valid.p, n, d_bitmap);
     }
     if (c->rlc_key_streak < 4) ++c->rlc_key_streak;
     c->rlc_key_skip = 1u << c->rlc_key_streak;
     if (mc32 == 0 || mc32 > m) { c->last_error = "internal: chunk list out of range"; return BLSBN254_E_HIP; }
     mc = mc32;
-    LAUNCH(c, "rlc2_compact", k_rlc2_compact, m, (const uint8_t*)c->r2_cneed.p, (const uint32_t*)c->r2_iota.p, (uint32_t)m, (const uint32_t*)c->r2_cbbase.p, (uint32_t*)c->r2_clist.p);
+    TRY(launch(c, c->stream, "rlc2_compact", grid_lanes(m), k_rlc2_compact, (const uint8_t*)c->r2_cneed.p, (const uint32_t*)c->r2_iota.p, (uint32_t)m, (const uint32_t*)c->r2_cbbase.p,
+               (uint32_t*)c->r2_clist.p));
     clist = (const uint32_t*)c->r2_clist.p;
     HIPCHK(c, hipMemsetAsync(c->r2_cpass.p, 1, m, c->stream));               // chunks of the keys that passed
   } else {
     c->stat_rlc[0] += n;
   }
   // the chunk round: every (listed) chunk is one virtual tuple on the prepared-key verify path
-  LAUNCH(c, "rlc2_virtual", k_rlc2_virtual, mc, (const int32_t*)c->r2_sa.p, (const int32_t*)c->r2_sb.p, m, (const uint32_t*)c->r2_celig.p, clist, mc, (uint8_t*)c->r2_csig.p,
-         (int32_t*)c->r2_ch.p, (uint8_t*)c->r2_cstate.p);
+  TRY(launch(c, c->stream, "rlc2_virtual", grid_lanes(mc), k_rlc2_virtual, (const int32_t*)c->r2_sa.p, (const int32_t*)c->r2_sb.p, m, (const uint32_t*)c->r2_celig.p, clist, mc,
+             (uint8_t*)c->r2_csig.p,
+             (int32_t*)c->r2_ch.p, (uint8_t*)c->r2_cstate.p));
   rc = prepared_round(c, clist ? clist : (const uint32_t*)c->r2_iota.p, (const uint32_t*)c->r2_ckid.p, (const uint8_t*)c->r2_csig.p, (const int32_t*)c->r2_ch.p, m, mc, (uint8_t*)c->r2_cisone.p);
   if (rc) return rc;
-  LAUNCH(c, "rlc2_chunk_pass", k_rlc2_chunk_pass, mc, clist, (const uint8_t*)c->r2_cstate.p, (const uint8_t*)c->r2_cisone.p, (const uint8_t*)c->flags.p, (uint32_t)mc, (uint8_t*)c->r2_cpass.p);
-  LAUNCH(c, "rlc2_resolve", k_rlc2_resolve, n, (const uint32_t*)perm, (const uint32_t*)kid, (const uint32_t*)c->r2_tchunk.p, (const uint8_t*)c->r2_sigok.p,
-         (const uint8_t*)c->prep_ok.p, (const uint8_t*)c->r2_cpass.p, n32, (uint8_t*)c->r2_valid.p, (uint8_t*)c->r2_need.p, (uint32_t*)c->r2_bcnt.p);
-  { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)c->r2_bcnt.p, (uint32_t)nblk + 1, (uint32_t*)c->r2_bbase.p); }
-  HIPCHK(c, hipGetLastError());
+  TRY(launch(c, c->stream, "rlc2_chunk_pass", grid_lanes(mc), k_rlc2_chunk_pass, clist, (const uint8_t*)c->r2_cstate.p, (const uint8_t*)c->r2_cisone.p, (const uint8_t*)c->flags.p,
+             (uint32_t)mc, (uint8_t*)c->r2_cpass.p));
+  TRY(launch(c, c->stream, "rlc2_resolve", grid_lanes(n), k_rlc2_resolve, (const uint32_t*)perm, (const uint32_t*)kid, (const uint32_t*)c->r2_tchunk.p, (const uint8_t*)c->r2_sigok.p,
+             (const uint8_t*)c->prep_ok.p, (const uint8_t*)c->r2_cpass.p, n32, (uint8_t*)c->r2_valid.p, (uint8_t*)c->r2_need.p, (uint32_t*)c->r2_bcnt.p));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)c->r2_bcnt.p, (uint32_t)nblk + 1, (uint32_t*)c->r2_bbase.p));
   uint32_t m2 = 0;
-  HIPCHK(c, hipMemcpyAsync(&m2, (uint32_t*)c->r2_bbase.p + nblk, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, &m2, (uint32_t*)c->r2_bbase.p + nblk, 4));
   if (m2 > n) { c->last_error = "internal: fallback count out of range"; return BLSBN254_E_HIP; }
   c->stat_rlc[1] += mc; c->stat_rlc[2] += m2;
   if (m2) {                                                                     // eligible tuples of failed chunks: the exact prepared-key path
     HIPCHK(c, c->prep_isone.reserve(m2));
-    LAUNCH(c, "rlc2_compact", k_rlc2_compact, n, (const uint8_t*)c->r2_need.p, (const uint32_t*)perm, n32, (const uint32_t*)c->r2_bbase.p, (uint32_t*)c->r2_list.p);
+    TRY(launch(c, c->stream, "rlc2_compact", grid_lanes(n), k_rlc2_compact, (const uint8_t*)c->r2_need.p, (const uint32_t*)perm, n32, (const uint32_t*)c->r2_bbase.p,
+               (uint32_t*)c->r2_list.p));
     rc = prepared_round(c, (const uint32_t*)c->r2_list.p, (const uint32_t*)kid, d_sigs, (const int32_t*)c->h_ws.p, n, m2, (uint8_t*)c->prep_isone.p);
     if (rc) return rc;
-    LAUNCH(c, "prep_unsort", k_prep_unsort, m2, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)c->r2_list.p, m2, (uint8_t*)c->r2_valid.p);
+    TRY(launch(c, c->stream, "prep_unsort", grid_lanes(m2), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)c->r2_list.p, m2,
+               (uint8_t*)c->r2_valid.p));
   }
-  LAUNCH(c, "pack_bitmap", k_pack_bitmap, n, (const uint8_t*)c->r2_valid.p, n, d_bitmap);
-  return 0;
+  return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->r2_valid.p, n, d_bitmap);
 }
 static int stage_seed(blsbn254_ctx* c, const uint8_t* seed) {
   uint8_t own[32];
@@ -229,8 +222,7 @@ static int stage_seed(blsbn254_ctx* c, const uint8_t* seed) {
     if (rc) return rc;
     seed = own;
   }
-  HIPCHK(c, c->r2_seed.reserve(32));
-  HIPCHK(c, hipMemcpyAsync(c->r2_seed.p, seed, 32, hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, c->r2_seed, seed, 32));
   HIPCHK(c, hipStreamSynchronize(c->stream));         // `own` is on the stack
   return 0;
 }
@@ -243,18 +235,13 @@ int blsbn254_verify_batch_rlc_dev(blsbn254_ctx* c, const uint8_t* d_pks, const u
   if (rc) return rc;
   rc = stage_seed(c, seed);
   if (rc) return rc;
-  for (size_t lo = 0; lo < n; lo += c->chunk) {        // chunk starts are multiples of 8: bitmap bytes do not straddle
-    size_t m = n - lo < c->chunk ? n - lo : c->chunk;
+  return for_chunks(c, n, [&](size_t lo, size_t m) -> int {
     bool took = false;
-    rc = rlc2_chunk_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, (const uint8_t*)c->r2_seed.p, d_bitmap + lo / 8, &took);
-    if (rc) return rc;
-    if (!took) {                                       // keys do not repeat: nothing to share per key, the exact per-tuple path
-      c->stat_rlc[3] += m;
-      rc = verify_exact_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, d_bitmap + lo / 8);
-      if (rc) return rc;
-    }
-  }
-  return 0;
+    TRY(rlc2_chunk_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, (const uint8_t*)c->r2_seed.p, d_bitmap + lo / 8, &took));
+    if (took) return 0;
+    c->stat_rlc[3] += m;                               // keys do not repeat: nothing to share per key, the exact per-tuple path
+    return verify_exact_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, d_bitmap + lo / 8);
+  });
 }
 int blsbn254_set_rlc_group(blsbn254_ctx* c, size_t group) {
   if (!c || group == 1 || group > 4096) return BLSBN254_E_ARG;
@@ -282,9 +269,9 @@ int blsbn254_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   const size_t nb = (n + 7) / 8;
-  HIPCHK(c, c->in_a.reserve(128 * n)); HIPCHK(c, c->in_b.reserve(64 * n)); HIPCHK(c, c->bitmap.reserve(nb + 8));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, sigs, 64 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->bitmap.reserve(nb + 8));
+  TRY(upload(c, c->in_a, pks, 128 * n));
+  TRY(upload(c, c->in_b, sigs, 64 * n));
   rc = stage_seed(c, seed);
   if (rc) return rc;
   // Repeated keys: per-key chunks as virtual tuples on the prepared-key path (k_rlc2.hip).  Batches beyond one launch chunk
@@ -301,9 +288,7 @@ int blsbn254_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
     took = true;
   }
   if (took) {
-    HIPCHK(c, hipMemcpyAsync(bm, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return download(c, bm, c->bitmap.p, nb);
   }
   // Distinct keys: groups of RLC_GROUP tuples in the caller's order share the signature-side Miller loop and the final exponentiation.
   c->stat_rlc[3] += n;
@@ -320,32 +305,32 @@ int blsbn254_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
     HIPCHK(c, hipStreamSynchronize(c->stream)); }
   const uint8_t* d_pks = (const uint8_t*)c->in_a.p; const uint8_t* d_sigs = (const uint8_t*)c->in_b.p;
   int32_t* f = (int32_t*)c->f_ws.p;
-  LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 0);
-  LAUNCH(c, "g2_check", k_g2_check, n, d_pks, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr);
-  LAUNCH(c, "rlc_prep", k_rlc_prep, n_pad, d_pks, d_sigs, (const int32_t*)c->h_ws.p, (const uint8_t*)c->sub_ok.p, (const uint8_t*)c->misc.p,
-         n, n_pad, (int32_t*)c->rlc_a.p, (int32_t*)c->rlc_b.p, (uint8_t*)c->rlc_elig.p);
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n,
+             (uint8_t*)nullptr, 0));
+  TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, d_pks, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
+  TRY(launch(c, c->stream, "rlc_prep", grid_lanes(n_pad), k_rlc_prep, d_pks, d_sigs, (const int32_t*)c->h_ws.p, (const uint8_t*)c->sub_ok.p, (const uint8_t*)c->misc.p,
+             n, n_pad, (int32_t*)c->rlc_a.p, (int32_t*)c->rlc_b.p, (uint8_t*)c->rlc_elig.p));
   // prod_i ML(r_i H_i, pk_i) per group: per-pair loops, ONE where not eligible, log2(G) levels of pairwise products
-  LAUNCH(c, "miller_hpk", k_miller_hpk, n, (const int32_t*)c->rlc_b.p, d_pks, n, f, n_pad, (uint8_t*)c->flags.p);
-  LAUNCH(c, "fp12_mask_one", k_fp12_mask_one, n_pad, f, n_pad, (const uint8_t*)c->rlc_elig.p, n_pad);
+  TRY(launch(c, c->stream, "miller_hpk", grid_lanes(n), k_miller_hpk, (const int32_t*)c->rlc_b.p, d_pks, n, f, n_pad, (uint8_t*)c->flags.p));
+  TRY(launch(c, c->stream, "fp12_mask_one", grid_lanes(n_pad), k_fp12_mask_one, f, n_pad, (const uint8_t*)c->rlc_elig.p, n_pad));
   HIPCHK(c, c->f_ws2.reserve((n_pad / 2) * 108 * 4)); HIPCHK(c, c->rlc_a2.reserve((n_pad / 2) * 27 * 4));
   int32_t *pa = f, *pb = (int32_t*)c->f_ws2.p, *ga = (int32_t*)c->rlc_a.p, *gb = (int32_t*)c->rlc_a2.p;
   size_t cnt = n_pad, st = n_pad;
   for (size_t lvl = 1; lvl < G; lvl <<= 1) {                          // adjacent pairs never straddle a group
     size_t mo = cnt / 2;
-    LAUNCH(c, "fp12_mul_pairs", k_fp12_mul_pairs, mo, (const int32_t*)pa, cnt, st, pb, mo);
-    LAUNCH(c, "g1_add_pairs", k_g1_add_pairs, mo, (const int32_t*)ga, cnt, st, gb, mo);
+    TRY(launch(c, c->stream, "fp12_mul_pairs", grid_lanes(mo), k_fp12_mul_pairs, (const int32_t*)pa, cnt, st, pb, mo));
+    TRY(launch(c, c->stream, "g1_add_pairs", grid_lanes(mo), k_g1_add_pairs, (const int32_t*)ga, cnt, st, gb, mo));
     std::swap(pa, pb); std::swap(ga, gb); st = mo; cnt = mo;
   }
   // e(sum_i r_i sig_i, -G2gen) per group, multiplied in; one final exponentiation per group
-  LAUNCH(c, "g1p_to_bytes", k_g1p_to_bytes, ng, (const int32_t*)ga, st, ng, (uint8_t*)c->rlc_bytes.p);
-  LAUNCH(c, "miller_1", k_miller_1, ng, (const uint8_t*)c->rlc_bytes.p, (const uint8_t*)c->rlc_neg.p, ng, (int32_t*)c->rlc_f2.p, ng, (uint8_t*)c->status.p);
-  LAUNCH(c, "fp12_mul_elem", k_fp12_mul_elem, ng, pa, st, (const int32_t*)c->rlc_f2.p, ng, ng);
+  TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)ga, st, ng, (uint8_t*)c->rlc_bytes.p));
+  TRY(launch(c, c->stream, "miller_1", grid_lanes(ng), k_miller_1, (const uint8_t*)c->rlc_bytes.p, (const uint8_t*)c->rlc_neg.p, ng, (int32_t*)c->rlc_f2.p, ng, (uint8_t*)c->status.p));
+  TRY(launch(c, c->stream, "fp12_mul_elem", grid_lanes(ng), k_fp12_mul_elem, pa, st, (const int32_t*)c->rlc_f2.p, ng, ng));
   rc = run_final_exp(c, pa, ng, st, 4, nullptr, nullptr, nullptr, (uint8_t*)c->rlc_ok.p, nullptr);
   if (rc) return rc;
   std::vector<uint8_t> h_ok(ng), h_elig(n_pad);
   HIPCHK(c, hipMemcpyAsync(h_ok.data(), c->rlc_ok.p, ng, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_elig.data(), c->rlc_elig.p, n_pad, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, h_elig.data(), c->rlc_elig.p, n_pad));
   std::memset(bm, 0, nb);
   std::vector<uint32_t> idx;
   for (size_t g = 0; g < ng; ++g) {
@@ -357,19 +342,18 @@ int blsbn254_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   }
   if (!idx.empty()) {                                                  // exact per-tuple path for the groups that failed
     size_t m = idx.size(), mb = (m + 7) / 8;
-    HIPCHK(c, c->rlc_idx.reserve(4 * m)); HIPCHK(c, c->rlc_cpk.reserve(128 * m)); HIPCHK(c, c->rlc_csig.reserve(64 * m));
+    HIPCHK(c, c->rlc_cpk.reserve(128 * m)); HIPCHK(c, c->rlc_csig.reserve(64 * m));
     HIPCHK(c, c->rlc_ch.reserve(18 * 4 * m)); HIPCHK(c, c->rlc_csub.reserve(m)); HIPCHK(c, c->rlc_cbm.reserve(mb + 8));
     HIPCHK(c, c->f_ws.reserve(m * 108 * 4)); HIPCHK(c, c->flags.reserve(m));
-    HIPCHK(c, hipMemcpyAsync(c->rlc_idx.p, idx.data(), 4 * m, hipMemcpyHostToDevice, c->stream));
-    LAUNCH(c, "rlc_gather", k_rlc_gather, m, (const uint32_t*)c->rlc_idx.p, m, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, (const uint8_t*)c->sub_ok.p,
-           (uint8_t*)c->rlc_cpk.p, (uint8_t*)c->rlc_csig.p, (int32_t*)c->rlc_ch.p, (uint8_t*)c->rlc_csub.p);
-    LAUNCH(c, "miller_verify", k_miller_verify, m, (const uint8_t*)c->rlc_cpk.p, (const uint8_t*)c->rlc_csig.p, (const int32_t*)c->rlc_ch.p, m,
-           (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
+    TRY(upload(c, c->rlc_idx, idx.data(), 4 * m));
+    TRY(launch(c, c->stream, "rlc_gather", grid_lanes(m), k_rlc_gather, (const uint32_t*)c->rlc_idx.p, m, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, (const uint8_t*)c->sub_ok.p,
+               (uint8_t*)c->rlc_cpk.p, (uint8_t*)c->rlc_csig.p, (int32_t*)c->rlc_ch.p, (uint8_t*)c->rlc_csub.p));
+    TRY(launch(c, c->stream, "miller_verify", grid_lanes(m), k_miller_verify, (const uint8_t*)c->rlc_cpk.p, (const uint8_t*)c->rlc_csig.p, (const int32_t*)c->rlc_ch.p, m,
+               (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p));
     rc = run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 0, (const uint8_t*)c->flags.p, (const uint8_t*)c->rlc_csub.p, (uint8_t*)c->rlc_cbm.p, nullptr, nullptr);
     if (rc) return rc;
     std::vector<uint8_t> cb(mb);
-    HIPCHK(c, hipMemcpyAsync(cb.data(), c->rlc_cbm.p, mb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    TRY(download(c, cb.data(), c->rlc_cbm.p, mb));
     for (size_t j = 0; j < m; ++j) if (cb[j >> 3] & (1u << (j & 7))) { size_t i = idx[j]; bm[i >> 3] |= (uint8_t)(1u << (i & 7)); }
   }
   return 0;

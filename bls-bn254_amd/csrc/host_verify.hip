@@ -8,16 +8,46 @@ extern "C" {
 // Workspace is ~7.4 KB per tuple (H, f, six final-exponentiation phase buffers, ten chain slots); batches
 // larger than ctx->chunk (4 Mi) tuples are processed chunk by chunk so that any n fits the 288 GB of HBM.
 
+// G2Prepared::from for u keys (decode, on-curve, psi subgroup test, 88 line triples) on stream s: four lanes per key
+// (k_keyprep_quad.hip, half the latency) while the 8 u lanes fit one round of waves, else one lane per key (k_keyprep.hip).
+int launch_g2_prepare(blsbn254_ctx* c, hipStream_t s, const uint8_t* pks, const uint32_t* keys, size_t u, int32_t* raw, uint8_t* ok, const uint32_t* d_u) {
+  if (c->quad_prep && 8 * u <= c->lanes_per_round)
+    return launch(c, s, "g2_prepare", grid_lanes(2 * 256 * (size_t)nblocks(4 * u)), k_g2_prepare_quad, pks, keys, (uint32_t)u, raw, ok, d_u);
+  return launch(c, s, "g2_prepare", grid_lanes(2 * 256 * (size_t)nblocks(u)), k_g2_prepare, pks, keys, (uint32_t)u, raw, ok, d_u);
+}
 // G2Prepared::from for u keys on the second stream (after ev_fork), ev_join recorded behind it.
 // keys == nullptr: key k = pks[128 k]; else key k = the public key of tuple keys[k].
 // d_u (optional): the key count on the device when u is only a capacity (the asynchronous path)
 int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_keys, size_t u, int32_t* table, uint8_t* key_ok, const uint32_t* d_u) {
   HIPCHK(c, c->prep_raw.reserve(u * PREP_RAW_LIMBS * 4));
   HIPCHK(c, fork_stream2(c));
-  LAUNCH_G2_PREPARE(c, LAUNCH2, d_pks, d_keys, u, (int32_t*)c->prep_raw.p, key_ok, d_u);
-  LAUNCH2(c, "g2_expand", k_g2_expand, u * (size_t)BN_NEG_G2_LINES, (const int32_t*)c->prep_raw.p, (uint32_t)u, table, d_u);
+  TRY(launch_g2_prepare(c, c->stream2, d_pks, d_keys, u, (int32_t*)c->prep_raw.p, key_ok, d_u));
+  TRY(launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)u, table, d_u));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   return 0;
+}
+// Are all n key indices at d_kid below u?  k_kd_hist counts the keys into hist (zeroed here) and folds the first index out of
+// range into misc[0]; read back (one 4-byte copy and a stream synchronisation).  armed: the caller has already put NO_INDEX there,
+// in one upload with words of its own behind it.  `what` names the element in the error text ("tuple" / "pair").
+int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u, uint32_t* hist, const char* what, bool armed) {
+  if (!armed) { HIPCHK(c, c->misc.reserve(64)); TRY(min_index_arm(c, (int*)c->misc.p, 1)); }
+  int* d_bad = (int*)c->misc.p;
+  HIPCHK(c, hipMemsetAsync(hist, 0, 4 * u, c->stream));
+  TRY(launch(c, c->stream, "kd_hist", grid_lanes(n), k_kd_hist, d_kid, (uint32_t)n, (uint32_t)u, hist, d_bad));
+  int bad;
+  TRY(min_index_read(c, d_bad, &bad));
+  if (bad >= 0) { c->last_error = std::string("key index out of range at ") + what + " " + std::to_string(bad); return BLSBN254_E_ARG; }
+  return 0;
+}
+// The table-only Miller loop over n tuples (f_ws, flags) in the form that fits n; the three forms give the same values.
+int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
+                           const int32_t* table, const uint8_t* key_ok, size_t n) {
+  int32_t* f = (int32_t*)c->f_ws.p; uint8_t* flags = (uint8_t*)c->flags.p;
+  if (c->wide_fe && n <= c->wide_fe_max)               // few tuples: one wave per tuple (k_miller_wide.hip)
+    return launch(c, c->stream, "miller_wide_prepared", grid_wide(n), k_miller_wide_prepared, perm, kid, sigs, h_ws, h_stride, table, key_ok, n, f, flags);
+  if (n <= c->tri_max && c->tri_miller)                // mid-size launches: three lanes per tuple (k_tri.hip)
+    return launch(c, c->stream, "miller_tri_prepared", grid_tri(n), k_miller_tri_prepared, perm, kid, sigs, h_ws, h_stride, table, key_ok, n, f, flags);
+  return launch(c, c->stream, "miller_prepared", grid_lanes(n), k_miller_prepared, perm, kid, sigs, h_ws, h_stride, table, key_ok, n, f, flags);
 }
 // Verify n tuples whose keys are given by index into a prepared table (d_kid[i] < u), everything device-resident.
 // The caller has put the preparation of the table on stream2 (ev_join) or the table is final (join = false).
@@ -25,39 +55,20 @@ int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* ke
                                const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join) {
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
   HIPCHK(c, c->kd_hist.reserve(4 * (u + 1))); HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
-  HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n)); HIPCHK(c, c->misc.reserve(64));
+  HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n));
   uint32_t* hist = (uint32_t*)c->kd_hist.p; uint32_t* cursor = (uint32_t*)c->kd_cursor.p; uint32_t* perm = (uint32_t*)c->kd_perm.p;
-  LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 3);   // homogeneous H: no inversion
-  if (!hist_done) {
-    int* d_bad = (int*)c->misc.p;
-    static const int init = 0x7fffffff;
-    HIPCHK(c, hipMemcpyAsync(d_bad, &init, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(hist, 0, 4 * u, c->stream));
-    LAUNCH(c, "kd_hist", k_kd_hist, n, d_kid, (uint32_t)n, (uint32_t)u, hist, d_bad);
-    int bad;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (bad != 0x7fffffff) { c->last_error = "key index out of range at tuple " + std::to_string(bad); return BLSBN254_E_ARG; }
-  }
-  { ProfScope ps_(c, "kd_scan"); hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)hist, (uint32_t)u, cursor); }
-  HIPCHK(c, hipGetLastError());
-  LAUNCH(c, "kd_scatter", k_kd_scatter, n, d_kid, (uint32_t)n, (uint32_t)u, cursor, perm);
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr,
+             3));   // homogeneous H: no inversion
+  if (!hist_done) TRY(check_key_indices(c, d_kid, n, u, hist, "tuple", false));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, (uint32_t)u, cursor));
+  TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, d_kid, (uint32_t)n, (uint32_t)u, cursor, perm));
   if (join) HIPCHK(c, join_stream2(c));
-  if (c->wide_fe && n <= c->wide_fe_max) {            // few tuples: one wave per tuple (k_miller_wide.hip), same values
-    LAUNCH_WIDE(c, "miller_wide_prepared", k_miller_wide_prepared, n, (const uint32_t*)perm, d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n,
-                (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
-  } else if (n <= c->tri_max && c->tri_miller) {       // mid-size launches: three lanes per tuple (k_tri.hip), same values
-    LAUNCH_TRI(c, "miller_tri_prepared", k_miller_tri_prepared, n, (const uint32_t*)perm, d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n,
-               (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
-  } else {
-    LAUNCH(c, "miller_prepared", k_miller_prepared, n, (const uint32_t*)perm, d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n,
-           (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
-  }
+  TRY(launch_miller_prepared(c, perm, d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n));
   int rc = run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 4, nullptr, nullptr, nullptr, (uint8_t*)c->prep_isone.p, nullptr);
   if (rc) return rc;
-  LAUNCH(c, "prep_unsort", k_prep_unsort, n, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)perm, (uint32_t)n, (uint8_t*)c->prep_valid.p);
-  LAUNCH(c, "pack_bitmap", k_pack_bitmap, n, (const uint8_t*)c->prep_valid.p, n, d_bitmap);
-  return 0;
+  TRY(launch(c, c->stream, "prep_unsort", grid_lanes(n), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)perm, (uint32_t)n,
+             (uint8_t*)c->prep_valid.p));
+  return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->prep_valid.p, n, d_bitmap);
 }
 // De-duplicate the public keys of a chunk: kd_rep / kd_kid / kd_keys and the count (kd_cnt) are filled on the device.
 static int dedup_enqueue(blsbn254_ctx* c, const uint8_t* d_pks, size_t n) {
@@ -68,17 +79,15 @@ static int dedup_enqueue(blsbn254_ctx* c, const uint8_t* d_pks, size_t n) {
   HIPCHK(c, c->kd_hist.reserve(4 * (n + 2))); HIPCHK(c, c->kd_cnt.reserve(64));
   HIPCHK(c, hipMemsetAsync(c->kd_slots.p, 0xff, 4 * m, c->stream));
   HIPCHK(c, hipMemsetAsync(c->kd_cnt.p, 0, 4, c->stream));
-  LAUNCH(c, "kd_insert", k_kd_insert, n, d_pks, (uint32_t)n, (uint32_t*)c->kd_slots.p, (uint32_t)(m - 1), c->kd_seed, (uint32_t*)c->kd_rep.p);
-  LAUNCH(c, "kd_assign", k_kd_assign, n, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_cnt.p, (uint32_t*)c->kd_keys.p);
-  return 0;
+  TRY(launch(c, c->stream, "kd_insert", grid_lanes(n), k_kd_insert, d_pks, (uint32_t)n, (uint32_t*)c->kd_slots.p, (uint32_t)(m - 1), c->kd_seed, (uint32_t*)c->kd_rep.p));
+  return launch(c, c->stream, "kd_assign", grid_lanes(n), k_kd_assign, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_cnt.p, (uint32_t*)c->kd_keys.p);
 }
 // ... and *u_out = the number of distinct keys, read back (one 4-byte copy and a stream synchronisation)
 int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out) {
   int rc = dedup_enqueue(c, d_pks, n);
   if (rc) return rc;
   uint32_t u = 0;
-  HIPCHK(c, hipMemcpyAsync(&u, c->kd_cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, &u, c->kd_cnt.p, 4));
   *u_out = u;
   return 0;
 }
@@ -88,9 +97,9 @@ int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
   ++c->stat_exact_chunks;
   HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
   HIPCHK(c, c->flags.reserve(n)); HIPCHK(c, c->sub_ok.reserve(n));
-  LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 0);
-  LAUNCH(c, "g2_check", k_g2_check, n, d_pks, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr);
-  LAUNCH(c, "miller_verify", k_miller_verify, n, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p);
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 0));
+  TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, d_pks, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
+  TRY(launch(c, c->stream, "miller_verify", grid_lanes(n), k_miller_verify, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p));
   return run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 0, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p, d_bitmap, nullptr, nullptr);
 }
 // Workspace is ~7.4 KB per tuple (H, f, six final-exponentiation phase buffers, ten chain slots); batches
@@ -105,7 +114,7 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
   // exponentiation can run one WAVE per tuple (k_miller_wide.hip, k_fe_wide.hip) instead of at the latency of one lane.
   // ... and mid-size chunks (up to tri_max tuples) likewise: three lanes per tuple (k_tri.hip) need the tables too, and a launch of
   // that size is bound by latency, not by the table work (16 384 distinct keys: ~2 ms of preparation against 4 ms saved).
-  const bool small = (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && c->tri_fe && n <= c->tri_max);
+  const bool small = small_for_prepared(c, n, true);
   if (c->auto_prepare && (n >= 1024 || small)) {
     size_t u = 0;
     int rc = dedup_keys(c, d_pks, n, &u);
@@ -115,7 +124,7 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
       rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, nullptr);
       if (rc) return rc;
       HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * u, c->stream));
-      LAUNCH(c, "kd_propagate", k_kd_propagate, n, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p);
+      TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p));
       ++c->stat_prepared_chunks;
       c->u_hint = u ? u : 1;
       if (u > c->u_max_seen) c->u_max_seen = u;
@@ -129,7 +138,7 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
 // The key capacity a chunk of n tuples would be enqueued with, or 0 when it has to take the counting path.  Host state only: the
 // caller decides with it BEFORE it stages its tag (see verify_batch_dev_impl).
 static size_t async_capacity(const blsbn254_ctx* c, size_t n, size_t dst_len) {
-  const bool small = (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && c->tri_fe && n <= c->tri_max);
+  const bool small = small_for_prepared(c, n, true);
   if (!c->async_verify || !c->auto_prepare || c->u_hint == 0 || !(n >= 1024 || small) || dst_len > 255) return 0;
   size_t cap = 2 * c->u_hint < 1024 ? 1024 : 2 * c->u_hint;
   if (cap < c->u_max_seen) cap = c->u_max_seen;
@@ -151,7 +160,7 @@ static size_t async_capacity(const blsbn254_ctx* c, size_t n, size_t dst_len) {
 // The caller has made room in the queue (fewer than four calls pending) and staged the tag; nothing in here settles a pending call.
 static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n,
                               size_t cap, uint32_t dl, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap) {
-  const bool small = (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && c->tri_fe && n <= c->tri_max);
+  const bool small = small_for_prepared(c, n, true);
   if (cap == 0 || c->pend_count >= 4) { c->last_error = "verify_chunk_async: not eligible or queue full"; return BLSBN254_E_ARG; }
   if (!c->pend_host) {
     HIPCHK(c, hipHostMalloc((void**)&c->pend_host, 4 * 2 * sizeof(uint32_t), hipHostMallocDefault));
@@ -163,13 +172,12 @@ static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8
   uint32_t* d_res = (uint32_t*)c->pend_dev.p + 2 * slot;
   int rc = dedup_enqueue(c, d_pks, n);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_kd_decide, dim3(1), dim3(1), 0, c->stream, (const uint32_t*)c->kd_cnt.p, (uint32_t)n, (uint32_t)cap, small ? 1 : 0, d_res);
-  HIPCHK(c, hipGetLastError());
+  TRY(launch(c, c->stream, nullptr, Shape{dim3(1), dim3(1)}, k_kd_decide, (const uint32_t*)c->kd_cnt.p, (uint32_t)n, (uint32_t)cap, small ? 1 : 0, d_res));
   HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
   rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, cap, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, d_res);
   if (rc) return rc;
   HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * cap, c->stream));
-  LAUNCH(c, "kd_propagate", k_kd_propagate, n, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)cap, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p);
+  TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)cap, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p));
   rc = verify_prepared_dev(c, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, cap, (const uint32_t*)c->kd_kid.p, true,
                            d_msgs, d_off, d_sigs, n, dl, d_bitmap, true);
   if (rc) return rc;
@@ -220,12 +228,9 @@ static int verify_batch_dev_impl(blsbn254_ctx* c, const uint8_t* d_pks, const ui
   uint32_t dl; rc = stage_dst(c, dst, dst_len, &dl);   // (a new tag waits for the kernels that still read the old one)
   if (rc) return rc;
   if (cap) return verify_chunk_async(c, d_pks, d_msgs, d_off, d_sigs, n, cap, dl, dst, dst_len, d_bitmap);
-  for (size_t lo = 0; lo < n; lo += c->chunk) {        // chunk starts are multiples of 8: bitmap bytes do not straddle
-    size_t m = n - lo < c->chunk ? n - lo : c->chunk;
-    rc = verify_chunk_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, d_bitmap + lo / 8);
-    if (rc) return rc;
-  }
-  return 0;
+  return for_chunks(c, n, [&](size_t lo, size_t m) {
+    return verify_chunk_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, d_bitmap + lo / 8);
+  });
 }
 int blsbn254_verify_batch_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                               const uint8_t* d_sigs, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap) {
@@ -254,11 +259,8 @@ int blsbn254_g2_prepare_batch(blsbn254_ctx* c, const uint8_t* pks, size_t u, bls
   *out = nullptr;
   if (u + 1 > PREP_MAX_KEYS) { c->last_error = "more than 65535 keys in one prepared table"; return BLSBN254_E_ARG; }
   ENTER(c);
-  // owned until handed to the caller: every failure path below releases the three device buffers and the object
-  struct Owner {
-    blsbn254_g2prepared* p;
-    ~Owner() { if (p) { p->table.release(); p->raw.release(); p->ok.release(); delete p; } }
-  } own{new blsbn254_g2prepared()};
+  // owned until handed to the caller: every failure path below frees the object and, with it, its three device buffers
+  struct Owner { blsbn254_g2prepared* p; ~Owner() { delete p; } } own{new blsbn254_g2prepared()};
   blsbn254_g2prepared* p = own.p;
   p->ctx = c; p->u = u;
   // entry u (one past the caller's keys) is -G2gen: the second member of the aggregate signature's pair
@@ -266,8 +268,8 @@ int blsbn254_g2_prepare_batch(blsbn254_ctx* c, const uint8_t* pks, size_t u, bls
   HIPCHK(c, p->table.reserve(u1 * PREP_KEY_LIMBS * 4)); HIPCHK(c, p->ok.reserve(u1)); HIPCHK(c, c->in_a.reserve(128 * u1)); HIPCHK(c, p->raw.reserve(u1 * PREP_RAW_LIMBS * 4));
   if (u) HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * u, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * u, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));
-  LAUNCH_G2_PREPARE(c, LAUNCH, (const uint8_t*)c->in_a.p, (const uint32_t*)nullptr, u1, (int32_t*)p->raw.p, (uint8_t*)p->ok.p, (const uint32_t*)nullptr);
-  LAUNCH(c, "g2_expand", k_g2_expand, u1 * (size_t)BN_NEG_G2_LINES, (const int32_t*)p->raw.p, (uint32_t)u1, (int32_t*)p->table.p, (const uint32_t*)nullptr);
+  TRY(launch_g2_prepare(c, c->stream, (const uint8_t*)c->in_a.p, nullptr, u1, (int32_t*)p->raw.p, (uint8_t*)p->ok.p, nullptr));
+  TRY(launch(c, c->stream, "g2_expand", grid_lanes(u1 * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)p->raw.p, (uint32_t)u1, (int32_t*)p->table.p, (const uint32_t*)nullptr));
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) { (void)hipDeviceSynchronize(); }       // nothing may still be writing the buffers the owner frees
   HIPCHK(c, es);
@@ -279,7 +281,6 @@ void blsbn254_g2prepared_destroy(blsbn254_g2prepared* p) {
   if (!p) return;
   (void)hipSetDevice(p->ctx->device);
   (void)hipStreamSynchronize(p->ctx->stream);
-  p->table.release(); p->raw.release(); p->ok.release();
   delete p;
 }
 size_t blsbn254_g2prepared_count(const blsbn254_g2prepared* p) { return p ? p->u : 0; }
@@ -289,10 +290,8 @@ int blsbn254_g2prepared_valid(blsbn254_ctx* c, const blsbn254_g2prepared* p, uin
   if (!p->u) return 0;
   ENTER(c);
   HIPCHK(c, c->bitmap.reserve((p->u + 7) / 8 + 8));
-  LAUNCH(c, "pack_bitmap", k_pack_bitmap, p->u, (const uint8_t*)p->ok.p, p->u, (uint8_t*)c->bitmap.p);
-  HIPCHK(c, hipMemcpyAsync(ok_bitmap, c->bitmap.p, (p->u + 7) / 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(p->u), k_pack_bitmap, (const uint8_t*)p->ok.p, p->u, (uint8_t*)c->bitmap.p));
+  return download(c, ok_bitmap, c->bitmap.p, (p->u + 7) / 8);
 }
 int blsbn254_verify_batch_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* keys, const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* off,
                                    const uint8_t* sigs, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* bm) {
@@ -304,18 +303,14 @@ int blsbn254_verify_batch_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* k
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   const size_t nb = (n + 7) / 8;
-  HIPCHK(c, c->in_b.reserve(64 * n)); HIPCHK(c, c->kd_kid.reserve(4 * n)); HIPCHK(c, c->bitmap.reserve(nb + 8));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, sigs, 64 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->kd_kid.p, key_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
-  for (size_t lo = 0; lo < n; lo += c->chunk) {
-    size_t m = n - lo < c->chunk ? n - lo : c->chunk;
-    rc = verify_prepared_dev(c, (const int32_t*)keys->table.p, (const uint8_t*)keys->ok.p, keys->u, (const uint32_t*)c->kd_kid.p + lo, false,
-                             (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo, (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8, false);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipMemcpyAsync(bm, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  HIPCHK(c, c->bitmap.reserve(nb + 8));
+  TRY(upload(c, c->in_b, sigs, 64 * n));
+  TRY(upload(c, c->kd_kid, key_idx, 4 * n));
+  TRY(for_chunks(c, n, [&](size_t lo, size_t m) {
+    return verify_prepared_dev(c, (const int32_t*)keys->table.p, (const uint8_t*)keys->ok.p, keys->u, (const uint32_t*)c->kd_kid.p + lo, false,
+                               (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo, (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8, false);
+  }));
+  return download(c, bm, c->bitmap.p, nb);
 }
 // multi_miller_loop(&[(&G1Affine, &G2Prepared)]) (pairings.rs:808-857) over prepared keys named by index: the Fp12 product of
 // the n Miller values, two pairs per lane sharing f^2, every line read from the keys' tables.  A pair whose G1 member is
@@ -327,21 +322,13 @@ int blsbn254_multi_miller_loop_prepared(blsbn254_ctx* c, const blsbn254_g2prepar
   CHECK_LANES(c, n);
   ENTER(c);
   const size_t n_lanes = (n + 1) / 2;
-  HIPCHK(c, c->in_a.reserve(64 * n)); HIPCHK(c, c->kd_kid.reserve(4 * n)); HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4));
-  HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->flags.reserve(n)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 1))); HIPCHK(c, c->misc.reserve(64)); HIPCHK(c, c->out.reserve(384));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, g1, 64 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->kd_kid.p, key_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
-  // key indices in range?
-  int* d_bad = (int*)c->misc.p;
-  static const int init = 0x7fffffff;
-  HIPCHK(c, hipMemcpyAsync(d_bad, &init, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * keys->u, c->stream));
-  LAUNCH(c, "kd_hist", k_kd_hist, n, (const uint32_t*)c->kd_kid.p, (uint32_t)n, (uint32_t)keys->u, (uint32_t*)c->kd_hist.p, d_bad);
+  HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4));
+  HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->flags.reserve(n)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 1))); HIPCHK(c, c->out.reserve(384));
+  TRY(upload(c, c->in_a, g1, 64 * n));
+  TRY(upload(c, c->kd_kid, key_idx, 4 * n));
+  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", false));
   int bad;
-  HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (bad != 0x7fffffff) { c->last_error = "key index out of range at pair " + std::to_string(bad); return BLSBN254_E_ARG; }
-  LAUNCH(c, "g1_to_ws", k_g1_to_ws_batch, n, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p);
+  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(n), k_g1_to_ws_batch, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p));
   int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_G1;
@@ -349,11 +336,11 @@ int blsbn254_multi_miller_loop_prepared(blsbn254_ctx* c, const blsbn254_g2prepar
   const size_t f_cnt = wide ? n : n_lanes;
   if (wide) {
     HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
-    LAUNCH_WIDE(c, "miller_wide_1p", k_miller_wide_1p, n, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
-                (const uint8_t*)keys->ok.p, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->flags.p, (const uint8_t*)c->status.p);
+    TRY(launch(c, c->stream, "miller_wide_1p", grid_wide(n), k_miller_wide_1p, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
+               (const uint8_t*)keys->ok.p, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->flags.p, (const uint8_t*)c->status.p));
   } else {
-    LAUNCH(c, "miller_hpk2p", k_miller_hpk2p, n_lanes, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
-           (const uint8_t*)keys->ok.p, n, (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)c->status.p);
+    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
+               (const uint8_t*)keys->ok.p, n, (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)c->status.p));
   }
   rc = first_bad(c, (const uint8_t*)c->flags.p, n, 1, 1, &bad);
   if (rc) return rc;
@@ -361,10 +348,8 @@ int blsbn254_multi_miller_loop_prepared(blsbn254_ctx* c, const blsbn254_g2prepar
   int32_t* res; size_t rs;
   rc = fp12_tree(c, (int32_t*)c->f_ws.p, f_cnt, f_cnt, &res, &rs);
   if (rc) return rc;
-  LAUNCH(c, "fp12_to_bytes", k_fp12_to_bytes, 1, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p);
-  HIPCHK(c, hipMemcpyAsync(ml_out, c->out.p, 384, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(1), k_fp12_to_bytes, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p));
+  return download(c, ml_out, c->out.p, 384);
 }
 // CoreAggregateVerify with the public keys given as prepared keys by index: prod_i e(H(msg_i), pk_[key_idx_i]) * e(agg_sig, -G2gen) == 1.
 // The signature's pair uses the table's own -G2gen entry; two pairs per lane, every line from the tables, ONE final exponentiation.
@@ -387,19 +372,15 @@ int blsbn254_aggregate_verify_prepared(blsbn254_ctx* c, const blsbn254_g2prepare
   HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_kid.p + n, &sig_key, 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sig, 64, hipMemcpyHostToDevice, c->stream));
   int* d_ok = (int*)c->misc.p;               // [0] first bad key index (kd_hist), [1] all keys valid, [2] (byte) signature valid
-  static const int init[3] = {0x7fffffff, 1, 1};
+  static const int init[3] = {NO_INDEX, 1, 1};         // the armed index shares its upload with the two validity words
   HIPCHK(c, hipMemcpyAsync(d_ok, init, 12, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * keys->u, c->stream));
-  LAUNCH(c, "kd_hist", k_kd_hist, n, (const uint32_t*)c->kd_kid.p, (uint32_t)n, (uint32_t)keys->u, (uint32_t*)c->kd_hist.p, d_ok);
-  int bad;
-  HIPCHK(c, hipMemcpyAsync(&bad, d_ok, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));          // also: sig_key is on the stack
-  if (bad != 0x7fffffff) { c->last_error = "key index out of range at pair " + std::to_string(bad); return BLSBN254_E_ARG; }
-  LAUNCH(c, "hash_to_g1", k_hash_to_g1, n, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, np, (uint8_t*)nullptr, 0);
-  LAUNCH(c, "g1_to_ws", k_g1_to_ws, 1, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 2));
-  LAUNCH(c, "miller_hpk2p", k_miller_hpk2p, n_lanes, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
-         (const uint8_t*)keys->ok.p, np, (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)nullptr);
-  LAUNCH(c, "and_reduce", k_and_reduce, n, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok + 1);
+  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", true));   // its read-back also waits for the copy of sig_key (on the stack)
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, np,
+             (uint8_t*)nullptr, 0));
+  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 2)));
+  TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
+             (const uint8_t*)keys->ok.p, np, (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)nullptr));
+  TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok + 1));
   int32_t* res; size_t rs;
   rc = fp12_tree(c, (int32_t*)c->f_ws.p, n_lanes, n_lanes, &res, &rs);
   if (rc) return rc;
@@ -407,8 +388,7 @@ int blsbn254_aggregate_verify_prepared(blsbn254_ctx* c, const blsbn254_g2prepare
   rc = run_final_exp(c, res, 1, rs, 3, nullptr, nullptr, nullptr, nullptr, d_one);
   if (rc) return rc;
   int h[5] = {0, 0, 0, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(h, d_ok, 20, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  TRY(download(c, h, d_ok, 20));
   *valid = (h[1] == 1 && (h[2] & 0xff) == 1 && h[4] == 1) ? 1 : 0;
   return 0;
 }
@@ -433,15 +413,13 @@ int blsbn254_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* ms
   int rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   size_t nb = (n + 7) / 8;
-  HIPCHK(c, c->in_a.reserve(128 * n)); HIPCHK(c, c->in_b.reserve(64 * n)); HIPCHK(c, c->bitmap.reserve(nb + 8));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, sigs, 64 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->bitmap.reserve(nb + 8));
+  TRY(upload(c, c->in_a, pks, 128 * n));
+  TRY(upload(c, c->in_b, sigs, 64 * n));
   rc = blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p,
                                  (const uint8_t*)c->in_b.p, n, dst, dst_len, (uint8_t*)c->bitmap.p);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(bm, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return download(c, bm, c->bitmap.p, nb);
 }
 
 }  // extern "C"
