@@ -324,11 +324,9 @@ static int lagrange_ids_reduce(blsbn254_ctx* c, size_t t) {
 }
 // Threshold combine (k_threshold.hip): Lagrange coefficients over t x sqrt(t) lanes, GLV-split 4-bit-window MSM over
 // 2t x 32 lanes with in-workgroup sums, one short finishing kernel.  One host synchronisation at the end.
-int blsbn254_threshold_combine(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]) {
-  if (!c || !out_sig || (t && (!ids || !partial_sigs))) return BLSBN254_E_ARG;
-  if (t == 0) { std::memset(out_sig, 0, 64); out_sig[63] = 1; return 0; }
-  CHECK_LANES(c, t);
-  ENTER(c);
+// (the body of blsbn254_threshold_combine for one group of 1 <= t <= MAX_LANES shares, after ENTER; the batched form sends its
+// large groups through it, host_threshold_batch.hip)
+int threshold_combine_one(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]) {
   size_t n_chunks = (2 * t + 255) / 256;
   HIPCHK(c, c->out.reserve(64)); HIPCHK(c, c->th_part.reserve(27 * 32 * n_chunks * 4)); HIPCHK(c, c->th_part2.reserve(27 * 32 * ((n_chunks + 1) / 2) * 4));
   TRY(upload(c, c->in_a, partial_sigs, 64 * t));
@@ -353,18 +351,29 @@ int blsbn254_threshold_combine(blsbn254_ctx* c, const uint8_t* ids, const uint8_
   if (bad[1] != NO_INDEX) return BLSBN254_ERR_G1;
   return 0;
 }
-// The Lagrange coefficients at zero alone (t x 32 bytes big-endian), for callers that combine elsewhere and for tests.
-int blsbn254_lagrange_at_zero(blsbn254_ctx* c, const uint8_t* ids, size_t t, uint8_t* out) {
-  if (!c || (t && (!ids || !out))) return BLSBN254_E_ARG;
-  if (t == 0) return 0;
+int blsbn254_threshold_combine(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]) {
+  if (!c || !out_sig || (t && (!ids || !partial_sigs))) return BLSBN254_E_ARG;
+  if (t == 0) { std::memset(out_sig, 0, 64); out_sig[63] = 1; return 0; }
   CHECK_LANES(c, t);
   ENTER(c);
+  return threshold_combine_one(c, ids, partial_sigs, t, out_sig);
+}
+// The Lagrange coefficients at zero alone (t x 32 bytes big-endian), for callers that combine elsewhere and for tests.
+// (lagrange_one: the body for 1 <= t <= MAX_LANES ids, after ENTER)
+int lagrange_one(blsbn254_ctx* c, const uint8_t* ids, size_t t, uint8_t* out) {
   TRY(lagrange_enqueue(c, ids, t));
   TRY(lagrange_ids_reduce(c, t));
   int bad;
   HIPCHK(c, hipMemcpyAsync(&bad, c->misc.p, 4, hipMemcpyDeviceToHost, c->stream));
   TRY(download(c, out, c->scalars.p, 32 * t));
   return bad != NO_INDEX ? BLSBN254_ERR_SCALAR : 0;
+}
+int blsbn254_lagrange_at_zero(blsbn254_ctx* c, const uint8_t* ids, size_t t, uint8_t* out) {
+  if (!c || (t && (!ids || !out))) return BLSBN254_E_ARG;
+  if (t == 0) return 0;
+  CHECK_LANES(c, t);
+  ENTER(c);
+  return lagrange_one(c, ids, t, out);
 }
 
 

@@ -50,6 +50,13 @@ struct BNH PcWs {
   DevBuf prod, ok, pair_ok, seg[2], seg_ok[2], start, len;
   std::vector<uint32_t> h_start, h_len;
 };
+// threshold combine over groups (host_threshold_batch.hip, k_threshold_batch.hip): the groups' offsets, per-share group words,
+// the products, the levels of the group sums (ping-pong), the sums, the per-group marks, the chunk descriptors (device and the
+// host copies they are uploaded from), the encodings and statuses
+struct BNH ThbWs {
+  DevBuf goff, gid, pts, seg[2], gsum, gstat, start, len, out, st;
+  std::vector<uint32_t> h_goff, h_start, h_len;
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -111,6 +118,8 @@ struct blsbn254_ctx {
   size_t chunk = (size_t)1 << 22;   // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
   MsmWs msm;
   PcWs pc;
+  ThbWs thb;
+  uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
   uint64_t stat_msm[4] = {0, 0, 0, 0};   // bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
   bool profiling = false;
@@ -244,6 +253,8 @@ BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* ki
                           size_t cnt, uint8_t* d_isone);   // host_rlc.hip
 BNH int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res, size_t* rs);   // host_aggregate.hip
 BNH int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]);   // host_aggregate.hip
+BNH int threshold_combine_one(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]);   // host_aggregate.hip
+BNH int lagrange_one(blsbn254_ctx* c, const uint8_t* ids, size_t t, uint8_t* out);   // host_aggregate.hip
 
 // A launch of n tuples is small enough that the prepared-key path wins whatever its keys: with line tables the Miller loop (and
 // the final exponentiation) can run one WAVE per tuple (wide.h) or, up to tri_max, three lanes per tuple (k_tri.hip) instead of

@@ -1,0 +1,209 @@
+// host_threshold_batch.hip -- threshold combine and Lagrange coefficients over ragged groups of shares: n_groups independent
+// blsbn254_threshold_combine / blsbn254_lagrange_at_zero in one call.  Host side of include/blsbn254.h; kernels in
+// k_threshold_batch.hip (one lane per SHARE over all groups of a launch); see host_common.h.
+//
+// All ids and partial signatures are uploaded once.  The shares run in launches of at most ctx->chunk shares that end on a
+// group boundary (a launch always takes at least one whole group): ids decoded, Lagrange coefficients per lane over the lane's
+// group, [lambda] sigma per lane, then each group's products summed level by level (k_g1_seg_sum; the last level writes into
+// the per-group sums, limb-major, stride n_groups).  After the last launch: one inversion per group (k_g1p_to_bytes), the
+// per-group marks folded into statuses (k_th_finish), ONE download and synchronisation.  All chunk descriptors are planned on
+// the host up front and uploaded in one copy.
+//
+// Groups of more than TH_BATCH_TBIG shares do not take that path: the per-lane Lagrange loop is quadratic in the group and serial in
+// the lane, which the single-group pipeline (t x sqrt(t) lanes, host_aggregate.hip) avoids.  Their lanes only test their point
+// here (decodes, on the curve -- the single pipeline tests only the decoding; such a group may be cut by a launch boundary
+// anywhere, its lanes are independent), their sum slot gets the identity, and after the synchronisation each goes through
+// threshold_combine_one / lagrange_one into its slot of the caller's outputs.
+#include "host_common.h"
+
+// The hand-over size.  In the sweep that places it (16 equal groups per call, t = 64 .. 4096, profiles/threshold_batch.json,
+// DESIGN.md 6d) the loop of single calls never became faster than the lane-per-share kernels, so it sits at the end of the
+// sweep.  A compile-time constant on purpose (not an option, not an environment variable); -DBN_TH_BATCH_TBIG=<n> is for the
+// measurement build of that sweep (scripts/bench_threshold_batch.py).
+#ifndef BN_TH_BATCH_TBIG
+#define BN_TH_BATCH_TBIG 4096
+#endif
+
+extern "C" {
+
+static const size_t TH_BATCH_TBIG = BN_TH_BATCH_TBIG;
+static const size_t TH_SUM_GROUP = 16;      // products per lane and level of the group sums
+
+namespace {
+// shares [lo, hi) of the call; groups [ga, gb) lie in it (gb - 1 may be a large group that continues in the next launch)
+struct ThLaunch { size_t lo, hi, ga, gb; std::vector<SegLevel> levels; };
+}
+
+static inline bool th_big(const std::vector<uint32_t>& rel, size_t g) { return (size_t)(rel[g + 1] - rel[g]) > TH_BATCH_TBIG; }
+
+// Launches and their sum levels for groups rel[0 .. n_groups] (offsets rebased to 0); descriptors appended to start / len.
+static int th_plan(blsbn254_ctx* c, const std::vector<uint32_t>& rel, size_t n_groups, std::vector<ThLaunch>& out, std::vector<uint32_t>& start,
+                   std::vector<uint32_t>& len, size_t* m_max, size_t* items_max) {
+  const size_t N = rel[n_groups];
+  size_t lo = 0, g = 0;
+  *m_max = 0; *items_max = 1;
+  while (g < n_groups) {
+    ThLaunch L;
+    const size_t lim = std::min(N, lo + c->chunk);
+    size_t hi = lo, gb = g;
+    bool cut = false;                                    // the launch ends inside the (large) group gb
+    while (gb < n_groups) {
+      const size_t b = rel[gb + 1];
+      if (b <= lim || (hi == lo && !th_big(rel, gb))) { hi = b; ++gb; if (b > lim) break; continue; }   // a whole group; the first one whatever its size
+      if (th_big(rel, gb) && lim > hi) { hi = lim; cut = true; }
+      break;
+    }
+    L.lo = lo; L.hi = hi; L.ga = g; L.gb = gb + (cut ? 1 : 0);
+    // level 0: every group's products in runs of at most TH_SUM_GROUP; an empty or a large group: ONE empty run (the identity)
+    const size_t ne = L.gb - L.ga, first = start.size();
+    std::vector<uint64_t> cur(ne + 1);
+    for (size_t e = 0; e < ne; ++e) {
+      const size_t gg = L.ga + e;
+      cur[e] = start.size() - first;
+      const size_t a = rel[gg], b = th_big(rel, gg) ? a : rel[gg + 1];
+      if (a == b) { start.push_back(0); len.push_back(0); }
+      for (size_t s = a; s < b; s += TH_SUM_GROUP) { start.push_back((uint32_t)(s - lo)); len.push_back((uint32_t)std::min(b - s, TH_SUM_GROUP)); }
+    }
+    const size_t m0 = start.size() - first;
+    cur[ne] = m0;
+    L.levels.push_back({first, m0});
+    if (m0 != ne) TRY(plan_seg_levels(c, cur, TH_SUM_GROUP, start, len, L.levels, "internal: group sums do not converge"));
+    for (size_t lv = 0; lv + 1 < L.levels.size(); ++lv) *items_max = std::max(*items_max, L.levels[lv].count);   // (the last level writes into the sums)
+    *m_max = std::max(*m_max, hi - lo);
+    out.push_back(std::move(L));
+    g = gb; lo = hi;
+  }
+  return 0;
+}
+
+// The device part for all groups: per-group statuses into c->thb.st, and with `sigs` the encodings into c->thb.out, else the
+// coefficients into c->scalars.  Everything is enqueued; the caller downloads and synchronises.
+static int th_enqueue(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* sigs, const uint64_t* off, size_t n_groups) {
+  ThbWs& w = c->thb;
+  std::vector<uint32_t>& rel = w.h_goff;                 // ctx-owned: outlive the asynchronous copies (every call ends synchronised)
+  rel.resize(n_groups + 1);
+  for (size_t g = 0; g <= n_groups; ++g) rel[g] = (uint32_t)(off[g] - off[0]);
+  const size_t N = rel[n_groups];
+  w.h_start.clear(); w.h_len.clear();
+  std::vector<ThLaunch> launches;
+  size_t m_max, items_max;
+  TRY(th_plan(c, rel, n_groups, launches, w.h_start, w.h_len, &m_max, &items_max));
+  const size_t m1 = m_max ? m_max : 1, N1 = N ? N : 1;
+  HIPCHK(c, c->in_b.reserve(32 * N1)); HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->th_glv.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
+  HIPCHK(c, w.goff.reserve(4 * (n_groups + 1))); HIPCHK(c, w.gid.reserve(4 * m1)); HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
+  if (sigs) {
+    HIPCHK(c, c->in_a.reserve(64 * N1)); HIPCHK(c, w.pts.reserve(27 * m1 * 4)); HIPCHK(c, w.seg[0].reserve(27 * items_max * 4)); HIPCHK(c, w.seg[1].reserve(27 * items_max * 4));
+    HIPCHK(c, w.gsum.reserve(27 * n_groups * 4)); HIPCHK(c, w.out.reserve(64 * n_groups));
+    HIPCHK(c, w.start.reserve(4 * w.h_start.size())); HIPCHK(c, w.len.reserve(4 * w.h_len.size()));
+  } else HIPCHK(c, c->scalars.reserve(32 * N1));
+  if (N) {
+    HIPCHK(c, hipMemcpyAsync(c->in_b.p, ids + 32 * off[0], 32 * N, hipMemcpyHostToDevice, c->stream));
+    if (sigs) HIPCHK(c, hipMemcpyAsync(c->in_a.p, sigs + 64 * off[0], 64 * N, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(w.goff.p, rel.data(), 4 * (n_groups + 1), hipMemcpyHostToDevice, c->stream));
+  if (sigs) {
+    HIPCHK(c, hipMemcpyAsync(w.start.p, w.h_start.data(), 4 * w.h_start.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w.len.p, w.h_len.data(), 4 * w.h_len.size(), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemsetAsync(w.gstat.p, 0, 4 * n_groups, c->stream));
+  const uint32_t* goff = (const uint32_t*)w.goff.p;
+  uint32_t* gstat = (uint32_t*)w.gstat.p;
+  for (const ThLaunch& L : launches) {
+    const size_t m = L.hi - L.lo;
+    ++c->stat_thb[2];
+    if (m) {
+      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)c->in_b.p + 32 * L.lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
+      TRY(launch(c, c->stream, "lagrange_seg", grid_lanes(m), k_lagrange_seg, (const int32_t*)c->th_x.p, (const uint8_t*)c->status.p, m, (uint32_t)L.lo, goff + L.ga,
+                 (uint32_t)(L.gb - L.ga), (uint32_t)TH_BATCH_TBIG, sigs ? (uint8_t*)nullptr : (uint8_t*)c->scalars.p + 32 * L.lo, (uint32_t*)c->th_glv.p, (uint32_t*)w.gid.p,
+                 gstat + L.ga));
+    }
+    if (!sigs) continue;
+    if (m) TRY(launch(c, c->stream, "g1_smul_glv", grid_lanes(m), k_g1_smul_glv, (const uint8_t*)c->in_a.p + 64 * L.lo, (const uint32_t*)c->th_glv.p, (const uint32_t*)w.gid.p, m,
+                      (int32_t*)w.pts.p, gstat + L.ga));
+    const int32_t* src = (const int32_t*)w.pts.p;
+    size_t src_stride = m ? m : 1;
+    int dst = 0;
+    for (size_t lv = 0; lv < L.levels.size(); ++lv) {
+      const SegLevel& P = L.levels[lv];
+      const bool last = lv + 1 == L.levels.size();
+      int32_t* out = last ? (int32_t*)w.gsum.p + L.ga : (int32_t*)w.seg[dst].p;
+      TRY(launch(c, c->stream, "g1_seg_sum", grid_lanes(P.count), k_g1_seg_sum, src, src_stride, (const uint32_t*)nullptr, (const uint32_t*)w.start.p + P.first,
+                 (const uint32_t*)w.len.p + P.first, P.count, out, last ? n_groups : P.count));
+      src = out; src_stride = P.count; dst ^= 1;
+    }
+  }
+  if (sigs) TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(n_groups), k_g1p_to_bytes, (const int32_t*)w.gsum.p, n_groups, n_groups, (uint8_t*)w.out.p));
+  return launch(c, c->stream, "th_finish", grid_lanes(n_groups), k_th_finish, (const uint32_t*)gstat, n_groups, sigs ? (uint8_t*)w.out.p : (uint8_t*)nullptr, (uint8_t*)w.st.p);
+}
+
+static int th_args(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* second, bool need_second, const uint64_t* off, size_t n_groups, const void* out, const void* status) {
+  if (!off || !status) return BLSBN254_E_ARG;
+  if (check_offsets(off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
+  const size_t N = (size_t)(off[n_groups] - off[0]);
+  if (N && (!ids || !out || (need_second && !second))) return BLSBN254_E_ARG;
+  if (need_second && !out) return BLSBN254_E_ARG;
+  CHECK_LANES(c, N);
+  CHECK_LANES(c, n_groups);
+  return 0;
+}
+
+int blsbn254_threshold_combine_batch(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, const uint64_t* off, size_t n_groups,
+                                     uint8_t* out_sigs, uint8_t* status) {
+  if (!c) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  int rc = th_args(c, ids, partial_sigs, true, off, n_groups, out_sigs, status);
+  if (rc) return rc;
+  ENTER(c);
+  rc = th_enqueue(c, ids, partial_sigs, off, n_groups);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(out_sigs, c->thb.out.p, 64 * n_groups, hipMemcpyDeviceToHost, c->stream));
+  TRY(download(c, status, c->thb.st.p, n_groups));
+  // the large groups, one after the other through the single-group pipeline; their point check came from the lanes above
+  for (size_t g = 0; g < n_groups; ++g) {
+    const size_t t = (size_t)(off[g + 1] - off[g]);
+    if (t <= TH_BATCH_TBIG) { ++c->stat_thb[0]; continue; }
+    ++c->stat_thb[1];
+    uint8_t* o = out_sigs + 64 * g;
+    rc = threshold_combine_one(c, ids + 32 * off[g], partial_sigs + 64 * off[g], t, o);
+    if (rc < 0) return rc;
+    const uint8_t code = rc == BLSBN254_ERR_SCALAR ? BLSBN254_ERR_SCALAR : (rc == BLSBN254_ERR_G1 || status[g] == BLSBN254_ERR_G1) ? BLSBN254_ERR_G1 : 0;
+    status[g] = code;
+    if (code) { std::memset(o, 0, 64); o[63] = 1; }
+  }
+  return 0;
+}
+
+int blsbn254_lagrange_at_zero_batch(blsbn254_ctx* c, const uint8_t* ids, const uint64_t* off, size_t n_groups, uint8_t* out, uint8_t* status) {
+  if (!c) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  int rc = th_args(c, ids, nullptr, false, off, n_groups, out, status);
+  if (rc) return rc;
+  ENTER(c);
+  rc = th_enqueue(c, ids, nullptr, off, n_groups);
+  if (rc) return rc;
+  const size_t N = (size_t)(off[n_groups] - off[0]);
+  if (N) HIPCHK(c, hipMemcpyAsync(out, c->scalars.p, 32 * N, hipMemcpyDeviceToHost, c->stream));
+  TRY(download(c, status, c->thb.st.p, n_groups));
+  for (size_t g = 0; g < n_groups; ++g) {
+    const size_t t = (size_t)(off[g + 1] - off[g]);
+    uint8_t* o = out + 32 * (off[g] - off[0]);
+    if (t <= TH_BATCH_TBIG) ++c->stat_thb[0];
+    else {
+      ++c->stat_thb[1];
+      rc = lagrange_one(c, ids + 32 * off[g], t, o);
+      if (rc < 0) return rc;
+      status[g] = rc == BLSBN254_ERR_SCALAR ? BLSBN254_ERR_SCALAR : 0;
+    }
+    if (status[g]) std::memset(o, 0, 32 * t);            // the coefficients of a bad group: zero bytes
+  }
+  return 0;
+}
+
+int blsbn254_threshold_batch_stats(blsbn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BLSBN254_E_ARG;
+  for (int k = 0; k < 3; ++k) out[k] = c->stat_thb[k];
+  out[3] = TH_BATCH_TBIG;
+  return 0;
+}
+
+}  // extern "C"

@@ -134,6 +134,10 @@ BN_KERNEL k_lagrange_finish(const int32_t* pnum, const int32_t* pden, size_t t, 
 BN_KERNEL k_msm_window(const uint8_t* g1, const uint32_t* glv_ws, size_t t, int32_t* part, uint8_t* status);
 __global__ void __launch_bounds__(64) k_msm_finish(const int32_t* part, size_t n_chunks, uint8_t* out);
 BN_KERNEL k_msm_fold(const int32_t* in, size_t n_in, int32_t* out);
+BN_KERNEL k_lagrange_seg(const int32_t* x_ws, const uint8_t* id_ok, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, uint32_t t_big,
+                         uint8_t* scalars, uint32_t* glv_ws, uint32_t* gid, uint32_t* gstat);
+BN_KERNEL k_g1_smul_glv(const uint8_t* g1, const uint32_t* glv_ws, const uint32_t* gid, size_t m, int32_t* out_ws, uint32_t* gstat);
+__global__ void __launch_bounds__(256) k_th_finish(const uint32_t* gstat, size_t n_groups, uint8_t* out, uint8_t* status);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

@@ -452,6 +452,48 @@ class Engine:
         self._chk(self._lib.blsbn254_lagrange_at_zero(self._ctx, pa, ctypes.c_size_t(t), po))
         return o[:32 * t].tobytes()
 
+    @staticmethod
+    def _group_offsets(sets, width, what):
+        lens = np.fromiter(map(len, sets), dtype=np.uint64, count=len(sets))
+        if (lens % width).any():
+            raise ValueError("%s must be a multiple of %d bytes" % (what, width))
+        off = np.zeros(len(sets) + 1, dtype=np.uint64)
+        np.cumsum(lens // width, out=off[1:])
+        return off
+
+    def threshold_combine_batch(self, id_sets, sig_sets):
+        """id_sets / sig_sets: lists of byte strings, one per group (32 bytes per id, 64 per partial signature).  Returns
+        (sigs, status): 64 bytes and one status byte per group (0, ERR_SCALAR = 1, ERR_G1 = 2); a bad group's signature is the
+        identity encoding.  No exception for a bad group."""
+        g = len(id_sets)
+        if len(sig_sets) != g:
+            raise ValueError("one set of partial signatures per set of ids")
+        off = self._group_offsets(id_sets, 32, "a set of ids")
+        if not np.array_equal(off, self._group_offsets(sig_sets, 64, "a set of partial signatures")):
+            raise ValueError("a group needs as many partial signatures as ids")
+        a, pa = _inbuf(b"".join(id_sets)); s, ps = _inbuf(b"".join(sig_sets)); o, po = _outbuf(64 * g)
+        st = np.zeros(max(g, 1), dtype=np.uint8); pst = st.ctypes.data_as(_u8p)      # (large outputs share ONE buffer per thread: not for two)
+        self._chk(self._lib.blsbn254_threshold_combine_batch(self._ctx, pa, ps, off.ctypes.data_as(_u64p), ctypes.c_size_t(g), po, pst))
+        return o[:64 * g].tobytes(), st[:g].tobytes()
+
+    def lagrange_at_zero_batch(self, id_sets):
+        """(coefficients, status): 32 bytes per id in the order given, one status byte per group; the coefficients of a bad
+        group are zero bytes."""
+        g = len(id_sets)
+        off = self._group_offsets(id_sets, 32, "a set of ids")
+        n = int(off[-1])
+        a, pa = _inbuf(b"".join(id_sets)); o, po = _outbuf(32 * n)
+        st = np.zeros(max(g, 1), dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_lagrange_at_zero_batch(self._ctx, pa, off.ctypes.data_as(_u64p), ctypes.c_size_t(g), po, pst))
+        return o[:32 * n].tobytes(), st[:g].tobytes()
+
+    def threshold_batch_stats(self):
+        """dict: groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches, and the
+        hand-over size t_big of this build"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_threshold_batch_stats(self._ctx, o))
+        return {"batched_groups": int(o[0]), "single_groups": int(o[1]), "launches": int(o[2]), "t_big": int(o[3])}
+
     # ---- Gt group operations and the field-primitive debug ABI
     FIELD_OP_WIDTH = {**{k: 32 for k in range(0, 9)}, **{k: 64 for k in range(16, 22)}, **{k: 192 for k in range(32, 36)},
                       **{k: 384 for k in range(48, 57)}}

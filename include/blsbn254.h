@@ -262,6 +262,28 @@ int blsbn254_threshold_combine(blsbn254_ctx* ctx, const uint8_t* ids, const uint
 /* The Lagrange coefficients alone: out[i] = prod_{j != i} x_j / (x_j - x_i) as 32 bytes big-endian (Scalar mul / invert,
  * scalar.rs:523-548, :216-219).  ids that do not decode (>= r), are zero or repeat return BLSBN254_ERR_SCALAR. */
 int blsbn254_lagrange_at_zero(blsbn254_ctx* ctx, const uint8_t* ids, size_t t, uint8_t* out /* t*32 */);
+/* n_groups independent blsbn254_threshold_combine in one call.  Group g owns the shares off[g] .. off[g+1] of ids (32 B
+ * each) and partial_sigs (64 B each); off = n_groups + 1 non-decreasing element offsets, host array (need not start at 0).
+ * out_sigs[64 g ..] = sum_i lambda_i sigma_i of group g, byte-identical to blsbn254_threshold_combine on that group.
+ * status[g] = 0, or the code the single call returns for that group alone: BLSBN254_ERR_SCALAR (an id >= r, == 0, or
+ * repeated INSIDE the group; the same id in two groups is fine), else BLSBN254_ERR_G1 (a partial signature that does not
+ * decode, or is off the curve).  The curve equation is tested here and NOT by the single call, which only requires a
+ * partial signature to decode and returns whatever the addition formulas give for an off-curve one: "equal to the single
+ * call" (bytes and code) therefore holds for inputs whose points are on the curve (the identity included) or do not
+ * decode.  A bad group is never an error of the call: its output is the identity encoding (0, 1) and its neighbours are
+ * unaffected.  An empty group gives the identity, status 0.  Groups of any size are accepted; the path is chosen by group
+ * size (blsbn254_threshold_batch_stats), never the result.
+ * Return: 0; BLSBN254_E_ARG for NULL arguments, decreasing offsets, more than 2^23 shares or groups.  n_groups == 0 -> 0. */
+int blsbn254_threshold_combine_batch(blsbn254_ctx* ctx, const uint8_t* ids, const uint8_t* partial_sigs, const uint64_t* off,
+                                     size_t n_groups, uint8_t* out_sigs /* n_groups*64 */, uint8_t* status /* n_groups */);
+/* The coefficients alone: out[32 i ..] for every share i = 0 .. off[n_groups] - off[0], per group as
+ * blsbn254_lagrange_at_zero; status as above (BLSBN254_ERR_SCALAR only); the coefficients of a bad group are zero bytes. */
+int blsbn254_lagrange_at_zero_batch(blsbn254_ctx* ctx, const uint8_t* ids, const uint64_t* off, size_t n_groups,
+                                    uint8_t* out /* N*32 */, uint8_t* status /* n_groups */);
+/* since context creation: out[0] groups served by the lane-per-share kernels, out[1] groups handed to the single-group
+ * pipeline (more shares than out[3]), out[2] launches of the lane-per-share pipeline; out[3] the hand-over size of this
+ * build (a constant) */
+int blsbn254_threshold_batch_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 
 /* ---- signing side (also used to generate large synthetic batches) ----------- */
 /* sig_i = [sk_i] H(msg_i): G1Projective::hash (g1.rs:910-919) + Mul<Scalar> (g1.rs:518-534, :821-841).
