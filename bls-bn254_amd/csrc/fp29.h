@@ -537,7 +537,9 @@ BN_INL void sg_update(int32_t* a, int32_t* b, int32_t u, int32_t v, int32_t q, i
   a[NL - 1] = (int32_t)ca; b[NL - 1] = (int32_t)cb;
 }
 constexpr int SG_BATCHES = 21;
-BN_FUNC Fp fp_inv(const Fp& a) {
+// The recurrence alone.  done = g reached 0, which the 590-step bound guarantees; a caller that cannot afford fp_inv's fallback
+// (its window table lives in scratch memory) takes the flag and fails closed on it.
+BN_FUNC Fp fp_inv_divsteps(const Fp& a, bool& done) {
   const Fp x = fp_from_mont(a);                       // the plain value as a canonical integer in [0, p), strict limbs
   int32_t f[NL], g[NL], d[NL], e[NL];
   BN_UNROLL for (int i = 0; i < NL; ++i) { f[i] = bnc::P[i]; g[i] = x.l[i]; d[i] = 0; e[i] = i == 0 ? 1 : 0; }
@@ -550,17 +552,23 @@ BN_FUNC Fp fp_inv(const Fp& a) {
   }
   int32_t gnz = 0;
   BN_UNROLL for (int i = 0; i < NL; ++i) gnz |= g[i];
-  // g = 0 is guaranteed by the 590-step bound; should a lane ever miss it the whole wave takes Fermat's route instead
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (__builtin_amdgcn_ballot_w64(gnz != 0) != 0) return fp_inv_pow(a);
-#else
-  if (gnz != 0) return fp_inv_pow(a);
-#endif
+  done = gnz == 0;
   const bool neg = f[NL - 1] < 0;                     // f = -1: limbs all ones below a negative top limb
   Fp di;
   BN_UNROLL for (int i = 0; i < NL; ++i) di.l[i] = neg ? -d[i] : d[i];
   BN_TRK(set_trk(di, -1, 1, -0.14, 0.14, 22);)
   return fp_mul(di, fp_const(bnc::R2));               // di = x^-1 as a plain integer: times R^2 / R = its Montgomery form
+}
+BN_FUNC Fp fp_inv(const Fp& a) {
+  bool done;
+  const Fp r = fp_inv_divsteps(a, done);
+  // g = 0 is guaranteed by the 590-step bound; should a lane ever miss it the whole wave takes Fermat's route instead
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (__builtin_amdgcn_ballot_w64(!done) != 0) return fp_inv_pow(a);
+#else
+  if (!done) return fp_inv_pow(a);
+#endif
+  return r;
 }
 // y = a^((p+1)/4); is_sq = (y^2 == a).  One exponentiation gives Euler's criterion (fp.rs:428-431)
 // and the square root (sqrt_ratio with v = 1, fp.rs:212-243) together.

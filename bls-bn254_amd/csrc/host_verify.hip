@@ -22,7 +22,7 @@ int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_
   HIPCHK(c, c->prep_raw.reserve(u * PREP_RAW_LIMBS * 4));
   HIPCHK(c, fork_stream2(c));
   TRY(launch_g2_prepare(c, c->stream2, d_pks, d_keys, u, (int32_t*)c->prep_raw.p, key_ok, d_u));
-  TRY(launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)u, table, d_u));
+  TRY(launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)u, table, d_u, key_ok));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   return 0;
 }
@@ -269,7 +269,7 @@ int blsbn254_g2_prepare_batch(blsbn254_ctx* c, const uint8_t* pks, size_t u, bls
   if (u) HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * u, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * u, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));
   TRY(launch_g2_prepare(c, c->stream, (const uint8_t*)c->in_a.p, nullptr, u1, (int32_t*)p->raw.p, (uint8_t*)p->ok.p, nullptr));
-  TRY(launch(c, c->stream, "g2_expand", grid_lanes(u1 * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)p->raw.p, (uint32_t)u1, (int32_t*)p->table.p, (const uint32_t*)nullptr));
+  TRY(launch(c, c->stream, "g2_expand", grid_lanes(u1 * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)p->raw.p, (uint32_t)u1, (int32_t*)p->table.p, (const uint32_t*)nullptr, (uint8_t*)p->ok.p));
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) { (void)hipDeviceSynchronize(); }       // nothing may still be writing the buffers the owner frees
   HIPCHK(c, es);

@@ -6,7 +6,7 @@
 //     optimal ate loop written as a table (g2_prepare_lines, pairing.h);
 //   * the small kernels that carry validity back from key-sorted order to the caller's order.
 // Own translation unit, tower / curve functions force-inlined.
-#define BN_WANT_LINE_TABLE
+#define BN_WANT_UNIT_LINE_TABLE
 #define BN_LINE_TABLE_QUAL static __device__ const
 #include "lane_ops.h"
 #include "kernels.h"
@@ -145,30 +145,47 @@ BN_KERNEL k_g2_prepare(const uint8_t* pks, const uint32_t* keys, uint32_t u, int
     g2_prepare_lines(q, Ws{table, 1, k * (uint32_t)(BN_NEG_G2_LINES * 54 * 4), true});
   }
 }
-// The pair tables: lane (key k, step t) multiplies the key's line t with the fixed -G2gen line t (pairing.h line_pair_expand):
-// raw (u x 88 x 54 limbs) -> expanded (u x 88 x 162 limbs).  u x 88 lanes: the part of the preparation that is not sequential.
+// The pair tables: lane (key k, step t) combines the key's line t with the fixed -G2gen line t into the step's unit entry (pairing.h
+// line_pair_expand_unit): raw (u x 88 x 54 limbs) -> expanded (u x 88 x 162 limbs).  u x 88 lanes: the part of the preparation that
+// is not sequential.  The entry is divided by a3 b3: a3^-1 is folded into the generated table of the fixed lines, and b3^-1 is ONE Fp
+// inversion per four entries (fp2_inv4), taken by the first wave of the workgroup for all 256 while the others wait at the barrier --
+// a lane per entry running its own divstep would triple the kernel.  A zero b3 (unreachable for a key of the r-torsion) clears key_ok.
 // A lane's entry is 648 consecutive bytes, so a lane-by-lane store instruction would touch 64 different cache lines with 4 bytes
 // each (the kernel was bound by exactly that: 233 MB of partial-line writes per 4096 keys).  The entries of a workgroup are one
 // contiguous block of 256 x 648 bytes: every product goes to LDS first ([lane][18 limbs]) and is written out by the workgroup
 // in runs of 18 consecutive dwords; the raw triples come in the same way.
-BN_KERNEL k_g2_expand(const int32_t* raw, uint32_t u, int32_t* expanded, const uint32_t* d_u) {
+BN_KERNEL k_g2_expand(const int32_t* raw, uint32_t u, int32_t* expanded, const uint32_t* d_u, uint8_t* key_ok) {
   __shared__ int32_t stage[256 * 54];                       // the workgroup's raw triples, then one Fp2 product per lane at a time
   const uint32_t e0 = blockIdx.x * blockDim.x, e = e0 + threadIdx.x;
   uint32_t total = u * (uint32_t)BN_NEG_G2_LINES;
   if (d_u && *d_u * (uint32_t)BN_NEG_G2_LINES < total) total = *d_u * (uint32_t)BN_NEG_G2_LINES;
   if (e0 >= total) return;                                  // whole workgroups leave together (barriers below)
-  const uint32_t here = total - e0 < 256u ? total - e0 : 256u;
+  const uint32_t here = total - e0 < 256u ? total - e0 : 256u;      // a multiple of 4: 88 and 256 are
   for (uint32_t x = threadIdx.x; x < here * 54u; x += 256u) stage[x] = raw[(size_t)e0 * 54u + x];      // coalesced: the block's triples are contiguous
+  __syncthreads();
+  if (threadIdx.x < 64u) {                                  // b3 -> b3^-1 in place, four entries per lane of the first wave
+    const uint32_t g = 4u * threadIdx.x;
+    const bool lg = g < here;
+    Fp2 x[4];
+    bool zero[4];
+    for (int q = 0; q < 4; ++q) x[q] = fp2_load_limbs(Ws{stage, 1, ((lg ? g + (uint32_t)q : 0u) * 54u + 18u) * 4u, false});
+    fp2_inv4(x, zero);
+    if (lg) {
+      for (int q = 0; q < 4; ++q) {
+        int32_t* o = stage + (g + (uint32_t)q) * 54u + 18u;
+        BN_UNROLL for (int l = 0; l < NL; ++l) { o[l] = x[q].c0.l[l]; o[NL + l] = x[q].c1.l[l]; }
+        if (zero[q]) key_ok[(e0 + g + (uint32_t)q) / (uint32_t)BN_NEG_G2_LINES] = 0;
+      }
+    }
+  }
   __syncthreads();
   const bool live = threadIdx.x < here;
   const uint32_t t = e % (uint32_t)BN_NEG_G2_LINES;
-  const Line a = line_from_table(BN_NEG_G2_LINE_TABLE[t]);
-  const Line b = line_load_limbs(Ws{stage, 1, (live ? threadIdx.x : 0u) * (uint32_t)(54 * 4), false});
+  const Ws bw = {stage, 1, (live ? threadIdx.x : 0u) * (uint32_t)(54 * 4), false};
+  const UnitPair up = unit_pair_of(BN_NEG_G2_UNIT_LINE_TABLE[t], fp2_load_limbs(bw), fp2_load_limbs_lazy(ws_at(bw, 18)), fp2_load_limbs(ws_at(bw, 36)));
   __syncthreads();
-  BN_UNROLL for (int j = 0; j < 9; ++j) {                   // T0 .. T8 in the order of line_pair_expand
-    const Fp2 p = j == 0 ? fp2_mul(a.c0, b.c0) : j == 1 ? fp2_mul_xi(fp2_mul(a.c2, b.c2)) : j == 2 ? fp2_mul(a.c1, b.c1) : j == 3 ? fp2_mul(a.c1, b.c2)
-                : j == 4 ? fp2_mul(a.c2, b.c1) : j == 5 ? fp2_mul(a.c0, b.c1) : j == 6 ? fp2_mul(a.c1, b.c0) : j == 7 ? fp2_mul(a.c0, b.c2) : fp2_mul(a.c2, b.c0);
-    fp2_store_limbs_lazy(Ws{stage, 1, threadIdx.x * (uint32_t)(18 * 4), false}, p);
+  BN_UNROLL for (int j = 0; j < 9; ++j) {                   // T0 .. T8 in the order of line_pair_expand_unit
+    fp2_store_limbs_lazy(Ws{stage, 1, threadIdx.x * (uint32_t)(18 * 4), false}, unit_pair_entry(up, j));
     __syncthreads();
     for (uint32_t x = threadIdx.x; x < here * 18u; x += 256u) {
       const uint32_t lane = x / 18u, limb = x - 18u * lane;

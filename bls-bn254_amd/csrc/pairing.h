@@ -430,21 +430,25 @@ BN_FUNC Fp12 fe_easy_tail(const Fp12& a, const FeEasyHead& h, const Fp& nu_inv) 
   Fp12 t = fp12_mul(fp12_conj(a), inv);
   return fp12_mul(fp12_frob<2>(t), t);
 }
-// x_i^-1, i < 4, with one inversion; x_i must be multiplication outputs (or normalised)
-BN_FUNC void fp_inv4(Fp x[4]) {
+// x_i^-1, i < 4, with one inversion; x_i must be multiplication outputs (or normalised).  POW_FALLBACK = false: the divstep
+// recurrence without fp_inv's fallback (no scratch memory); returns whether it finished, as the 590-step bound guarantees.
+template <bool POW_FALLBACK = true>
+BN_FUNC bool fp_inv4(Fp x[4]) {
   BN_CTX;
   bool z[4];
   Fp v[4], pre[4];
   for (int i = 0; i < 4; ++i) { z[i] = fp_is_zero(x[i]); v[i] = fp_select(z[i], fp_one(), fp_norm(x[i])); }
   pre[0] = v[0];
   for (int i = 1; i < 4; ++i) pre[i] = fp_mul(pre[i - 1], v[i]);
-  Fp inv = fp_inv(pre[3]);
+  bool done = true;
+  Fp inv = POW_FALLBACK ? fp_inv(pre[3]) : fp_inv_divsteps(pre[3], done);
   for (int i = 3; i >= 1; --i) {
     Fp r = fp_mul(inv, pre[i - 1]);
     inv = fp_mul(inv, v[i]);
     x[i] = fp_select(z[i], fp_zero(), r);
   }
   x[0] = fp_select(z[0], fp_zero(), inv);
+  return done;
 }
 // x0 = t^x  ->  a = t^-2x, b = t^-6x
 BN_FUNC void fe_h1(const Fp12& x0, Fp12& a, Fp12& b) {
@@ -695,55 +699,113 @@ BN_FUNC Fp12 miller_loop_prepared(const Ws& inv, const Ws& ktab_in) {
   }
   return f;
 }
-// The same loop when EVERY lane of the wave reads the same key's table (key-sorted order: the usual case): the entries are read
-// through a constant-address-space pointer with no per-lane part, i.e. by SCALAR loads into scalar registers -- no vector
-// registers held for them, the fetch runs ahead of the arithmetic -- and the double products take them as scalar operands.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const __attribute__((address_space(4))) int32_t* bn_const_i32p;
-#else
-typedef const int32_t* bn_const_i32p;
-#endif
-BN_INL Fp2 fp2_load_limbs_const(bn_const_i32p e) {
-  Fp2 c;
-  BN_UNROLL for (int k = 0; k < NL; ++k) { c.c0.l[k] = e[k]; c.c1.l[k] = e[9 + k]; }
-  BN_TRK(set_trk(c.c0, -4e-6, 1.0 + 4e-6, -0.02, 0.02, 1.2); set_trk(c.c1, -4e-6, 1.0 + 4e-6, -0.02, 0.02, 1.2);
-         check_actual(c.c0, "pair table entry"); check_actual(c.c1, "pair table entry");)
-  return c;
+// ---- Line pairs scaled to a unit coefficient.  Any factor in a proper subfield of Fp12 is removed by the easy part of the final
+// exponentiation (the loop above already relies on it for the powers of Z); so is an Fp2 factor chosen per (key, step) and an Fp
+// factor chosen per tuple.  The v-coefficient of the pair, T2 xs X, is the one coefficient that is a single table entry times a
+// single tuple value: with the table divided by T2 = a3 b3 and the tuple's coordinate values by xs X it is exactly 1.  The
+// evaluation loses its scaling (fp2_mul_fp) and the sparse product one of its 17 Fp2 products (a1 * 1): 810 MADs per pair.
+//   unit entry (same 162-limb layout, read unchanged by tri.h / wide.h, whose values change by that Fp2 factor only), with
+//   a' = (a0 / a3, 1, a4 / a3) generated offline (BN_NEG_G2_UNIT_LINE_TABLE) and b' = (b0 / b3, 1, b4 / b3):
+//   T0 = a'0 b'0, T1 = xi a'4 b'4, T2 = 1, T3 = b'4, T4 = a'4, T5 = a'0, T6 = b'0, T7 = a'0 b'4, T8 = a'4 b'0
+// -- four Fp2 products and two for b' instead of nine, plus b3^-1, shared four ways (fp2_inv4).
+// b3 never vanishes for a key of the r-torsion (tests/test_unit_pairs.py walks the loop's scalars); a zero b3 (inv0: its
+// inverse is taken as zero) leaves a well-defined entry and is reported, so that the caller clears the key's validity.
+BN_FUNC void fp2_inv4(Fp2 x[4], bool zero[4]) {                   // x_i^-1 with ONE Fp inversion; x_i canonical / normalised
+  BN_CTX;
+  Fp2 n[4];
+  Fp nu[4];
+  for (int i = 0; i < 4; ++i) { n[i] = fp2_norm(x[i]); nu[i] = fp_dot2(n[i].c0, n[i].c0, n[i].c1, n[i].c1); }
+  const bool done = fp_inv4<false>(nu);                           // an unfinished recurrence (excluded by its bound) is reported like a zero
+  for (int i = 0; i < 4; ++i) {
+    zero[i] = !done | fp_is_zero(nu[i]);                         // the norm c0^2 + c1^2 vanishes for x = 0 only (-1 is a non-residue)
+    x[i] = {fp_mul(n[i].c0, nu[i]), fp_mul(fp_neg(n[i].c1), nu[i])};
+  }
 }
-BN_FUNC Fp12 ell_pair_expanded_uniform(const Fp12& f, bn_const_i32p e, const Ws& cw) {
-  Fp X = fp_load_mem(cw), Y = fp_load_mem(ws_at(cw, 9)), Z = fp_load_mem(ws_at(cw, 18));
-  Fp xsX = fp_load_mem(ws_at(cw, 27)), ysY = fp_load_mem(ws_at(cw, 36)), xsZ = fp_load_mem(ws_at(cw, 45));
-  Fp ysZ = fp_load_mem(ws_at(cw, 54)), ysX = fp_load_mem(ws_at(cw, 63)), xsY = fp_load_mem(ws_at(cw, 72));
-  Fp6 l0 = {fp2_dot_fp(fp2_load_limbs_const(e), ysY, fp2_load_limbs_const(e + 18), Z),
-            fp2_mul_fp(fp2_load_limbs_const(e + 36), xsX),
-            fp2_dot_fp(fp2_load_limbs_const(e + 54), xsZ, fp2_load_limbs_const(e + 72), X)};
-  Fp2 l10 = fp2_dot_fp(fp2_load_limbs_const(e + 90), ysX, fp2_load_limbs_const(e + 108), xsY);
-  Fp2 l11 = fp2_dot_fp(fp2_load_limbs_const(e + 126), ysZ, fp2_load_limbs_const(e + 144), Y);
-  Fp6 v0 = fp6_mul(f.c0, l0);
+BN_INL Fp2 fp2_unit_line_const(const int32_t* c) {                // an entry half of BN_NEG_G2_UNIT_LINE_TABLE: canonical, < p
+  Fp2 r;
+  BN_UNROLL for (int i = 0; i < NL; ++i) { r.c0.l[i] = c[i]; r.c1.l[i] = c[NL + i]; }
+  BN_TRK(set_trk(r.c0, 0, 1, 0, 0.006, 1); set_trk(r.c1, 0, 1, 0, 0.006, 1);)
+  return r;
+}
+struct UnitPair { Fp2 a0, a4, u0, u4; };                         // a'0, a'4 and b'0 = b0 / b3, b'4 = b4 / b3
+BN_FUNC UnitPair unit_pair_of(const int32_t* au, const Fp2& b0, const Fp2& b3_inv, const Fp2& b4) {
+  BN_CTX;
+  return {fp2_unit_line_const(au), fp2_unit_line_const(au + 18), fp2_mul(b0, b3_inv), fp2_mul(b4, b3_inv)};
+}
+BN_INL Fp2 unit_pair_entry(const UnitPair& q, int j) {            // T_j of the list above (slot 2 holds the Montgomery form of one)
+  return j == 0 ? fp2_mul(q.a0, q.u0) : j == 1 ? fp2_mul_xi(fp2_mul(q.a4, q.u4)) : j == 2 ? fp2_one() : j == 3 ? q.u4 : j == 4 ? q.a4
+       : j == 5 ? q.a0 : j == 6 ? q.u0 : j == 7 ? fp2_mul(q.a0, q.u4) : fp2_mul(q.a4, q.u0);
+}
+BN_FUNC void line_pair_expand_unit(const int32_t* au, const Fp2& b0, const Fp2& b3_inv, const Fp2& b4, const Ws& out) {
+  BN_CTX;
+  const UnitPair q = unit_pair_of(au, b0, b3_inv, b4);
+  for (int j = 0; j < 9; ++j) fp2_store_limbs_lazy(ws_at(out, 18 * (size_t)j), unit_pair_entry(q, j));
+}
+// The tuple's side: the eight coordinate values of ell_pair_unit, each times s = (xs X)^-1, into cw (72 limbs):
+//   cw: 0 Y, 1 Z, 2 ys Y, 3 xs Z, 4 ys Z, 5 ys X, 6 xs Y, 7 X        (all times s)
+// xs is never zero (x = 0 is not on y^2 = x^3 + 3: 3 is a non-residue).  X = 0 is H(msg) = the identity: the true v-coefficient is
+// then 0, not 1 -- the lane keeps scale 1 and carries the 0 / 1 of that coefficient as the returned flag (`unit`), so the loop's
+// value stays an Fp multiple of the unscaled loop's for every input.  Inputs normalised.  ok: the inversion finished (the divstep
+// recurrence without fp_inv's fallback, whose table would live in scratch memory); the caller fails the tuple otherwise.
+BN_FUNC bool miller_unit_coords(const Fp& xs, const Fp& ys, const Fp& X, const Fp& Y, const Fp& Z, const Ws& cw, bool& ok) {
+  BN_CTX;
+  const Fp xsX = fp_mul(xs, X);
+  const bool unit = !fp_is_zero(xsX);
+  const Fp s = fp_select(unit, fp_inv_divsteps(xsX, ok), fp_one());
+  const Fp Xs = fp_mul(X, s), Ys = fp_mul(Y, s), Zs = fp_mul(Z, s);
+  fp_store_mem(cw, Ys); fp_store_mem(ws_at(cw, 9), Zs);
+  fp_store_mem(ws_at(cw, 18), fp_mul(ys, Ys)); fp_store_mem(ws_at(cw, 27), fp_mul(xs, Zs)); fp_store_mem(ws_at(cw, 36), fp_mul(ys, Zs));
+  fp_store_mem(ws_at(cw, 45), fp_mul(ys, Xs)); fp_store_mem(ws_at(cw, 54), fp_mul(xs, Ys)); fp_store_mem(ws_at(cw, 63), Xs);
+  return unit;
+}
+// a * (b0 + m v + b2 v^2), m = unit ? 1 : 0: fp6_mul with a1 b1 = a1 (or 0), five Fp2 products; the other Karatsuba products keep their shape
+BN_FUNC Fp6 fp6_mul_unit1(const Fp6& a, const Fp2& b0, const Fp2& b2, bool unit) {
+  BN_CTX;
+  const Fp2 b1 = fp2_select(unit, fp2_one(), fp2_zero());
+  Fp2 v0 = fp2_mul(a.c0, b0), v1 = fp2_select(unit, a.c1, fp2_zero()), v2 = fp2_mul(a.c2, b2);
+  Fp2 w0 = fp2_mul(fp2_sub(a.c1, a.c2), fp2_sub(b1, b2));
+  Fp2 w1 = fp2_mul(fp2_sub(a.c0, a.c1), fp2_sub(b0, b1));
+  Fp2 w2 = fp2_mul(fp2_sub(a.c0, a.c2), fp2_sub(b0, b2));
+  Fp2 t0 = fp2_sub(fp2_add(v1, v2), w0);        // a1 b2 + a2 b1
+  Fp2 t1 = fp2_sub(fp2_add(v0, v1), w1);        // a0 b1 + a1 b0
+  Fp2 t2 = fp2_sub(fp2_add(v0, v2), w2);        // a0 b2 + a2 b0
+  return {fp2_add_mul_xi(v0, t0), fp2_add_mul_xi(t1, v2), fp2_norm(fp2_add(t2, v1))};
+}
+// f * (la lb Z s / T2) from the unit entry `e` and the scaled coordinate values in `cw` (miller_unit_coords):
+//   (T0 ysY + T1 Z) + m v + (T3 xsZ + T4 X) v^2 + [(T5 ysX + T6 xsY) + (T7 ysZ + T8 Y) v] w
+BN_FUNC Fp12 ell_pair_unit(const Fp12& f, const Ws& e, const Ws& cw, bool unit) {
+  BN_CTX;
+  Fp Y = fp_load_mem(cw), Z = fp_load_mem(ws_at(cw, 9)), ysY = fp_load_mem(ws_at(cw, 18)), xsZ = fp_load_mem(ws_at(cw, 27));
+  Fp ysZ = fp_load_mem(ws_at(cw, 36)), ysX = fp_load_mem(ws_at(cw, 45)), xsY = fp_load_mem(ws_at(cw, 54)), X = fp_load_mem(ws_at(cw, 63));
+  Fp2 l00 = fp2_dot_fp(fp2_load_limbs_lazy(e), ysY, fp2_load_limbs_lazy(ws_at(e, 18)), Z);
+  Fp2 l02 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 54)), xsZ, fp2_load_limbs_lazy(ws_at(e, 72)), X);
+  Fp2 l10 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 90)), ysX, fp2_load_limbs_lazy(ws_at(e, 108)), xsY);
+  Fp2 l11 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 126)), ysZ, fp2_load_limbs_lazy(ws_at(e, 144)), Y);
+  Fp6 v0 = fp6_mul_unit1(f.c0, l00, l02, unit);
   Fp6 v1 = fp6_mul_by_01(f.c1, l10, l11);
-  Fp6 dl = {fp2_norm(fp2_sub(l10, l0.c0)), fp2_norm(fp2_sub(l11, l0.c1)), fp2_norm(fp2_neg(l0.c2))};       // l1 - l0
+  Fp6 dl = {fp2_norm(fp2_sub(l10, l00)), fp2_norm(fp2_sub(l11, fp2_select(unit, fp2_one(), fp2_zero()))), fp2_norm(fp2_neg(l02))};       // l1 - l0
   Fp6 w = fp6_mul(fp6_norm(fp6_sub(f.c0, f.c1)), dl);
   return {fp6_add_mul_v(v0, v1), fp6_norm(fp6_add(fp6_add(w, v0), v1))};
 }
-BN_FUNC Fp12 miller_loop_prepared_uniform(const Ws& inv, const int32_t* ktab_uniform) {
+// cw (LDS, 72 limbs) and `unit` from miller_unit_coords; ktab: this lane's key, 88 x 162 limbs of unit entries
+BN_FUNC Fp12 miller_loop_prepared_unit(const Ws& cw, const Ws& ktab_in, bool unit) {
   Fp12 f = fp12_one();
-  Ws p = inv;
-  bn_const_i32p kt = (bn_const_i32p)ktab_uniform;
+  Ws p = cw, kt = ktab_in;
   int ti = 0;
   for (int j = bnc::ATE_NAF_LEN - 2; j >= 0; --j) {
     f = fp12_sqr(f);
-    BN_OPAQUE(p);
-    f = ell_pair_expanded_uniform(f, kt + 162 * ti, p);
+    BN_OPAQUE(kt); BN_OPAQUE(p);
+    f = ell_pair_unit(f, ws_at(kt, 162 * (size_t)ti), p, unit);
     ++ti;
     if (ate_naf_digit(j) != 0) {
-      BN_OPAQUE(p);
-      f = ell_pair_expanded_uniform(f, kt + 162 * ti, p);
+      BN_OPAQUE(kt); BN_OPAQUE(p);
+      f = ell_pair_unit(f, ws_at(kt, 162 * (size_t)ti), p, unit);
       ++ti;
     }
   }
   for (int e = 0; e < 2; ++e) {
-    BN_OPAQUE(p);
-    f = ell_pair_expanded_uniform(f, kt + 162 * ti, p);
+    BN_OPAQUE(kt); BN_OPAQUE(p);
+    f = ell_pair_unit(f, ws_at(kt, 162 * (size_t)ti), p, unit);
     ++ti;
   }
   return f;

@@ -271,6 +271,19 @@ def main():
             ls += mont(v[0]) + mont(v[1])
         s.append(" " + fmt_limbs(ls) + ",\n")
     s.append("};\n#endif\n")
+    # the same lines scaled to a unit x-coefficient, (c0 / c1, c2 / c1): the fixed half of the unit pair table (pairing.h
+    # line_pair_expand_unit).  c1 of a tangent is -6 x^2 z^2 and of a chord -4 (y_Q z^3 - y), both non-zero on the r-torsion.
+    assert all(c[1] != (0, 0) for c in tab), "a fixed line with a zero x-coefficient"
+    s.append("// The same lines divided by their x-coefficient c1: (c0 / c1, c2 / c1), 36 limbs per entry.\n")
+    s.append("#ifdef BN_WANT_UNIT_LINE_TABLE\n")
+    s.append("BN_LINE_TABLE_QUAL int32_t BN_NEG_G2_UNIT_LINE_TABLE[%d][36] = {\n" % len(tab))
+    for c in tab:
+        ci = f2inv(c[1])
+        ls = []
+        for v in (f2mul(c[0], ci), f2mul(c[2], ci)):
+            ls += mont(v[0]) + mont(v[1])
+        s.append(" " + fmt_limbs(ls) + ",\n")
+    s.append("};\n#endif\n")
     with open(out, "w") as f:
         f.write("".join(s))
     print("wrote", os.path.normpath(out), "(%d line entries)" % len(tab))
