@@ -3,7 +3,9 @@
 // (pairings.rs:808-857) for two terms -- and since the first term's table (-G2gen) is the same for every tuple, the per-key
 // table holds the nine coefficient products of each step's line PAIR, divided by the one that multiplies xs X (k_g2_expand;
 // pairing.h line_pair_expand_unit), and the tuple's coordinate values are divided by xs X: that coefficient of the pair is 1.
-// No point arithmetic, no running point: per loop digit one squaring of f, four coefficient evaluations and one sparse product.
+// No point arithmetic, no running point: per loop digit one squaring of f, four coefficient evaluations and one product of f with the
+// pair in twelve Fp2 products (three 3 x 2 products over Fp2[w] by evaluation at 0, inf, 1, -1; pairing.h ell_pair_unit), which
+// yields twice the value: the loop's result carries 2^88, removed by the final exponentiation like the other subfield factors.
 // Lanes run in key-sorted order (perm), so a wave reads one key's table at (mostly) one address.
 // Same compile policy as the other Miller units (-DBN_FORCE_INLINE -DBN_LC_MAD).
 #include "lane_ops.h"

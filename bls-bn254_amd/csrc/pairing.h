@@ -758,34 +758,85 @@ BN_FUNC bool miller_unit_coords(const Fp& xs, const Fp& ys, const Fp& X, const F
   fp_store_mem(ws_at(cw, 45), fp_mul(ys, Xs)); fp_store_mem(ws_at(cw, 54), fp_mul(xs, Ys)); fp_store_mem(ws_at(cw, 63), Xs);
   return unit;
 }
-// a * (b0 + m v + b2 v^2), m = unit ? 1 : 0: fp6_mul with a1 b1 = a1 (or 0), five Fp2 products; the other Karatsuba products keep their shape
-BN_FUNC Fp6 fp6_mul_unit1(const Fp6& a, const Fp2& b0, const Fp2& b2, bool unit) {
-  BN_CTX;
-  const Fp2 b1 = fp2_select(unit, fp2_one(), fp2_zero());
-  Fp2 v0 = fp2_mul(a.c0, b0), v1 = fp2_select(unit, a.c1, fp2_zero()), v2 = fp2_mul(a.c2, b2);
-  Fp2 w0 = fp2_mul(fp2_sub(a.c1, a.c2), fp2_sub(b1, b2));
-  Fp2 w1 = fp2_mul(fp2_sub(a.c0, a.c1), fp2_sub(b0, b1));
-  Fp2 w2 = fp2_mul(fp2_sub(a.c0, a.c2), fp2_sub(b0, b2));
-  Fp2 t0 = fp2_sub(fp2_add(v1, v2), w0);        // a1 b2 + a2 b1
-  Fp2 t1 = fp2_sub(fp2_add(v0, v1), w1);        // a0 b1 + a1 b0
-  Fp2 t2 = fp2_sub(fp2_add(v0, v2), w2);        // a0 b2 + a2 b0
-  return {fp2_add_mul_xi(v0, t0), fp2_add_mul_xi(t1, v2), fp2_norm(fp2_add(t2, v1))};
-}
-// f * (la lb Z s / T2) from the unit entry `e` and the scaled coordinate values in `cw` (miller_unit_coords):
-//   (T0 ysY + T1 Z) + m v + (T3 xsZ + T4 X) v^2 + [(T5 ysX + T6 xsY) + (T7 ysZ + T8 Y) v] w
+// 2 f * (la lb Z s / T2) from the unit entry `e` and the scaled coordinate values in `cw` (miller_unit_coords).  The pair is
+//   (T0 ysY + T1 Z) + m v + (T3 xsZ + T4 X) v^2 + [(T5 ysX + T6 xsY) + (T7 ysZ + T8 Y) v] w,   m = unit ? 1 : 0
+// Over Fp2[w] / (w^6 - xi), f = sum g_k w^k (g0, g2, g4 = f.c0.c0..c2; g1, g3, g5 = f.c1.c0..c2), it reads
+//   l = U + m w^2 + w^3 V,   U = l0 + l1 w,   V = l3 + l4 w        (l0 = l00, l1 = l10, l3 = l11, l4 = l02)
+// and with f = f_lo + w^3 f_hi (f_lo = g0 + g1 w + g2 w^2, f_hi = g3 + g4 w + g5 w^2)
+//   f l = m w^2 f + P1 + xi P2 + w^3 (P1 + P2 - P3),   P1 = f_lo U,   P2 = f_hi V,   P3 = (f_lo - f_hi)(U - V)
+// Each P is a (3-term x 2-term) product, taken by evaluation at 0, inf, 1, -1 (Toom-Cook): four Fp2 products give TWICE its
+// four coefficients with no division,
+//   m0 = a0 b0, mi = a2 b1, m1 = (a0 + a1 + a2)(b0 + b1), mm = (a0 - a1 + a2)(b0 - b1)
+//   2 a b = 2 m0 + (m1 - mm - 2 mi) x + (m1 + mm - 2 m0) x^2 + 2 mi x^3
+// so twelve Fp2 products give 2 f l (the sparse Karatsuba form over Fp6[w] took sixteen).  The factor 2 per step lies in Fp: the easy
+// part of the final exponentiation removes it, like the powers of Z, the key's Fp2 factor and the tuple's Fp factor.
+// Interval discipline: P3 is the SUBTRACTIVE middle product, so its operands are differences of values that are already
+// normalised for P1 and P2 (the evaluation sums included) and only one of them, (l0 - l1) - (l3 - l4), needs a carry pass of its
+// own: seven Fp2 carry passes feed the twelve products.  With A, B, C the values of P1, P2, P3, p = m1 + mm, d = m1 - mm and
+// T = A + B - C per point, the six coefficients of 2 f l are
+//   w^0: 2 A0 + xi 2 (B0 + Ti + m g4)            w^1: (Ad - 2 Ai) + xi (Bd - 2 Bi + 2 m g5)
+//   w^2: (Ap - 2 A0 + 2 m g0) + xi (Bp - 2 B0)   w^3: 2 (Ai + T0 + m g1) + xi 2 Bi
+//   w^4: Td - 2 Ti + 2 m g2                      w^5: Tp - 2 T0 + 2 m g3
+// formed as lazy limb-wise sums where they stay below four limb widths and as fp_lc terms where they do not; every output is
+// brought back to (-eps p, (1 + eps) p): the term 2 m g_k would otherwise double the value bound with every step.
+template <int K1, int K2, int K3, int K4>
+BN_INL Fp fp_lc4r(const Fp& x1, const Fp& x2, const Fp& x3, const Fp& x4) { return fp_lc4<K1, K2, K3, K4, true>(x1, x2, x3, x4); }
 BN_FUNC Fp12 ell_pair_unit(const Fp12& f, const Ws& e, const Ws& cw, bool unit) {
   BN_CTX;
   Fp Y = fp_load_mem(cw), Z = fp_load_mem(ws_at(cw, 9)), ysY = fp_load_mem(ws_at(cw, 18)), xsZ = fp_load_mem(ws_at(cw, 27));
   Fp ysZ = fp_load_mem(ws_at(cw, 36)), ysX = fp_load_mem(ws_at(cw, 45)), xsY = fp_load_mem(ws_at(cw, 54)), X = fp_load_mem(ws_at(cw, 63));
-  Fp2 l00 = fp2_dot_fp(fp2_load_limbs_lazy(e), ysY, fp2_load_limbs_lazy(ws_at(e, 18)), Z);
-  Fp2 l02 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 54)), xsZ, fp2_load_limbs_lazy(ws_at(e, 72)), X);
-  Fp2 l10 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 90)), ysX, fp2_load_limbs_lazy(ws_at(e, 108)), xsY);
-  Fp2 l11 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 126)), ysZ, fp2_load_limbs_lazy(ws_at(e, 144)), Y);
-  Fp6 v0 = fp6_mul_unit1(f.c0, l00, l02, unit);
-  Fp6 v1 = fp6_mul_by_01(f.c1, l10, l11);
-  Fp6 dl = {fp2_norm(fp2_sub(l10, l00)), fp2_norm(fp2_sub(l11, fp2_select(unit, fp2_one(), fp2_zero()))), fp2_norm(fp2_neg(l02))};       // l1 - l0
-  Fp6 w = fp6_mul(fp6_norm(fp6_sub(f.c0, f.c1)), dl);
-  return {fp6_add_mul_v(v0, v1), fp6_norm(fp6_add(fp6_add(w, v0), v1))};
+  const Fp2 l0 = fp2_dot_fp(fp2_load_limbs_lazy(e), ysY, fp2_load_limbs_lazy(ws_at(e, 18)), Z);
+  const Fp2 l4 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 54)), xsZ, fp2_load_limbs_lazy(ws_at(e, 72)), X);
+  const Fp2 l1 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 90)), ysX, fp2_load_limbs_lazy(ws_at(e, 108)), xsY);
+  const Fp2 l3 = fp2_dot_fp(fp2_load_limbs_lazy(ws_at(e, 126)), ysZ, fp2_load_limbs_lazy(ws_at(e, 144)), Y);
+  const Fp2 &g0 = f.c0.c0, &g2 = f.c0.c1, &g4 = f.c0.c2, &g1 = f.c1.c0, &g3 = f.c1.c1, &g5 = f.c1.c2;
+  // P1 = (g0 + g1 w + g2 w^2)(l0 + l1 w); its normalised evaluation sums stay for P3
+  const Fp2 sa = fp2_add(g0, g2);
+  Fp2 e1 = fp2_norm(fp2_add(sa, g1)), em = fp2_norm(fp2_sub(sa, g1));
+  Fp2 h1 = fp2_norm(fp2_add(l0, l1)), hm = fp2_sub(l0, l1);
+  const Fp2 A0 = fp2_mul(g0, l0), Ai = fp2_mul(g2, l1);
+  Fp2 Ap, Ad;
+  { const Fp2 m1 = fp2_mul(e1, h1), mm = fp2_mul(em, hm); Ap = fp2_add(m1, mm); Ad = fp2_sub(m1, mm); }
+  BN_SCHED_BARRIER;
+  // P2 = (g3 + g4 w + g5 w^2)(l3 + l4 w); each evaluation sum turns into P3's operand once its own product is taken
+  const Fp2 sb = fp2_add(g3, g5);
+  const Fp2 B0 = fp2_mul(g3, l3), Bi = fp2_mul(g5, l4);
+  Fp2 Bp, Bd;
+  { const Fp2 k1 = fp2_norm(fp2_add(sb, g4)), n1 = fp2_norm(fp2_add(l3, l4));
+    const Fp2 m1 = fp2_mul(k1, n1);
+    e1 = fp2_sub(e1, k1); h1 = fp2_sub(h1, n1);
+    const Fp2 km = fp2_norm(fp2_sub(sb, g4)), nm = fp2_sub(l3, l4);
+    const Fp2 mm = fp2_mul(km, nm);
+    em = fp2_sub(em, km); hm = fp2_norm(fp2_sub(hm, nm));
+    Bp = fp2_add(m1, mm); Bd = fp2_sub(m1, mm); }
+  // P3 = (f_lo - f_hi)(U - V): differences of normalised values, one limb width
+  Fp2 Cp, Cd;
+  { const Fp2 m1 = fp2_mul(e1, h1), mm = fp2_mul(em, hm); Cp = fp2_add(m1, mm); Cd = fp2_sub(m1, mm); }
+  const Fp2 C0 = fp2_mul(fp2_sub(g0, g3), fp2_sub(l0, l3)), Ci = fp2_mul(fp2_sub(g2, g5), fp2_sub(l1, l4));
+  // The six coefficients, two at a time.  The scheduling barriers (here and after P1) keep the twelve carry passes from being
+  // interleaved into one: their 64-bit column sums would need more registers than there are, and the kernel would spill to memory.
+  BN_SCHED_BARRIER;
+  const Fp2 T0 = fp2_sub(fp2_add(A0, B0), C0), Ti = fp2_sub(fp2_add(Ai, Bi), Ci);
+  const Fp2 z = fp2_zero();
+  Fp12 r;
+  { const Fp2 u2 = fp2_select(unit, g2, z), u5 = fp2_select(unit, g5, z);
+    const Fp2 d = fp2_sub(fp2_add(Ad, Bd), Cd), t = fp2_sub(Ti, u2);                                      // w^4
+    r.c0.c2 = {fp_lc4r<1, -2, 0, 0>(d.c0, t.c0, d.c0, d.c0), fp_lc4r<1, -2, 0, 0>(d.c1, t.c1, d.c1, d.c1)};
+    const Fp2 x = fp2_sub(Ad, fp2_dbl(Ai)), y = fp2_add(Bd, fp2_dbl(fp2_sub(u5, Bi)));                    // w^1
+    r.c1.c0 = fp2_add_mul_xi(x, y); }
+  BN_SCHED_BARRIER;
+  { const Fp2 u0 = fp2_select(unit, g0, z), u3 = fp2_select(unit, g3, z);
+    const Fp2 p = fp2_sub(Ap, Cp), t = fp2_sub(T0, u3);                                                   // w^5
+    r.c1.c2 = {fp_lc4r<1, 1, -2, 0>(p.c0, Bp.c0, t.c0, p.c0), fp_lc4r<1, 1, -2, 0>(p.c1, Bp.c1, t.c1, p.c1)};
+    const Fp2 s = fp2_sub(u0, A0), y = fp2_sub(Bp, fp2_dbl(B0));                                          // w^2
+    r.c0.c1 = {fp_lc4<1, 2, 9, -1>(Ap.c0, s.c0, y.c0, y.c1), fp_lc4<1, 2, 1, 9>(Ap.c1, s.c1, y.c0, y.c1)}; }
+  BN_SCHED_BARRIER;
+  { const Fp2 u1 = fp2_select(unit, g1, z), u4 = fp2_select(unit, g4, z);
+    const Fp2 x = fp2_add(Ai, u1);                                                                        // w^3
+    r.c1.c1 = {fp_lc4<2, 2, 18, -2>(x.c0, T0.c0, Bi.c0, Bi.c1), fp_lc4<2, 2, 2, 18>(x.c1, T0.c1, Bi.c0, Bi.c1)};
+    const Fp2 y = fp2_add(B0, Ti);                                                                        // w^0: xi m g4 enters as (9 c0 - c1, c0 + 9 c1)
+    r.c0.c0 = {fp_lc4<2, 18, -2, 18>(fp_sub(A0.c0, u4.c1), y.c0, y.c1, u4.c0), fp_lc4<2, 2, 18, 18>(fp_add(A0.c1, u4.c0), y.c0, y.c1, u4.c1)}; }
+  return r;
 }
 // cw (LDS, 72 limbs) and `unit` from miller_unit_coords; ktab: this lane's key, 88 x 162 limbs of unit entries
 BN_FUNC Fp12 miller_loop_prepared_unit(const Ws& cw, const Ws& ktab_in, bool unit) {
