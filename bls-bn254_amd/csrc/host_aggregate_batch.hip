@@ -1,0 +1,106 @@
+// host_aggregate_batch.hip -- aggregate verify over ragged groups of (key, message) pairs: bit g = blsbn254_aggregate_verify on
+// group g alone, for many groups in one call.  Host side of include/blsbn254.h; kernels in k_aggregate_batch.hip; see host_common.h.
+//
+// Everything stays on the device between the upload and the bitmap's download.  The N pairs are hashed into slots 0 .. N - 1 of
+// one H workspace, the G signatures are placed behind them (slot N + g), the caller's N keys get the r-torsion test.  Then the
+// Miller loops run two slots per lane sharing one f^2 (k_miller_hpk2r, the loop of k_miller_hpk2): group g of k pairs takes
+// ceil((k + 1) / 2) consecutive lanes over the slot sequence [its pairs ..., its signature], the signature's slot pairing with
+// the constant -G2gen.  The lanes are the "items" of the pairing-product equations' planner (pc_plan_launches): launches of at
+// most ctx->chunk lanes cut at a group boundary where one lies in the window, a group cut by a launch boundary carried, each
+// group's lanes multiplied level by level (k_fp12_seg_prod) with the validity byte folded per lane (k_agb_fold); the products
+// then finish as blsbn254_pairing_check_batch's do (final exponentiation, mode 0 bitmap).  Slot and chunk descriptors are
+// planned on the host from the offsets and uploaded once.
+#include "host_common.h"
+
+extern "C" {
+
+int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+  if (!c) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  if (!grp_off || !agg_sigs || !valid_bitmap || (dst_len && !dst)) return BLSBN254_E_ARG;
+  if (check_offsets(grp_off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
+  const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
+  if (N && (!pks || !off)) return BLSBN254_E_ARG;
+  if (N > MAX_LANES || G > MAX_LANES || N + G > MAX_LANES) {
+    c->last_error = "more than 2^23 pairs (the signatures' pairs counted) in one aggregate_verify_batch call";
+    return BLSBN254_E_ARG;
+  }
+  if (N && check_offsets(off + base, N)) { c->last_error = "message offsets decrease"; return BLSBN254_E_ARG; }
+  if (N && !msgs && off[base + N] != off[base]) return BLSBN254_E_ARG;
+  ENTER(c);                                             // settles pending asynchronous verify calls BEFORE the tag is staged
+  if (N == 0) {                                         // every group is empty: invalid, as the single call's n == 0 (nothing to launch)
+    std::memset(valid_bitmap, 0, (G + 7) / 8);
+    c->stat_agb[0] += G;
+    return 0;
+  }
+  uint32_t dl = 0;
+  TRY(stage_dst(c, dst, dst_len, &dl));
+  TRY(stage_msgs(c, msgs, off + base, N));
+
+  // lanes: group g's slot sequence [base-relative pairs ..., N + g] two by two
+  AgbWs& a = c->agb;
+  PcWs& w = c->pc;
+  std::vector<uint32_t> &sa = a.h_slot_a, &sb = a.h_slot_b, &goff = a.h_goff;       // ctx-owned: outlive the asynchronous copies
+  std::vector<uint64_t> lane_off(G + 1);
+  goff.resize(G + 1);
+  sa.clear(); sb.clear();
+  sa.reserve((N + G) / 2 + G); sb.reserve((N + G) / 2 + G);
+  lane_off[0] = 0; goff[0] = 0;
+  for (size_t g = 0; g < G; ++g) {
+    const size_t p0 = (size_t)grp_off[g] - base, k = (size_t)(grp_off[g + 1] - grp_off[g]);
+    for (size_t j = 0; j <= k; j += 2) {                // positions j, j + 1 of the k + 1 slots
+      sa.push_back((uint32_t)(j < k ? p0 + j : N + g));
+      sb.push_back(j + 1 < k ? (uint32_t)(p0 + j + 1) : (j + 1 == k ? (uint32_t)(N + g) : AGB_NO_SLOT));
+    }
+    goff[g + 1] = (uint32_t)(p0 + k);
+    lane_off[g + 1] = sa.size();
+  }
+  const size_t lanes = sa.size();
+  std::vector<uint32_t>& start = w.h_start;
+  std::vector<uint32_t>& len = w.h_len;
+  start.clear(); len.clear();
+  std::vector<PcLaunch> launches;
+  size_t items_max;
+  TRY(pc_plan_launches(c, lane_off, G, launches, start, len, &items_max));
+  const size_t m_max = std::min(lanes, c->chunk), S = N + G;
+  TRY(pc_reserve_products(c, G, items_max));
+  HIPCHK(c, w.start.reserve(4 * start.size())); HIPCHK(c, w.len.reserve(4 * len.size())); HIPCHK(c, w.pair_ok.reserve(m_max + 1));
+  HIPCHK(c, a.slot_a.reserve(4 * lanes)); HIPCHK(c, a.slot_b.reserve(4 * lanes)); HIPCHK(c, a.goff.reserve(4 * (G + 1))); HIPCHK(c, a.sig_ok.reserve(G));
+  HIPCHK(c, c->in_a.reserve(128 * N)); HIPCHK(c, c->in_b.reserve(64 * G)); HIPCHK(c, c->h_ws.reserve(S * 18 * 4));
+  HIPCHK(c, c->f_ws.reserve(m_max * 108 * 4)); HIPCHK(c, c->q_ws.reserve(m_max * 72 * 4)); HIPCHK(c, c->flags.reserve(N)); HIPCHK(c, c->sub_ok.reserve(N));
+  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks + 128 * base, 128 * N, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sigs, 64 * G, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(a.slot_a.p, sa.data(), 4 * lanes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(a.slot_b.p, sb.data(), 4 * lanes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(a.goff.p, goff.data(), 4 * (G + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(w.start.p, start.data(), 4 * start.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(w.len.p, len.data(), 4 * len.size(), hipMemcpyHostToDevice, c->stream));
+
+  const uint8_t* d_pks = (const uint8_t*)c->in_a.p;
+  int32_t* h = (int32_t*)c->h_ws.p;
+  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(N), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, (const uint8_t*)c->dst.p, dl, h, S,
+             (uint8_t*)nullptr, 0));
+  TRY(launch(c, c->stream, "agb_place_sigs", grid_lanes(G), k_agb_place_sigs, (const uint8_t*)c->in_b.p, G, h, N, S, (uint8_t*)a.sig_ok.p));
+  TRY(launch(c, c->stream, "g2_check", grid_lanes(N), k_g2_check, d_pks, N, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));   // the caller's keys only: never -G2gen
+  const uint32_t *d_sa = (const uint32_t*)a.slot_a.p, *d_sb = (const uint32_t*)a.slot_b.p;
+  for (const PcLaunch& L : launches) {
+    const size_t m = L.hi - L.lo;                       // (every group has its signature's lane: no launch is empty)
+    TRY(launch(c, c->stream, "miller_hpk2r", grid_lanes(m), k_miller_hpk2r, (const int32_t*)h, S, d_pks, N, d_sa + L.lo, d_sb + L.lo, m, (int32_t*)c->q_ws.p,
+               (int32_t*)c->f_ws.p, m, (uint8_t*)c->flags.p));
+    TRY(launch(c, c->stream, "agb_fold", grid_lanes(m), k_agb_fold, d_sa + L.lo, d_sb + L.lo, m, N, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p,
+               (const uint8_t*)a.sig_ok.p, (const uint32_t*)a.goff.p, (uint8_t*)w.pair_ok.p));
+    TRY(pc_run_levels(c, L, (const int32_t*)c->f_ws.p, (const uint8_t*)w.pair_ok.p, m, G, true));
+  }
+  TRY(pc_finish_bitmap(c, G, valid_bitmap));
+  c->stat_agb[0] += G; c->stat_agb[1] += lanes; c->stat_agb[3] += launches.size();      // counted once the call has succeeded
+  return 0;
+}
+
+int blsbn254_aggregate_batch_stats(blsbn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BLSBN254_E_ARG;
+  for (int i = 0; i < 4; ++i) out[i] = c->stat_agb[i];
+  return 0;
+}
+
+}  // extern "C"

@@ -57,6 +57,13 @@ struct BNH ThbWs {
   DevBuf goff, gid, pts, seg[2], gsum, gstat, start, len, out, st;
   std::vector<uint32_t> h_goff, h_start, h_len;
 };
+// aggregate verify over groups (host_aggregate_batch.hip, k_aggregate_batch.hip): the lanes' slot descriptors, the groups' pair
+// offsets (rebased to 0), the signatures' flags; device buffers and the host copies they are uploaded from.  The products, their
+// levels and chunk descriptors are PcWs's.
+struct BNH AgbWs {
+  DevBuf slot_a, slot_b, goff, sig_ok;
+  std::vector<uint32_t> h_slot_a, h_slot_b, h_goff;
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -119,6 +126,8 @@ struct blsbn254_ctx {
   MsmWs msm;
   PcWs pc;
   ThbWs thb;
+  AgbWs agb;
+  uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
   uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
   uint64_t stat_msm[4] = {0, 0, 0, 0};   // bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
@@ -218,6 +227,7 @@ static const size_t PREP_RAW_LIMBS = (size_t)BN_NEG_G2_LINES * 54;       // a ke
 static const size_t PREP_KEY_LIMBS = (size_t)BN_NEG_G2_LINES * 162;      // a key's 88 expanded line pairs (key line x -G2gen line)
 struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok; };   // pair tables (verify), raw line triples (multi_miller_loop), validity
 
+struct SegLevel { size_t first, count; };   // one level of a segmented reduction (plan_seg_levels below)
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip
 BNH int check_offsets(const uint64_t* off, size_t n);   // host.hip
@@ -251,6 +261,15 @@ BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip
 BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
                           size_t cnt, uint8_t* d_isone);   // host_rlc.hip
+// pairing-product planning and products, shared with the aggregate verify over groups (host_pairing_check.hip): the launches over
+// items rel[0..n_eq] (rebased offsets) with their product levels; one launch's levels from its items' values / flags into
+// c->pc.prod / c->pc.ok; the products' final exponentiation into the bitmap, by chunks of equations
+struct PcLaunch { size_t lo, hi, ga, gb; bool carry; std::vector<SegLevel> levels; };
+BNH int pc_plan_launches(blsbn254_ctx* c, const std::vector<uint64_t>& rel, size_t n_eq, std::vector<PcLaunch>& out,
+                         std::vector<uint32_t>& start, std::vector<uint32_t>& len, size_t* items_max);
+BNH int pc_reserve_products(blsbn254_ctx* c, size_t n_eq, size_t items_max);
+BNH int pc_run_levels(blsbn254_ctx* c, const PcLaunch& L, const int32_t* src, const uint8_t* src_ok, size_t src_stride, size_t n_eq, bool check);
+BNH int pc_finish_bitmap(blsbn254_ctx* c, size_t n_eq, uint8_t* valid_bitmap);
 BNH int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res, size_t* rs);   // host_aggregate.hip
 BNH int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]);   // host_aggregate.hip
 BNH int threshold_combine_one(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]);   // host_aggregate.hip
@@ -268,7 +287,6 @@ static inline bool small_for_prepared(const blsbn254_ctx* c, size_t n, bool per_
 // items: every segment is cut into runs of at most G items, one (start, len) descriptor per run (an empty segment: ONE empty run),
 // the runs are the next level's items, and so on until there is one run per segment.  Descriptors are appended to start / len,
 // one {first descriptor, count} per level to `levels`; `cur` is consumed.  `what` names the reduction in the (internal) error.
-struct SegLevel { size_t first, count; };
 BNH int plan_seg_levels(blsbn254_ctx* c, std::vector<uint64_t>& cur, size_t G, std::vector<uint32_t>& start, std::vector<uint32_t>& len,
                         std::vector<SegLevel>& levels, const char* what);   // host_groupops.hip
 }  // extern "C"

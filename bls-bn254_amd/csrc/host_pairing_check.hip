@@ -14,13 +14,9 @@ extern "C" {
 
 static const size_t FP12_SEG_GROUP = 8;     // Miller values per lane of the segmented product
 
-namespace {
-struct PcLaunch { size_t lo, hi, ga, gb; bool carry; std::vector<SegLevel> levels; };
-}
-
 // Launches and their product levels for equations rel[0..n_eq] (offsets rebased to 0); descriptors appended to start / len.
-static int plan_launches(blsbn254_ctx* c, const std::vector<uint64_t>& rel, size_t n_eq, std::vector<PcLaunch>& out,
-                         std::vector<uint32_t>& start, std::vector<uint32_t>& len, size_t* items_max) {
+int pc_plan_launches(blsbn254_ctx* c, const std::vector<uint64_t>& rel, size_t n_eq, std::vector<PcLaunch>& out,
+                     std::vector<uint32_t>& start, std::vector<uint32_t>& len, size_t* items_max) {
   const size_t N = (size_t)rel[n_eq];
   size_t lo = 0, g = 0;
   *items_max = 1;
@@ -45,6 +41,32 @@ static int plan_launches(blsbn254_ctx* c, const std::vector<uint64_t>& rel, size
   return 0;
 }
 
+// The products' buffers: per-equation products and flags, the levels' ping-pong items (items_max of pc_plan_launches)
+int pc_reserve_products(blsbn254_ctx* c, size_t n_eq, size_t items_max) {
+  PcWs& w = c->pc;
+  HIPCHK(c, w.prod.reserve(n_eq * 108 * 4)); HIPCHK(c, w.ok.reserve(n_eq));
+  HIPCHK(c, w.seg[0].reserve(items_max * 108 * 4)); HIPCHK(c, w.seg[1].reserve(items_max * 108 * 4));
+  HIPCHK(c, w.seg_ok[0].reserve(items_max)); HIPCHK(c, w.seg_ok[1].reserve(items_max));
+  return 0;
+}
+// One launch's product levels: its items' values at src (limb-major, src_stride; nullptr for a launch of empty equations) and,
+// with `check`, their flags at src_ok, into the products / flags of equations L.ga .. L.gb (stride n_eq).  The descriptors are
+// c->pc.start / len, uploaded by the caller.
+int pc_run_levels(blsbn254_ctx* c, const PcLaunch& L, const int32_t* src, const uint8_t* src_ok, size_t src_stride, size_t n_eq, bool check) {
+  PcWs& w = c->pc;
+  int dst = 0;
+  for (size_t lv = 0; lv < L.levels.size(); ++lv) {
+    const SegLevel& P = L.levels[lv];
+    const bool last = lv + 1 == L.levels.size();
+    int32_t* out = last ? (int32_t*)w.prod.p + L.ga : (int32_t*)w.seg[dst].p;
+    uint8_t* out_ok = check ? (last ? (uint8_t*)w.ok.p + L.ga : (uint8_t*)w.seg_ok[dst].p) : nullptr;
+    TRY(launch(c, c->stream, "fp12_seg_prod", grid_lanes(P.count), k_fp12_seg_prod, src, src_stride, src_ok, (const uint32_t*)w.start.p + P.first,
+               (const uint32_t*)w.len.p + P.first, P.count, out, last ? n_eq : P.count, out_ok, (last && L.carry) ? 1 : 0));
+    src = out; src_ok = out_ok; src_stride = P.count; dst ^= 1;
+  }
+  return 0;
+}
+
 // Products of every equation into c->pc.prod (limb-major, stride n_eq) and, with `check`, their validity into c->pc.ok.
 static int pc_products(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint64_t* off, size_t n_eq, bool check) {
   const size_t N = (size_t)(off[n_eq] - off[0]);
@@ -56,11 +78,9 @@ static int pc_products(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, co
   start.clear(); len.clear();
   std::vector<PcLaunch> launches;
   size_t items_max;
-  int rc = plan_launches(c, rel, n_eq, launches, start, len, &items_max);
+  int rc = pc_plan_launches(c, rel, n_eq, launches, start, len, &items_max);
   if (rc) return rc;
-  HIPCHK(c, w.prod.reserve(n_eq * 108 * 4)); HIPCHK(c, w.ok.reserve(n_eq));
-  HIPCHK(c, w.seg[0].reserve(items_max * 108 * 4)); HIPCHK(c, w.seg[1].reserve(items_max * 108 * 4));
-  HIPCHK(c, w.seg_ok[0].reserve(items_max)); HIPCHK(c, w.seg_ok[1].reserve(items_max));
+  TRY(pc_reserve_products(c, n_eq, items_max));
   HIPCHK(c, w.start.reserve(4 * start.size())); HIPCHK(c, w.len.reserve(4 * len.size()));
   HIPCHK(c, c->in_a.reserve(64 * (N ? N : 1))); HIPCHK(c, c->in_b.reserve(128 * (N ? N : 1)));
   if (check) HIPCHK(c, w.pair_ok.reserve(std::min(N, c->chunk) + 1));
@@ -95,16 +115,8 @@ static int pc_products(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, co
         }
       }
     }
-    int dst = 0;
-    for (size_t lv = 0; lv < L.levels.size(); ++lv) {
-      const SegLevel& P = L.levels[lv];
-      const bool last = lv + 1 == L.levels.size();
-      int32_t* out = last ? (int32_t*)w.prod.p + L.ga : (int32_t*)w.seg[dst].p;
-      uint8_t* out_ok = check ? (last ? (uint8_t*)w.ok.p + L.ga : (uint8_t*)w.seg_ok[dst].p) : nullptr;
-      TRY(launch(c, c->stream, "fp12_seg_prod", grid_lanes(P.count), k_fp12_seg_prod, src, src_stride, src_ok, (const uint32_t*)w.start.p + P.first,
-                 (const uint32_t*)w.len.p + P.first, P.count, out, last ? n_eq : P.count, out_ok, (last && L.carry) ? 1 : 0));
-      src = out; src_ok = out_ok; src_stride = P.count; dst ^= 1;
-    }
+    rc = pc_run_levels(c, L, src, src_ok, src_stride, n_eq, check);
+    if (rc) return rc;
   }
   return 0;
 }
@@ -140,6 +152,10 @@ int blsbn254_pairing_check_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8
   ENTER(c);
   rc = pc_products(c, g1, g2, off, n_eq, true);
   if (rc) return rc;
+  return pc_finish_bitmap(c, n_eq, valid_bitmap);
+}
+// The final exponentiation of the n_eq products in c->pc.prod with their flags c->pc.ok (mode 0), and the bitmap's download
+int pc_finish_bitmap(blsbn254_ctx* c, size_t n_eq, uint8_t* valid_bitmap) {
   const size_t nb = (n_eq + 7) / 8;
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   int32_t* prod = (int32_t*)c->pc.prod.p;

@@ -70,6 +70,13 @@ BN_KERNEL k_g2_seg_sum(const int32_t* in_ws, size_t in_stride, const uint8_t* ok
 BN_KERNEL k_pair_ok(const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* ok);
 BN_KERNEL k_fp12_seg_prod(const int32_t* in_ws, size_t in_stride, const uint8_t* ok_in, const uint32_t* chunk_start, const uint32_t* chunk_len,
                           size_t m, int32_t* out_ws, size_t out_stride, uint8_t* ok_out, int carry);
+// aggregate verify over groups (k_aggregate_batch.hip): the missing half of a two-slot lane descriptor
+#define AGB_NO_SLOT 0xffffffffu
+BN_KERNEL k_agb_place_sigs(const uint8_t* sigs, size_t n_groups, int32_t* h_ws, size_t n_pairs, size_t h_stride, uint8_t* sig_ok);
+BN_KERNEL k_miller_hpk2r(const int32_t* h_ws, size_t h_stride, const uint8_t* pks, size_t n_pairs, const uint32_t* slot_a, const uint32_t* slot_b,
+                         size_t m, int32_t* q_ws, int32_t* f_ws, size_t f_stride, uint8_t* flags);
+__global__ void __launch_bounds__(256) k_agb_fold(const uint32_t* slot_a, const uint32_t* slot_b, size_t m, size_t n_pairs, const uint8_t* flags,
+                                                  const uint8_t* sub_ok, const uint8_t* sig_ok, const uint32_t* goff, uint8_t* ok);
 BN_KERNEL k_g2p_to_bytes(const int32_t* ws, size_t stride, const uint8_t* ok, size_t m, uint8_t* out, int poison);
 BN_KERNEL k_keygen(const uint8_t* ikm, size_t ikm_len, size_t n, const uint8_t* key_info, size_t key_info_len,
                    uint8_t* sks, uint8_t* status);

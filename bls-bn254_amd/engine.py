@@ -407,6 +407,41 @@ class Engine:
                                                                  ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po))
         return o[:(g + 7) // 8].tobytes()
 
+    def aggregate_verify_batch(self, key_sets, msg_sets, agg_sigs, dst=DEFAULT_DST):
+        """Many independent aggregate signatures in one call.  key_sets: list of byte strings (each a multiple of 128 bytes: the
+        keys of one group); msg_sets: one list of messages per group, as many as the group has keys; agg_sigs: 64 bytes per group.
+        Returns the LSB-first bitmap over the groups: bit g = aggregate_verify(key_sets[g], msg_sets[g], agg_sigs[64 g ..]).  An
+        empty group is invalid."""
+        g = len(key_sets)
+        if len(msg_sets) != g:
+            raise ValueError("one list of messages per key set")
+        goff = self._group_offsets(key_sets, 128, "a key set")
+        if any(int(goff[i + 1] - goff[i]) != len(ms) for i, ms in enumerate(msg_sets)):
+            raise ValueError("a group needs as many messages as keys")
+        return self.aggregate_verify_batch_flat(b"".join(key_sets), [m for ms in msg_sets for m in ms], goff, agg_sigs, dst)
+
+    def aggregate_verify_batch_flat(self, pks, msgs, grp_off, agg_sigs, dst=DEFAULT_DST):
+        """The same over flat arrays, as the C ABI takes them: group g owns the pairs grp_off[g] .. grp_off[g + 1] of pks (128 B each)
+        and msgs (a list); the offsets need not start at 0 (pairs in front of grp_off[0] belong to no group)."""
+        goff = np.ascontiguousarray(np.asarray(grp_off, dtype=np.uint64))
+        if goff.ndim != 1 or goff.size < 1:
+            raise ValueError("grp_off needs n_groups + 1 entries")
+        g = goff.size - 1
+        if g and int(goff[-1]) > len(msgs):
+            raise ValueError("grp_off names more pairs than there are messages")
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(pks, 128 * len(msgs)); m, pm = _inbuf(data); s, ps = _inbuf(agg_sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        self._chk(self._lib.blsbn254_aggregate_verify_batch(self._ctx, pa, pm, off.ctypes.data_as(_u64p), goff.ctypes.data_as(_u64p), ps,
+                                                            ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po))
+        return o[:(g + 7) // 8].tobytes()
+
+    def aggregate_batch_stats(self):
+        """dict: groups served by aggregate_verify_batch, lanes run by its two-pairs-per-lane Miller kernel, calls served by the
+        small forms, launches"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_aggregate_batch_stats(self._ctx, o))
+        return {"groups": int(o[0]), "lanes": int(o[1]), "small_calls": int(o[2]), "launches": int(o[3])}
+
     def g1_mul_batch(self, g1, scalars, n):
         """Mul<Scalar> for G1Projective (g1.rs:518-534), element-wise: [k_i] P_i."""
         a, pa = _inbuf(g1, 64 * n); k, pk = _inbuf(scalars, 32 * n); o, po = _outbuf(64 * n)

@@ -115,6 +115,24 @@ int blsbn254_verify_batch(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* 
  * The library does not detect duplicate messages (the reference has no BLS layer to pin either behaviour). */
 int blsbn254_aggregate_verify(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, size_t n,
                               const uint8_t agg_sig[64], const uint8_t* dst, size_t dst_len, int* valid);
+/* blsbn254_aggregate_verify for many independent aggregates in one call: bit g (LSB-first) of valid_bitmap = *valid of
+ * blsbn254_aggregate_verify on group g alone.  Group g owns the pairs grp_off[g] .. grp_off[g + 1] (element offsets, non-decreasing,
+ * need not start at 0); pair indices are absolute: pair i has key pks[128 i ..] and message msgs[off[i] .. off[i + 1]), so off
+ * holds grp_off[n_groups] + 1 entries; group g's aggregate signature is agg_sigs[64 g ..]; one dst serves all groups.
+ * A group is valid when it has at least one pair (an empty group is INVALID, as the single call's n == 0), its signature decodes,
+ * is not the identity and is on the curve, every key decodes, is not the identity, is on the curve and in the r-torsion, and
+ * e(agg_sig, -G2gen) * prod_i e(H(msg_i), pk_i) == 1.  A bad point clears its group's bit and nothing else; it is never an
+ * error of the call.  The PRECONDITION of blsbn254_aggregate_verify (rogue keys / repeated messages) holds per group, unchanged.
+ * Two pairs per lane share one f^2 (the signature's pair, whose -G2gen is a constant and is never validated, included); the hash
+ * points never leave the device.  BLSBN254_E_ARG: NULL arguments, decreasing offsets, pairs + n_groups > 2^23 (the signatures'
+ * pairs count).  n_groups == 0 returns 0.  Launches span at most BLSBN254_CHUNK_LANES lanes.
+ * blsbn254_aggregate_batch_stats, since the context was created: out[0] groups served, out[1] lanes run by the two-pair kernel,
+ * out[2] calls served by the small forms (none in this build: every size takes the two-pair kernel), out[3] launches. */
+int blsbn254_aggregate_verify_batch(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
+                                    const uint64_t* grp_off /* n_groups+1 */, const uint8_t* agg_sigs /* n_groups*64 */,
+                                    size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                    uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_aggregate_batch_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Repeated signers.  blsbn254_verify_batch (and _dev) de-duplicates the public keys of a batch on the GPU (hash table over
  * the 128-byte encodings, full comparison on every hit) and, when at most half of them are distinct (and at most 65536),
  * validates each DISTINCT key once and turns it into its table of 88 line-coefficient triples -- G2Prepared::from,

@@ -291,6 +291,29 @@ pub fn fast_aggregate_verify_batch(groups: &[&[[u8; 128]]], msgs: &[&[u8]], sigs
     bits(&bm, n)
 }
 
+/// Many independent aggregate signatures in one call (`blsbn254_aggregate_verify_batch`): `groups[g]` = the (key, message) pairs
+/// of group g, `sigs[g]` its aggregate signature.  Element g = `aggregate_verify` on group g alone; an empty group is invalid.
+pub fn aggregate_verify_batch(groups: &[&[([u8; 128], &[u8])]], sigs: &[[u8; 64]], dst: &[u8]) -> Vec<bool> {
+    assert!(groups.len() == sigs.len());
+    let n = groups.len();
+    let mut goff = Vec::with_capacity(n + 1);
+    goff.push(0u64);
+    let mut flat: Vec<u8> = Vec::new();
+    let mut msgs: Vec<&[u8]> = Vec::new();
+    for g in groups {
+        for (k, m) in g.iter() { flat.extend_from_slice(k); msgs.push(m); }
+        goff.push(msgs.len() as u64);
+    }
+    let (data, off) = pack(&msgs);
+    let sg: Vec<u8> = sigs.iter().flatten().copied().collect();
+    let mut bm = vec![0u8; (n + 7) / 8];
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_aggregate_verify_batch(c, flat.as_ptr(), data.as_ptr(), off.as_ptr(), goff.as_ptr(), sg.as_ptr(), n, dst.as_ptr(), dst.len(), bm.as_mut_ptr())
+    }))
+    .expect("per-group failures are reported in the bitmap");
+    bits(&bm, n)
+}
+
 // ---------------------------------------------------------------- repeated signers: keys prepared once (G2Prepared, batched)
 
 /// The line tables of a set of public keys, resident on the GPU (`blsbn254_g2prepared`): what `G2Prepared::from`
