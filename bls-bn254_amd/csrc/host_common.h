@@ -64,6 +64,16 @@ struct BNH AgbWs {
   DevBuf slot_a, slot_b, goff, sig_ok;
   std::vector<uint32_t> h_slot_a, h_slot_b, h_goff;
 };
+// key shares and their public keys over groups (host_threshold_deal.hip, k_threshold_deal.hip): the staged coefficients /
+// commitments and ids, the decoded coefficients (9 x T limbs) / loaded commitments (54 x T limbs) with their validity bytes, the
+// shares before their encoding (9 x N / 54 x N limbs), the groups' id and coefficient offsets, the per-group marks and statuses,
+// the public key shares in wire format; the host copies the offsets and the per-share messages are uploaded from
+struct BNH TdlWs {
+  DevBuf coef, ids, cf_ws, c_ws, c_ok, c_sub, r_ws, goff, coff, gstat, st, pks;
+  std::vector<uint32_t> h_goff, h_coff;
+  std::vector<uint8_t> h_msgs;
+  std::vector<uint64_t> h_moff;
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -127,6 +137,8 @@ struct blsbn254_ctx {
   PcWs pc;
   ThbWs thb;
   AgbWs agb;
+  TdlWs tdl;
+  uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
   uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)

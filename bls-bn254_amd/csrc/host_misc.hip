@@ -5,8 +5,8 @@
 extern "C" {
 
 // ---------------- field / tower primitives (debug ABI) and Gt group operations
-static size_t field_op_width(int op) { return op < 0 ? 0 : op <= 8 ? 32 : (op >= 16 && op <= 21) ? 64 : (op >= 32 && op <= 35) ? 192 : (op >= 48 && op <= 56) ? 384 : 0; }
-static bool field_op_binary(int op) { return op == 0 || op == 3 || op == 4 || op == 16 || op == 32 || op == 48 || op == 56; }
+static size_t field_op_width(int op) { return op < 0 ? 0 : op <= 8 ? 32 : (op >= 16 && op <= 21) ? 64 : (op >= 32 && op <= 35) ? 192 : (op >= 48 && op <= 56) ? 384 : (op >= 64 && op <= 69) ? 32 : 0; }
+static bool field_op_binary(int op) { return op == 0 || op == 3 || op == 4 || op == 16 || op == 32 || op == 48 || op == 56 || op == 64 || op == 67 || op == 68; }
 int blsbn254_field_op_batch(blsbn254_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
   const size_t w = field_op_width(op);
   if (!c || w == 0 || (n && (!a || !out || (field_op_binary(op) && !b)))) return BLSBN254_E_ARG;
@@ -21,7 +21,7 @@ int blsbn254_field_op_batch(blsbn254_ctx* c, int op, const uint8_t* a, const uin
              (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
-  if (bad >= 0) return BLSBN254_ERR_GT;
+  if (bad >= 0) return op >= 64 ? BLSBN254_ERR_SCALAR : BLSBN254_ERR_GT;
   return download(c, out, c->out.p, w * n);
 }
 int blsbn254_gt_mul_batch(blsbn254_ctx* c, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {

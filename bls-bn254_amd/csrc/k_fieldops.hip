@@ -3,8 +3,10 @@
 // vectors for Fp6 / Fp12, so this entry point fuzzed against the CPU oracle is the isolated pin of
 // fp.rs:388-416, fp2.rs:377-437, fp6.rs:225-287, fp12.rs:120-219 on the device arithmetic (fp29.h / tower.h).
 // Operands and results are canonical big-endian bytes: Fp 32 B; Fp2 64 B (c0 || c1); Fp6 192 B (c0.c0, c0.c1, c1.c0 ..);
-// Fp12 384 B in the Gt::to_repr order (pairings.rs:499-514).
+// Fp12 384 B in the Gt::to_repr order (pairings.rs:499-514).  Operations 64 .. 69 are the reference's Scalar (scalar.rs:523-548,
+// :216-219) on fr29.h, 32 B: the isolated pin of the arithmetic the threshold kernels run on.
 #include "lane_ops.h"
+#include "fr29.h"
 #include "kernels.h"
 using namespace bn;
 
@@ -17,7 +19,7 @@ __device__ inline Fp6 fp6_from_be(const uint8_t* in, bool& ok) {
 __device__ inline void fp6_to_be(uint8_t* out, const Fp6& a) { fp2_to_be(out, a.c0); fp2_to_be(out + 64, a.c1); fp2_to_be(out + 128, a.c2); }
 }  // namespace
 
-// op codes: include/blsbn254.h (BLSBN254_OP_*).  status[i] = 1 when every coefficient decoded (< p).
+// op codes: include/blsbn254.h (BLSBN254_OP_*).  status[i] = 1 when every coefficient decoded (< p; Fr: < r).
 BN_KERNEL k_field_op(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out, uint8_t* status) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -62,6 +64,19 @@ BN_KERNEL k_field_op(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8
       default: r = fp6_mul_v(x); break;                    // 35: mul_by_non_residue, fp6.rs:146-152
     }
     fp6_to_be(out + 192 * i, r);
+  } else if (op >= 64) {                                   // ---- Fr
+    bool o1 = true, o2 = true;
+    Fr x = fr_from_be(a + 32 * i, o1), y = b ? fr_from_be(b + 32 * i, o2) : fr_const(bnc::FR_ONE), r;
+    ok = o1 & o2;
+    switch (op) {
+      case 64: r = fr_mul(x, y); break;
+      case 65: r = fr_mul(x, x); break;
+      case 66: r = fr_inv(x); break;                       // 0 -> 0
+      case 67: r = fr_add(x, y); break;
+      case 68: r = fr_sub(x, y); break;
+      default: r = fr_sub(Fr{}, x); break;                 // 69: 0 - x
+    }
+    fr_to_be(out + 32 * i, r);
   } else {                                                 // ---- Fp12
     bool o1 = true, o2 = true;
     Fp12 x = fp12_from_be(a + 384 * i, o1), y = fp12_one(), r;

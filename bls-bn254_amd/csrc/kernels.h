@@ -145,6 +145,15 @@ BN_KERNEL k_lagrange_seg(const int32_t* x_ws, const uint8_t* id_ok, size_t m, ui
                          uint8_t* scalars, uint32_t* glv_ws, uint32_t* gid, uint32_t* gstat);
 BN_KERNEL k_g1_smul_glv(const uint8_t* g1, const uint32_t* glv_ws, const uint32_t* gid, size_t m, int32_t* out_ws, uint32_t* gstat);
 __global__ void __launch_bounds__(256) k_th_finish(const uint32_t* gstat, size_t n_groups, uint8_t* out, uint8_t* status);
+BN_KERNEL k_fr_coef_decode(const uint8_t* coeffs, size_t T, int32_t* cf_ws, uint8_t* cf_ok);
+BN_KERNEL k_fr_poly_eval(const int32_t* x_ws, const uint8_t* id_ok, size_t m, uint32_t lo, const uint32_t* goff, const uint32_t* coff, uint32_t ng,
+                         const int32_t* cf_ws, size_t T, int32_t* r_ws, size_t N, uint32_t* gstat);
+BN_KERNEL k_g2_poly_eval(const int32_t* x_ws, const uint8_t* id_ok, size_t m, uint32_t lo, const uint32_t* goff, const uint32_t* coff, uint32_t ng,
+                         const int32_t* c_ws, size_t T, int nbits, int32_t* r_ws, size_t N, uint32_t* gstat);
+BN_KERNEL k_td_fr_encode(const int32_t* r_ws, size_t N, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, const uint32_t* gstat, uint8_t* out);
+BN_KERNEL k_td_g2_encode(const int32_t* r_ws, size_t N, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, const uint32_t* gstat, uint8_t* out);
+__global__ void __launch_bounds__(256) k_td_finish(uint32_t* gstat, size_t n_groups, const uint32_t* coff, const uint8_t* ok_a, const uint8_t* ok_b, uint32_t mark,
+                                                  uint8_t* status);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

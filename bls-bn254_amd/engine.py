@@ -529,10 +529,66 @@ class Engine:
         self._chk(self._lib.blsbn254_threshold_batch_stats(self._ctx, o))
         return {"batched_groups": int(o[0]), "single_groups": int(o[1]), "launches": int(o[2]), "t_big": int(o[3])}
 
+    def _deal_args(self, coef_sets, coef_width, id_sets):
+        if len(coef_sets) != len(id_sets):
+            raise ValueError("one set of ids per set of coefficients")
+        coff = self._group_offsets(coef_sets, coef_width, "a set of coefficients")
+        goff = self._group_offsets(id_sets, 32, "a set of ids")
+        return coff, goff, int(goff[-1])
+
+    def fr_poly_eval_batch(self, coef_sets, id_sets):
+        """Key shares: group g's polynomial (coef_sets[g]: 32 bytes per coefficient, low order first) evaluated at each id of
+        id_sets[g] (32 bytes each).  Returns (shares, status): 32 bytes per id in the order given and one status byte per group
+        (0, ERR_SCALAR = 1: a coefficient or an id >= r, or an id 0); a bad group's shares are zero bytes.  Signing side: not
+        constant time."""
+        coff, goff, n = self._deal_args(coef_sets, 32, id_sets)
+        g = len(id_sets)
+        a, pa = _inbuf(b"".join(coef_sets)); x, px = _inbuf(b"".join(id_sets)); o, po = _outbuf(32 * n)
+        st = np.zeros(max(g, 1), dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_fr_poly_eval_batch(self._ctx, pa, coff.ctypes.data_as(_u64p), px, goff.ctypes.data_as(_u64p), ctypes.c_size_t(g), po, pst))
+        return o[:32 * n].tobytes(), st[:g].tobytes()
+
+    def g2_poly_eval_batch(self, commit_sets, id_sets):
+        """Public key shares: sum_j [id^j] C_j for group g's Feldman commitments (commit_sets[g]: 128 bytes each, low order
+        first) at each id of id_sets[g].  Returns (pks, status): 128 bytes per id and one status byte per group (0,
+        ERR_SCALAR = 1: an id >= r or 0, ERR_G2 = 3: a commitment that is not a valid subgroup point); a bad group's keys are
+        the identity encoding."""
+        coff, goff, n = self._deal_args(commit_sets, 128, id_sets)
+        g = len(id_sets)
+        a, pa = _inbuf(b"".join(commit_sets)); x, px = _inbuf(b"".join(id_sets)); o, po = _outbuf(128 * n)
+        st = np.zeros(max(g, 1), dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_g2_poly_eval_batch(self._ctx, pa, coff.ctypes.data_as(_u64p), px, goff.ctypes.data_as(_u64p), ctypes.c_size_t(g), po, pst))
+        return o[:128 * n].tobytes(), st[:g].tobytes()
+
+    def threshold_verify_shares_batch(self, commit_sets, id_sets, sig_sets, msgs, dst=DEFAULT_DST):
+        """Partial signatures checked against the key shares of g2_poly_eval_batch, which stay on the device: sig_sets[g] holds
+        64 bytes per id of id_sets[g], msgs[g] is the group's message.  Returns (bitmap, status): bit i (LSB-first, in the order
+        given) = partial signature i verifies under its key share; status as g2_poly_eval_batch, every bit of a bad group 0."""
+        coff, goff, n = self._deal_args(commit_sets, 128, id_sets)
+        g = len(id_sets)
+        if len(sig_sets) != g or len(msgs) != g:
+            raise ValueError("one set of partial signatures and one message per set of ids")
+        if not np.array_equal(goff, self._group_offsets(sig_sets, 64, "a set of partial signatures")):
+            raise ValueError("a group needs as many partial signatures as ids")
+        data, moff = pack_messages(list(msgs))
+        a, pa = _inbuf(b"".join(commit_sets)); x, px = _inbuf(b"".join(id_sets)); s, ps = _inbuf(b"".join(sig_sets))
+        m, pm = _inbuf(data); d, pd = _inbuf(dst); o, po = _outbuf((n + 7) // 8)
+        st = np.zeros(max(g, 1), dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_threshold_verify_shares_batch(self._ctx, pa, coff.ctypes.data_as(_u64p), px, ps, goff.ctypes.data_as(_u64p), pm,
+                                                                   moff.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po, pst))
+        return o[:(n + 7) // 8].tobytes(), st[:g].tobytes()
+
+    def threshold_deal_stats(self):
+        """dict: launches of the G2 evaluation kernel, shares evaluated in G2, shares evaluated in Fr, and the bit count the last
+        G2 launch looped over"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_threshold_deal_stats(self._ctx, o))
+        return {"g2_launches": int(o[0]), "g2_shares": int(o[1]), "fr_shares": int(o[2]), "id_bits": int(o[3])}
+
     # ---- Gt group operations and the field-primitive debug ABI
     FIELD_OP_WIDTH = {**{k: 32 for k in range(0, 9)}, **{k: 64 for k in range(16, 22)}, **{k: 192 for k in range(32, 36)},
-                      **{k: 384 for k in range(48, 57)}}
-    FIELD_OP_BINARY = (0, 3, 4, 16, 32, 48, 56)
+                      **{k: 384 for k in range(48, 57)}, **{k: 32 for k in range(64, 70)}}
+    FIELD_OP_BINARY = (0, 3, 4, 16, 32, 48, 56, 64, 67, 68)
 
     def field_op_batch(self, op, a, b, n):
         """One field / tower primitive element-wise (op = BLSBN254_OP_* of the header); n * width bytes back."""

@@ -302,6 +302,45 @@ int blsbn254_lagrange_at_zero_batch(blsbn254_ctx* ctx, const uint8_t* ids, const
  * pipeline (more shares than out[3]), out[2] launches of the lane-per-share pipeline; out[3] the hand-over size of this
  * build (a constant) */
 int blsbn254_threshold_batch_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* The dealing side, over ragged groups.  A group g stands for one threshold key: t_g coefficients of its polynomial f_g, low
+ * order first -- secret scalars a_0 .. a_{t-1} (32 B each) or their Feldman commitments C_j = [a_j] G2gen (128 B each) -- at
+ * coef_off[g] .. coef_off[g+1], and n_g participant ids (32 B each) at id_off[g] .. id_off[g+1].  coef_off / id_off:
+ * n_groups + 1 non-decreasing element offsets, host arrays, need not start at 0; outputs are indexed from the first id.
+ * N = ids, T = coefficients of the call.  One lane per share; Horner from the highest coefficient down.
+ * Return of all three: 0; BLSBN254_E_ARG for NULL arguments, decreasing offsets, more than 2^23 ids, coefficients or groups.
+ * n_groups == 0 -> 0.  A bad group or share is never an error of the call.
+ *
+ * Key shares: out[32 i ..] = f_g(id_i) = sum_j a_j id_i^j mod r, canonical big-endian (Scalar multiply / add,
+ * scalar.rs:523-548).  status[g] = BLSBN254_ERR_SCALAR when a coefficient or an id of the group is >= r or an id is 0 (which
+ * would hand out the secret); the outputs of such a group are zero bytes.  Repeated ids are fine.  A group without coefficients
+ * is the zero polynomial: zero bytes, status 0.  Signing side: not constant time (see blsbn254_sign_batch); the staged
+ * coefficients and the device copy of the shares are zeroed in device memory before return. */
+int blsbn254_fr_poly_eval_batch(blsbn254_ctx* ctx, const uint8_t* coeffs /* T*32 */, const uint64_t* coef_off, const uint8_t* ids /* N*32 */,
+                                const uint64_t* id_off, size_t n_groups, uint8_t* out /* N*32 */, uint8_t* status /* n_groups */);
+/* Public key shares: out_pks[128 i ..] = sum_j [id_i^j] C_j, uncompressed (Mul<Scalar> g2.rs:866-886 and Add g2.rs:789-831 for
+ * G2Projective: acc = [id] acc + C_j with plain double-and-add over the complete formulas).  Every commitment is tested as
+ * blsbn254_g2_check_batch tests a key (decodes, on the curve, in the r-torsion; the identity passes), so [id^j mod r] and the
+ * integer Horner agree.  status[g] = BLSBN254_ERR_SCALAR for an id >= r or == 0, else BLSBN254_ERR_G2 for a commitment that
+ * fails the test; the outputs of such a group are the identity encoding (what blsbn254_g2_mul_batch returns for k = 0).  A
+ * group without commitments gives the identity, status 0.  The double-and-add loops over ONE bit count per launch, the largest
+ * bit length of the launch's ids (computed on the host from the id bytes, ids that will be rejected included; at least 1, at
+ * most 254): participant ids are small integers in practice, and ids below 2^16 cost 16/254 of full-width ones. */
+int blsbn254_g2_poly_eval_batch(blsbn254_ctx* ctx, const uint8_t* commitments /* T*128 */, const uint64_t* coef_off, const uint8_t* ids /* N*32 */,
+                                const uint64_t* id_off, size_t n_groups, uint8_t* out_pks /* N*128 */, uint8_t* status /* n_groups */);
+/* Which partial signatures to leave out before blsbn254_threshold_combine_batch: bit i (LSB-first) of valid_bitmap = the bit
+ * blsbn254_verify_batch gives for (out_pks_i, msg_g, partial_sigs_i) with out_pks of blsbn254_g2_poly_eval_batch, whose
+ * arguments and status these are; group g's message is msgs[msg_off[g] .. msg_off[g+1]) (byte offsets, one message per group).
+ * Every bit of a bad group is 0; a bad partial signature (does not decode, off the curve, the identity) clears its own bit only.
+ * The public key shares never leave the device.  The group's message is hashed once per share.  Pending asynchronous verify
+ * calls are settled on entry and none is left pending: the result is final on return. */
+int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* ctx, const uint8_t* commitments /* T*128 */, const uint64_t* coef_off,
+                                           const uint8_t* ids /* N*32 */, const uint8_t* partial_sigs /* N*64 */, const uint64_t* id_off,
+                                           const uint8_t* msgs, const uint64_t* msg_off /* n_groups+1 */, size_t n_groups,
+                                           const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap /* ceil(N/8) */,
+                                           uint8_t* status /* n_groups */);
+/* since context creation: out[0] launches of the G2 evaluation kernel, out[1] shares evaluated in G2, out[2] shares evaluated
+ * in Fr, out[3] the bit count the last G2 launch looped over */
+int blsbn254_threshold_deal_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 
 /* ---- signing side (also used to generate large synthetic batches) ----------- */
 /* sig_i = [sk_i] H(msg_i): G1Projective::hash (g1.rs:910-919) + Mul<Scalar> (g1.rs:518-534, :821-841).
@@ -378,7 +417,7 @@ int blsbn254_gt_pow_batch(blsbn254_ctx* ctx, const uint8_t* gt /* n*384 */, cons
  * (the reference's fp6.rs / fp12.rs have no test vectors; tests fuzz this against the CPU oracle).
  * Element bytes are canonical big-endian coefficients: Fp 32 B; Fp2 64 B = c0 || c1 (NOT the c1 || c0 wire order of G2);
  * Fp6 192 B = c0.c0 c0.c1 c1.c0 c1.c1 c2.c0 c2.c1; Fp12 384 B in Gt::to_repr order.  b is read by the binary ops only
- * (pass NULL otherwise); a coefficient >= p returns BLSBN254_ERR_GT. */
+ * (pass NULL otherwise); a coefficient >= p returns BLSBN254_ERR_GT.  Fr 32 B (operations 64 .. 69). */
 #define BLSBN254_OP_FP_MUL 0          /* Fp::multiply        fp.rs:404-407 */
 #define BLSBN254_OP_FP_SQR 1          /* Fp::square          fp.rs:409-412 */
 #define BLSBN254_OP_FP_INV 2          /* Fp::invert          fp.rs:207-210 (0 -> 0) */
@@ -407,6 +446,13 @@ int blsbn254_gt_pow_batch(blsbn254_ctx* ctx, const uint8_t* gt /* n*384 */, cons
 #define BLSBN254_OP_FP12_FROB3 54
 #define BLSBN254_OP_FP12_CYC_SQR 55   /* cyclotomic_square pairings.rs:68-115 (the Granger-Scott formula on any input) */
 #define BLSBN254_OP_FP12_MUL_034 56   /* sparse line product, a * (b.c0.c0 + b.c1.c0 w + b.c1.c1 v w)  (E7) */
+/* the reference's Scalar, 32 B big-endian; an operand >= r returns BLSBN254_ERR_SCALAR */
+#define BLSBN254_OP_FR_MUL 64         /* scalar.rs:523-548 */
+#define BLSBN254_OP_FR_SQR 65
+#define BLSBN254_OP_FR_INV 66         /* Scalar::invert scalar.rs:216-219 (0 -> 0) */
+#define BLSBN254_OP_FR_ADD 67
+#define BLSBN254_OP_FR_SUB 68
+#define BLSBN254_OP_FR_NEG 69
 int blsbn254_field_op_batch(blsbn254_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out);
 
 /* ---- multi-device (SURVEY.md 8b "ctx over a device list", 8e) -------------------------------------------- */
