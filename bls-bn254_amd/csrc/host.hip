@@ -22,6 +22,7 @@ const char* blsbn254_strerror(int code) {
     case 2: return "invalid G1 bytes";
     case 3: return "invalid G2 bytes";
     case 4: return "invalid Gt bytes";
+    case BLSBN254_ST_SHORT: return "too few usable partial signatures";
     case BLSBN254_E_ARG: return "invalid argument";
     case BLSBN254_E_HIP: return "HIP runtime error";
     case BLSBN254_E_NOMEM: return "out of device memory";

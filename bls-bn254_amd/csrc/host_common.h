@@ -74,6 +74,18 @@ struct BNH TdlWs {
   std::vector<uint8_t> h_msgs;
   std::vector<uint64_t> h_moff;
 };
+// checked threshold combine over groups (host_threshold_checked.hip, k_threshold_checked.hip): the staged ids and partial
+// signatures, the candidate and used bitmaps over the call's shares, the compacted ids / partial signatures (t_g slots per group),
+// the groups' id and coefficient offsets, marks and statuses, the groups' keys C_0 and their verification bits; the host copies
+// the offsets are uploaded from and the marks / bits are downloaded to, and the repacked arrays and results of the fallback's
+// sub-call.  The commitments are staged and checked in TdlWs's buffers.
+struct BNH TcWs {
+  DevBuf ids, sigs, cand, used, c_ids, c_sigs, goff, coff, gstat, st, keys, gbits;
+  std::vector<uint32_t> h_goff, h_coff, h_gstat;
+  std::vector<uint8_t> h_gbits, s_commit, s_ids, s_sigs, s_msgs, s_out, s_used;
+  std::vector<uint64_t> s_coff, s_goff, s_moff;
+  std::vector<size_t> fail;
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -138,6 +150,8 @@ struct blsbn254_ctx {
   ThbWs thb;
   AgbWs agb;
   TdlWs tdl;
+  TcWs tc;
+  uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
   uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
@@ -286,6 +300,16 @@ BNH int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** 
 BNH int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]);   // host_aggregate.hip
 BNH int threshold_combine_one(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]);   // host_aggregate.hip
 BNH int lagrange_one(blsbn254_ctx* c, const uint8_t* ids, size_t t, uint8_t* out);   // host_aggregate.hip
+// threshold combine over groups on ids / partial signatures ALREADY ON THE DEVICE (d_sigs == null: the coefficients alone); off:
+// host offsets as the entry points take them.  Enqueues only: statuses into c->thb.st, encodings into c->thb.out.
+BNH int th_enqueue_dev(blsbn254_ctx* c, const uint8_t* d_ids, const uint8_t* d_sigs, const uint64_t* off, size_t n_groups);   // host_threshold_batch.hip
+BNH size_t th_batch_tbig();   // host_threshold_batch.hip: the largest group the lane-per-share kernels serve
+// the argument checks the dealing-side entry points share, and the device part of blsbn254_threshold_verify_shares_batch: the
+// shares' bits into c->bitmap, the groups' statuses into c->tdl.st (enqueued; the caller downloads and synchronises)
+BNH int td_args(blsbn254_ctx* c, const void* coefs, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, const void* out,
+                const void* status);   // host_threshold_deal.hip
+BNH int td_verify_shares_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint8_t* partial_sigs,
+                                 const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len);   // host_threshold_deal.hip
 
 // A launch of n tuples is small enough that the prepared-key path wins whatever its keys: with line tables the Miller loop (and
 // the final exponentiation) can run one WAVE per tuple (wide.h) or, up to tri_max, three lanes per tuple (k_tri.hip) instead of

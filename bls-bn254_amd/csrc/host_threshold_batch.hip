@@ -76,9 +76,13 @@ static int th_plan(blsbn254_ctx* c, const std::vector<uint32_t>& rel, size_t n_g
   return 0;
 }
 
-// The device part for all groups: per-group statuses into c->thb.st, and with `sigs` the encodings into c->thb.out, else the
-// coefficients into c->scalars.  Everything is enqueued; the caller downloads and synchronises.
-static int th_enqueue(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* sigs, const uint64_t* off, size_t n_groups) {
+size_t th_batch_tbig() { return TH_BATCH_TBIG; }
+
+// The device part for all groups, on ids (and partial signatures) already on the device: per-group statuses into c->thb.st, and
+// with `d_sigs` the encodings into c->thb.out, else the coefficients into c->scalars.  Everything is enqueued; the caller
+// downloads and synchronises.
+int th_enqueue_dev(blsbn254_ctx* c, const uint8_t* d_ids, const uint8_t* d_sigs, const uint64_t* off, size_t n_groups) {
+  const bool sigs = d_sigs != nullptr;
   ThbWs& w = c->thb;
   std::vector<uint32_t>& rel = w.h_goff;                 // ctx-owned: outlive the asynchronous copies (every call ends synchronised)
   rel.resize(n_groups + 1);
@@ -89,17 +93,13 @@ static int th_enqueue(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* sigs, 
   size_t m_max, items_max;
   TRY(th_plan(c, rel, n_groups, launches, w.h_start, w.h_len, &m_max, &items_max));
   const size_t m1 = m_max ? m_max : 1, N1 = N ? N : 1;
-  HIPCHK(c, c->in_b.reserve(32 * N1)); HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->th_glv.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
+  HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->th_glv.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
   HIPCHK(c, w.goff.reserve(4 * (n_groups + 1))); HIPCHK(c, w.gid.reserve(4 * m1)); HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
   if (sigs) {
-    HIPCHK(c, c->in_a.reserve(64 * N1)); HIPCHK(c, w.pts.reserve(27 * m1 * 4)); HIPCHK(c, w.seg[0].reserve(27 * items_max * 4)); HIPCHK(c, w.seg[1].reserve(27 * items_max * 4));
+    HIPCHK(c, w.pts.reserve(27 * m1 * 4)); HIPCHK(c, w.seg[0].reserve(27 * items_max * 4)); HIPCHK(c, w.seg[1].reserve(27 * items_max * 4));
     HIPCHK(c, w.gsum.reserve(27 * n_groups * 4)); HIPCHK(c, w.out.reserve(64 * n_groups));
     HIPCHK(c, w.start.reserve(4 * w.h_start.size())); HIPCHK(c, w.len.reserve(4 * w.h_len.size()));
   } else HIPCHK(c, c->scalars.reserve(32 * N1));
-  if (N) {
-    HIPCHK(c, hipMemcpyAsync(c->in_b.p, ids + 32 * off[0], 32 * N, hipMemcpyHostToDevice, c->stream));
-    if (sigs) HIPCHK(c, hipMemcpyAsync(c->in_a.p, sigs + 64 * off[0], 64 * N, hipMemcpyHostToDevice, c->stream));
-  }
   HIPCHK(c, hipMemcpyAsync(w.goff.p, rel.data(), 4 * (n_groups + 1), hipMemcpyHostToDevice, c->stream));
   if (sigs) {
     HIPCHK(c, hipMemcpyAsync(w.start.p, w.h_start.data(), 4 * w.h_start.size(), hipMemcpyHostToDevice, c->stream));
@@ -112,13 +112,13 @@ static int th_enqueue(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* sigs, 
     const size_t m = L.hi - L.lo;
     ++c->stat_thb[2];
     if (m) {
-      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)c->in_b.p + 32 * L.lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
+      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, d_ids + 32 * L.lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
       TRY(launch(c, c->stream, "lagrange_seg", grid_lanes(m), k_lagrange_seg, (const int32_t*)c->th_x.p, (const uint8_t*)c->status.p, m, (uint32_t)L.lo, goff + L.ga,
                  (uint32_t)(L.gb - L.ga), (uint32_t)TH_BATCH_TBIG, sigs ? (uint8_t*)nullptr : (uint8_t*)c->scalars.p + 32 * L.lo, (uint32_t*)c->th_glv.p, (uint32_t*)w.gid.p,
                  gstat + L.ga));
     }
     if (!sigs) continue;
-    if (m) TRY(launch(c, c->stream, "g1_smul_glv", grid_lanes(m), k_g1_smul_glv, (const uint8_t*)c->in_a.p + 64 * L.lo, (const uint32_t*)c->th_glv.p, (const uint32_t*)w.gid.p, m,
+    if (m) TRY(launch(c, c->stream, "g1_smul_glv", grid_lanes(m), k_g1_smul_glv, d_sigs + 64 * L.lo, (const uint32_t*)c->th_glv.p, (const uint32_t*)w.gid.p, m,
                       (int32_t*)w.pts.p, gstat + L.ga));
     const int32_t* src = (const int32_t*)w.pts.p;
     size_t src_stride = m ? m : 1;
@@ -134,6 +134,18 @@ static int th_enqueue(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* sigs, 
   }
   if (sigs) TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(n_groups), k_g1p_to_bytes, (const int32_t*)w.gsum.p, n_groups, n_groups, (uint8_t*)w.out.p));
   return launch(c, c->stream, "th_finish", grid_lanes(n_groups), k_th_finish, (const uint32_t*)gstat, n_groups, sigs ? (uint8_t*)w.out.p : (uint8_t*)nullptr, (uint8_t*)w.st.p);
+}
+
+// the same for ids (and partial signatures) of the caller: staged in c->in_b (c->in_a) first
+static int th_enqueue(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* sigs, const uint64_t* off, size_t n_groups) {
+  const size_t N = (size_t)(off[n_groups] - off[0]), N1 = N ? N : 1;
+  HIPCHK(c, c->in_b.reserve(32 * N1));
+  if (sigs) HIPCHK(c, c->in_a.reserve(64 * N1));
+  if (N) {
+    HIPCHK(c, hipMemcpyAsync(c->in_b.p, ids + 32 * off[0], 32 * N, hipMemcpyHostToDevice, c->stream));
+    if (sigs) HIPCHK(c, hipMemcpyAsync(c->in_a.p, sigs + 64 * off[0], 64 * N, hipMemcpyHostToDevice, c->stream));
+  }
+  return th_enqueue_dev(c, (const uint8_t*)c->in_b.p, sigs ? (const uint8_t*)c->in_a.p : nullptr, off, n_groups);
 }
 
 static int th_args(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* second, bool need_second, const uint64_t* off, size_t n_groups, const void* out, const void* status) {

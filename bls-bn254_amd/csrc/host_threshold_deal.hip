@@ -43,7 +43,7 @@ static int td_id_bits(const uint8_t* ids, size_t m) {
   }
   return std::min(best, TD_MAX_BITS);
 }
-static int td_args(blsbn254_ctx* c, const void* coefs, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, const void* out, const void* status) {
+int td_args(blsbn254_ctx* c, const void* coefs, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, const void* out, const void* status) {
   if (!coef_off || !id_off || !status) return BLSBN254_E_ARG;
   if (check_offsets(coef_off, n_groups) || check_offsets(id_off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
   const size_t N = (size_t)(id_off[n_groups] - id_off[0]), T = (size_t)(coef_off[n_groups] - coef_off[0]);
@@ -147,6 +147,35 @@ int blsbn254_g2_poly_eval_batch(blsbn254_ctx* c, const uint8_t* commitments, con
   return download(c, status, c->tdl.st.p, n_groups);
 }
 
+// The device part of the check of partial signatures (arguments already checked): the key shares evaluated into c->tdl.pks,
+// the N bits into c->bitmap, the groups' statuses into c->tdl.st.  Enqueued; the caller downloads and synchronises.
+int td_verify_shares_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint8_t* partial_sigs,
+                             const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len) {
+  const size_t N = (size_t)(id_off[n_groups] - id_off[0]);
+  TdlWs& w = c->tdl;
+  HIPCHK(c, w.pks.reserve(128 * (N ? N : 1)));
+  TRY(td_g2_enqueue(c, commitments, coef_off, ids, id_off, n_groups, (uint8_t*)w.pks.p));
+  if (!N) return 0;
+  // the verify pipeline takes one message per tuple: the group's message once per share (ctx-owned: outlives the upload)
+  w.h_msgs.clear(); w.h_moff.resize(N + 1);
+  size_t i = 0;
+  w.h_moff[0] = 0;
+  for (size_t g = 0; g < n_groups; ++g) {
+    const size_t len = (size_t)(msg_off[g + 1] - msg_off[g]);
+    for (uint64_t s = id_off[g]; s < id_off[g + 1]; ++s, ++i) {
+      if (len) w.h_msgs.insert(w.h_msgs.end(), msgs + msg_off[g], msgs + msg_off[g + 1]);
+      w.h_moff[i + 1] = w.h_moff[i] + len;
+    }
+  }
+  TRY(stage_msgs(c, w.h_msgs.data(), w.h_moff.data(), N));
+  HIPCHK(c, c->bitmap.reserve((N + 7) / 8 + 8));
+  TRY(upload(c, c->in_b, partial_sigs + 64 * id_off[0], 64 * N));
+  // the public key shares never leave the device; the counting path, so that nothing is left pending and the bitmap is
+  // final behind this call on the stream
+  return blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)w.pks.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, N, dst, dst_len,
+                                                 (uint8_t*)c->bitmap.p);
+}
+
 int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint8_t* partial_sigs,
                                            const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
                                            uint8_t* valid_bitmap, uint8_t* status) {
@@ -160,32 +189,9 @@ int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* c, const uint8_t* commi
   if (N && !partial_sigs) return BLSBN254_E_ARG;
   if (!msgs && msg_off[n_groups] != msg_off[0]) return BLSBN254_E_ARG;
   ENTER(c);
-  TdlWs& w = c->tdl;
-  HIPCHK(c, w.pks.reserve(128 * (N ? N : 1)));
-  TRY(td_g2_enqueue(c, commitments, coef_off, ids, id_off, n_groups, (uint8_t*)w.pks.p));
-  if (N) {
-    // the verify pipeline takes one message per tuple: the group's message once per share (ctx-owned: outlives the upload)
-    w.h_msgs.clear(); w.h_moff.resize(N + 1);
-    size_t i = 0;
-    w.h_moff[0] = 0;
-    for (size_t g = 0; g < n_groups; ++g) {
-      const size_t len = (size_t)(msg_off[g + 1] - msg_off[g]);
-      for (uint64_t s = id_off[g]; s < id_off[g + 1]; ++s, ++i) {
-        if (len) w.h_msgs.insert(w.h_msgs.end(), msgs + msg_off[g], msgs + msg_off[g + 1]);
-        w.h_moff[i + 1] = w.h_moff[i] + len;
-      }
-    }
-    TRY(stage_msgs(c, w.h_msgs.data(), w.h_moff.data(), N));
-    const size_t nb = (N + 7) / 8;
-    HIPCHK(c, c->bitmap.reserve(nb + 8));
-    TRY(upload(c, c->in_b, partial_sigs + 64 * id_off[0], 64 * N));
-    // the public key shares never leave the device; the counting path, so that nothing is left pending and the bitmap is
-    // final behind this call on the stream
-    TRY(blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)w.pks.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, N, dst, dst_len,
-                                                (uint8_t*)c->bitmap.p));
-    HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, nb, hipMemcpyDeviceToHost, c->stream));
-  }
-  return download(c, status, w.st.p, n_groups);
+  TRY(td_verify_shares_enqueue(c, commitments, coef_off, ids, partial_sigs, id_off, msgs, msg_off, n_groups, dst, dst_len));
+  if (N) HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, (N + 7) / 8, hipMemcpyDeviceToHost, c->stream));
+  return download(c, status, c->tdl.st.p, n_groups);
 }
 
 int blsbn254_threshold_deal_stats(blsbn254_ctx* c, uint64_t out[4]) {

@@ -154,6 +154,13 @@ BN_KERNEL k_td_fr_encode(const int32_t* r_ws, size_t N, size_t m, uint32_t lo, c
 BN_KERNEL k_td_g2_encode(const int32_t* r_ws, size_t N, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, const uint32_t* gstat, uint8_t* out);
 __global__ void __launch_bounds__(256) k_td_finish(uint32_t* gstat, size_t n_groups, const uint32_t* coff, const uint8_t* ok_a, const uint8_t* ok_b, uint32_t mark,
                                                   uint8_t* status);
+BN_KERNEL k_tc_scan(const uint8_t* ids, const uint8_t* sigs, const uint8_t* id_ok, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, uint32_t* gstat,
+                    uint8_t* cand);
+__global__ void __launch_bounds__(256) k_tc_select(const uint8_t* bits_a, const uint8_t* bits_b, size_t m, uint32_t lo, const uint32_t* goff, const uint32_t* coff,
+                                                  uint32_t ng, uint32_t* gstat, const uint32_t* ids, const uint32_t* sigs, uint32_t* c_ids, uint32_t* c_sigs,
+                                                  uint8_t* used);
+__global__ void __launch_bounds__(256) k_tc_gather_c0(const uint32_t* commitments, const uint32_t* coff, const uint32_t* goff, size_t n_groups, uint32_t* gstat,
+                                                     uint32_t* keys);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

@@ -16,6 +16,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_DST = b"BLS_SIG_BN254G1_XMD:SHA-256_SVDW_RO_NUL_"
+ST_SHORT = 5           # BLSBN254_ST_SHORT: a per-group status of threshold_combine_checked_batch, never an exception
 POP_DST = b"BLS_POP_BN254G1_XMD:SHA-256_SVDW_RO_POP_"
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -584,6 +585,37 @@ class Engine:
         o = (ctypes.c_uint64 * 4)()
         self._chk(self._lib.blsbn254_threshold_deal_stats(self._ctx, o))
         return {"g2_launches": int(o[0]), "g2_shares": int(o[1]), "fr_shares": int(o[2]), "id_bits": int(o[3])}
+
+    def threshold_combine_checked_batch(self, commit_sets, id_sets, sig_sets, msgs, dst=DEFAULT_DST):
+        """The combiner's call: from group g's Feldman commitments (commit_sets[g], 128 bytes each; their number is the threshold
+        t_g), the ids and partial signatures it received (id_sets[g], sig_sets[g]) and its message msgs[g], the group signature
+        over t_g good partials.  Returns (sigs, used_bitmap, status): 64 bytes per group, bit i (LSB-first, in the order given) =
+        share i was interpolated, one status byte per group (0, ERR_SCALAR = 1: an id >= r, 0 or repeated, ERR_G2 = 3: a bad
+        commitment, ST_SHORT = 5: no t_g shares whose combination verifies).  The first t_g decodable partials are tried first
+        and checked with one pairing equation under C_0; only a group that fails it has every partial verified.  A bad group's
+        signature is the identity encoding and its used bits are 0.  No exception for a bad group."""
+        coff, goff, n = self._deal_args(commit_sets, 128, id_sets)
+        g = len(id_sets)
+        if len(sig_sets) != g or len(msgs) != g:
+            raise ValueError("one set of partial signatures and one message per set of ids")
+        if not np.array_equal(goff, self._group_offsets(sig_sets, 64, "a set of partial signatures")):
+            raise ValueError("a group needs as many partial signatures as ids")
+        data, moff = pack_messages(list(msgs))
+        a, pa = _inbuf(b"".join(commit_sets)); x, px = _inbuf(b"".join(id_sets)); s, ps = _inbuf(b"".join(sig_sets))
+        m, pm = _inbuf(data); d, pd = _inbuf(dst); o, po = _outbuf(64 * g)
+        nb = (n + 7) // 8
+        used = np.zeros(max(nb, 1), dtype=np.uint8); st = np.zeros(max(g, 1), dtype=np.uint8)
+        self._chk(self._lib.blsbn254_threshold_combine_checked_batch(self._ctx, pa, coff.ctypes.data_as(_u64p), px, ps, goff.ctypes.data_as(_u64p), pm,
+                                                                     moff.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po,
+                                                                     used.ctypes.data_as(_u8p), st.ctypes.data_as(_u8p)))
+        return o[:64 * g].tobytes(), used[:nb].tobytes(), st[:g].tobytes()
+
+    def threshold_checked_stats(self):
+        """dict: groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually,
+        groups that ended in ST_SHORT"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_threshold_checked_stats(self._ctx, o))
+        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_shares": int(o[2]), "short_groups": int(o[3])}
 
     # ---- Gt group operations and the field-primitive debug ABI
     FIELD_OP_WIDTH = {**{k: 32 for k in range(0, 9)}, **{k: 64 for k in range(16, 22)}, **{k: 192 for k in range(32, 36)},

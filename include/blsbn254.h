@@ -341,6 +341,37 @@ int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* ctx, const uint8_t* com
 /* since context creation: out[0] launches of the G2 evaluation kernel, out[1] shares evaluated in G2, out[2] shares evaluated
  * in Fr, out[3] the bit count the last G2 launch looped over */
 int blsbn254_threshold_deal_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* The combiner's call, over ragged groups: from a group's commitments, its message and the n_g >= t_g partial signatures it
+ * received, the group signature sum_i lambda_i sigma_i over t_g good ones.  Arguments, offsets and argument errors are those of
+ * blsbn254_threshold_verify_shares_batch (host arrays that need not start at 0; BLSBN254_E_ARG for NULL arguments, decreasing
+ * offsets, more than 2^23 ids, coefficients or groups; n_groups == 0 -> 0), and out_sigs must not be NULL.  The threshold of
+ * group g is its number of commitments, t_g = coef_off[g+1] - coef_off[g].  A group of more than 4096 shares (the size up to
+ * which blsbn254_threshold_combine_batch runs one lane per share, blsbn254_threshold_batch_stats out[3]) makes the call return
+ * BLSBN254_E_ARG.  The result never depends on the path taken, on launch boundaries or on how many groups share the call.
+ *
+ * A share is a CANDIDATE when its partial signature decodes, is on the curve and is not the identity; the others are left out
+ * and never fail their group.  status[g], in this precedence: BLSBN254_ERR_SCALAR (an id of the group -- any of the n_g, not
+ * only the ones used -- is >= r, is 0, or is repeated in the group), BLSBN254_ERR_G2 (a commitment fails the test of
+ * blsbn254_g2_poly_eval_batch), BLSBN254_ST_SHORT (t_g == 0, or no t_g shares could be found whose combination verifies: fewer
+ * than t_g candidates, or fewer than t_g candidates that verify individually), else 0.  A bad group is never an error of the
+ * call: its out_sigs is the identity encoding (0, 1), all its used bits are 0, and its neighbours are unaffected.
+ * With status 0, out_sigs[64 g ..] verifies under C_0 = commitments[coef_off[g]] for the group's message and dst, and
+ * used_bitmap (LSB-first, in the order of the ids) marks exactly the t_g shares that were interpolated: the group's first t_g
+ * candidates if their combination verifies under C_0 (ONE pairing equation per group, no key share evaluated), otherwise the
+ * first t_g candidates whose bit blsbn254_threshold_verify_shares_batch sets (the per-share check runs for such groups only,
+ * and its result is not verified again: partial signatures that verify individually interpolate to [f_g(0)] H(msg)).
+ * A consequence of the optimistic rule: partial signatures whose errors cancel in the interpolation (lambda_1 delta_1 +
+ * lambda_2 delta_2 = 0) are used and the group's signature is correct, although blsbn254_threshold_verify_shares_batch would
+ * clear their bits.  Pending asynchronous verify calls are settled on entry and none is left pending. */
+#define BLSBN254_ST_SHORT 5   /* a per-group status only, never a return value: no signature could be produced */
+int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* ctx, const uint8_t* commitments /* T*128 */, const uint64_t* coef_off,
+                                             const uint8_t* ids /* N*32 */, const uint8_t* partial_sigs /* N*64 */, const uint64_t* id_off,
+                                             const uint8_t* msgs, const uint64_t* msg_off /* n_groups+1 */, size_t n_groups,
+                                             const uint8_t* dst, size_t dst_len, uint8_t* out_sigs /* n_groups*64 */,
+                                             uint8_t* used_bitmap /* ceil(N/8) */, uint8_t* status /* n_groups */);
+/* since context creation: out[0] groups settled by the optimistic attempt, out[1] groups sent to the per-share fallback, out[2]
+ * shares verified individually, out[3] groups ending in BLSBN254_ST_SHORT */
+int blsbn254_threshold_checked_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 
 /* ---- signing side (also used to generate large synthetic batches) ----------- */
 /* sig_i = [sk_i] H(msg_i): G1Projective::hash (g1.rs:910-919) + Mul<Scalar> (g1.rs:518-534, :821-841).

@@ -226,6 +226,43 @@ pub fn threshold_combine(ids: &[[u8; 32]], partials: &[[u8; 64]]) -> Result<[u8;
     Ok(out)
 }
 
+/// What a combiner needs, for many committees at once (`blsbn254_threshold_combine_checked_batch`): `groups[g]` = the Feldman
+/// commitments of group g (their number is its threshold), the (id, partial signature) pairs it received and its message.
+/// Element g = `Ok((signature, used))` with `used[i]` telling whether share i was interpolated, or `Err(status)` with the
+/// group's status byte (1 = a bad or repeated id, 3 = a bad commitment, 5 = too few usable partial signatures).  The first
+/// t_g decodable partials are tried first and checked with ONE pairing equation under C_0; only a group that fails it has
+/// every partial verified against its key share.
+pub fn threshold_combine_checked_batch(groups: &[(&[[u8; 128]], &[([u8; 32], [u8; 64])], &[u8])], dst: &[u8]) -> Vec<Result<([u8; 64], Vec<bool>), u8>> {
+    let n = groups.len();
+    let (mut coff, mut goff) = (Vec::with_capacity(n + 1), Vec::with_capacity(n + 1));
+    coff.push(0u64);
+    goff.push(0u64);
+    let (mut cm, mut id, mut ps): (Vec<u8>, Vec<u8>, Vec<u8>) = (Vec::new(), Vec::new(), Vec::new());
+    let mut msgs: Vec<&[u8]> = Vec::with_capacity(n);
+    for (commitments, shares, msg) in groups {
+        for c in commitments.iter() { cm.extend_from_slice(c); }
+        for (i, s) in shares.iter() { id.extend_from_slice(i); ps.extend_from_slice(s); }
+        coff.push((cm.len() / 128) as u64);
+        goff.push((id.len() / 32) as u64);
+        msgs.push(msg);
+    }
+    let (data, moff) = pack(&msgs);
+    let total = id.len() / 32;
+    let mut out = vec![0u8; 64 * n];
+    let mut used = vec![0u8; (total + 7) / 8];
+    let mut status = vec![0u8; n];
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_threshold_combine_checked_batch(c, cm.as_ptr(), coff.as_ptr(), id.as_ptr(), ps.as_ptr(), goff.as_ptr(), data.as_ptr(), moff.as_ptr(), n,
+                                                      dst.as_ptr(), dst.len(), out.as_mut_ptr(), used.as_mut_ptr(), status.as_mut_ptr())
+    }))
+    .expect("per-group failures are reported in the status bytes");
+    let all = bits(&used, total);
+    (0..n).map(|g| match status[g] {
+        0 => Ok((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), all[goff[g] as usize..goff[g + 1] as usize].to_vec())),
+        st => Err(st),
+    }).collect()
+}
+
 // ---------------------------------------------------------------- group operators on the crate's own types
 
 /// Body of `impl Mul<Scalar> for G1Projective` (`g1.rs:518-534`, `multiply :821-841`), element-wise over a slice:
