@@ -5,9 +5,9 @@
 // one H workspace, the G signatures are placed behind them (slot N + g), the caller's N keys get the r-torsion test.  Then the
 // Miller loops run two slots per lane sharing one f^2 (k_miller_hpk2r, the loop of k_miller_hpk2): group g of k pairs takes
 // ceil((k + 1) / 2) consecutive lanes over the slot sequence [its pairs ..., its signature], the signature's slot pairing with
-// the constant -G2gen.  The lanes are the "items" of the pairing-product equations' planner (pc_plan_launches): launches of at
-// most ctx->chunk lanes cut at a group boundary where one lies in the window, a group cut by a launch boundary carried, each
-// group's lanes multiplied level by level (k_fp12_seg_prod) with the validity byte folded per lane (k_agb_fold); the products
+// the constant -G2gen.  The lanes are the "items" of the planner the pairing-product equations use (plan_launches_cut): launches
+// of at most ctx->chunk lanes cut at a group boundary where one lies in the window, a group cut by a launch boundary carried, each
+// group's lanes multiplied level by level (seg_run_levels with k_fp12_seg_prod) with the validity byte folded per lane (k_agb_fold); the products
 // then finish as blsbn254_pairing_check_batch's do (final exponentiation, mode 0 bitmap).  Slot and chunk descriptors are
 // planned on the host from the offsets and uploaded once.
 #include "host_common.h"
@@ -41,41 +41,37 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const u
   // lanes: group g's slot sequence [base-relative pairs ..., N + g] two by two
   AgbWs& a = c->agb;
   PcWs& w = c->pc;
-  std::vector<uint32_t> &sa = a.h_slot_a, &sb = a.h_slot_b, &goff = a.h_goff;       // ctx-owned: outlive the asynchronous copies
+  std::vector<uint32_t> &sa = a.h_slot_a, &sb = a.h_slot_b;
   std::vector<uint64_t> lane_off(G + 1);
-  goff.resize(G + 1);
   sa.clear(); sb.clear();
   sa.reserve((N + G) / 2 + G); sb.reserve((N + G) / 2 + G);
-  lane_off[0] = 0; goff[0] = 0;
+  lane_off[0] = 0;
   for (size_t g = 0; g < G; ++g) {
     const size_t p0 = (size_t)grp_off[g] - base, k = (size_t)(grp_off[g + 1] - grp_off[g]);
     for (size_t j = 0; j <= k; j += 2) {                // positions j, j + 1 of the k + 1 slots
       sa.push_back((uint32_t)(j < k ? p0 + j : N + g));
       sb.push_back(j + 1 < k ? (uint32_t)(p0 + j + 1) : (j + 1 == k ? (uint32_t)(N + g) : AGB_NO_SLOT));
     }
-    goff[g + 1] = (uint32_t)(p0 + k);
     lane_off[g + 1] = sa.size();
   }
   const size_t lanes = sa.size();
-  std::vector<uint32_t>& start = w.h_start;
-  std::vector<uint32_t>& len = w.h_len;
-  start.clear(); len.clear();
-  std::vector<PcLaunch> launches;
+  w.seg.h_start.clear(); w.seg.h_len.clear();
+  std::vector<SegLaunch> launches;
   size_t items_max;
-  TRY(pc_plan_launches(c, lane_off, G, launches, start, len, &items_max));
+  if (!plan_launches_cut(lane_off, G, c->chunk, FP12_SEG_GROUP, launches, w.seg.h_start, w.seg.h_len, &items_max)) {
+    c->last_error = "internal: segmented products do not converge";
+    return BLSBN254_E_HIP;
+  }
   const size_t m_max = std::min(lanes, c->chunk), S = N + G;
   TRY(pc_reserve_products(c, G, items_max));
-  HIPCHK(c, w.start.reserve(4 * start.size())); HIPCHK(c, w.len.reserve(4 * len.size())); HIPCHK(c, w.pair_ok.reserve(m_max + 1));
-  HIPCHK(c, a.slot_a.reserve(4 * lanes)); HIPCHK(c, a.slot_b.reserve(4 * lanes)); HIPCHK(c, a.goff.reserve(4 * (G + 1))); HIPCHK(c, a.sig_ok.reserve(G));
+  TRY(stage_group_offsets(c, a.goff, grp_off, G));
+  HIPCHK(c, w.pair_ok.reserve(m_max + 1)); HIPCHK(c, a.sig_ok.reserve(G));
   HIPCHK(c, c->in_a.reserve(128 * N)); HIPCHK(c, c->in_b.reserve(64 * G)); HIPCHK(c, c->h_ws.reserve(S * 18 * 4));
   HIPCHK(c, c->f_ws.reserve(m_max * 108 * 4)); HIPCHK(c, c->q_ws.reserve(m_max * 72 * 4)); HIPCHK(c, c->flags.reserve(N)); HIPCHK(c, c->sub_ok.reserve(N));
   HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks + 128 * base, 128 * N, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sigs, 64 * G, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(a.slot_a.p, sa.data(), 4 * lanes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(a.slot_b.p, sb.data(), 4 * lanes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(a.goff.p, goff.data(), 4 * (G + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(w.start.p, start.data(), 4 * start.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(w.len.p, len.data(), 4 * len.size(), hipMemcpyHostToDevice, c->stream));
+  TRY(upload(c, a.slot_a, sa.data(), 4 * lanes));
+  TRY(upload(c, a.slot_b, sb.data(), 4 * lanes));
 
   const uint8_t* d_pks = (const uint8_t*)c->in_a.p;
   int32_t* h = (int32_t*)c->h_ws.p;
@@ -84,13 +80,17 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(launch(c, c->stream, "agb_place_sigs", grid_lanes(G), k_agb_place_sigs, (const uint8_t*)c->in_b.p, G, h, N, S, (uint8_t*)a.sig_ok.p));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(N), k_g2_check, d_pks, N, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));   // the caller's keys only: never -G2gen
   const uint32_t *d_sa = (const uint32_t*)a.slot_a.p, *d_sb = (const uint32_t*)a.slot_b.p;
-  for (const PcLaunch& L : launches) {
+  for (const SegLaunch& L : launches) {
     const size_t m = L.hi - L.lo;                       // (every group has its signature's lane: no launch is empty)
     TRY(launch(c, c->stream, "miller_hpk2r", grid_lanes(m), k_miller_hpk2r, (const int32_t*)h, S, d_pks, N, d_sa + L.lo, d_sb + L.lo, m, (int32_t*)c->q_ws.p,
                (int32_t*)c->f_ws.p, m, (uint8_t*)c->flags.p));
     TRY(launch(c, c->stream, "agb_fold", grid_lanes(m), k_agb_fold, d_sa + L.lo, d_sb + L.lo, m, N, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p,
-               (const uint8_t*)a.sig_ok.p, (const uint32_t*)a.goff.p, (uint8_t*)w.pair_ok.p));
-    TRY(pc_run_levels(c, L, (const int32_t*)c->f_ws.p, (const uint8_t*)w.pair_ok.p, m, G, true));
+               (const uint8_t*)a.sig_ok.p, (const uint32_t*)a.goff.d.p, (uint8_t*)w.pair_ok.p));
+    TRY(seg_run_levels(w.seg, L.levels, {(const int32_t*)c->f_ws.p, m, (const uint8_t*)w.pair_ok.p}, {(int32_t*)w.prod.p + L.ga, G, (uint8_t*)w.ok.p + L.ga},
+                       [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool last) {
+      return launch(c, c->stream, "fp12_seg_prod", grid_lanes(runs), k_fp12_seg_prod, in.v, in.stride, in.ok, start, len, runs, out.v, out.stride, out.ok,
+                    (last && L.carry) ? 1 : 0);
+    }));
   }
   TRY(pc_finish_bitmap(c, G, valid_bitmap));
   c->stat_agb[0] += G; c->stat_agb[1] += lanes; c->stat_agb[3] += launches.size();      // counted once the call has succeeded

@@ -15,6 +15,7 @@
 #include "sha256.h"      // host-side use: pre-hashing an oversize DST only (RFC 9380 5.3.3)
 #include "lane_ops.h"    // flag constants
 #include "kernels.h"
+#include "seg_plan.h"    // SegLevel, SegLaunch, the planners of the segmented reductions
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -43,45 +44,49 @@ struct BNH DevBuf {
 // multi-scalar multiplication (host_msm.hip, k_msm_bucket.hip): point rows, bucket entries, sorted entries, bucket counts and ends,
 // the levels' partial sums (ping-pong), the bucket sums, the window segments, the device-side counters; reserved for the largest call
 struct BNH MsmWs { DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, stat; };
-// pairing-product equations (host_pairing_check.hip, k_pairing_check.hip): per-equation products (limb-major, stride n_eq) and
-// validity, per-pair validity of a launch, the product levels (ping-pong) with their flags, the chunk descriptors (device and
-// the host copies they are uploaded from)
-struct BNH PcWs {
-  DevBuf prod, ok, pair_ok, seg[2], seg_ok[2], start, len;
+// A segmented reduction over ragged groups (seg_plan.h, seg_stage / seg_run_levels below): the levels between the first and the
+// last (ping-pong) with their flags, and the run descriptors of every level of every launch of a call, on the device and as the
+// host copies they are uploaded from.  The rule for every host copy an upload reads (these, GroupOff::h, the h_* / s_* vectors
+// below): it is a member of the context, so it outlives the asynchronous copy, because every entry point ends synchronised.
+// One instance per user: the host copies live for a whole call, and one call may run two reductions.
+struct BNH SegWs {
+  DevBuf seg[2], seg_ok[2], start, len;
   std::vector<uint32_t> h_start, h_len;
 };
+// a call's group offsets rebased to 0, 32-bit: on the device and the host copy they are uploaded from (stage_group_offsets)
+struct BNH GroupOff { DevBuf d; std::vector<uint32_t> h; };
+// pairing-product equations (host_pairing_check.hip, k_pairing_check.hip): per-equation products (limb-major, stride n_eq) and
+// validity, per-pair validity of a launch, the product levels
+struct BNH PcWs { DevBuf prod, ok, pair_ok; SegWs seg; };
 // threshold combine over groups (host_threshold_batch.hip, k_threshold_batch.hip): the groups' offsets, per-share group words,
-// the products, the levels of the group sums (ping-pong), the sums, the per-group marks, the chunk descriptors (device and the
-// host copies they are uploaded from), the encodings and statuses
-struct BNH ThbWs {
-  DevBuf goff, gid, pts, seg[2], gsum, gstat, start, len, out, st;
-  std::vector<uint32_t> h_goff, h_start, h_len;
-};
-// aggregate verify over groups (host_aggregate_batch.hip, k_aggregate_batch.hip): the lanes' slot descriptors, the groups' pair
-// offsets (rebased to 0), the signatures' flags; device buffers and the host copies they are uploaded from.  The products, their
-// levels and chunk descriptors are PcWs's.
+// the products, the levels of the group sums, the sums, the per-group marks, the encodings and statuses
+struct BNH ThbWs { GroupOff goff; DevBuf gid, pts, gsum, gstat, out, st; SegWs seg; };
+// aggregate verify over groups (host_aggregate_batch.hip, k_aggregate_batch.hip): the lanes' slot descriptors (device buffers and
+// the host copies they are uploaded from), the groups' pair offsets, the signatures' flags.  The products and their levels are PcWs's.
 struct BNH AgbWs {
-  DevBuf slot_a, slot_b, goff, sig_ok;
-  std::vector<uint32_t> h_slot_a, h_slot_b, h_goff;
+  DevBuf slot_a, slot_b, sig_ok;
+  GroupOff goff;
+  std::vector<uint32_t> h_slot_a, h_slot_b;
 };
 // key shares and their public keys over groups (host_threshold_deal.hip, k_threshold_deal.hip): the staged coefficients /
 // commitments and ids, the decoded coefficients (9 x T limbs) / loaded commitments (54 x T limbs) with their validity bytes, the
 // shares before their encoding (9 x N / 54 x N limbs), the groups' id and coefficient offsets, the per-group marks and statuses,
-// the public key shares in wire format; the host copies the offsets and the per-share messages are uploaded from
+// the public key shares in wire format; the host copies the per-share messages are uploaded from
 struct BNH TdlWs {
-  DevBuf coef, ids, cf_ws, c_ws, c_ok, c_sub, r_ws, goff, coff, gstat, st, pks;
-  std::vector<uint32_t> h_goff, h_coff;
+  DevBuf coef, ids, cf_ws, c_ws, c_ok, c_sub, r_ws, gstat, st, pks;
+  GroupOff goff, coff;
   std::vector<uint8_t> h_msgs;
   std::vector<uint64_t> h_moff;
 };
 // checked threshold combine over groups (host_threshold_checked.hip, k_threshold_checked.hip): the staged ids and partial
 // signatures, the candidate and used bitmaps over the call's shares, the compacted ids / partial signatures (t_g slots per group),
 // the groups' id and coefficient offsets, marks and statuses, the groups' keys C_0 and their verification bits; the host copies
-// the offsets are uploaded from and the marks / bits are downloaded to, and the repacked arrays and results of the fallback's
-// sub-call.  The commitments are staged and checked in TdlWs's buffers.
+// the marks / bits are downloaded to, and the repacked arrays and results of the fallback's sub-call.  The commitments are
+// staged and checked in TdlWs's buffers (td_stage_commitments).
 struct BNH TcWs {
-  DevBuf ids, sigs, cand, used, c_ids, c_sigs, goff, coff, gstat, st, keys, gbits;
-  std::vector<uint32_t> h_goff, h_coff, h_gstat;
+  DevBuf ids, sigs, cand, used, c_ids, c_sigs, gstat, st, keys, gbits;
+  GroupOff goff, coff;
+  std::vector<uint32_t> h_gstat;
   std::vector<uint8_t> h_gbits, s_commit, s_ids, s_sigs, s_msgs, s_out, s_used;
   std::vector<uint64_t> s_coff, s_goff, s_moff;
   std::vector<size_t> fail;
@@ -140,7 +145,8 @@ struct blsbn254_ctx {
   bool split_easy = true;            // BLSBN254_SPLIT_EASY=0: the one-launch easy part at every size
   size_t wide_fe_max = 2048;         // ... used for launches of at most this many tuples (BLSBN254_WIDE_FE_MAX): two rounds of a wave per tuple
                                      // cost what the three-lanes-per-tuple kernels cost for anything up to 16384 (r03: 4096 wide = 7.8 ms, 4100 on quads = 5.6 ms)
-  DevBuf gs_ws[3], gs_ok[3], gs_start, gs_len, gs_pk;   // segmented G2 sums (host_groupops.hip): items / chunk sums (ping-pong), flags, chunk descriptors, the sums' encodings
+  DevBuf gs_items, gs_items_ok, gs_sum, gs_sum_ok, gs_pk;   // segmented G2 sums (host_groupops.hip): the loaded points and the groups' sums with their flags, the sums' encodings
+  SegWs gs;                                                 // ... and the levels between them
   DevBuf fe_slots;       // the ten named powers of the t -> t^x addition chain, 10 x 108 x n limbs
   uint8_t dst_host[256];  // the (pre-hashed if oversize) DST currently resident in `dst`, and its length; -1 = none
   int dst_host_len = -1;
@@ -212,6 +218,25 @@ static inline int for_chunks(const blsbn254_ctx* c, size_t n, F body) {
   for (size_t lo = 0; lo < n; lo += c->chunk) TRY(body(lo, std::min(n - lo, c->chunk)));
   return 0;
 }
+// The levels of one launch of a segmented reduction, written once: level 0 reads `src`, every level but the last writes w's
+// ping-pong buffers (flags only where the final destination has them), the last one writes `fin`.  level(src, start, len, m, out,
+// last) launches one level's kernel over m runs; the descriptors are w's, staged by seg_stage.
+struct SegSrc { const int32_t* v; size_t stride; const uint8_t* ok; };
+struct SegDst { int32_t* v; size_t stride; uint8_t* ok; };
+template <typename F>
+static inline int seg_run_levels(const SegWs& w, const std::vector<SegLevel>& levels, SegSrc src, SegDst fin, F level) {
+  int dst = 0;
+  for (size_t lv = 0; lv < levels.size(); ++lv) {
+    const SegLevel& P = levels[lv];
+    const bool last = lv + 1 == levels.size();
+    const SegDst out = last ? fin : SegDst{(int32_t*)w.seg[dst].p, P.count, fin.ok ? (uint8_t*)w.seg_ok[dst].p : nullptr};
+    TRY(level(src, (const uint32_t*)w.start.p + P.first, (const uint32_t*)w.len.p + P.first, P.count, out, last));
+    src = {out.v, out.stride, out.ok}; dst ^= 1;
+  }
+  return 0;
+}
+// G1Affine::identity on the wire: x = 0, y = 1
+static inline void g1_identity_bytes(uint8_t o[64]) { std::memset(o, 0, 64); o[63] = 1; }
 
 // Work forked onto stream2 must never outlive a failing call: a function that forks holds one of these, and an early
 // error return (before the main stream has waited for ev_join) then waits for stream2 on the way out, so nothing is
@@ -253,7 +278,6 @@ static const size_t PREP_RAW_LIMBS = (size_t)BN_NEG_G2_LINES * 54;       // a ke
 static const size_t PREP_KEY_LIMBS = (size_t)BN_NEG_G2_LINES * 162;      // a key's 88 expanded line pairs (key line x -G2gen line)
 struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok; };   // pair tables (verify), raw line triples (multi_miller_loop), validity
 
-struct SegLevel { size_t first, count; };   // one level of a segmented reduction (plan_seg_levels below)
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip
 BNH int check_offsets(const uint64_t* off, size_t n);   // host.hip
@@ -287,14 +311,16 @@ BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip
 BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
                           size_t cnt, uint8_t* d_isone);   // host_rlc.hip
-// pairing-product planning and products, shared with the aggregate verify over groups (host_pairing_check.hip): the launches over
-// items rel[0..n_eq] (rebased offsets) with their product levels; one launch's levels from its items' values / flags into
-// c->pc.prod / c->pc.ok; the products' final exponentiation into the bitmap, by chunks of equations
-struct PcLaunch { size_t lo, hi, ga, gb; bool carry; std::vector<SegLevel> levels; };
-BNH int pc_plan_launches(blsbn254_ctx* c, const std::vector<uint64_t>& rel, size_t n_eq, std::vector<PcLaunch>& out,
-                         std::vector<uint32_t>& start, std::vector<uint32_t>& len, size_t* items_max);
+// The segmented reductions' device side.  seg_stage: w's ping-pong buffers for levels of at most items_max items of `limbs` limbs
+// (with `flags`, a byte per item too) and the upload of the descriptors planned into w.h_start / w.h_len.
+BNH int seg_stage(blsbn254_ctx* c, SegWs& w, size_t items_max, size_t limbs, bool flags);   // host_seg.hip
+// the caller's offsets off[0 .. n_groups], rebased to 0, into o.h and o.d (enqueued); more than MAX_LANES elements: an internal error
+BNH int stage_group_offsets(blsbn254_ctx* c, GroupOff& o, const uint64_t* off, size_t n_groups);   // host_seg.hip
+// pairing products, shared with the aggregate verify over groups (host_pairing_check.hip): the products' buffers and the staging
+// of c->pc.seg for a planned call (the callers run the levels, seg_run_levels with k_fp12_seg_prod, into c->pc.prod / c->pc.ok);
+// the products' final exponentiation into the bitmap, by chunks of equations
+static const size_t FP12_SEG_GROUP = 8;     // Miller values per lane of the segmented product
 BNH int pc_reserve_products(blsbn254_ctx* c, size_t n_eq, size_t items_max);
-BNH int pc_run_levels(blsbn254_ctx* c, const PcLaunch& L, const int32_t* src, const uint8_t* src_ok, size_t src_stride, size_t n_eq, bool check);
 BNH int pc_finish_bitmap(blsbn254_ctx* c, size_t n_eq, uint8_t* valid_bitmap);
 BNH int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res, size_t* rs);   // host_aggregate.hip
 BNH int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]);   // host_aggregate.hip
@@ -308,6 +334,11 @@ BNH size_t th_batch_tbig();   // host_threshold_batch.hip: the largest group the
 // shares' bits into c->bitmap, the groups' statuses into c->tdl.st (enqueued; the caller downloads and synchronises)
 BNH int td_args(blsbn254_ctx* c, const void* coefs, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, const void* out,
                 const void* status);   // host_threshold_deal.hip
+// the checks of the arguments that come with one message per group (after td_args; same codes and text in both callers)
+BNH int td_msg_args(blsbn254_ctx* c, const uint8_t* partial_sigs, const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups,
+                    const uint8_t* dst, size_t dst_len);   // host_threshold_deal.hip
+// the call's commitments uploaded, loaded and tested into c->tdl (coef, c_ws, c_ok, c_sub); enqueued
+BNH int td_stage_commitments(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, size_t n_groups);   // host_threshold_deal.hip
 BNH int td_verify_shares_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint8_t* partial_sigs,
                                  const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len);   // host_threshold_deal.hip
 
@@ -319,10 +350,4 @@ static inline bool small_for_prepared(const blsbn254_ctx* c, size_t n, bool per_
   return (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && (c->tri_fe || !per_tuple_fe) && n <= c->tri_max);
 }
 
-// Level planner of the segmented reductions (k_g2_seg_sum, k_fp12_seg_prod).  cur[0..ne] are the boundaries of ne segments of
-// items: every segment is cut into runs of at most G items, one (start, len) descriptor per run (an empty segment: ONE empty run),
-// the runs are the next level's items, and so on until there is one run per segment.  Descriptors are appended to start / len,
-// one {first descriptor, count} per level to `levels`; `cur` is consumed.  `what` names the reduction in the (internal) error.
-BNH int plan_seg_levels(blsbn254_ctx* c, std::vector<uint64_t>& cur, size_t G, std::vector<uint32_t>& start, std::vector<uint32_t>& len,
-                        std::vector<SegLevel>& levels, const char* what);   // host_groupops.hip
 }  // extern "C"

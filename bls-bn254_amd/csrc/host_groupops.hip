@@ -31,60 +31,28 @@ static int mul_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalar
 int blsbn254_g1_mul_batch(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* scalars, size_t n, uint8_t* out) { return mul_common(c, g1, scalars, n, out, 0); }
 int blsbn254_g2_mul_batch(blsbn254_ctx* c, const uint8_t* g2, const uint8_t* scalars, size_t n, uint8_t* out) { return mul_common(c, g2, scalars, n, out, 1); }
 
-int plan_seg_levels(blsbn254_ctx* c, std::vector<uint64_t>& cur, size_t G, std::vector<uint32_t>& start, std::vector<uint32_t>& len,
-                    std::vector<SegLevel>& levels, const char* what) {
-  const size_t ne = cur.size() - 1;
-  std::vector<uint64_t> nxt(ne + 1);
-  for (int level = 0; ; ++level) {
-    if (level > 40) { c->last_error = what; return BLSBN254_E_HIP; }
-    const size_t first = start.size();
-    for (size_t e = 0; e < ne; ++e) {
-      const uint64_t a = cur[e], b = cur[e + 1];
-      nxt[e] = start.size() - first;
-      if (a == b) { start.push_back((uint32_t)a); len.push_back(0); }            // empty segment: one empty run (identity, flag 0)
-      for (uint64_t s = a; s < b; s += G) { start.push_back((uint32_t)s); len.push_back((uint32_t)std::min<uint64_t>(b - s, G)); }
-    }
-    const size_t m = start.size() - first;
-    nxt[ne] = m;
-    levels.push_back({first, m});
-    if (m == ne) return 0;
-    cur.swap(nxt);
-  }
-}
-
 // Segmented sums of G2 points: n points already staged at d_pks, groups [goff[g], goff[g + 1]).  Level by level every group is
 // cut into chunks of at most G2_SUM_GROUP items, one lane sums a chunk, and the chunk sums (group-major order) are the next
-// level's items, until every group is ONE item.  The chunk descriptors of all levels come from the host (the offsets are
-// the caller's host array).  On return the sums are at *sum_ws (limb-major, stride = n_groups) with their flags at *sum_ok.
+// level's items, until every group is ONE item (plan_seg_levels, seg_plan.h; seg_run_levels with k_g2_seg_sum).  The chunk
+// descriptors of all levels come from the host (the offsets are the caller's host array) in one copy: nothing synchronises
+// between the levels or behind them.  The sums end up in c->gs_sum (limb-major, stride n_groups), their flags in c->gs_sum_ok.
 static const size_t G2_SUM_GROUP = 16;
-static int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups, const int32_t** sum_ws, const uint8_t** sum_ok) {
-  const size_t G = G2_SUM_GROUP;
-  // chunk descriptors of ALL levels first (host arithmetic on the offsets), uploaded in one copy: no synchronisation between levels
-  std::vector<uint64_t> cur(goff, goff + n_groups + 1);
-  for (size_t g = 0; g <= n_groups; ++g) cur[g] -= goff[0];
-  std::vector<uint32_t> start, len;
+static int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups) {
+  SegWs& w = c->gs;
+  std::vector<SegRange> seg(n_groups);
+  for (size_t g = 0; g < n_groups; ++g) seg[g] = {goff[g] - goff[0], goff[g + 1] - goff[0]};
+  w.h_start.clear(); w.h_len.clear();
   std::vector<SegLevel> levels;
-  TRY(plan_seg_levels(c, cur, G, start, len, levels, "internal: group sums do not converge"));
-  const size_t total = start.size(), m_max = levels[0].count;
-  // ping-pong workspaces: the level-0 items (n) and the largest chunk array (the first level's)
-  HIPCHK(c, c->gs_ws[0].reserve((n ? n : 1) * 54 * 4)); HIPCHK(c, c->gs_ok[0].reserve(n ? n : 1));
-  HIPCHK(c, c->gs_ws[1].reserve(m_max * 54 * 4)); HIPCHK(c, c->gs_ok[1].reserve(m_max));
-  HIPCHK(c, c->gs_ws[2].reserve(m_max * 54 * 4)); HIPCHK(c, c->gs_ok[2].reserve(m_max));
-  TRY(upload(c, c->gs_start, start.data(), 4 * total));
-  TRY(upload(c, c->gs_len, len.data(), 4 * total));
-  if (n) TRY(launch(c, c->stream, "g2_load", grid_lanes(n), k_g2_load, d_pks, n, (int32_t*)c->gs_ws[0].p, (uint8_t*)c->gs_ok[0].p));
-  int src = 0;
-  size_t items = n;
-  for (const SegLevel& L : levels) {
-    const size_t m = L.count;
-    const int dst = src == 1 ? 2 : 1;
-    TRY(launch(c, c->stream, "g2_seg_sum", grid_lanes(m), k_g2_seg_sum, (const int32_t*)c->gs_ws[src].p, items ? items : 1, (const uint8_t*)c->gs_ok[src].p,
-               (const uint32_t*)c->gs_start.p + L.first, (const uint32_t*)c->gs_len.p + L.first, m, (int32_t*)c->gs_ws[dst].p, m, (uint8_t*)c->gs_ok[dst].p));
-    src = dst; items = m;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));                                   // `start` / `len` go out of scope
-  *sum_ws = (const int32_t*)c->gs_ws[src].p; *sum_ok = (const uint8_t*)c->gs_ok[src].p;
-  return 0;
+  size_t items_max = 1;
+  if (!plan_seg_levels(seg, G2_SUM_GROUP, w.h_start, w.h_len, levels, &items_max)) { c->last_error = "internal: group sums do not converge"; return BLSBN254_E_HIP; }
+  HIPCHK(c, c->gs_items.reserve((n ? n : 1) * 54 * 4)); HIPCHK(c, c->gs_items_ok.reserve(n ? n : 1));
+  HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
+  TRY(seg_stage(c, w, items_max, 54, true));
+  if (n) TRY(launch(c, c->stream, "g2_load", grid_lanes(n), k_g2_load, d_pks, n, (int32_t*)c->gs_items.p, (uint8_t*)c->gs_items_ok.p));
+  return seg_run_levels(w, levels, {(const int32_t*)c->gs_items.p, n ? n : 1, (const uint8_t*)c->gs_items_ok.p}, {(int32_t*)c->gs_sum.p, n_groups, (uint8_t*)c->gs_sum_ok.p},
+                        [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
+    return launch(c, c->stream, "g2_seg_sum", grid_lanes(runs), k_g2_seg_sum, in.v, in.stride, in.ok, start, len, runs, out.v, out.stride, out.ok);
+  });
 }
 
 // impl Sum for G2Projective (g2.rs:579-583): out = sum of the n points (the identity encoding for n == 0)
@@ -96,13 +64,12 @@ int blsbn254_aggregate_pks(blsbn254_ctx* c, const uint8_t* pks, size_t n, uint8_
   HIPCHK(c, c->out.reserve(128));
   TRY(upload(c, c->in_a, pks, 128 * n));
   const uint64_t goff[2] = {0, (uint64_t)n};
-  const int32_t* ws; const uint8_t* ok;
-  int rc = g2_group_sums(c, (const uint8_t*)c->in_a.p, n, goff, 1, &ws, &ok);
-  if (rc) return rc;
+  TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n, goff, 1));
   uint8_t good = 0;
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(1), k_g2p_to_bytes, ws, (size_t)1, ok, (size_t)1, (uint8_t*)c->out.p, 0));
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(1), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, (size_t)1, (const uint8_t*)c->gs_sum_ok.p, (size_t)1,
+             (uint8_t*)c->out.p, 0));
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, 128, hipMemcpyDeviceToHost, c->stream));
-  TRY(download(c, &good, ok, 1));
+  TRY(download(c, &good, c->gs_sum_ok.p, 1));
   if (!good) { c->last_error = "a point does not decode or is off the curve"; return BLSBN254_ERR_G2; }
   return 0;
 }
@@ -129,10 +96,9 @@ int blsbn254_fast_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, co
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   if (n_keys) HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks + 128 * (size_t)key_off[0], 128 * n_keys, hipMemcpyHostToDevice, c->stream));
   TRY(upload(c, c->in_b, sigs, 64 * n_groups));
-  const int32_t* ws; const uint8_t* ok;
-  rc = g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, key_off, n_groups, &ws, &ok);
-  if (rc) return rc;
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, ws, n_groups, ok, n_groups, (uint8_t*)c->gs_pk.p, 1));
+  TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, key_off, n_groups));
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
+             (uint8_t*)c->gs_pk.p, 1));
   rc = verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
                         (uint8_t*)c->bitmap.p);
   if (rc) return rc;

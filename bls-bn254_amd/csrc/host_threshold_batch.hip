@@ -4,10 +4,10 @@
 //
 // All ids and partial signatures are uploaded once.  The shares run in launches of at most ctx->chunk shares that end on a
 // group boundary (a launch always takes at least one whole group): ids decoded, Lagrange coefficients per lane over the lane's
-// group, [lambda] sigma per lane, then each group's products summed level by level (k_g1_seg_sum; the last level writes into
-// the per-group sums, limb-major, stride n_groups).  After the last launch: one inversion per group (k_g1p_to_bytes), the
-// per-group marks folded into statuses (k_th_finish), ONE download and synchronisation.  All chunk descriptors are planned on
-// the host up front and uploaded in one copy.
+// group, [lambda] sigma per lane, then each group's products summed level by level (seg_run_levels with k_g1_seg_sum; the last
+// level writes into the per-group sums, limb-major, stride n_groups).  After the last launch: one inversion per group
+// (k_g1p_to_bytes), the per-group marks folded into statuses (k_th_finish), ONE download and synchronisation.  All launches and
+// their levels are planned on the host up front (plan_launches_whole, seg_plan.h) and the descriptors uploaded in one copy.
 //
 // Groups of more than TH_BATCH_TBIG shares do not take that path: the per-lane Lagrange loop is quadratic in the group and serial in
 // the lane, which the single-group pipeline (t x sqrt(t) lanes, host_aggregate.hip) avoids.  Their lanes only test their point
@@ -29,53 +29,6 @@ extern "C" {
 static const size_t TH_BATCH_TBIG = BN_TH_BATCH_TBIG;
 static const size_t TH_SUM_GROUP = 16;      // products per lane and level of the group sums
 
-namespace {
-// shares [lo, hi) of the call; groups [ga, gb) lie in it (gb - 1 may be a large group that continues in the next launch)
-struct ThLaunch { size_t lo, hi, ga, gb; std::vector<SegLevel> levels; };
-}
-
-static inline bool th_big(const std::vector<uint32_t>& rel, size_t g) { return (size_t)(rel[g + 1] - rel[g]) > TH_BATCH_TBIG; }
-
-// Launches and their sum levels for groups rel[0 .. n_groups] (offsets rebased to 0); descriptors appended to start / len.
-static int th_plan(blsbn254_ctx* c, const std::vector<uint32_t>& rel, size_t n_groups, std::vector<ThLaunch>& out, std::vector<uint32_t>& start,
-                   std::vector<uint32_t>& len, size_t* m_max, size_t* items_max) {
-  const size_t N = rel[n_groups];
-  size_t lo = 0, g = 0;
-  *m_max = 0; *items_max = 1;
-  while (g < n_groups) {
-    ThLaunch L;
-    const size_t lim = std::min(N, lo + c->chunk);
-    size_t hi = lo, gb = g;
-    bool cut = false;                                    // the launch ends inside the (large) group gb
-    while (gb < n_groups) {
-      const size_t b = rel[gb + 1];
-      if (b <= lim || (hi == lo && !th_big(rel, gb))) { hi = b; ++gb; if (b > lim) break; continue; }   // a whole group; the first one whatever its size
-      if (th_big(rel, gb) && lim > hi) { hi = lim; cut = true; }
-      break;
-    }
-    L.lo = lo; L.hi = hi; L.ga = g; L.gb = gb + (cut ? 1 : 0);
-    // level 0: every group's products in runs of at most TH_SUM_GROUP; an empty or a large group: ONE empty run (the identity)
-    const size_t ne = L.gb - L.ga, first = start.size();
-    std::vector<uint64_t> cur(ne + 1);
-    for (size_t e = 0; e < ne; ++e) {
-      const size_t gg = L.ga + e;
-      cur[e] = start.size() - first;
-      const size_t a = rel[gg], b = th_big(rel, gg) ? a : rel[gg + 1];
-      if (a == b) { start.push_back(0); len.push_back(0); }
-      for (size_t s = a; s < b; s += TH_SUM_GROUP) { start.push_back((uint32_t)(s - lo)); len.push_back((uint32_t)std::min(b - s, TH_SUM_GROUP)); }
-    }
-    const size_t m0 = start.size() - first;
-    cur[ne] = m0;
-    L.levels.push_back({first, m0});
-    if (m0 != ne) TRY(plan_seg_levels(c, cur, TH_SUM_GROUP, start, len, L.levels, "internal: group sums do not converge"));
-    for (size_t lv = 0; lv + 1 < L.levels.size(); ++lv) *items_max = std::max(*items_max, L.levels[lv].count);   // (the last level writes into the sums)
-    *m_max = std::max(*m_max, hi - lo);
-    out.push_back(std::move(L));
-    g = gb; lo = hi;
-  }
-  return 0;
-}
-
 size_t th_batch_tbig() { return TH_BATCH_TBIG; }
 
 // The device part for all groups, on ids (and partial signatures) already on the device: per-group statuses into c->thb.st, and
@@ -84,31 +37,26 @@ size_t th_batch_tbig() { return TH_BATCH_TBIG; }
 int th_enqueue_dev(blsbn254_ctx* c, const uint8_t* d_ids, const uint8_t* d_sigs, const uint64_t* off, size_t n_groups) {
   const bool sigs = d_sigs != nullptr;
   ThbWs& w = c->thb;
-  std::vector<uint32_t>& rel = w.h_goff;                 // ctx-owned: outlive the asynchronous copies (every call ends synchronised)
-  rel.resize(n_groups + 1);
-  for (size_t g = 0; g <= n_groups; ++g) rel[g] = (uint32_t)(off[g] - off[0]);
-  const size_t N = rel[n_groups];
-  w.h_start.clear(); w.h_len.clear();
-  std::vector<ThLaunch> launches;
+  TRY(stage_group_offsets(c, w.goff, off, n_groups));
+  const size_t N = w.goff.h[n_groups];
+  w.seg.h_start.clear(); w.seg.h_len.clear();
+  std::vector<SegLaunch> launches;
   size_t m_max, items_max;
-  TRY(th_plan(c, rel, n_groups, launches, w.h_start, w.h_len, &m_max, &items_max));
+  if (!plan_launches_whole(w.goff.h, n_groups, c->chunk, TH_SUM_GROUP, TH_BATCH_TBIG, launches, w.seg.h_start, w.seg.h_len, &m_max, &items_max)) {
+    c->last_error = "internal: group sums do not converge";
+    return BLSBN254_E_HIP;
+  }
   const size_t m1 = m_max ? m_max : 1, N1 = N ? N : 1;
   HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->th_glv.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
-  HIPCHK(c, w.goff.reserve(4 * (n_groups + 1))); HIPCHK(c, w.gid.reserve(4 * m1)); HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
+  HIPCHK(c, w.gid.reserve(4 * m1)); HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
   if (sigs) {
-    HIPCHK(c, w.pts.reserve(27 * m1 * 4)); HIPCHK(c, w.seg[0].reserve(27 * items_max * 4)); HIPCHK(c, w.seg[1].reserve(27 * items_max * 4));
-    HIPCHK(c, w.gsum.reserve(27 * n_groups * 4)); HIPCHK(c, w.out.reserve(64 * n_groups));
-    HIPCHK(c, w.start.reserve(4 * w.h_start.size())); HIPCHK(c, w.len.reserve(4 * w.h_len.size()));
+    HIPCHK(c, w.pts.reserve(27 * m1 * 4)); HIPCHK(c, w.gsum.reserve(27 * n_groups * 4)); HIPCHK(c, w.out.reserve(64 * n_groups));
+    TRY(seg_stage(c, w.seg, items_max, 27, false));
   } else HIPCHK(c, c->scalars.reserve(32 * N1));
-  HIPCHK(c, hipMemcpyAsync(w.goff.p, rel.data(), 4 * (n_groups + 1), hipMemcpyHostToDevice, c->stream));
-  if (sigs) {
-    HIPCHK(c, hipMemcpyAsync(w.start.p, w.h_start.data(), 4 * w.h_start.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w.len.p, w.h_len.data(), 4 * w.h_len.size(), hipMemcpyHostToDevice, c->stream));
-  }
   HIPCHK(c, hipMemsetAsync(w.gstat.p, 0, 4 * n_groups, c->stream));
-  const uint32_t* goff = (const uint32_t*)w.goff.p;
+  const uint32_t* goff = (const uint32_t*)w.goff.d.p;
   uint32_t* gstat = (uint32_t*)w.gstat.p;
-  for (const ThLaunch& L : launches) {
+  for (const SegLaunch& L : launches) {
     const size_t m = L.hi - L.lo;
     ++c->stat_thb[2];
     if (m) {
@@ -120,17 +68,10 @@ int th_enqueue_dev(blsbn254_ctx* c, const uint8_t* d_ids, const uint8_t* d_sigs,
     if (!sigs) continue;
     if (m) TRY(launch(c, c->stream, "g1_smul_glv", grid_lanes(m), k_g1_smul_glv, d_sigs + 64 * L.lo, (const uint32_t*)c->th_glv.p, (const uint32_t*)w.gid.p, m,
                       (int32_t*)w.pts.p, gstat + L.ga));
-    const int32_t* src = (const int32_t*)w.pts.p;
-    size_t src_stride = m ? m : 1;
-    int dst = 0;
-    for (size_t lv = 0; lv < L.levels.size(); ++lv) {
-      const SegLevel& P = L.levels[lv];
-      const bool last = lv + 1 == L.levels.size();
-      int32_t* out = last ? (int32_t*)w.gsum.p + L.ga : (int32_t*)w.seg[dst].p;
-      TRY(launch(c, c->stream, "g1_seg_sum", grid_lanes(P.count), k_g1_seg_sum, src, src_stride, (const uint32_t*)nullptr, (const uint32_t*)w.start.p + P.first,
-                 (const uint32_t*)w.len.p + P.first, P.count, out, last ? n_groups : P.count));
-      src = out; src_stride = P.count; dst ^= 1;
-    }
+    TRY(seg_run_levels(w.seg, L.levels, {(const int32_t*)w.pts.p, m ? m : 1, nullptr}, {(int32_t*)w.gsum.p + L.ga, n_groups, nullptr},
+                       [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
+      return launch(c, c->stream, "g1_seg_sum", grid_lanes(runs), k_g1_seg_sum, in.v, in.stride, (const uint32_t*)nullptr, start, len, runs, out.v, out.stride);
+    }));
   }
   if (sigs) TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(n_groups), k_g1p_to_bytes, (const int32_t*)w.gsum.p, n_groups, n_groups, (uint8_t*)w.out.p));
   return launch(c, c->stream, "th_finish", grid_lanes(n_groups), k_th_finish, (const uint32_t*)gstat, n_groups, sigs ? (uint8_t*)w.out.p : (uint8_t*)nullptr, (uint8_t*)w.st.p);
@@ -180,7 +121,7 @@ int blsbn254_threshold_combine_batch(blsbn254_ctx* c, const uint8_t* ids, const 
     if (rc < 0) return rc;
     const uint8_t code = rc == BLSBN254_ERR_SCALAR ? BLSBN254_ERR_SCALAR : (rc == BLSBN254_ERR_G1 || status[g] == BLSBN254_ERR_G1) ? BLSBN254_ERR_G1 : 0;
     status[g] = code;
-    if (code) { std::memset(o, 0, 64); o[63] = 1; }
+    if (code) g1_identity_bytes(o);
   }
   return 0;
 }

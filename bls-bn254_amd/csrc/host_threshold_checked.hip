@@ -30,36 +30,25 @@ struct TcCall {
 static inline uint8_t tc_code(uint32_t marks) {
   return (marks & TC_MARK_SCALAR) ? BLSBN254_ERR_SCALAR : (marks & TC_MARK_POINT) ? BLSBN254_ERR_G2 : (marks & TC_MARK_SHORT) ? BLSBN254_ST_SHORT : 0;
 }
-static inline void tc_identity(uint8_t* o) { std::memset(o, 0, 64); o[63] = 1; }
 
 // One attempt over the groups of A, enqueued: the combined signatures into c->thb.out, the used bits into c->tc.used, the marks
 // into c->tc.gstat; the optimistic one also the bits of the groups' verification into c->tc.gbits.
 static int tc_attempt(blsbn254_ctx* c, const TcCall& A, bool fallback) {
   TcWs& w = c->tc;
   const size_t ng = A.n_groups;
-  w.h_goff.resize(ng + 1); w.h_coff.resize(ng + 1);
-  for (size_t g = 0; g <= ng; ++g) { w.h_goff[g] = (uint32_t)(A.id_off[g] - A.id_off[0]); w.h_coff[g] = (uint32_t)(A.coef_off[g] - A.coef_off[0]); }
-  const size_t N = w.h_goff[ng], T = w.h_coff[ng], N1 = N ? N : 1, T1 = T ? T : 1, nb = (N + 7) / 8;
+  TRY(stage_group_offsets(c, w.goff, A.id_off, ng)); TRY(stage_group_offsets(c, w.coff, A.coef_off, ng));
+  const size_t N = w.goff.h[ng], T = w.coff.h[ng], T1 = T ? T : 1, nb = (N + 7) / 8;
   // the fallback's per-share verification first: it stages the sub-call's commitments, messages and partial signatures in the
   // buffers of its own pipelines and leaves the shares' bits in c->bitmap
   if (fallback) TRY(td_verify_shares_enqueue(c, A.commitments, A.coef_off, A.ids, A.sigs, A.id_off, A.msgs, A.msg_off, ng, A.dst, A.dst_len));
-  HIPCHK(c, w.goff.reserve(4 * (ng + 1))); HIPCHK(c, w.coff.reserve(4 * (ng + 1))); HIPCHK(c, w.gstat.reserve(4 * ng)); HIPCHK(c, w.st.reserve(ng));
+  HIPCHK(c, w.gstat.reserve(4 * ng)); HIPCHK(c, w.st.reserve(ng));
   HIPCHK(c, w.cand.reserve(nb + 8)); HIPCHK(c, w.used.reserve(nb + 8)); HIPCHK(c, w.c_ids.reserve(32 * T1)); HIPCHK(c, w.c_sigs.reserve(64 * T1));
-  HIPCHK(c, hipMemcpyAsync(w.goff.p, w.h_goff.data(), 4 * (ng + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(w.coff.p, w.h_coff.data(), 4 * (ng + 1), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(w.gstat.p, 0, 4 * ng, c->stream));
   HIPCHK(c, hipMemsetAsync(w.c_ids.p, 0, 32 * T1, c->stream)); HIPCHK(c, hipMemsetAsync(w.c_sigs.p, 0, 64 * T1, c->stream));
-  const uint32_t* goff = (const uint32_t*)w.goff.p; const uint32_t* coff = (const uint32_t*)w.coff.p;
+  const uint32_t* goff = (const uint32_t*)w.goff.d.p; const uint32_t* coff = (const uint32_t*)w.coff.d.p;
   uint32_t* gstat = (uint32_t*)w.gstat.p;
   TdlWs& d = c->tdl;                                     // the commitments: staged and tested where the dealing side does it
-  if (!fallback) {
-    HIPCHK(c, d.c_ws.reserve(54 * T1 * 4)); HIPCHK(c, d.c_ok.reserve(T1)); HIPCHK(c, d.c_sub.reserve(T1)); HIPCHK(c, d.coef.reserve(128 * T1));
-    if (T) {
-      TRY(upload(c, d.coef, A.commitments + 128 * A.coef_off[0], 128 * T));
-      TRY(launch(c, c->stream, "g2_load", grid_lanes(T), k_g2_load, (const uint8_t*)d.coef.p, T, (int32_t*)d.c_ws.p, (uint8_t*)d.c_ok.p));
-      TRY(launch(c, c->stream, "g2_check", grid_lanes(T), k_g2_check, (const uint8_t*)d.coef.p, T, (uint8_t*)d.c_sub.p, (uint8_t*)nullptr));
-    }
-  }
+  if (!fallback) TRY(td_stage_commitments(c, A.commitments, A.coef_off, ng));
   if (N) {
     const size_t m1 = std::min(N, c->chunk);
     HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
@@ -95,11 +84,9 @@ int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* c, const uint8_t* com
   if (n_groups == 0) return 0;
   int rc = td_args(c, commitments, coef_off, ids, id_off, n_groups, used_bitmap, status);
   if (rc) return rc;
-  if (!out_sigs || !msg_off || (dst_len && !dst)) return BLSBN254_E_ARG;
-  if (check_offsets(msg_off, n_groups)) { c->last_error = "message offsets decrease"; return BLSBN254_E_ARG; }
+  if (!out_sigs) return BLSBN254_E_ARG;
+  TRY(td_msg_args(c, partial_sigs, id_off, msgs, msg_off, n_groups, dst, dst_len));
   const size_t N = (size_t)(id_off[n_groups] - id_off[0]), nb = (N + 7) / 8;
-  if (N && !partial_sigs) return BLSBN254_E_ARG;
-  if (!msgs && msg_off[n_groups] != msg_off[0]) return BLSBN254_E_ARG;
   for (size_t g = 0; g < n_groups; ++g)
     if (id_off[g + 1] - id_off[g] > th_batch_tbig()) { c->last_error = "a group of more shares than the lane-per-share combine serves"; return BLSBN254_E_ARG; }
   ENTER(c);
@@ -120,7 +107,7 @@ int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* c, const uint8_t* com
     if (!code && good) { ++c->stat_tc[0]; continue; }
     if (code == BLSBN254_ST_SHORT) ++c->stat_tc[3];
     if (!code) w.fail.push_back(g);
-    tc_identity(out_sigs + 64 * g);
+    g1_identity_bytes(out_sigs + 64 * g);
     for (uint64_t s = id_off[g] - id_off[0]; s < id_off[g + 1] - id_off[0]; ++s) used_bitmap[s >> 3] &= (uint8_t)~(1u << (s & 7));
   }
   if (w.fail.empty()) return 0;

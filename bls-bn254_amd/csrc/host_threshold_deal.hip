@@ -16,18 +16,6 @@ extern "C" {
 static const int TD_MAX_BITS = 254;                               // threshold_deal.h: the bit length of r - 1
 static const uint32_t TD_MARK_SCALAR = 1u, TD_MARK_POINT = 2u;     // threshold_deal.h: the bits of a group's mark word
 
-// offsets rebased to 0 into the ctx-owned host copies (they outlive the asynchronous uploads: every call ends synchronised)
-static int td_stage_offsets(blsbn254_ctx* c, const uint64_t* coef_off, const uint64_t* id_off, size_t n_groups) {
-  TdlWs& w = c->tdl;
-  w.h_goff.resize(n_groups + 1); w.h_coff.resize(n_groups + 1);
-  for (size_t g = 0; g <= n_groups; ++g) { w.h_goff[g] = (uint32_t)(id_off[g] - id_off[0]); w.h_coff[g] = (uint32_t)(coef_off[g] - coef_off[0]); }
-  HIPCHK(c, w.goff.reserve(4 * (n_groups + 1))); HIPCHK(c, w.coff.reserve(4 * (n_groups + 1)));
-  HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
-  HIPCHK(c, hipMemcpyAsync(w.goff.p, w.h_goff.data(), 4 * (n_groups + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(w.coff.p, w.h_coff.data(), 4 * (n_groups + 1), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(w.gstat.p, 0, 4 * n_groups, c->stream));
-  return 0;
-}
 // the largest bit length among the m ids at `ids` (32 B big-endian each), at least 1 and capped at TD_MAX_BITS: ids that the
 // kernels will reject (>= r) are counted like any other
 static int td_id_bits(const uint8_t* ids, size_t m) {
@@ -43,6 +31,15 @@ static int td_id_bits(const uint8_t* ids, size_t m) {
   }
   return std::min(best, TD_MAX_BITS);
 }
+int td_stage_commitments(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, size_t n_groups) {
+  TdlWs& w = c->tdl;
+  const size_t T = (size_t)(coef_off[n_groups] - coef_off[0]), T1 = T ? T : 1;
+  HIPCHK(c, w.c_ws.reserve(54 * T1 * 4)); HIPCHK(c, w.c_ok.reserve(T1)); HIPCHK(c, w.c_sub.reserve(T1)); HIPCHK(c, w.coef.reserve(128 * T1));
+  if (!T) return 0;
+  TRY(upload(c, w.coef, commitments + 128 * coef_off[0], 128 * T));
+  TRY(launch(c, c->stream, "g2_load", grid_lanes(T), k_g2_load, (const uint8_t*)w.coef.p, T, (int32_t*)w.c_ws.p, (uint8_t*)w.c_ok.p));
+  return launch(c, c->stream, "g2_check", grid_lanes(T), k_g2_check, (const uint8_t*)w.coef.p, T, (uint8_t*)w.c_sub.p, (uint8_t*)nullptr);
+}
 int td_args(blsbn254_ctx* c, const void* coefs, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, const void* out, const void* status) {
   if (!coef_off || !id_off || !status) return BLSBN254_E_ARG;
   if (check_offsets(coef_off, n_groups) || check_offsets(id_off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
@@ -53,21 +50,27 @@ int td_args(blsbn254_ctx* c, const void* coefs, const uint64_t* coef_off, const 
   CHECK_LANES(c, n_groups);
   return 0;
 }
+// the arguments a call with one message per group adds to td_args (checked after it)
+int td_msg_args(blsbn254_ctx* c, const uint8_t* partial_sigs, const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups,
+                const uint8_t* dst, size_t dst_len) {
+  if (!msg_off || (dst_len && !dst)) return BLSBN254_E_ARG;
+  if (check_offsets(msg_off, n_groups)) { c->last_error = "message offsets decrease"; return BLSBN254_E_ARG; }
+  if (id_off[n_groups] != id_off[0] && !partial_sigs) return BLSBN254_E_ARG;
+  if (!msgs && msg_off[n_groups] != msg_off[0]) return BLSBN254_E_ARG;
+  return 0;
+}
 
 // The device part of the G2 evaluation for all groups: the N public key shares in wire format into d_pks (device), the
 // per-group statuses into c->tdl.st.  Everything is enqueued; the caller downloads and synchronises.
 static int td_g2_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, uint8_t* d_pks) {
   TdlWs& w = c->tdl;
-  TRY(td_stage_offsets(c, coef_off, id_off, n_groups));
-  const size_t N = w.h_goff[n_groups], T = w.h_coff[n_groups], T1 = T ? T : 1;
-  const uint32_t* goff = (const uint32_t*)w.goff.p; const uint32_t* coff = (const uint32_t*)w.coff.p;
+  TRY(stage_group_offsets(c, w.goff, id_off, n_groups)); TRY(stage_group_offsets(c, w.coff, coef_off, n_groups));
+  HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
+  HIPCHK(c, hipMemsetAsync(w.gstat.p, 0, 4 * n_groups, c->stream));
+  const size_t N = w.goff.h[n_groups], T = w.coff.h[n_groups];
+  const uint32_t* goff = (const uint32_t*)w.goff.d.p; const uint32_t* coff = (const uint32_t*)w.coff.d.p;
   uint32_t* gstat = (uint32_t*)w.gstat.p;
-  HIPCHK(c, w.c_ws.reserve(54 * T1 * 4)); HIPCHK(c, w.c_ok.reserve(T1)); HIPCHK(c, w.c_sub.reserve(T1));
-  if (T) {
-    TRY(upload(c, w.coef, commitments + 128 * coef_off[0], 128 * T));
-    TRY(launch(c, c->stream, "g2_load", grid_lanes(T), k_g2_load, (const uint8_t*)w.coef.p, T, (int32_t*)w.c_ws.p, (uint8_t*)w.c_ok.p));
-    TRY(launch(c, c->stream, "g2_check", grid_lanes(T), k_g2_check, (const uint8_t*)w.coef.p, T, (uint8_t*)w.c_sub.p, (uint8_t*)nullptr));
-  }
+  TRY(td_stage_commitments(c, commitments, coef_off, n_groups));
   if (N) {
     const size_t m1 = std::min(N, c->chunk);
     HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1)); HIPCHK(c, w.r_ws.reserve(54 * N * 4));
@@ -96,9 +99,11 @@ int blsbn254_fr_poly_eval_batch(blsbn254_ctx* c, const uint8_t* coeffs, const ui
   if (rc) return rc;
   ENTER(c);
   TdlWs& w = c->tdl;
-  TRY(td_stage_offsets(c, coef_off, id_off, n_groups));
-  const size_t N = w.h_goff[n_groups], T = w.h_coff[n_groups], T1 = T ? T : 1;
-  const uint32_t* goff = (const uint32_t*)w.goff.p; const uint32_t* coff = (const uint32_t*)w.coff.p;
+  TRY(stage_group_offsets(c, w.goff, id_off, n_groups)); TRY(stage_group_offsets(c, w.coff, coef_off, n_groups));
+  HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
+  HIPCHK(c, hipMemsetAsync(w.gstat.p, 0, 4 * n_groups, c->stream));
+  const size_t N = w.goff.h[n_groups], T = w.coff.h[n_groups], T1 = T ? T : 1;
+  const uint32_t* goff = (const uint32_t*)w.goff.d.p; const uint32_t* coff = (const uint32_t*)w.coff.d.p;
   uint32_t* gstat = (uint32_t*)w.gstat.p;
   HIPCHK(c, w.cf_ws.reserve(9 * T1 * 4)); HIPCHK(c, w.c_ok.reserve(T1));
   if (T) {
@@ -183,11 +188,8 @@ int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* c, const uint8_t* commi
   if (n_groups == 0) return 0;
   int rc = td_args(c, commitments, coef_off, ids, id_off, n_groups, valid_bitmap, status);
   if (rc) return rc;
-  if (!msg_off || (dst_len && !dst)) return BLSBN254_E_ARG;
-  if (check_offsets(msg_off, n_groups)) { c->last_error = "message offsets decrease"; return BLSBN254_E_ARG; }
+  TRY(td_msg_args(c, partial_sigs, id_off, msgs, msg_off, n_groups, dst, dst_len));
   const size_t N = (size_t)(id_off[n_groups] - id_off[0]);
-  if (N && !partial_sigs) return BLSBN254_E_ARG;
-  if (!msgs && msg_off[n_groups] != msg_off[0]) return BLSBN254_E_ARG;
   ENTER(c);
   TRY(td_verify_shares_enqueue(c, commitments, coef_off, ids, partial_sigs, id_off, msgs, msg_off, n_groups, dst, dst_len));
   if (N) HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, (N + 7) / 8, hipMemcpyDeviceToHost, c->stream));
