@@ -82,6 +82,27 @@ template <class F> BN_FUNC Proj<F> proj_add(const Proj<F>& a, const Proj<F>& b) 
   F zz = f_norm(f_add(f_mul(z3, t4), f_mul(t0_3, t3)));
   return {x3, yy, zz};
 }
+// complete MIXED addition, RCB Alg 8 with a = 0: b is affine (Z2 = 1) and NOT the identity (b.inf is not looked at: an affine
+// pair cannot encode it).  proj_add with t2 = Z1 and the two cross terms against Z2 = 1 formed directly: 11 products + 2
+// f_mul_b3 against 12 + 2.  Complete for every curve point a, in or out of the r-torsion: the exceptional case of the formula
+// needs a point of order two, and the group orders (r, and r (2p - r) on the twist) are odd.  Inputs/outputs normalised.
+template <class F> BN_FUNC Proj<F> proj_add_mixed(const Proj<F>& a, const Aff<F>& b) {
+  BN_CTX;
+  F t0 = f_mul(a.x, b.x), t1 = f_mul(a.y, b.y);
+  F m3 = f_mul(f_sub(a.x, a.y), f_sub(b.x, b.y));
+  F t3 = f_lc3<1, 1, -1>(t0, t1, m3);              // X1Y2 + X2Y1
+  F t4 = f_norm(f_add(f_mul(b.y, a.z), a.y));      // Y1 + Y2Z1
+  F y3 = f_norm(f_add(f_mul(b.x, a.z), a.x));      // X1 + X2Z1
+  F t0_3 = f_lc2<3, 0>(t0, t0);                    // 3 X1X2
+  F bt2 = f_mul_b3(a.z);
+  F z3 = f_norm(f_add(t1, bt2));
+  F t1m = f_norm(f_sub(t1, bt2));
+  F by3 = f_mul_b3(y3);
+  F x3 = f_norm(f_sub(f_mul(t3, t1m), f_mul(t4, by3)));
+  F yy = f_norm(f_add(f_mul(t1m, z3), f_mul(by3, t0_3)));
+  F zz = f_norm(f_add(f_mul(z3, t4), f_mul(t0_3, t3)));
+  return {x3, yy, zz};
+}
 // doubling, RCB Alg 9 (g1.rs:788-818, g2.rs:834-863)
 template <class F> BN_FUNC Proj<F> proj_dbl(const Proj<F>& a) {
   BN_CTX;

@@ -91,6 +91,9 @@ struct BNH TcWs {
   std::vector<uint64_t> s_coff, s_goff, s_moff;
   std::vector<size_t> fail;
 };
+// sums over a registered key set selected by bitmaps (host_keyset.hip, k_keyset.hip): the call's rows, the groups' flip / ok bytes,
+// the word-major partials of a launch and of its reduction passes (ping-pong); the host copy the flip bytes are downloaded to
+struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; };
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -157,6 +160,8 @@ struct blsbn254_ctx {
   AgbWs agb;
   TdlWs tdl;
   TcWs tc;
+  KsetWs kset;
+  uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
@@ -277,6 +282,9 @@ static const size_t PREP_MAX_KEYS = (size_t)1 << 16;
 static const size_t PREP_RAW_LIMBS = (size_t)BN_NEG_G2_LINES * 54;       // a key's 88 line triples
 static const size_t PREP_KEY_LIMBS = (size_t)BN_NEG_G2_LINES * 162;      // a key's 88 expanded line pairs (key line x -G2gen line)
 struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok; };   // pair tables (verify), raw line triples (multi_miller_loop), validity
+// a registered key set (host_keyset.hip): the keys as affine limb-major rows (36 x n limbs), the bad / skip words (keyset.h), the
+// total of the non-skipped keys (54 limbs), KeyValidate per key (bytes)
+struct blsbn254_keyset { blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid; };
 
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip
@@ -306,6 +314,8 @@ BNH int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
 BNH int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
+// segmented sums of n G2 encodings staged at d_pks over the groups goff (host offsets) into c->gs_sum / c->gs_sum_ok
+BNH int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups);   // host_groupops.hip
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip

@@ -37,7 +37,7 @@ int blsbn254_g2_mul_batch(blsbn254_ctx* c, const uint8_t* g2, const uint8_t* sca
 // descriptors of all levels come from the host (the offsets are the caller's host array) in one copy: nothing synchronises
 // between the levels or behind them.  The sums end up in c->gs_sum (limb-major, stride n_groups), their flags in c->gs_sum_ok.
 static const size_t G2_SUM_GROUP = 16;
-static int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups) {
+int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups) {
   SegWs& w = c->gs;
   std::vector<SegRange> seg(n_groups);
   for (size_t g = 0; g < n_groups; ++g) seg[g] = {goff[g] - goff[0], goff[g + 1] - goff[0]};

@@ -1,0 +1,160 @@
+// host_keyset.hip -- a registered set of public keys and the sums over it selected by participation bitmaps: impl Sum for
+// G2Projective (g2.rs:579-583) and FastAggregateVerify over the subset of a committee a bitmap names.  The keys are uploaded,
+// decoded and curve-checked ONCE (blsbn254_keyset_create); a call then carries one bit per (group, key) instead of 128 bytes,
+// and a group in which more than half of the set signed is summed through its complement, total - sum of the unselected keys.
+// Host side of include/blsbn254.h; kernels in k_keyset.hip, lane functions and layout in keyset.h; see host_common.h.
+#include "host_common.h"
+
+extern "C" {
+
+static const size_t KS_MAX_KEYS = (size_t)1 << 16;
+static const size_t KS_LAUNCH_ITEMS = (size_t)1 << 20;      // word partials of one launch: 54 x 4 B each, about 226 MB
+static const size_t KS_RUN_ITEMS = 16;                      // keyset.h KS_RUN
+static inline size_t ks_nwords(size_t n) { return (n + 31) / 32; }
+
+int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, blsbn254_keyset** out) {
+  if (!c || !out) return BLSBN254_E_ARG;
+  *out = nullptr;
+  if (!pks || n_keys == 0) return BLSBN254_E_ARG;
+  if (n_keys > KS_MAX_KEYS) { c->last_error = "more than 65536 keys in one key set"; return BLSBN254_E_ARG; }
+  ENTER(c);
+  // owned until handed to the caller: every failure path below frees the object and, with it, its device buffers
+  struct Owner { blsbn254_keyset* p; ~Owner() { delete p; } } own{new blsbn254_keyset()};
+  blsbn254_keyset* k = own.p;
+  k->ctx = c; k->n = n_keys;
+  const size_t W = ks_nwords(n_keys);
+  HIPCHK(c, k->aff.reserve(36 * n_keys * 4)); HIPCHK(c, k->bad.reserve(W * 4)); HIPCHK(c, k->skip.reserve(W * 4));
+  HIPCHK(c, k->total.reserve(54 * 4)); HIPCHK(c, k->valid.reserve(n_keys)); HIPCHK(c, c->sub_ok.reserve(n_keys));
+  TRY(upload(c, c->in_a, pks, 128 * n_keys));
+  TRY(launch(c, c->stream, "g2_check", grid_lanes(n_keys), k_g2_check, (const uint8_t*)c->in_a.p, n_keys, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
+  TRY(launch(c, c->stream, "ks_register", grid_lanes(n_keys), k_ks_register, (const uint8_t*)c->in_a.p, (uint32_t)n_keys, (const uint8_t*)c->sub_ok.p,
+             (int32_t*)k->aff.p, (uint32_t*)k->bad.p, (uint32_t*)k->skip.p, (uint8_t*)k->valid.p));
+  // the total: k_g2_load stores a bad key as the identity, and adding an identity key changes nothing, so the sum of ALL the
+  // encodings is the sum of the non-skipped keys (the flag of that sum is not looked at)
+  const uint64_t goff[2] = {0, (uint64_t)n_keys};
+  TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, goff, 1));
+  HIPCHK(c, hipMemcpyAsync(k->total.p, c->gs_sum.p, 54 * 4, hipMemcpyDeviceToDevice, c->stream));
+  hipError_t es = hipStreamSynchronize(c->stream);
+  if (es != hipSuccess) { (void)hipDeviceSynchronize(); }       // nothing may still be writing the buffers the owner frees
+  HIPCHK(c, es);
+  ++c->stat_kset[3];
+  own.p = nullptr;
+  *out = k;
+  return 0;
+}
+void blsbn254_keyset_destroy(blsbn254_keyset* k) {
+  if (!k) return;
+  (void)hipSetDevice(k->ctx->device);
+  (void)hipStreamSynchronize(k->ctx->stream);
+  delete k;
+}
+size_t blsbn254_keyset_count(const blsbn254_keyset* k) { return k ? k->n : 0; }
+// KeyValidate per registered key: decodes, not the identity, on the curve, in the r-torsion
+int blsbn254_keyset_valid(blsbn254_ctx* c, const blsbn254_keyset* k, uint8_t* ok_bitmap) {
+  if (!c || !k || k->ctx != c || !ok_bitmap) return BLSBN254_E_ARG;
+  ENTER(c);
+  HIPCHK(c, c->bitmap.reserve((k->n + 7) / 8 + 8));
+  TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(k->n), k_pack_bitmap, (const uint8_t*)k->valid.p, k->n, (uint8_t*)c->bitmap.p));
+  return download(c, ok_bitmap, c->bitmap.p, (k->n + 7) / 8);
+}
+
+// the argument checks the two calls share (n_groups > 0): the limit, and no row may set a bit that names no key
+static int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups) {
+  if (n_groups > c->chunk) { c->last_error = "more groups than one launch chunk"; return BLSBN254_E_ARG; }
+  const size_t rb = (k->n + 7) / 8;
+  if (k->n & 7) {
+    const uint8_t pad = (uint8_t)(0xffu << (k->n & 7));
+    for (size_t g = 0; g < n_groups; ++g)
+      if (sel[g * rb + rb - 1] & pad) { c->last_error = "row " + std::to_string(g) + " sets a bit past the last key"; return BLSBN254_E_ARG; }
+  }
+  return 0;
+}
+// The sums of every row into c->gs_sum / c->gs_sum_ok (enqueued), the flip bytes into c->kset.h_flip (enqueued: read after the
+// caller's synchronising download).  A launch covers as many groups as keep groups x W within KS_LAUNCH_ITEMS partials (within
+// ctx->chunk when that is smaller); launch starts are multiples of 8 groups.
+static int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches) {
+  KsetWs& w = c->kset;
+  const size_t W = ks_nwords(k->n), rb = (k->n + 7) / 8;
+  const size_t Gl = std::max((size_t)8, (std::min(KS_LAUNCH_ITEMS, c->chunk) / W) & ~(size_t)7), Gmax = std::min(Gl, n_groups);
+  const size_t runs0 = (W + KS_RUN_ITEMS - 1) / KS_RUN_ITEMS;
+  TRY(upload(c, w.sel, sel, rb * n_groups));
+  HIPCHK(c, w.flip.reserve(n_groups)); HIPCHK(c, w.ok.reserve(n_groups));
+  HIPCHK(c, w.part[0].reserve(54 * 4 * W * Gmax)); HIPCHK(c, w.part[1].reserve(54 * 4 * runs0 * Gmax));
+  HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
+  *launches = 0;
+  for (size_t lo = 0; lo < n_groups; lo += Gl, ++*launches) {
+    const size_t m = std::min(Gl, n_groups - lo);
+    const uint8_t *flip = (const uint8_t*)w.flip.p + lo, *ok = (const uint8_t*)w.ok.p + lo, *rows = (const uint8_t*)w.sel.p + lo * rb;
+    TRY(launch(c, c->stream, "ks_count", grid_lanes(m), k_ks_count, rows, m, (uint32_t)k->n, (const uint32_t*)k->bad.p, (uint8_t*)w.flip.p + lo, (uint8_t*)w.ok.p + lo));
+    TRY(launch(c, c->stream, "ks_word_sum", Shape{dim3(nblocks(m), (unsigned)W), dim3(256)}, k_ks_word_sum, (const int32_t*)k->aff.p, (uint32_t)k->n,
+               (const uint32_t*)k->skip.p, rows, flip, m, (int32_t*)w.part[0].p, W * m));
+    int src = 0;
+    for (size_t cnt = W;;) {
+      const size_t runs = (cnt + KS_RUN_ITEMS - 1) / KS_RUN_ITEMS;
+      const bool last = runs == 1;
+      TRY(launch(c, c->stream, "ks_group_sum", grid_lanes(runs * m), k_ks_group_sum, (const int32_t*)w.part[src].p, cnt * m, (uint32_t)cnt, m, flip, ok,
+                 (const int32_t*)k->total.p, last ? 1 : 0, last ? (int32_t*)c->gs_sum.p + lo : (int32_t*)w.part[src ^ 1].p, last ? n_groups : runs * m,
+                 last ? (uint8_t*)c->gs_sum_ok.p + lo : (uint8_t*)nullptr));
+      if (last) break;
+      src ^= 1; cnt = runs;
+    }
+  }
+  w.h_flip.resize(n_groups);
+  HIPCHK(c, hipMemcpyAsync(w.h_flip.data(), w.flip.p, n_groups, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+// counted once the call has succeeded (and synchronised: the flip bytes are on the host)
+static void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches) {
+  c->stat_kset[0] += n_groups; c->stat_kset[2] += launches;
+  for (size_t g = 0; g < n_groups; ++g) c->stat_kset[1] += c->kset.h_flip[g] ? 1 : 0;
+}
+
+// row g: out = blsbn254_aggregate_pks on the selected keys in index order, status 1; a row that selects a key that does not
+// decode or is off the curve: the identity encoding, status 0
+int blsbn254_keyset_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, uint8_t* out, uint8_t* status) {
+  if (!c || !k || k->ctx != c || (n_groups && (!sel || !out || !status))) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  TRY(ks_args(c, k, sel, n_groups));
+  ENTER(c);
+  size_t launches;
+  TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
+  HIPCHK(c, c->out.reserve(128 * n_groups));
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
+             (uint8_t*)c->out.p, 0));
+  HIPCHK(c, hipMemcpyAsync(out, c->out.p, 128 * n_groups, hipMemcpyDeviceToHost, c->stream));
+  TRY(download(c, status, c->gs_sum_ok.p, n_groups));
+  ks_tally(c, n_groups, launches);
+  return 0;
+}
+
+// bit g = blsbn254_fast_aggregate_verify_batch on the selected keys of row g: from the sums on, the same pipeline
+int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off,
+                                                const uint8_t* sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+  if (!c || !k || k->ctx != c || !off || (n_groups && (!sel || !sigs || !valid_bitmap)) || (dst_len && !dst)) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  TRY(ks_args(c, k, sel, n_groups));
+  ENTER(c);
+  uint32_t dl;
+  TRY(stage_dst(c, dst, dst_len, &dl));
+  TRY(stage_msgs(c, msgs, off, n_groups));
+  const size_t nb = (n_groups + 7) / 8;
+  HIPCHK(c, c->gs_pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve(nb + 8));
+  TRY(upload(c, c->in_b, sigs, 64 * n_groups));
+  size_t launches;
+  TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
+             (uint8_t*)c->gs_pk.p, 1));
+  TRY(verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
+                       (uint8_t*)c->bitmap.p));
+  TRY(download(c, valid_bitmap, c->bitmap.p, nb));
+  ks_tally(c, n_groups, launches);
+  return 0;
+}
+
+int blsbn254_keyset_stats(blsbn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BLSBN254_E_ARG;
+  for (int i = 0; i < 4; ++i) out[i] = c->stat_kset[i];
+  return 0;
+}
+
+}  // extern "C"

@@ -161,6 +161,13 @@ __global__ void __launch_bounds__(256) k_tc_select(const uint8_t* bits_a, const 
                                                   uint8_t* used);
 __global__ void __launch_bounds__(256) k_tc_gather_c0(const uint32_t* commitments, const uint32_t* coff, const uint32_t* goff, size_t n_groups, uint32_t* gstat,
                                                      uint32_t* keys);
+// sums over a registered key set selected by bitmaps (k_keyset.hip)
+BN_KERNEL k_ks_register(const uint8_t* pks, uint32_t n_keys, const uint8_t* sub_ok, int32_t* aff, uint32_t* bad, uint32_t* skip, uint8_t* valid);
+BN_KERNEL k_ks_count(const uint8_t* sel, size_t G, uint32_t n_keys, const uint32_t* bad, uint8_t* flip, uint8_t* ok);
+BN_KERNEL k_ks_word_sum(const int32_t* aff, uint32_t n_keys, const uint32_t* skip, const uint8_t* sel, const uint8_t* flip, size_t G,
+                        int32_t* out, size_t out_stride);
+BN_KERNEL k_ks_group_sum(const int32_t* in, size_t in_stride, uint32_t cnt, size_t G, const uint8_t* flip, const uint8_t* ok, const int32_t* total,
+                         int last, int32_t* out, size_t out_stride, uint8_t* ok_out);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

@@ -408,6 +408,46 @@ class Engine:
                                                                  ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po))
         return o[:(g + 7) // 8].tobytes()
 
+    def _keyset_rows(self, ks, sel_rows):
+        """sel_rows: bytes (n_groups rows of ceil(n_keys / 8) bytes), or a list of per-group rows -> (flat bytes, n_groups)"""
+        rb = (ks.count() + 7) // 8
+        if not isinstance(sel_rows, (bytes, bytearray, memoryview, np.ndarray)):
+            rows = [bytes(r) for r in sel_rows]
+            if any(len(r) != rb for r in rows):
+                raise ValueError("a row must be %d bytes" % rb)
+            sel_rows = b"".join(rows)
+        sel = bytes(sel_rows)
+        if len(sel) % rb:
+            raise ValueError("the rows must be a multiple of %d bytes" % rb)
+        return sel, len(sel) // rb
+
+    def keyset_sum_batch(self, ks, sel_rows):
+        """impl Sum for G2Projective over the keys each row of bitmaps selects from a registered KeySet: (n_groups x 128 bytes,
+        n_groups status bytes).  status 1: the row's sum, as aggregate_pks gives it on the selected keys; status 0: the row selects
+        a key that does not decode or is off the curve, and its output is the identity encoding."""
+        sel, g = self._keyset_rows(ks, sel_rows)
+        a, pa = _inbuf(sel); o, po = _outbuf(128 * g); st, pst = _outbuf(g)
+        self._chk(self._lib.blsbn254_keyset_sum_batch(self._ctx, ks._h, pa, ctypes.c_size_t(g), po, pst))
+        return o[:128 * g].tobytes(), st[:g].tobytes()
+
+    def keyset_fast_aggregate_verify_batch(self, ks, sel_rows, msgs, sigs, dst=DEFAULT_DST):
+        """fast_aggregate_verify_batch with every group's keys named by a bitmap over a registered KeySet: one message and 64
+        signature bytes per group.  Returns the LSB-first bitmap over the groups."""
+        sel, g = self._keyset_rows(ks, sel_rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(sel); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        self._chk(self._lib.blsbn254_keyset_fast_aggregate_verify_batch(self._ctx, ks._h, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(g), pd,
+                                                                        ctypes.c_size_t(len(dst)), po))
+        return o[:(g + 7) // 8].tobytes()
+
+    def keyset_stats(self):
+        """dict: groups served by the keyset calls, groups summed through the complement, launches of the word kernel, key sets created"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_stats(self._ctx, o))
+        return {"groups": int(o[0]), "complement_groups": int(o[1]), "launches": int(o[2]), "key_sets": int(o[3])}
+
     def aggregate_verify_batch(self, key_sets, msg_sets, agg_sigs, dst=DEFAULT_DST):
         """Many independent aggregate signatures in one call.  key_sets: list of byte strings (each a multiple of 128 bytes: the
         keys of one group); msg_sets: one list of messages per group, as many as the group has keys; agg_sigs: 64 bytes per group.
@@ -778,6 +818,40 @@ class PreparedKeys:
     def close(self):
         if getattr(self, "_h", None) and getattr(self._eng, "_ctx", None):
             self._lib.blsbn254_g2prepared_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeySet:
+    """blsbn254_keyset: n_keys public keys registered once on the engine's GPU (decoded, curve-checked, with their total), to be
+    summed by participation bitmaps (Engine.keyset_sum_batch, Engine.keyset_fast_aggregate_verify_batch)."""
+
+    def __init__(self, engine, pks, n_keys):
+        self._eng = engine
+        self._lib = engine._lib
+        self._lib.blsbn254_keyset_count.restype = ctypes.c_size_t
+        self._h = ctypes.c_void_p()
+        a, pa = _inbuf(pks, 128 * n_keys)
+        engine._chk(self._lib.blsbn254_keyset_create(engine._ctx, pa, ctypes.c_size_t(n_keys), ctypes.byref(self._h)))
+
+    def count(self):
+        return int(self._lib.blsbn254_keyset_count(self._h))
+
+    def valid_bitmap(self):
+        """KeyValidate per registered key: decodes, not the identity, on the curve, in the r-torsion"""
+        n = self.count()
+        o, po = _outbuf((n + 7) // 8)
+        self._eng._chk(self._lib.blsbn254_keyset_valid(self._eng._ctx, self._h, po))
+        return o[:(n + 7) // 8].tobytes()
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._eng, "_ctx", None):
+            self._lib.blsbn254_keyset_destroy(self._h)
         self._h = None
 
     def __del__(self):

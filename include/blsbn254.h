@@ -254,6 +254,38 @@ int blsbn254_fast_aggregate_verify(blsbn254_ctx* ctx, const uint8_t* pks /* n*12
 int blsbn254_fast_aggregate_verify_batch(blsbn254_ctx* ctx, const uint8_t* pks, const uint64_t* key_off /* n_groups+1 */,
                                          const uint8_t* msgs, const uint64_t* off /* n_groups+1 */, const uint8_t* sigs /* n_groups*64 */,
                                          size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+/* FastAggregateVerify over a REGISTERED key set, the signers named by bitmaps -- the consumer that holds one committee and
+ * receives a participation bitmap with each aggregate.  blsbn254_keyset_create uploads n_keys keys (1 <= n_keys <= 65536), decodes
+ * and curve-checks each ONCE (G2Affine::from_uncompressed + is_on_curve, g2.rs:350-414) and keeps them on ctx's GPU with their
+ * total; the handle owns its device memory, is tied to ctx, and several may be alive on one context.  A key that does not decode
+ * or is off the curve is kept as a BAD key, never an error of the registration.  blsbn254_keyset_valid: KeyValidate per
+ * registered key (decodes, not the identity, on the curve, in the r-torsion: is_torsion_free g2.rs:733-736) for the registrar;
+ * the sums do not use it.
+ * sel = n_groups rows of ceil(n_keys/8) bytes; bit i of a row (LSB-first, as every bitmap here) = key i signed.  A set bit at an
+ * index >= n_keys (padding of a row's last byte) is BLSBN254_E_ARG, as are NULL arguments, a key set of another context and
+ * n_groups above BLSBN254_CHUNK_LANES (4 Mi); n_groups == 0 returns 0.
+ * blsbn254_keyset_sum_batch (impl Sum for G2Projective, g2.rs:579-583): out[128 g ..] = the bytes blsbn254_aggregate_pks gives on
+ * the selected keys of row g in index order (the identity encoding for an empty row), status[g] = 1; a row that selects a bad
+ * key gets status[g] = 0 and the identity encoding -- never an error of the call.
+ * blsbn254_keyset_fast_aggregate_verify_batch: bit g of valid_bitmap = bit g of blsbn254_fast_aggregate_verify_batch on those
+ * lists with the same msgs / off / sigs / dst: KeyValidate on the SUM only, a selected bad key makes the group invalid, an
+ * identity member changes nothing, an empty row and an identity signature are invalid.
+ * One bit per (group, key) crosses the boundary instead of 128 bytes; a lane adds the selected keys of ONE 32-key word with
+ * mixed additions (Renes-Costello-Batina Alg 8); a row that selects more than half of the set is summed through its complement,
+ * total - sum of the unselected keys, so no row costs more than n_keys/2 additions.  The path never changes a result.
+ * blsbn254_keyset_stats, since the context was created: out[0] groups served, out[1] groups summed through the complement,
+ * out[2] launches of the word kernel, out[3] key sets created. */
+typedef struct blsbn254_keyset blsbn254_keyset;
+int blsbn254_keyset_create(blsbn254_ctx* ctx, const uint8_t* pks /* n_keys*128 */, size_t n_keys, blsbn254_keyset** out);
+void blsbn254_keyset_destroy(blsbn254_keyset* keys);
+size_t blsbn254_keyset_count(const blsbn254_keyset* keys);
+int blsbn254_keyset_valid(blsbn254_ctx* ctx, const blsbn254_keyset* keys, uint8_t* ok_bitmap /* ceil(n_keys/8) */);
+int blsbn254_keyset_sum_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* sel, size_t n_groups,
+                              uint8_t* out /* n_groups*128 */, uint8_t* status /* n_groups */);
+int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* sel,
+                                                const uint8_t* msgs, const uint64_t* off /* n_groups+1 */, const uint8_t* sigs /* n_groups*64 */,
+                                                size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_keyset_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Mul<Scalar> for G1Projective (g1.rs:518-534, multiply :821-841) and G2Projective (g2.rs:866-886), element-wise:
  * out_i = [k_i] P_i.  Points uncompressed, scalars 32 bytes big-endian (scalar.rs:229-233) and < r.  A point that does not
  * decode or is off the curve returns BLSBN254_ERR_G1 / BLSBN254_ERR_G2, a scalar >= r BLSBN254_ERR_SCALAR (the reference's

@@ -394,6 +394,63 @@ pub fn multi_miller_loop_prepared(keys: &PreparedKeys, terms: &[(&G1Affine, u32)
     Ok(MillerLoopResult(Option::<Gt>::from(Gt::from_repr(&out)).expect("engine output is canonical").0))
 }
 
+// ---------------------------------------------------------------- a registered committee, signers named by bitmaps
+
+/// A committee's public keys, resident on the GPU (`blsbn254_keyset`): decoded and curve-checked once, then summed per
+/// aggregate by a participation bitmap (`ceil(n/8)` bytes per row, bit i LSB-first = key i signed).  Tied to the process-wide
+/// engine context.
+pub struct KeySet(*mut ffi::KeySet);
+unsafe impl Send for KeySet {}
+
+impl KeySet {
+    pub fn new(pks: &[[u8; 128]]) -> Self {
+        let flat: Vec<u8> = pks.iter().flatten().copied().collect();
+        let mut h: *mut ffi::KeySet = core::ptr::null_mut();
+        with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_create(c, flat.as_ptr(), pks.len(), &mut h) })).expect("an empty key set, or a device error");
+        KeySet(h)
+    }
+    pub fn len(&self) -> usize { unsafe { ffi::blsbn254_keyset_count(self.0) } }
+    /// KeyValidate per registered key (decodes, not the identity, on the curve, in the r-torsion): for the registrar.
+    pub fn valid(&self) -> Vec<bool> {
+        let n = self.len();
+        let mut bm = vec![0u8; (n + 7) / 8];
+        with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_valid(c, self.0, bm.as_mut_ptr()) })).expect("device error");
+        bits(&bm, n)
+    }
+}
+impl Drop for KeySet {
+    fn drop(&mut self) { let _g = engine().lock(); unsafe { ffi::blsbn254_keyset_destroy(self.0) } }
+}
+
+/// `impl Sum for G2Projective` (`g2.rs:579-583`) over the keys each row selects: element g = `Some(aggregate key)`, or `None`
+/// when the row selects a key that does not decode or is off the curve.
+pub fn keyset_sum_batch(keys: &KeySet, rows: &[&[u8]]) -> Vec<Option<[u8; 128]>> {
+    let n = rows.len();
+    let sel: Vec<u8> = rows.iter().flat_map(|r| r.iter().copied()).collect();
+    assert_eq!(sel.len(), n * ((keys.len() + 7) / 8));
+    let mut out = vec![0u8; 128 * n];
+    let mut status = vec![0u8; n];
+    with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_sum_batch(c, keys.0, sel.as_ptr(), n, out.as_mut_ptr(), status.as_mut_ptr()) }))
+        .expect("a padding bit is set");
+    (0..n).map(|g| if status[g] == 1 { Some(out[128 * g..128 * g + 128].try_into().expect("128 bytes")) } else { None }).collect()
+}
+
+/// `fast_aggregate_verify_batch` with every group's keys named by a bitmap over a registered set.
+pub fn keyset_fast_aggregate_verify_batch(keys: &KeySet, rows: &[&[u8]], msgs: &[&[u8]], sigs: &[[u8; 64]], dst: &[u8]) -> Vec<bool> {
+    assert!(rows.len() == msgs.len() && msgs.len() == sigs.len());
+    let n = rows.len();
+    let sel: Vec<u8> = rows.iter().flat_map(|r| r.iter().copied()).collect();
+    assert_eq!(sel.len(), n * ((keys.len() + 7) / 8));
+    let (data, off) = pack(msgs);
+    let sg: Vec<u8> = sigs.iter().flatten().copied().collect();
+    let mut bm = vec![0u8; (n + 7) / 8];
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_keyset_fast_aggregate_verify_batch(c, keys.0, sel.as_ptr(), data.as_ptr(), off.as_ptr(), sg.as_ptr(), n, dst.as_ptr(), dst.len(), bm.as_mut_ptr())
+    }))
+    .expect("a padding bit is set");
+    bits(&bm, n)
+}
+
 // ---------------------------------------------------------------- N GPUs of one node
 
 /// All GPUs named in `BLSBN254_DEVICES` (comma-separated HIP ordinals, default "0"): one context and one host thread per
