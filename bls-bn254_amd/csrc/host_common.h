@@ -15,6 +15,7 @@
 #include "sha256.h"      // host-side use: pre-hashing an oversize DST only (RFC 9380 5.3.3)
 #include "lane_ops.h"    // flag constants
 #include "kernels.h"
+#include "key_cache.h"   // the store of prepared keys: its state words and kernels
 #include "seg_plan.h"    // SegLevel, SegLaunch, the planners of the segmented reductions
 #include "../../include/blsbn254.h"
 
@@ -117,6 +118,13 @@ struct blsbn254_ctx {
   DevBuf status_all;     // per-element decode status of a chunked call, all chunks
   // prepared-key verify path (k_keyprep.hip, k_miller_prep.hip)
   DevBuf kd_slots, kd_rep, kd_kid, kd_keys, kd_hist, kd_cursor, kd_perm, kd_cnt, prep_table, prep_raw, prep_ok, prep_isone, prep_valid;
+  // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys_cached): the keys' encodings, pair tables
+  // and validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss
+  // list, and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
+  DevBuf kc_keys, kc_table, kc_valid, kc_slots, kc_state, kc_slot_of, kc_miss_rep, kc_miss_slot, kc_tslot, kc_cslot, kc_batch_ok;
+  size_t kc_max = 4096;              // keys the store is made for (blsbn254_set_key_cache, BLSBN254_KEY_CACHE); 0: no store, every call prepares its keys
+  size_t kc_cap = 0;                 // keys the store has room for: max(kc_max, the largest key capacity a call was enqueued with); 0: not set up
+  uint32_t kc_mask = 0;              // slot-table entries - 1
   hipStream_t stream2 = nullptr;     // the per-key preparation runs beside hash-to-G1
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool s2_pending = false;           // work was forked onto stream2 and the main stream has not waited for ev_join yet
@@ -305,7 +313,11 @@ BNH int stage_msgs(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off, si
 BNH int launch_g2_prepare(blsbn254_ctx* c, hipStream_t s, const uint8_t* pks, const uint32_t* keys, size_t u, int32_t* raw, uint8_t* ok, const uint32_t* d_u);   // host_verify.hip
 BNH int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_keys, size_t u, int32_t* table, uint8_t* key_ok, const uint32_t* d_u);   // host_verify.hip
 BNH int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* key_ok, size_t u, const uint32_t* d_kid, bool hist_done,
-                               const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join);   // host_verify.hip
+                               const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join,
+                               const uint32_t* slot_of);   // host_verify.hip
+// the store of prepared keys behind dedup_keys / dedup_enqueue: see host_verify.hip
+BNH int prepare_keys_cached(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap);   // host_verify.hip
+BNH int map_to_store(blsbn254_ctx* c, const uint32_t* ids, size_t n, DevBuf& out);   // host_verify.hip
 BNH int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u, uint32_t* hist, const char* what, bool armed);   // host_verify.hip
 BNH int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
                                const int32_t* table, const uint8_t* key_ok, size_t n);   // host_verify.hip
@@ -319,8 +331,8 @@ BNH int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uin
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip
-BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
-                          size_t cnt, uint8_t* d_isone);   // host_rlc.hip
+BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const int32_t* table, const uint8_t* key_ok, const uint8_t* sigs,
+                          const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone);   // host_rlc.hip
 // The segmented reductions' device side.  seg_stage: w's ping-pong buffers for levels of at most items_max items of `limbs` limbs
 // (with `flags`, a byte per item too) and the upload of the descriptors planned into w.h_start / w.h_len.
 BNH int seg_stage(blsbn254_ctx* c, SegWs& w, size_t items_max, size_t limbs, bool flags);   // host_seg.hip

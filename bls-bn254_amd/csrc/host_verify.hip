@@ -26,6 +26,62 @@ int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   return 0;
 }
+// ---- the store of prepared keys (key_cache.h, k_keycache.hip).  In real use a validator set's keys stay the same from batch to
+// batch: a key whose 128 bytes an earlier call on this context prepared keeps its table in the store, and only the keys that
+// are new to the context are prepared.  57 024 B of table + 128 B of encoding + 1 B per key (and 8 B of slot table); the default
+// of 4096 keys is 234 MB of the 288 GB, allocated by the first call that uses it.
+// The store with room for at least `need` keys: max(kc_max, need), so that an empty store takes the call's keys whatever kc_max
+// is.  Growing it is a reallocation (DevBuf::reserve waits for the device) that empties it; the running totals stay.
+static int kc_reserve(blsbn254_ctx* c, size_t need) {
+  if (!c->kc_state.p) {
+    HIPCHK(c, c->kc_state.reserve(64));          // KC_STATE_WORDS words, then (at byte 32) KC_STAT_WORDS 64-bit totals
+    HIPCHK(c, hipMemsetAsync(c->kc_state.p, 0, 64, c->stream));
+  }
+  const size_t want = std::max(c->kc_max, need);
+  if (want <= c->kc_cap) return 0;
+  size_t m = 1;
+  while (m < 2 * want) m <<= 1;
+  c->kc_cap = 0;
+  HIPCHK(c, c->kc_table.reserve(want * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->kc_keys.reserve(128 * want)); HIPCHK(c, c->kc_valid.reserve(want));
+  HIPCHK(c, c->kc_slots.reserve(4 * m));
+  HIPCHK(c, hipMemsetAsync(c->kc_slots.p, 0xff, 4 * m, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->kc_state.p, 0, 4 * KC_STATE_WORDS, c->stream));
+  c->kc_cap = want; c->kc_mask = (uint32_t)(m - 1);
+  return 0;
+}
+// Behind dedup_enqueue (kd_keys[j] = representative tuple of the batch's distinct key j, kd_cnt of them on the device; cap = the
+// key count the call is enqueued with): on the second stream (after ev_fork), ev_join recorded behind it -- look the distinct keys
+// up, prepare the misses as prepare_keys_async prepares all keys (dense, into prep_raw / prep_table / prep_ok, bounded by the
+// device-side miss count: with every key resident these launches leave at once) and copy their tables into the store.
+// Afterwards kc_slot_of[j] is key j's place in kc_table / kc_valid.  No host decision, no read-back.
+int prepare_keys_cached(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap) {
+  TRY(kc_reserve(c, cap));
+  HIPCHK(c, c->kc_slot_of.reserve(4 * cap)); HIPCHK(c, c->kc_miss_rep.reserve(4 * cap)); HIPCHK(c, c->kc_miss_slot.reserve(4 * cap));
+  HIPCHK(c, c->prep_raw.reserve(cap * PREP_RAW_LIMBS * 4)); HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
+  uint32_t* st = (uint32_t*)c->kc_state.p;
+  unsigned long long* stats = (unsigned long long*)((uint8_t*)c->kc_state.p + 32);
+  const uint32_t* d_miss = st + KC_MISS;
+  const uint32_t key_words = (uint32_t)(PREP_KEY_LIMBS / 4);
+  HIPCHK(c, fork_stream2(c));
+  TRY(launch(c, c->stream2, "kd_cache_begin", Shape{dim3(1), dim3(1)}, k_kd_cache_begin, (const uint32_t*)c->kd_cnt.p, (uint32_t)cap, (uint32_t)c->kc_max, (uint32_t)c->kc_cap,
+             st, stats));
+  TRY(launch(c, c->stream2, "kd_cache_clear", grid_lanes((size_t)c->kc_mask + 1), k_kd_cache_clear, (const uint32_t*)st, (uint32_t*)c->kc_slots.p, c->kc_mask + 1));
+  TRY(launch(c, c->stream2, "kd_cache_lookup", grid_lanes(cap), k_kd_cache_lookup, d_pks, (const uint32_t*)c->kd_keys.p, st, (uint32_t*)c->kc_slots.p, c->kc_mask, c->kd_seed,
+             (uint8_t*)c->kc_keys.p, (uint32_t*)c->kc_slot_of.p, (uint32_t*)c->kc_miss_rep.p, (uint32_t*)c->kc_miss_slot.p));
+  TRY(launch_g2_prepare(c, c->stream2, d_pks, (const uint32_t*)c->kc_miss_rep.p, cap, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, d_miss));
+  TRY(launch(c, c->stream2, "g2_expand", grid_lanes(cap * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)cap, (int32_t*)c->prep_table.p, d_miss,
+             (uint8_t*)c->prep_ok.p));
+  const size_t copy_blocks = std::min<size_t>(nblocks(cap * (size_t)key_words), 2048);
+  TRY(launch(c, c->stream2, "kd_cache_scatter", Shape{dim3((unsigned)copy_blocks), dim3(256)}, k_kd_cache_scatter, (const int4*)c->prep_table.p, (const uint8_t*)c->prep_ok.p,
+             (const uint32_t*)c->kc_miss_slot.p, key_words, st, stats, (int4*)c->kc_table.p, (uint8_t*)c->kc_valid.p));
+  HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+  return 0;
+}
+// out[i] = the store index of the key of element i (ids[i] = its batch key id), on the main stream: after join_stream2
+int map_to_store(blsbn254_ctx* c, const uint32_t* ids, size_t n, DevBuf& out) {
+  HIPCHK(c, out.reserve(4 * n));
+  return launch(c, c->stream, "kd_cache_map", grid_lanes(n), k_kd_cache_map, ids, (uint32_t)n, (const uint32_t*)c->kc_slot_of.p, (uint32_t*)out.p);
+}
 // Are all n key indices at d_kid below u?  k_kd_hist counts the keys into hist (zeroed here) and folds the first index out of
 // range into misc[0]; read back (one 4-byte copy and a stream synchronisation).  armed: the caller has already put NO_INDEX there,
 // in one upload with words of its own behind it.  `what` names the element in the error text ("tuple" / "pair").
@@ -51,8 +107,11 @@ int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t
 }
 // Verify n tuples whose keys are given by index into a prepared table (d_kid[i] < u), everything device-resident.
 // The caller has put the preparation of the table on stream2 (ev_join) or the table is final (join = false).
+// slot_of (optional): table / key_ok are the store's and key j's entry is slot_of[j] (prepare_keys_cached); the key ids keep
+// giving the key-sorted order, and the Miller loop takes every tuple's store index in their place.
 int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* key_ok, size_t u, const uint32_t* d_kid, bool hist_done,
-                               const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join) {
+                               const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join,
+                               const uint32_t* slot_of) {
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
   HIPCHK(c, c->kd_hist.reserve(4 * (u + 1))); HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
   HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n));
@@ -63,7 +122,8 @@ int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* ke
   TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, (uint32_t)u, cursor));
   TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, d_kid, (uint32_t)n, (uint32_t)u, cursor, perm));
   if (join) HIPCHK(c, join_stream2(c));
-  TRY(launch_miller_prepared(c, perm, d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n));
+  if (slot_of) TRY(map_to_store(c, d_kid, n, c->kc_tslot));
+  TRY(launch_miller_prepared(c, perm, slot_of ? (const uint32_t*)c->kc_tslot.p : d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n));
   int rc = run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 4, nullptr, nullptr, nullptr, (uint8_t*)c->prep_isone.p, nullptr);
   if (rc) return rc;
   TRY(launch(c, c->stream, "prep_unsort", grid_lanes(n), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)perm, (uint32_t)n,
@@ -120,16 +180,21 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
     int rc = dedup_keys(c, d_pks, n, &u);
     if (rc) return rc;
     if ((u * 2 <= n || small) && u <= PREP_MAX_KEYS) {
-      HIPCHK(c, c->prep_table.reserve(u * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(u));
-      rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, nullptr);
+      const bool cached = c->kc_max != 0;
+      if (cached) {
+        rc = prepare_keys_cached(c, d_pks, u);
+      } else {
+        HIPCHK(c, c->prep_table.reserve(u * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(u));
+        rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, nullptr);
+      }
       if (rc) return rc;
       HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * u, c->stream));
       TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p));
       ++c->stat_prepared_chunks;
       c->u_hint = u ? u : 1;
       if (u > c->u_max_seen) c->u_max_seen = u;
-      return verify_prepared_dev(c, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, u, (const uint32_t*)c->kd_kid.p, true,
-                                 d_msgs, d_off, d_sigs, n, dl, d_bitmap, true);
+      return verify_prepared_dev(c, (const int32_t*)(cached ? c->kc_table.p : c->prep_table.p), (const uint8_t*)(cached ? c->kc_valid.p : c->prep_ok.p), u,
+                                 (const uint32_t*)c->kd_kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap, true, cached ? (const uint32_t*)c->kc_slot_of.p : nullptr);
     }
   }
   c->u_hint = 0;                                      // keys did not repeat: the next call counts them first again
@@ -173,13 +238,18 @@ static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8
   int rc = dedup_enqueue(c, d_pks, n);
   if (rc) return rc;
   TRY(launch(c, c->stream, nullptr, Shape{dim3(1), dim3(1)}, k_kd_decide, (const uint32_t*)c->kd_cnt.p, (uint32_t)n, (uint32_t)cap, small ? 1 : 0, d_res));
-  HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
-  rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, cap, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, d_res);
+  const bool cached = c->kc_max != 0;
+  if (cached) {                                        // (a count beyond the capacity: the first `cap` keys are looked up, the run is discarded as before)
+    rc = prepare_keys_cached(c, d_pks, cap);
+  } else {
+    HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
+    rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, cap, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, d_res);
+  }
   if (rc) return rc;
   HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * cap, c->stream));
   TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)cap, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p));
-  rc = verify_prepared_dev(c, (const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, cap, (const uint32_t*)c->kd_kid.p, true,
-                           d_msgs, d_off, d_sigs, n, dl, d_bitmap, true);
+  rc = verify_prepared_dev(c, (const int32_t*)(cached ? c->kc_table.p : c->prep_table.p), (const uint8_t*)(cached ? c->kc_valid.p : c->prep_ok.p), cap,
+                           (const uint32_t*)c->kd_kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap, true, cached ? (const uint32_t*)c->kc_slot_of.p : nullptr);
   if (rc) return rc;
   blsbn254_ctx::PendingVerify& pv = c->pend[slot];
   HIPCHK(c, hipMemcpyAsync(c->pend_host + 2 * slot, d_res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -247,6 +317,28 @@ int blsbn254_async_stats(blsbn254_ctx* c, uint64_t out[2]) {
   out[0] = c->stat_async_chunks; out[1] = c->stat_async_reruns;
   return 0;
 }
+// The store's size in keys (0: no store -- every call prepares its keys, the kernels and arguments of a build without one).
+// Settles what is pending, waits for the device and empties the store; its memory is taken by the next call that uses it.
+int blsbn254_set_key_cache(blsbn254_ctx* c, size_t max_keys) {
+  if (!c || max_keys > PREP_MAX_KEYS) return BLSBN254_E_ARG;
+  ENTER(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->kc_max = max_keys; c->kc_cap = 0;
+  return 0;
+}
+// out: keys found resident, keys prepared, times the store was emptied because a batch did not fit behind the resident keys
+// (all three counted on the device, over every enqueued run, a discarded one included), keys resident now.  Waits for the device.
+int blsbn254_key_cache_stats(blsbn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BLSBN254_E_ARG;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  ENTER(c);
+  if (!c->kc_state.p) return 0;
+  uint64_t h[7];
+  TRY(download(c, h, c->kc_state.p, sizeof h));
+  out[0] = h[4 + KC_STAT_HITS]; out[1] = h[4 + KC_STAT_MISSES]; out[2] = h[4 + KC_STAT_RESETS];
+  out[3] = c->kc_cap ? (uint32_t)(h[KC_COUNT / 2] >> (32 * (KC_COUNT % 2))) : 0;
+  return 0;
+}
 int blsbn254_set_async_verify(blsbn254_ctx* c, int on) {
   if (!c) return BLSBN254_E_ARG;
   ENTER(c);
@@ -308,7 +400,7 @@ int blsbn254_verify_batch_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* k
   TRY(upload(c, c->kd_kid, key_idx, 4 * n));
   TRY(for_chunks(c, n, [&](size_t lo, size_t m) {
     return verify_prepared_dev(c, (const int32_t*)keys->table.p, (const uint8_t*)keys->ok.p, keys->u, (const uint32_t*)c->kd_kid.p + lo, false,
-                               (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo, (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8, false);
+                               (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo, (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8, false, nullptr);
   }));
   return download(c, bm, c->bitmap.p, nb);
 }

@@ -10,22 +10,8 @@
 #define BN_LINE_TABLE_QUAL static __device__ const
 #include "lane_ops.h"
 #include "kernels.h"
+#include "key_cache.h"   // key_hash, key_equal (shared with the store of prepared keys)
 using namespace bn;
-
-namespace {
-__device__ inline uint32_t load_u32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-__device__ inline uint32_t key_hash(const uint8_t* pk, uint32_t seed) {
-  uint32_t h = seed ^ 0x9e3779b9u;
-  for (int k = 0; k < 32; ++k) { h ^= load_u32(pk + 4 * k); h *= 0x01000193u; h = (h << 13) | (h >> 19); }
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-__device__ inline bool key_equal(const uint8_t* a, const uint8_t* b) {
-  uint32_t d = 0;
-  for (int k = 0; k < 32; ++k) d |= load_u32(a + 4 * k) ^ load_u32(b + 4 * k);
-  return d == 0;
-}
-}  // namespace
 
 // rep[i] = index of the first-inserted tuple whose public key has the same 128 bytes.  slots: M = 2^log2m entries, all 0xffffffff.
 __global__ void k_kd_insert(const uint8_t* pks, uint32_t n, uint32_t* slots, uint32_t mask, uint32_t seed, uint32_t* rep) {

@@ -244,6 +244,16 @@ class Engine:
         """verify_batch's automatic key de-duplication + per-key preparation (default on); off = exact per-tuple path."""
         self._chk(self._lib.blsbn254_set_auto_prepare(self._ctx, ctypes.c_int(1 if on else 0)))
 
+    def set_key_cache(self, max_keys):
+        """size (in keys) of the context's store of prepared keys; 0 = off: every call prepares its keys.  Empties the store."""
+        self._chk(self._lib.blsbn254_set_key_cache(self._ctx, ctypes.c_size_t(max_keys)))
+
+    def key_cache_stats(self):
+        """(keys found resident, keys prepared, times the store was emptied for a batch that did not fit, keys resident now)"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_key_cache_stats(self._ctx, o))
+        return int(o[0]), int(o[1]), int(o[2]), int(o[3])
+
     def path_stats(self):
         """(chunks served by the prepared-key path, chunks served by the exact per-tuple path)"""
         o = (ctypes.c_uint64 * 2)()

@@ -148,6 +148,21 @@ int blsbn254_aggregate_batch_stats(blsbn254_ctx* ctx, uint64_t out[4]);
  * lanes per key).  BLSBN254_WIDE_FE=0 / BLSBN254_TRI_MAX=0 switch the two forms off, BLSBN254_WIDE_FE_MAX=<n> /
  * BLSBN254_TRI_MAX=<n> move the limits, BLSBN254_QUAD_PREP=0 keeps the per-key preparation on one lane per key. */
 int blsbn254_set_auto_prepare(blsbn254_ctx* ctx, int on);
+/* Prepared keys stay resident.  A validator set's keys are the same from batch to batch, so the context keeps the tables of the
+ * keys it has prepared: blsbn254_verify_batch (and _dev, on the counting and on the asynchronous path) and
+ * blsbn254_verify_batch_rlc(_dev) look every distinct key of a batch up by its 128 bytes (hash table, full comparison) and
+ * prepare only the keys that are new to the context; an invalid key is kept as invalid.  The store holds max_keys keys (default
+ * 4096, BLSBN254_KEY_CACHE=<n>; 57 KB of device memory per key, 234 MB at the default, taken by the first call that uses it); it
+ * has room for at least the key capacity of the call at hand -- a larger call reallocates it, which empties it.  A batch whose
+ * distinct keys do not fit behind the resident ones (resident + distinct > max_keys; the keys are counted before they are looked
+ * up, so a key set stays resident when it is at most half of max_keys) empties the store first -- decided on the device, no
+ * read-back -- and costs what every batch costs without a store.  Results never depend on what is resident.  blsbn254_set_key_cache(ctx, 0) turns the store off: every call
+ * prepares its keys.  Any other value empties the store and sets its size; the call waits for the device.
+ * blsbn254_key_cache_stats (waits for the device too): out[0] keys found resident, out[1] keys prepared, out[2] times the store
+ * was emptied because a batch did not fit, all counted on the device over every enqueued run (a run that the asynchronous path
+ * discards and repeats counts twice); out[3] keys resident now. */
+int blsbn254_set_key_cache(blsbn254_ctx* ctx, size_t max_keys /* <= 65536 */);
+int blsbn254_key_cache_stats(blsbn254_ctx* ctx, uint64_t out[4] /* hits, misses, resets, resident */);
 int blsbn254_path_stats(blsbn254_ctx* ctx, uint64_t out[2] /* prepared, exact */);
 /* blsbn254_aggregate_verify over repeated keys (auto-prepare on; at most half of the n >= 1024 keys distinct, or at most 16383 pairs):
  * by bilinearity in the first argument  prod_{i: pk_i = pk} e(H(msg_i), pk) = e(sum_i H(msg_i), pk)  -- exact, no randomness --
