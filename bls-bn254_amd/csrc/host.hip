@@ -57,7 +57,7 @@ int blsbn254_ctx_create(int device, blsbn254_ctx** out) {
   if (const char* e = std::getenv("BLSBN254_RLC_KEY_ROUND")) c->rlc_key_round = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_WIDE_FE")) c->wide_fe = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_ASYNC_VERIFY")) c->async_verify = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_KEY_CACHE")) { long v = std::atol(e); if (v >= 0 && v <= (long)PREP_MAX_KEYS) c->kc_max = (size_t)v; }
+  if (const char* e = std::getenv("BLSBN254_KEY_CACHE")) { long v = std::atol(e); if (v >= 0 && v <= (long)PREP_MAX_KEYS) c->kc.max = (size_t)v; }
   if (const char* e = std::getenv("BLSBN254_QUAD_PREP")) c->quad_prep = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_SPLIT_EASY")) c->split_easy = std::atoi(e) != 0;
   c->tri_max = c->lanes_per_round / 4;        // four lanes per tuple: one round of waves

@@ -64,8 +64,7 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
       HIPCHK(c, fork_stream2(c));
       TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
       HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-      TRY(launch(c, c->stream, "kd_propagate", grid_lanes(np), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)np, (uint32_t)u, (uint32_t*)c->kd_kid.p,
-                 (uint32_t*)nullptr));   // no sorting here: no histogram
+      TRY(dedup_key_ids(c, np, u, false));   // no sorting here: no histogram
       prepared = true;
     }
   }
@@ -184,9 +183,8 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   if (!((u * 2 <= n || small) && u + 1 <= PREP_MAX_KEYS)) return 0;
   *took = true;
   const size_t np = u + 1, n_lanes = (np + 1) / 2;
-  const uint32_t n32 = (uint32_t)n, u32 = (uint32_t)u;
   // the u keys and -G2gen (key id u) become line tables on the second stream, beside the hashing
-  const uint32_t last_key = n32;
+  const uint32_t last_key = (uint32_t)n;
   HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_keys.p + u, &last_key, 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));                                   // last_key and the staged copies are consumed
   HIPCHK(c, c->prep_ok.reserve(np)); HIPCHK(c, c->prep_raw.reserve(np * PREP_RAW_LIMBS * 4));
@@ -194,14 +192,11 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, np, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   // key ids, key-sorted order
-  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
-  HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->status.reserve(np + 8)); HIPCHK(c, c->misc.reserve(64));
+  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->status.reserve(np + 8)); HIPCHK(c, c->misc.reserve(64));
   HIPCHK(c, c->rlc_b.reserve(np * 18 * 4)); HIPCHK(c, c->rlc_idx.reserve(4 * np));
-  uint32_t *hist = (uint32_t*)c->kd_hist.p, *cursor = (uint32_t*)c->kd_cursor.p, *perm = (uint32_t*)c->kd_perm.p, *kid = (uint32_t*)c->kd_kid.p;
-  HIPCHK(c, hipMemsetAsync(hist, 0, 4 * u, c->stream));
-  TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, n32, u32, kid, hist));
-  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, u32, cursor));
-  TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, (const uint32_t*)kid, n32, u32, cursor, perm));          // cursor[k] is now the END of run k
+  TRY(dedup_key_ids(c, n, u, true));
+  TRY(key_sorted_order(c, (const uint32_t*)c->kd_kid.p, n, u));                 // cursor[k] is now the END of run k
+  const uint32_t *hist = (const uint32_t*)c->kd_hist.p, *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p, *kid = (const uint32_t*)c->kd_kid.p;
   TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n,
              (uint8_t*)nullptr, 3));
   // sums per key: the tuples in sorted order (columns perm[s] of h_ws) -> one sum per key (key_sums)

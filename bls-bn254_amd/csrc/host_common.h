@@ -95,6 +95,15 @@ struct BNH TcWs {
 // sums over a registered key set selected by bitmaps (host_keyset.hip, k_keyset.hip): the call's rows, the groups' flip / ok bytes,
 // the word-major partials of a launch and of its reduction passes (ping-pong); the host copy the flip bytes are downloaded to
 struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; };
+// The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
+// validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
+// and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
+struct BNH KeyStore {
+  DevBuf keys, table, valid, slots, state, slot_of, miss_rep, miss_slot, tslot, cslot, batch_ok;
+  size_t max = 4096;                 // keys the store is made for (blsbn254_set_key_cache, BLSBN254_KEY_CACHE); 0: no store, every call prepares its keys
+  size_t cap = 0;                    // keys the store has room for: max(max, the largest key capacity a call was enqueued with); 0: not set up
+  uint32_t mask = 0;                 // slot-table entries - 1
+};
 struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
 
 struct blsbn254_ctx {
@@ -118,13 +127,7 @@ struct blsbn254_ctx {
   DevBuf status_all;     // per-element decode status of a chunked call, all chunks
   // prepared-key verify path (k_keyprep.hip, k_miller_prep.hip)
   DevBuf kd_slots, kd_rep, kd_kid, kd_keys, kd_hist, kd_cursor, kd_perm, kd_cnt, prep_table, prep_raw, prep_ok, prep_isone, prep_valid;
-  // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys_cached): the keys' encodings, pair tables
-  // and validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss
-  // list, and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
-  DevBuf kc_keys, kc_table, kc_valid, kc_slots, kc_state, kc_slot_of, kc_miss_rep, kc_miss_slot, kc_tslot, kc_cslot, kc_batch_ok;
-  size_t kc_max = 4096;              // keys the store is made for (blsbn254_set_key_cache, BLSBN254_KEY_CACHE); 0: no store, every call prepares its keys
-  size_t kc_cap = 0;                 // keys the store has room for: max(kc_max, the largest key capacity a call was enqueued with); 0: not set up
-  uint32_t kc_mask = 0;              // slot-table entries - 1
+  KeyStore kc;                       // the store of prepared keys
   hipStream_t stream2 = nullptr;     // the per-key preparation runs beside hash-to-G1
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool s2_pending = false;           // work was forked onto stream2 and the main stream has not waited for ev_join yet
@@ -311,16 +314,24 @@ BNH int miller_to_ws(blsbn254_ctx* c, const uint8_t* d_g1, const uint8_t* d_g2, 
 BNH int decode_status_rc(blsbn254_ctx* c, const uint8_t* d_status, size_t n);   // host.hip
 BNH int stage_msgs(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off, size_t n);   // host.hip
 BNH int launch_g2_prepare(blsbn254_ctx* c, hipStream_t s, const uint8_t* pks, const uint32_t* keys, size_t u, int32_t* raw, uint8_t* ok, const uint32_t* d_u);   // host_verify.hip
-BNH int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_keys, size_t u, int32_t* table, uint8_t* key_ok, const uint32_t* d_u);   // host_verify.hip
-BNH int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* key_ok, size_t u, const uint32_t* d_kid, bool hist_done,
-                               const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join,
-                               const uint32_t* slot_of);   // host_verify.hip
-// the store of prepared keys behind dedup_keys / dedup_enqueue: see host_verify.hip
-BNH int prepare_keys_cached(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap);   // host_verify.hip
-BNH int map_to_store(blsbn254_ctx* c, const uint32_t* ids, size_t n, DevBuf& out);   // host_verify.hip
+// A batch's prepared keys as their consumers see them: the entry of batch key j in table / ok is slot_of ? slot_of[j] : j.
+// prepare_keys fills one for the keys left by dedup_keys / dedup_enqueue, from the context's store or prepared for this call, on
+// stream2 with ev_join behind it (cap: the key count the call is enqueued with; d_u, optional: the count on the device when cap is
+// only a capacity); the explicit G2Prepared API builds one with slot_of = nullptr.  Consumers do not ask which: key_miller_ids /
+// miller_ids give the ids the Miller loops take (of the keys themselves -- iota = 0, 1, ... serves without a store -- and of
+// elements given by batch key id, mapped into buf with one), keys_valid the validity bytes in batch key order (after join_stream2).
+struct KeyTables { const int32_t* table; const uint8_t* ok; const uint32_t* slot_of; };
+static inline const uint32_t* key_miller_ids(const KeyTables& kt, const uint32_t* iota) { return kt.slot_of ? kt.slot_of : iota; }
+BNH int prepare_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap, const uint32_t* d_u, KeyTables* kt);   // host_verify.hip
+BNH int miller_ids(blsbn254_ctx* c, const KeyTables& kt, const uint32_t* ids, size_t n, DevBuf& buf, const uint32_t** out);   // host_verify.hip
+BNH int keys_valid(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint8_t** out);   // host_verify.hip
+// behind dedup_keys / dedup_enqueue: key ids (kd_kid; hist: their counts, kd_hist), then the key-sorted order of d_kid (kd_perm, kd_cursor)
+BNH int dedup_key_ids(blsbn254_ctx* c, size_t n, size_t u, bool hist);   // host_verify.hip
+BNH int key_sorted_order(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u);   // host_verify.hip
+BNH int verify_prepared_dev(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint32_t* d_kid, bool deduped, const uint8_t* d_msgs, const uint64_t* d_off,
+                            const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
 BNH int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u, uint32_t* hist, const char* what, bool armed);   // host_verify.hip
-BNH int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
-                               const int32_t* table, const uint8_t* key_ok, size_t n);   // host_verify.hip
+BNH int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, const KeyTables& kt, size_t n);   // host_verify.hip
 BNH int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out);   // host_verify.hip
 BNH int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
@@ -331,8 +342,7 @@ BNH int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uin
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip
-BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const int32_t* table, const uint8_t* key_ok, const uint8_t* sigs,
-                          const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone);   // host_rlc.hip
+BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const KeyTables& kt, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone);   // host_rlc.hip
 // The segmented reductions' device side.  seg_stage: w's ping-pong buffers for levels of at most items_max items of `limbs` limbs
 // (with `flags`, a byte per item too) and the upload of the descriptors planned into w.h_start / w.h_len.
 BNH int seg_stage(blsbn254_ctx* c, SegWs& w, size_t items_max, size_t limbs, bool flags);   // host_seg.hip

@@ -60,11 +60,10 @@ int draw_seed(blsbn254_ctx* c, uint8_t out[32]) {
   return 0;
 }
 // One table-only Miller loop + final exponentiation over `cnt` (virtual or real) tuples: is_one bytes to d_isone, flags in ctx->flags.
-// kid[perm[s]] names the key's entry in table / key_ok: the batch key id, or its store index when the tables are the store's.
-int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const int32_t* table, const uint8_t* key_ok, const uint8_t* sigs,
-                          const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone) {
+// kid[perm[s]] names the key's entry in kt's tables: what miller_ids / key_miller_ids make of the batch key ids.
+int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const KeyTables& kt, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone) {
   HIPCHK(c, c->f_ws.reserve(cnt * 108 * 4)); HIPCHK(c, c->flags.reserve(cnt));
-  TRY(launch_miller_prepared(c, perm, kid, sigs, h_ws, h_stride, table, key_ok, cnt));
+  TRY(launch_miller_prepared(c, perm, kid, sigs, h_ws, h_stride, kt, cnt));
   return run_final_exp(c, (int32_t*)c->f_ws.p, cnt, cnt, 4, nullptr, nullptr, nullptr, d_isone, nullptr);
 }
 // n <= ctx->chunk tuples, everything device-resident; d_seed = 32 bytes in device memory.  *took = 0 when the keys do not repeat
@@ -97,32 +96,19 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   }
   const size_t nblk = (n + 255) / 256;
   const uint32_t G32 = (uint32_t)G, n32 = (uint32_t)n, u32 = (uint32_t)u;
-  // The keys' tables: from the context's store of prepared keys (only the keys new to it are prepared; the Miller loops then take
-  // store indices where they take key ids, the other kernels the validity bytes gathered into batch key order), else prepared here.
-  const bool cached = c->kc_max != 0;
-  if (cached) {
-    HIPCHK(c, c->kc_batch_ok.reserve(u));
-    rc = prepare_keys_cached(c, d_pks, u);
-  } else {
-    HIPCHK(c, c->prep_table.reserve(u * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(u));
-    rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, nullptr);
-  }
-  if (rc) return rc;
-  const int32_t* table = (const int32_t*)(cached ? c->kc_table.p : c->prep_table.p);
-  const uint8_t* table_ok = (const uint8_t*)(cached ? c->kc_valid.p : c->prep_ok.p);      // indexed as the tables are
-  const uint8_t* key_ok = (const uint8_t*)(cached ? c->kc_batch_ok.p : c->prep_ok.p);     // indexed by batch key id
-  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
-  HIPCHK(c, c->r2_a.reserve(n * 27 * 4)); HIPCHK(c, c->r2_b.reserve(n * 27 * 4)); HIPCHK(c, c->r2_sigok.reserve(n)); HIPCHK(c, c->r2_tchunk.reserve(4 * n));
-  HIPCHK(c, c->r2_ccnt.reserve(4 * (u + 2))); HIPCHK(c, c->r2_cbase.reserve(4 * (u + 2)));
+  // The keys' tables, on the second stream (with a store of prepared keys only the keys new to it are prepared: the Miller loops
+  // take miller_ids where they take key ids, the other kernels keys_valid's bytes in batch key order)
+  KeyTables kt;
+  TRY(prepare_keys(c, d_pks, u, nullptr, &kt));
+  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->r2_a.reserve(n * 27 * 4)); HIPCHK(c, c->r2_b.reserve(n * 27 * 4)); HIPCHK(c, c->r2_sigok.reserve(n));
+  HIPCHK(c, c->r2_tchunk.reserve(4 * n)); HIPCHK(c, c->r2_ccnt.reserve(4 * (u + 2))); HIPCHK(c, c->r2_cbase.reserve(4 * (u + 2)));
   HIPCHK(c, c->r2_need.reserve(n)); HIPCHK(c, c->r2_bcnt.reserve(4 * (nblk + 2))); HIPCHK(c, c->r2_bbase.reserve(4 * (nblk + 2)));
   HIPCHK(c, c->r2_list.reserve(4 * n)); HIPCHK(c, c->r2_valid.reserve(n));
-  uint32_t *hist = (uint32_t*)c->kd_hist.p, *cursor = (uint32_t*)c->kd_cursor.p, *perm = (uint32_t*)c->kd_perm.p, *kid = (uint32_t*)c->kd_kid.p;
-  uint32_t *ccnt = (uint32_t*)c->r2_ccnt.p, *cbase = (uint32_t*)c->r2_cbase.p;
+  uint32_t *hist = (uint32_t*)c->kd_hist.p, *kid = (uint32_t*)c->kd_kid.p, *ccnt = (uint32_t*)c->r2_ccnt.p, *cbase = (uint32_t*)c->r2_cbase.p;
   // key ids, key-sorted order, chunk numbering
-  HIPCHK(c, hipMemsetAsync(hist, 0, 4 * u, c->stream));
-  TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, n32, u32, kid, hist));
-  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, u32, cursor));
-  TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, (const uint32_t*)kid, n32, u32, cursor, perm));          // cursor[k] is now the END of run k
+  TRY(dedup_key_ids(c, n, u, true));
+  TRY(key_sorted_order(c, kid, n, u));                 // cursor[k] is now the END of run k
+  const uint32_t *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p;
   TRY(launch(c, c->stream, "rlc2_counts", grid_lanes(u + 1), k_rlc2_chunk_counts, (const uint32_t*)hist, u32, G32, ccnt));
   TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)ccnt, u32 + 1, cbase));
   uint32_t m32 = 0;
@@ -143,13 +129,10 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   TRY(launch(c, c->stream, "rlc2_sum", grid_lanes(m), k_rlc2_sum, (const int32_t*)c->r2_a.p, (const int32_t*)c->r2_b.p, n, (const uint8_t*)c->r2_sigok.p, (const uint32_t*)c->r2_cstart.p,
              (const uint32_t*)c->r2_clen.p, m, (int32_t*)c->r2_sa.p, (int32_t*)c->r2_sb.p, (uint32_t*)c->r2_celig.p));
   HIPCHK(c, join_stream2(c));                      // the key tables are ready
-  const uint32_t *key_slot = nullptr, *tuple_slot = kid, *chunk_slot = (const uint32_t*)c->r2_ckid.p;      // the Miller loops' key ids of keys, tuples, chunks
-  if (cached) {
-    TRY(launch(c, c->stream, "kd_cache_ok", grid_lanes(u), k_kd_cache_ok, (const uint32_t*)c->kc_slot_of.p, u32, table_ok, (uint8_t*)c->kc_batch_ok.p));
-    TRY(map_to_store(c, kid, n, c->kc_tslot));
-    TRY(map_to_store(c, (const uint32_t*)c->r2_ckid.p, m, c->kc_cslot));
-    key_slot = (const uint32_t*)c->kc_slot_of.p; tuple_slot = (const uint32_t*)c->kc_tslot.p; chunk_slot = (const uint32_t*)c->kc_cslot.p;
-  }
+  const uint8_t* key_ok; const uint32_t *tuple_slot, *chunk_slot;      // validity by batch key id; the Miller loops' key ids of tuples, chunks
+  TRY(keys_valid(c, kt, u, &key_ok));
+  TRY(miller_ids(c, kt, kid, n, c->kc.tslot, &tuple_slot));
+  TRY(miller_ids(c, kt, (const uint32_t*)c->r2_ckid.p, m, c->kc.cslot, &chunk_slot));
   // The key round: ALL tuples of a key as one virtual tuple (the chunk sums of the key, summed) -- u checks, few enough for the
   // wave-per-tuple kernels.  A batch without invalid signatures (the usual case) is decided here, in a fraction of a chunk round;
   // otherwise only the chunks of the keys that failed are looked at below.  Same weights, hence the same 2^-64 bound per check.
@@ -175,7 +158,7 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
     TRY(launch(c, c->stream, "rlc2_virtual", grid_lanes(u), k_rlc2_virtual, ksa, ksb, u, (const uint32_t*)c->r2_kelig.p, (const uint32_t*)nullptr, u, (uint8_t*)c->r2_ksig.p,
                (int32_t*)c->r2_kh.p,
                (uint8_t*)c->r2_kstate.p));
-    rc = prepared_round(c, (const uint32_t*)c->r2_iota.p, key_slot ? key_slot : (const uint32_t*)c->r2_iota.p, table, table_ok, (const uint8_t*)c->r2_ksig.p, (const int32_t*)c->r2_kh.p,
+    rc = prepared_round(c, (const uint32_t*)c->r2_iota.p, key_miller_ids(kt, (const uint32_t*)c->r2_iota.p), kt, (const uint8_t*)c->r2_ksig.p, (const int32_t*)c->r2_kh.p,
                         u, u, (uint8_t*)c->r2_kisone.p);
     if (rc) return rc;
     int* d_all = (int*)c->misc.p;
@@ -213,7 +196,7 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   TRY(launch(c, c->stream, "rlc2_virtual", grid_lanes(mc), k_rlc2_virtual, (const int32_t*)c->r2_sa.p, (const int32_t*)c->r2_sb.p, m, (const uint32_t*)c->r2_celig.p, clist, mc,
              (uint8_t*)c->r2_csig.p,
              (int32_t*)c->r2_ch.p, (uint8_t*)c->r2_cstate.p));
-  rc = prepared_round(c, clist ? clist : (const uint32_t*)c->r2_iota.p, chunk_slot, table, table_ok, (const uint8_t*)c->r2_csig.p, (const int32_t*)c->r2_ch.p, m, mc,
+  rc = prepared_round(c, clist ? clist : (const uint32_t*)c->r2_iota.p, chunk_slot, kt, (const uint8_t*)c->r2_csig.p, (const int32_t*)c->r2_ch.p, m, mc,
                       (uint8_t*)c->r2_cisone.p);
   if (rc) return rc;
   TRY(launch(c, c->stream, "rlc2_chunk_pass", grid_lanes(mc), k_rlc2_chunk_pass, clist, (const uint8_t*)c->r2_cstate.p, (const uint8_t*)c->r2_cisone.p, (const uint8_t*)c->flags.p,
@@ -229,7 +212,7 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
     HIPCHK(c, c->prep_isone.reserve(m2));
     TRY(launch(c, c->stream, "rlc2_compact", grid_lanes(n), k_rlc2_compact, (const uint8_t*)c->r2_need.p, (const uint32_t*)perm, n32, (const uint32_t*)c->r2_bbase.p,
                (uint32_t*)c->r2_list.p));
-    rc = prepared_round(c, (const uint32_t*)c->r2_list.p, tuple_slot, table, table_ok, d_sigs, (const int32_t*)c->h_ws.p, n, m2, (uint8_t*)c->prep_isone.p);
+    rc = prepared_round(c, (const uint32_t*)c->r2_list.p, tuple_slot, kt, d_sigs, (const int32_t*)c->h_ws.p, n, m2, (uint8_t*)c->prep_isone.p);
     if (rc) return rc;
     TRY(launch(c, c->stream, "prep_unsort", grid_lanes(m2), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)c->r2_list.p, m2,
                (uint8_t*)c->r2_valid.p));

@@ -15,72 +15,103 @@ int launch_g2_prepare(blsbn254_ctx* c, hipStream_t s, const uint8_t* pks, const 
     return launch(c, s, "g2_prepare", grid_lanes(2 * 256 * (size_t)nblocks(4 * u)), k_g2_prepare_quad, pks, keys, (uint32_t)u, raw, ok, d_u);
   return launch(c, s, "g2_prepare", grid_lanes(2 * 256 * (size_t)nblocks(u)), k_g2_prepare, pks, keys, (uint32_t)u, raw, ok, d_u);
 }
-// G2Prepared::from for u keys on the second stream (after ev_fork), ev_join recorded behind it.
-// keys == nullptr: key k = pks[128 k]; else key k = the public key of tuple keys[k].
-// d_u (optional): the key count on the device when u is only a capacity (the asynchronous path)
-int prepare_keys_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* d_keys, size_t u, int32_t* table, uint8_t* key_ok, const uint32_t* d_u) {
-  HIPCHK(c, c->prep_raw.reserve(u * PREP_RAW_LIMBS * 4));
-  HIPCHK(c, fork_stream2(c));
-  TRY(launch_g2_prepare(c, c->stream2, d_pks, d_keys, u, (int32_t*)c->prep_raw.p, key_ok, d_u));
-  TRY(launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)u, table, d_u, key_ok));
-  HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-  return 0;
+// G2Prepared::from for at most u of the tuples `keys` names (u a capacity when d_u gives the count on the device), dense into
+// prep_raw / prep_table / prep_ok, on the second stream
+static int prepare_dense(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* keys, size_t u, const uint32_t* d_u) {
+  TRY(launch_g2_prepare(c, c->stream2, d_pks, keys, u, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, d_u));
+  return launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)u, (int32_t*)c->prep_table.p, d_u,
+                (uint8_t*)c->prep_ok.p);
 }
 // ---- the store of prepared keys (key_cache.h, k_keycache.hip).  In real use a validator set's keys stay the same from batch to
 // batch: a key whose 128 bytes an earlier call on this context prepared keeps its table in the store, and only the keys that
 // are new to the context are prepared.  57 024 B of table + 128 B of encoding + 1 B per key (and 8 B of slot table); the default
 // of 4096 keys is 234 MB of the 288 GB, allocated by the first call that uses it.
-// The store with room for at least `need` keys: max(kc_max, need), so that an empty store takes the call's keys whatever kc_max
+// The store with room for at least `need` keys: max(kc.max, need), so that an empty store takes the call's keys whatever kc.max
 // is.  Growing it is a reallocation (DevBuf::reserve waits for the device) that empties it; the running totals stay.
 static int kc_reserve(blsbn254_ctx* c, size_t need) {
-  if (!c->kc_state.p) {
-    HIPCHK(c, c->kc_state.reserve(64));          // KC_STATE_WORDS words, then (at byte 32) KC_STAT_WORDS 64-bit totals
-    HIPCHK(c, hipMemsetAsync(c->kc_state.p, 0, 64, c->stream));
+  KeyStore& s = c->kc;
+  if (!s.state.p) {
+    HIPCHK(c, s.state.reserve(64));          // KC_STATE_WORDS words, then (at byte 32) KC_STAT_WORDS 64-bit totals
+    HIPCHK(c, hipMemsetAsync(s.state.p, 0, 64, c->stream));
   }
-  const size_t want = std::max(c->kc_max, need);
-  if (want <= c->kc_cap) return 0;
+  const size_t want = std::max(s.max, need);
+  if (want <= s.cap) return 0;
   size_t m = 1;
   while (m < 2 * want) m <<= 1;
-  c->kc_cap = 0;
-  HIPCHK(c, c->kc_table.reserve(want * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->kc_keys.reserve(128 * want)); HIPCHK(c, c->kc_valid.reserve(want));
-  HIPCHK(c, c->kc_slots.reserve(4 * m));
-  HIPCHK(c, hipMemsetAsync(c->kc_slots.p, 0xff, 4 * m, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->kc_state.p, 0, 4 * KC_STATE_WORDS, c->stream));
-  c->kc_cap = want; c->kc_mask = (uint32_t)(m - 1);
+  s.cap = 0;
+  HIPCHK(c, s.table.reserve(want * PREP_KEY_LIMBS * 4)); HIPCHK(c, s.keys.reserve(128 * want)); HIPCHK(c, s.valid.reserve(want));
+  HIPCHK(c, s.slots.reserve(4 * m));
+  HIPCHK(c, hipMemsetAsync(s.slots.p, 0xff, 4 * m, c->stream));
+  HIPCHK(c, hipMemsetAsync(s.state.p, 0, 4 * KC_STATE_WORDS, c->stream));
+  s.cap = want; s.mask = (uint32_t)(m - 1);
   return 0;
 }
-// Behind dedup_enqueue (kd_keys[j] = representative tuple of the batch's distinct key j, kd_cnt of them on the device; cap = the
-// key count the call is enqueued with): on the second stream (after ev_fork), ev_join recorded behind it -- look the distinct keys
-// up, prepare the misses as prepare_keys_async prepares all keys (dense, into prep_raw / prep_table / prep_ok, bounded by the
-// device-side miss count: with every key resident these launches leave at once) and copy their tables into the store.
-// Afterwards kc_slot_of[j] is key j's place in kc_table / kc_valid.  No host decision, no read-back.
-int prepare_keys_cached(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap) {
-  TRY(kc_reserve(c, cap));
-  HIPCHK(c, c->kc_slot_of.reserve(4 * cap)); HIPCHK(c, c->kc_miss_rep.reserve(4 * cap)); HIPCHK(c, c->kc_miss_slot.reserve(4 * cap));
-  HIPCHK(c, c->prep_raw.reserve(cap * PREP_RAW_LIMBS * 4)); HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
-  uint32_t* st = (uint32_t*)c->kc_state.p;
-  unsigned long long* stats = (unsigned long long*)((uint8_t*)c->kc_state.p + 32);
-  const uint32_t* d_miss = st + KC_MISS;
+// The store's branch of prepare_keys, on the second stream: look the distinct keys up, prepare the misses as prepare_dense
+// prepares all keys (bounded by the device-side miss count: with every key resident these launches leave at once) and copy
+// their tables into the store.  Afterwards kc.slot_of[j] is key j's place in kc.table / kc.valid.  No host decision, no read-back.
+static int prepare_into_store(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap) {
+  KeyStore& s = c->kc;
+  uint32_t* st = (uint32_t*)s.state.p;
+  unsigned long long* stats = (unsigned long long*)((uint8_t*)s.state.p + 32);
   const uint32_t key_words = (uint32_t)(PREP_KEY_LIMBS / 4);
-  HIPCHK(c, fork_stream2(c));
-  TRY(launch(c, c->stream2, "kd_cache_begin", Shape{dim3(1), dim3(1)}, k_kd_cache_begin, (const uint32_t*)c->kd_cnt.p, (uint32_t)cap, (uint32_t)c->kc_max, (uint32_t)c->kc_cap,
-             st, stats));
-  TRY(launch(c, c->stream2, "kd_cache_clear", grid_lanes((size_t)c->kc_mask + 1), k_kd_cache_clear, (const uint32_t*)st, (uint32_t*)c->kc_slots.p, c->kc_mask + 1));
-  TRY(launch(c, c->stream2, "kd_cache_lookup", grid_lanes(cap), k_kd_cache_lookup, d_pks, (const uint32_t*)c->kd_keys.p, st, (uint32_t*)c->kc_slots.p, c->kc_mask, c->kd_seed,
-             (uint8_t*)c->kc_keys.p, (uint32_t*)c->kc_slot_of.p, (uint32_t*)c->kc_miss_rep.p, (uint32_t*)c->kc_miss_slot.p));
-  TRY(launch_g2_prepare(c, c->stream2, d_pks, (const uint32_t*)c->kc_miss_rep.p, cap, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, d_miss));
-  TRY(launch(c, c->stream2, "g2_expand", grid_lanes(cap * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)cap, (int32_t*)c->prep_table.p, d_miss,
-             (uint8_t*)c->prep_ok.p));
+  TRY(launch(c, c->stream2, "kd_cache_begin", Shape{dim3(1), dim3(1)}, k_kd_cache_begin, (const uint32_t*)c->kd_cnt.p, (uint32_t)cap, (uint32_t)s.max, (uint32_t)s.cap, st, stats));
+  TRY(launch(c, c->stream2, "kd_cache_clear", grid_lanes((size_t)s.mask + 1), k_kd_cache_clear, (const uint32_t*)st, (uint32_t*)s.slots.p, s.mask + 1));
+  TRY(launch(c, c->stream2, "kd_cache_lookup", grid_lanes(cap), k_kd_cache_lookup, d_pks, (const uint32_t*)c->kd_keys.p, st, (uint32_t*)s.slots.p, s.mask, c->kd_seed,
+             (uint8_t*)s.keys.p, (uint32_t*)s.slot_of.p, (uint32_t*)s.miss_rep.p, (uint32_t*)s.miss_slot.p));
+  TRY(prepare_dense(c, d_pks, (const uint32_t*)s.miss_rep.p, cap, st + KC_MISS));
   const size_t copy_blocks = std::min<size_t>(nblocks(cap * (size_t)key_words), 2048);
-  TRY(launch(c, c->stream2, "kd_cache_scatter", Shape{dim3((unsigned)copy_blocks), dim3(256)}, k_kd_cache_scatter, (const int4*)c->prep_table.p, (const uint8_t*)c->prep_ok.p,
-             (const uint32_t*)c->kc_miss_slot.p, key_words, st, stats, (int4*)c->kc_table.p, (uint8_t*)c->kc_valid.p));
+  return launch(c, c->stream2, "kd_cache_scatter", Shape{dim3((unsigned)copy_blocks), dim3(256)}, k_kd_cache_scatter, (const int4*)c->prep_table.p, (const uint8_t*)c->prep_ok.p,
+                (const uint32_t*)s.miss_slot.p, key_words, st, stats, (int4*)s.table.p, (uint8_t*)s.valid.p);
+}
+// The prepared keys of the batch behind dedup_enqueue (kd_keys[j] = the representative tuple of the batch's distinct key j, kd_cnt
+// of them on the device): see KeyTables in host_common.h.  THE place that chooses between the store and tables of this call:
+// it reserves what the branch needs, forks, and records ev_join behind the branch's launches.  d_u bounds the work without a
+// store, the miss count with one (a count beyond the capacity: the first `cap` keys are prepared or looked up, and
+// verify_chunk_async's caller discards the run as before).
+int prepare_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap, const uint32_t* d_u, KeyTables* kt) {
+  KeyStore& s = c->kc;
+  const bool store = s.max != 0;
+  if (store) {
+    TRY(kc_reserve(c, cap));
+    HIPCHK(c, s.slot_of.reserve(4 * cap)); HIPCHK(c, s.miss_rep.reserve(4 * cap)); HIPCHK(c, s.miss_slot.reserve(4 * cap));
+  }
+  HIPCHK(c, c->prep_raw.reserve(cap * PREP_RAW_LIMBS * 4)); HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
+  HIPCHK(c, fork_stream2(c));
+  TRY(store ? prepare_into_store(c, d_pks, cap) : prepare_dense(c, d_pks, (const uint32_t*)c->kd_keys.p, cap, d_u));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+  *kt = store ? KeyTables{(const int32_t*)s.table.p, (const uint8_t*)s.valid.p, (const uint32_t*)s.slot_of.p}
+              : KeyTables{(const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, nullptr};
   return 0;
 }
-// out[i] = the store index of the key of element i (ids[i] = its batch key id), on the main stream: after join_stream2
-int map_to_store(blsbn254_ctx* c, const uint32_t* ids, size_t n, DevBuf& out) {
-  HIPCHK(c, out.reserve(4 * n));
-  return launch(c, c->stream, "kd_cache_map", grid_lanes(n), k_kd_cache_map, ids, (uint32_t)n, (const uint32_t*)c->kc_slot_of.p, (uint32_t*)out.p);
+// *out = the ids the Miller loops take for n elements given by batch key id: the ids themselves, or with a store its indices,
+// mapped into buf on the main stream (after join_stream2)
+int miller_ids(blsbn254_ctx* c, const KeyTables& kt, const uint32_t* ids, size_t n, DevBuf& buf, const uint32_t** out) {
+  *out = ids;
+  if (!kt.slot_of) return 0;
+  HIPCHK(c, buf.reserve(4 * n));
+  *out = (const uint32_t*)buf.p;
+  return launch(c, c->stream, "kd_cache_map", grid_lanes(n), k_kd_cache_map, ids, (uint32_t)n, kt.slot_of, (uint32_t*)buf.p);
+}
+// *out = the u keys' validity bytes in batch key order: the tables' own, or gathered from the store's (after join_stream2)
+int keys_valid(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint8_t** out) {
+  *out = kt.ok;
+  if (!kt.slot_of) return 0;
+  HIPCHK(c, c->kc.batch_ok.reserve(u));
+  *out = (const uint8_t*)c->kc.batch_ok.p;
+  return launch(c, c->stream, "kd_cache_ok", grid_lanes(u), k_kd_cache_ok, kt.slot_of, (uint32_t)u, kt.ok, (uint8_t*)c->kc.batch_ok.p);
+}
+// Behind dedup_enqueue, on the main stream: every tuple's key id (kd_kid; ids beyond u clamped) and, hist: how many tuples each
+// key has (kd_hist).  Then, from that histogram: the key-sorted order of the n tuples d_kid (kd_perm; kd_cursor[k] ends as the END
+// of run k).  Two steps: verify_prepared_dev enqueues hash-to-G1 (and checks the explicit API's indices) between them.
+int dedup_key_ids(blsbn254_ctx* c, size_t n, size_t u, bool hist) {
+  if (hist) HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * u, c->stream));
+  return launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_kid.p,
+                hist ? (uint32_t*)c->kd_hist.p : nullptr);
+}
+int key_sorted_order(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u) {
+  HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)c->kd_hist.p, (uint32_t)u, (uint32_t*)c->kd_cursor.p));
+  return launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, d_kid, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_cursor.p, (uint32_t*)c->kd_perm.p);
 }
 // Are all n key indices at d_kid below u?  k_kd_hist counts the keys into hist (zeroed here) and folds the first index out of
 // range into misc[0]; read back (one 4-byte copy and a stream synchronisation).  armed: the caller has already put NO_INDEX there,
@@ -96,37 +127,32 @@ int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u
   return 0;
 }
 // The table-only Miller loop over n tuples (f_ws, flags) in the form that fits n; the three forms give the same values.
-int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride,
-                           const int32_t* table, const uint8_t* key_ok, size_t n) {
+int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, const KeyTables& kt, size_t n) {
   int32_t* f = (int32_t*)c->f_ws.p; uint8_t* flags = (uint8_t*)c->flags.p;
   if (c->wide_fe && n <= c->wide_fe_max)               // few tuples: one wave per tuple (k_miller_wide.hip)
-    return launch(c, c->stream, "miller_wide_prepared", grid_wide(n), k_miller_wide_prepared, perm, kid, sigs, h_ws, h_stride, table, key_ok, n, f, flags);
+    return launch(c, c->stream, "miller_wide_prepared", grid_wide(n), k_miller_wide_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
   if (n <= c->tri_max && c->tri_miller)                // mid-size launches: three lanes per tuple (k_tri.hip)
-    return launch(c, c->stream, "miller_tri_prepared", grid_tri(n), k_miller_tri_prepared, perm, kid, sigs, h_ws, h_stride, table, key_ok, n, f, flags);
-  return launch(c, c->stream, "miller_prepared", grid_lanes(n), k_miller_prepared, perm, kid, sigs, h_ws, h_stride, table, key_ok, n, f, flags);
+    return launch(c, c->stream, "miller_tri_prepared", grid_tri(n), k_miller_tri_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
+  return launch(c, c->stream, "miller_prepared", grid_lanes(n), k_miller_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
 }
-// Verify n tuples whose keys are given by index into a prepared table (d_kid[i] < u), everything device-resident.
-// The caller has put the preparation of the table on stream2 (ev_join) or the table is final (join = false).
-// slot_of (optional): table / key_ok are the store's and key j's entry is slot_of[j] (prepare_keys_cached); the key ids keep
-// giving the key-sorted order, and the Miller loop takes every tuple's store index in their place.
-int verify_prepared_dev(blsbn254_ctx* c, const int32_t* table, const uint8_t* key_ok, size_t u, const uint32_t* d_kid, bool hist_done,
-                               const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap, bool join,
-                               const uint32_t* slot_of) {
+// Verify n tuples whose keys are given by index into prepared tables (d_kid[i] < u), everything device-resident.
+// deduped: the ids are dedup_key_ids' -- their histogram is filled, and the tables' preparation is on stream2 (prepare_keys: ev_join).
+// Else they are a caller's (checked here) and the tables are final.  The key ids give the key-sorted order whatever the
+// tables; the Miller loop takes what miller_ids makes of them.
+int verify_prepared_dev(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint32_t* d_kid, bool deduped, const uint8_t* d_msgs, const uint64_t* d_off,
+                        const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap) {
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
-  HIPCHK(c, c->kd_hist.reserve(4 * (u + 1))); HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
-  HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n));
-  uint32_t* hist = (uint32_t*)c->kd_hist.p; uint32_t* cursor = (uint32_t*)c->kd_cursor.p; uint32_t* perm = (uint32_t*)c->kd_perm.p;
+  HIPCHK(c, c->kd_hist.reserve(4 * (u + 1))); HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n));
   TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr,
              3));   // homogeneous H: no inversion
-  if (!hist_done) TRY(check_key_indices(c, d_kid, n, u, hist, "tuple", false));
-  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)hist, (uint32_t)u, cursor));
-  TRY(launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, d_kid, (uint32_t)n, (uint32_t)u, cursor, perm));
-  if (join) HIPCHK(c, join_stream2(c));
-  if (slot_of) TRY(map_to_store(c, d_kid, n, c->kc_tslot));
-  TRY(launch_miller_prepared(c, perm, slot_of ? (const uint32_t*)c->kc_tslot.p : d_kid, d_sigs, (const int32_t*)c->h_ws.p, n, table, key_ok, n));
-  int rc = run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 4, nullptr, nullptr, nullptr, (uint8_t*)c->prep_isone.p, nullptr);
-  if (rc) return rc;
-  TRY(launch(c, c->stream, "prep_unsort", grid_lanes(n), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, (const uint32_t*)perm, (uint32_t)n,
+  if (!deduped) TRY(check_key_indices(c, d_kid, n, u, (uint32_t*)c->kd_hist.p, "tuple", false));
+  TRY(key_sorted_order(c, d_kid, n, u));
+  if (deduped) HIPCHK(c, join_stream2(c));
+  const uint32_t *perm = (const uint32_t*)c->kd_perm.p, *ids;
+  TRY(miller_ids(c, kt, d_kid, n, c->kc.tslot, &ids));
+  TRY(launch_miller_prepared(c, perm, ids, d_sigs, (const int32_t*)c->h_ws.p, n, kt, n));
+  TRY(run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 4, nullptr, nullptr, nullptr, (uint8_t*)c->prep_isone.p, nullptr));
+  TRY(launch(c, c->stream, "prep_unsort", grid_lanes(n), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, perm, (uint32_t)n,
              (uint8_t*)c->prep_valid.p));
   return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->prep_valid.p, n, d_bitmap);
 }
@@ -150,6 +176,14 @@ int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out) {
   TRY(download(c, &u, c->kd_cnt.p, 4));
   *u_out = u;
   return 0;
+}
+// Behind dedup_enqueue / dedup_keys: the prepared-key pipeline of a chunk enqueued for `cap` distinct keys (d_u: see prepare_keys)
+static int verify_deduped_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n, size_t cap,
+                              const uint32_t* d_u, uint32_t dl, uint8_t* d_bitmap) {
+  KeyTables kt;
+  TRY(prepare_keys(c, d_pks, cap, d_u, &kt));
+  TRY(dedup_key_ids(c, n, cap, true));
+  return verify_prepared_dev(c, kt, cap, (const uint32_t*)c->kd_kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap);
 }
 // the exact per-tuple path: every tuple validates its own key and runs the two-pair Miller loop with a variable-Q pair
 int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
@@ -180,21 +214,10 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
     int rc = dedup_keys(c, d_pks, n, &u);
     if (rc) return rc;
     if ((u * 2 <= n || small) && u <= PREP_MAX_KEYS) {
-      const bool cached = c->kc_max != 0;
-      if (cached) {
-        rc = prepare_keys_cached(c, d_pks, u);
-      } else {
-        HIPCHK(c, c->prep_table.reserve(u * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(u));
-        rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, nullptr);
-      }
-      if (rc) return rc;
-      HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * u, c->stream));
-      TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p));
       ++c->stat_prepared_chunks;
       c->u_hint = u ? u : 1;
       if (u > c->u_max_seen) c->u_max_seen = u;
-      return verify_prepared_dev(c, (const int32_t*)(cached ? c->kc_table.p : c->prep_table.p), (const uint8_t*)(cached ? c->kc_valid.p : c->prep_ok.p), u,
-                                 (const uint32_t*)c->kd_kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap, true, cached ? (const uint32_t*)c->kc_slot_of.p : nullptr);
+      return verify_deduped_dev(c, d_pks, d_msgs, d_off, d_sigs, n, u, nullptr, dl, d_bitmap);
     }
   }
   c->u_hint = 0;                                      // keys did not repeat: the next call counts them first again
@@ -235,22 +258,9 @@ static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8
   Stream2Guard s2_guard(c);
   const int slot = (c->pend_head + c->pend_count) & 3;
   uint32_t* d_res = (uint32_t*)c->pend_dev.p + 2 * slot;
-  int rc = dedup_enqueue(c, d_pks, n);
-  if (rc) return rc;
+  TRY(dedup_enqueue(c, d_pks, n));
   TRY(launch(c, c->stream, nullptr, Shape{dim3(1), dim3(1)}, k_kd_decide, (const uint32_t*)c->kd_cnt.p, (uint32_t)n, (uint32_t)cap, small ? 1 : 0, d_res));
-  const bool cached = c->kc_max != 0;
-  if (cached) {                                        // (a count beyond the capacity: the first `cap` keys are looked up, the run is discarded as before)
-    rc = prepare_keys_cached(c, d_pks, cap);
-  } else {
-    HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
-    rc = prepare_keys_async(c, d_pks, (const uint32_t*)c->kd_keys.p, cap, (int32_t*)c->prep_table.p, (uint8_t*)c->prep_ok.p, d_res);
-  }
-  if (rc) return rc;
-  HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * cap, c->stream));
-  TRY(launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)cap, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_hist.p));
-  rc = verify_prepared_dev(c, (const int32_t*)(cached ? c->kc_table.p : c->prep_table.p), (const uint8_t*)(cached ? c->kc_valid.p : c->prep_ok.p), cap,
-                           (const uint32_t*)c->kd_kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap, true, cached ? (const uint32_t*)c->kc_slot_of.p : nullptr);
-  if (rc) return rc;
+  TRY(verify_deduped_dev(c, d_pks, d_msgs, d_off, d_sigs, n, cap, d_res, dl, d_bitmap));   // (d_res[0]: the key count k_kd_decide left)
   blsbn254_ctx::PendingVerify& pv = c->pend[slot];
   HIPCHK(c, hipMemcpyAsync(c->pend_host + 2 * slot, d_res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(pv.ev, c->stream));
@@ -323,7 +333,7 @@ int blsbn254_set_key_cache(blsbn254_ctx* c, size_t max_keys) {
   if (!c || max_keys > PREP_MAX_KEYS) return BLSBN254_E_ARG;
   ENTER(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->kc_max = max_keys; c->kc_cap = 0;
+  c->kc.max = max_keys; c->kc.cap = 0;
   return 0;
 }
 // out: keys found resident, keys prepared, times the store was emptied because a batch did not fit behind the resident keys
@@ -332,11 +342,11 @@ int blsbn254_key_cache_stats(blsbn254_ctx* c, uint64_t out[4]) {
   if (!c || !out) return BLSBN254_E_ARG;
   out[0] = out[1] = out[2] = out[3] = 0;
   ENTER(c);
-  if (!c->kc_state.p) return 0;
+  if (!c->kc.state.p) return 0;
   uint64_t h[7];
-  TRY(download(c, h, c->kc_state.p, sizeof h));
+  TRY(download(c, h, c->kc.state.p, sizeof h));
   out[0] = h[4 + KC_STAT_HITS]; out[1] = h[4 + KC_STAT_MISSES]; out[2] = h[4 + KC_STAT_RESETS];
-  out[3] = c->kc_cap ? (uint32_t)(h[KC_COUNT / 2] >> (32 * (KC_COUNT % 2))) : 0;
+  out[3] = c->kc.cap ? (uint32_t)(h[KC_COUNT / 2] >> (32 * (KC_COUNT % 2))) : 0;
   return 0;
 }
 int blsbn254_set_async_verify(blsbn254_ctx* c, int on) {
@@ -398,9 +408,10 @@ int blsbn254_verify_batch_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* k
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   TRY(upload(c, c->in_b, sigs, 64 * n));
   TRY(upload(c, c->kd_kid, key_idx, 4 * n));
+  const KeyTables kt{(const int32_t*)keys->table.p, (const uint8_t*)keys->ok.p, nullptr};
   TRY(for_chunks(c, n, [&](size_t lo, size_t m) {
-    return verify_prepared_dev(c, (const int32_t*)keys->table.p, (const uint8_t*)keys->ok.p, keys->u, (const uint32_t*)c->kd_kid.p + lo, false,
-                               (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo, (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8, false, nullptr);
+    return verify_prepared_dev(c, kt, keys->u, (const uint32_t*)c->kd_kid.p + lo, false, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo,
+                               (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8);
   }));
   return download(c, bm, c->bitmap.p, nb);
 }

@@ -1,4 +1,4 @@
-// key_cache.h -- what ONE lane does in the per-context store of prepared keys (k_keycache.hip, host_verify.hip), and the hash /
+// key_cache.h -- what ONE lane does in the per-context store of prepared keys (k_keycache.hip, host_verify.hip prepare_keys), and the hash /
 // comparison of the 128-byte key encodings that the batch de-duplication (k_keyprep.hip) shares with it.
 // The store has room for R keys: their encodings (R x 128 B), their expanded pair tables, one validity byte each, and an
 // open-addressing slot table of M >= 2 R entries (M a power of two) whose entries are store indices (KC_EMPTY: free).  Store

@@ -247,3 +247,35 @@ def test_rlc_reuses_the_entries(eng, oracle, M, pair_of):
     assert p.on.key_cache_stats() == (40, 40, 0, 40)                          # no miss
     p.call("A", A)
     assert p.on.key_cache_stats() == (80, 40, 0, 40)
+
+
+# what a call on the context with the store launches beyond its twin, by profile name (key_cache.h; host_verify.hip prepare_keys,
+# miller_ids, keys_valid): the lookup and the copy of the misses' tables, the tuples' store indices -- and on the RLC path the
+# chunks' store indices as well, with the validity bytes gathered into batch key order
+STORE_LAUNCHES = {"kd_cache_begin": 1, "kd_cache_clear": 1, "kd_cache_lookup": 1, "kd_cache_scatter": 1, "kd_cache_map": 1}
+STORE_LAUNCHES_RLC = dict(STORE_LAUNCHES, kd_cache_map=2, kd_cache_ok=1)
+
+
+@pytest.mark.parametrize("name,rlc,miller", [("A_small", False, "miller_wide_prepared"), ("A_tri", False, "miller_tri_prepared"), ("A", True, "miller_wide_prepared")])
+def test_both_sources_of_tables_run_the_same_pipeline(eng, oracle, M, pair_of, name, rlc, miller):
+    """The tables come from the store or from the call; everything else a call launches is the same.  Launch counts by name
+    (profile_read) of the first call on a fresh context (it counts its keys; every key is new to the store) and of the second
+    (enqueued on the first one's key count; every key resident): equal for every name of the twin, and the store's context has
+    exactly the store's own launches besides.  In batch A every fifth signature is invalid: its RLC call fails the key round and
+    runs the chunk round and the per-tuple fallback, so the store indices of keys, chunks and tuples are all used."""
+    b = batch(eng, oracle, M, name)
+    p = pair_of()
+    for e in (p.on, p.off):
+        e.profile_enable(True)
+    for rep in range(2):
+        for e in (p.on, p.off):
+            e.profile_reset()
+        p.call(name, b, rlc=rlc)                                              # settles: both contexts are synchronised
+        on, off = ({k: v["launches"] for k, v in e.profile_read().items()} for e in (p.on, p.off))
+        print(name, "call", rep, "with the store:", on, "twin:", off)
+        assert off.get(miller, 0) >= 1 and "kd_propagate" in off and not any(k.startswith("kd_cache_") for k in off)
+        assert {k: on.get(k) for k in off} == off
+        assert {k: v for k, v in on.items() if k not in off} == (STORE_LAUNCHES_RLC if rlc else STORE_LAUNCHES)
+    if not rlc:
+        assert p.on.async_stats() == p.off.async_stats() == (1, 0)            # the second call took the asynchronous path
+    assert p.on.key_cache_stats() == (40, 40, 0, 40)
