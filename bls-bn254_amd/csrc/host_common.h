@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "key_cache.h"   // the store of prepared keys: its state words and kernels
 #include "seg_plan.h"    // SegLevel, SegLaunch, the planners of the segmented reductions
+#include "keyset_agg_plan.h"   // KaRepack, the argument walk of the checked aggregation over a key set
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -95,6 +96,21 @@ struct BNH TcWs {
 // sums over a registered key set selected by bitmaps (host_keyset.hip, k_keyset.hip): the call's rows, the groups' flip / ok bytes,
 // the word-major partials of a launch and of its reduction passes (ping-pong); the host copy the flip bytes are downloaded to
 struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; };
+// checked signature aggregation over a registered key set (host_keyset_agg.hip, k_keyset_agg.hip): the staged indices and
+// signatures, the candidate bitmap over the call's entries, the signatures as points (27 x N limbs) and the groups' sums with
+// the levels between them, the sums' encodings, the groups' rows, their verification bits, the entry offsets; for the fallback
+// the gathered keys and the bits of the per-signature verification.  Host side: the bits and rows an attempt downloads, the
+// groups that go to the fallback and their sub-call (keyset_agg.h KaRepack) with its signatures, messages (one per group for the
+// equation, one per entry for the per-signature verification), offsets and results.
+struct BNH KaggWs {
+  DevBuf idx, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits;
+  GroupOff goff;
+  SegWs seg;
+  KaRepack sub;
+  std::vector<uint8_t> h_gbits, s_sigs, s_msgs, s_emsgs, s_out, s_rows;
+  std::vector<uint64_t> s_moff, s_emoff;
+  std::vector<size_t> fail;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -172,7 +188,9 @@ struct blsbn254_ctx {
   TdlWs tdl;
   TcWs tc;
   KsetWs kset;
+  KaggWs kagg;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
+  uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
@@ -294,8 +312,9 @@ static const size_t PREP_RAW_LIMBS = (size_t)BN_NEG_G2_LINES * 54;       // a ke
 static const size_t PREP_KEY_LIMBS = (size_t)BN_NEG_G2_LINES * 162;      // a key's 88 expanded line pairs (key line x -G2gen line)
 struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok; };   // pair tables (verify), raw line triples (multi_miller_loop), validity
 // a registered key set (host_keyset.hip): the keys as affine limb-major rows (36 x n limbs), the bad / skip words (keyset.h), the
-// total of the non-skipped keys (54 limbs), KeyValidate per key (bytes)
-struct blsbn254_keyset { blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid; };
+// total of the non-skipped keys (54 limbs), KeyValidate per key (bytes), the encodings as they were uploaded (128 B per key: the
+// per-signature fallback of host_keyset_agg.hip gathers its keys from them)
+struct blsbn254_keyset { blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid, enc; };
 
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip
@@ -339,6 +358,9 @@ BNH int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
 // segmented sums of n G2 encodings staged at d_pks over the groups goff (host offsets) into c->gs_sum / c->gs_sum_ok
 BNH int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups);   // host_groupops.hip
+// the sums of n_groups rows ALREADY ON THE DEVICE (ceil(k->n / 8) bytes each) over the key set k into c->gs_sum / c->gs_sum_ok,
+// the flip bytes into c->kset.h_flip (enqueued); *launches: launches of the word kernel
+BNH int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* d_rows, size_t n_groups, size_t* launches);   // host_keyset.hip
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip

@@ -24,8 +24,9 @@ int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, b
   k->ctx = c; k->n = n_keys;
   const size_t W = ks_nwords(n_keys);
   HIPCHK(c, k->aff.reserve(36 * n_keys * 4)); HIPCHK(c, k->bad.reserve(W * 4)); HIPCHK(c, k->skip.reserve(W * 4));
-  HIPCHK(c, k->total.reserve(54 * 4)); HIPCHK(c, k->valid.reserve(n_keys)); HIPCHK(c, c->sub_ok.reserve(n_keys));
+  HIPCHK(c, k->total.reserve(54 * 4)); HIPCHK(c, k->valid.reserve(n_keys)); HIPCHK(c, c->sub_ok.reserve(n_keys)); HIPCHK(c, k->enc.reserve(128 * n_keys));
   TRY(upload(c, c->in_a, pks, 128 * n_keys));
+  HIPCHK(c, hipMemcpyAsync(k->enc.p, c->in_a.p, 128 * n_keys, hipMemcpyDeviceToDevice, c->stream));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(n_keys), k_g2_check, (const uint8_t*)c->in_a.p, n_keys, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
   TRY(launch(c, c->stream, "ks_register", grid_lanes(n_keys), k_ks_register, (const uint8_t*)c->in_a.p, (uint32_t)n_keys, (const uint8_t*)c->sub_ok.p,
              (int32_t*)k->aff.p, (uint32_t*)k->bad.p, (uint32_t*)k->skip.p, (uint8_t*)k->valid.p));
@@ -69,22 +70,21 @@ static int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel
   }
   return 0;
 }
-// The sums of every row into c->gs_sum / c->gs_sum_ok (enqueued), the flip bytes into c->kset.h_flip (enqueued: read after the
-// caller's synchronising download).  A launch covers as many groups as keep groups x W within KS_LAUNCH_ITEMS partials (within
-// ctx->chunk when that is smaller); launch starts are multiples of 8 groups.
-static int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches) {
+// The sums of every row (d_rows: on the device) into c->gs_sum / c->gs_sum_ok (enqueued), the flip bytes into c->kset.h_flip
+// (enqueued: read after the caller's synchronising download).  A launch covers as many groups as keep groups x W within
+// KS_LAUNCH_ITEMS partials (within ctx->chunk when that is smaller); launch starts are multiples of 8 groups.
+int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* d_rows, size_t n_groups, size_t* launches) {
   KsetWs& w = c->kset;
   const size_t W = ks_nwords(k->n), rb = (k->n + 7) / 8;
   const size_t Gl = std::max((size_t)8, (std::min(KS_LAUNCH_ITEMS, c->chunk) / W) & ~(size_t)7), Gmax = std::min(Gl, n_groups);
   const size_t runs0 = (W + KS_RUN_ITEMS - 1) / KS_RUN_ITEMS;
-  TRY(upload(c, w.sel, sel, rb * n_groups));
   HIPCHK(c, w.flip.reserve(n_groups)); HIPCHK(c, w.ok.reserve(n_groups));
   HIPCHK(c, w.part[0].reserve(54 * 4 * W * Gmax)); HIPCHK(c, w.part[1].reserve(54 * 4 * runs0 * Gmax));
   HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
   *launches = 0;
   for (size_t lo = 0; lo < n_groups; lo += Gl, ++*launches) {
     const size_t m = std::min(Gl, n_groups - lo);
-    const uint8_t *flip = (const uint8_t*)w.flip.p + lo, *ok = (const uint8_t*)w.ok.p + lo, *rows = (const uint8_t*)w.sel.p + lo * rb;
+    const uint8_t *flip = (const uint8_t*)w.flip.p + lo, *ok = (const uint8_t*)w.ok.p + lo, *rows = d_rows + lo * rb;
     TRY(launch(c, c->stream, "ks_count", grid_lanes(m), k_ks_count, rows, m, (uint32_t)k->n, (const uint32_t*)k->bad.p, (uint8_t*)w.flip.p + lo, (uint8_t*)w.ok.p + lo));
     TRY(launch(c, c->stream, "ks_word_sum", Shape{dim3(nblocks(m), (unsigned)W), dim3(256)}, k_ks_word_sum, (const int32_t*)k->aff.p, (uint32_t)k->n,
                (const uint32_t*)k->skip.p, rows, flip, m, (int32_t*)w.part[0].p, W * m));
@@ -102,6 +102,11 @@ static int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint
   w.h_flip.resize(n_groups);
   HIPCHK(c, hipMemcpyAsync(w.h_flip.data(), w.flip.p, n_groups, hipMemcpyDeviceToHost, c->stream));
   return 0;
+}
+// the same for rows of the caller: staged in c->kset.sel first
+static int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches) {
+  TRY(upload(c, c->kset.sel, sel, (k->n + 7) / 8 * n_groups));
+  return ks_enqueue_sums_dev(c, k, (const uint8_t*)c->kset.sel.p, n_groups, launches);
 }
 // counted once the call has succeeded (and synchronised: the flip bytes are on the host)
 static void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches) {

@@ -168,6 +168,11 @@ BN_KERNEL k_ks_word_sum(const int32_t* aff, uint32_t n_keys, const uint32_t* ski
                         int32_t* out, size_t out_stride);
 BN_KERNEL k_ks_group_sum(const int32_t* in, size_t in_stride, uint32_t cnt, size_t G, const uint8_t* flip, const uint8_t* ok, const int32_t* total,
                          int last, int32_t* out, size_t out_stride, uint8_t* ok_out);
+// checked signature aggregation over a registered key set (k_keyset_agg.hip)
+BN_KERNEL k_ka_scan(const uint8_t* key_valid, const uint32_t* idx, const uint8_t* sigs, const uint8_t* mask, size_t m, uint32_t lo, size_t N, uint8_t* cand,
+                    int32_t* pts);
+__global__ void __launch_bounds__(256) k_ka_rows(const uint32_t* idx, const uint8_t* cand, const uint32_t* goff, size_t m, size_t lo, uint32_t n_keys, uint8_t* rows);
+__global__ void __launch_bounds__(256) k_ka_gather_keys(const uint4* enc, const uint32_t* idx, size_t m, uint4* out);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

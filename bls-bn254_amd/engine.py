@@ -458,6 +458,45 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_stats(self._ctx, o))
         return {"groups": int(o[0]), "complement_groups": int(o[1]), "launches": int(o[2]), "key_sets": int(o[3])}
 
+    def keyset_aggregate_checked_batch(self, ks, entry_sets, msgs, dst=DEFAULT_DST):
+        """The collecting node's call: entry_sets[g] = the signatures received for msgs[g], a list of (key index, 64-byte
+        signature) pairs or a dict {index: signature} over the registered KeySet (sorted by index here; a repeated index raises
+        ValueError).  Returns (out_sigs, rows, status): 64 bytes, one participation row of ceil(n_keys / 8) bytes and one status
+        byte per group.  status 0: the aggregate of the entries the row names, which keyset_fast_aggregate_verify_batch accepts
+        for (row, message); ST_SHORT = 5: nothing usable, the identity encoding and a zero row.  Entries on a key that fails
+        KeyValidate or with a signature that is no curve point are left out; all candidates are checked with one pairing
+        equation per group, and only a group that fails it has every signature verified.  No exception for a bad group."""
+        g = len(msgs)
+        if len(entry_sets) != g:
+            raise ValueError("one set of entries per message")
+        idx, sigs, soff = [], [], np.zeros(g + 1, dtype=np.uint64)
+        for i, es in enumerate(entry_sets):
+            es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
+            if any(a[0] == b[0] for a, b in zip(es, es[1:])):
+                raise ValueError("entry set %d names a key twice" % i)
+            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != 64 for _, s in es):
+                raise ValueError("an entry is (key index, 64 signature bytes)")
+            idx += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
+            soff[i + 1] = len(idx)
+        rb = (ks.count() + 7) // 8
+        ia = np.asarray(idx if idx else [0], dtype=np.uint32)
+        data, moff = pack_messages(msgs)
+        s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
+        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        r = np.zeros(max(rb * g, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
+        st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_keyset_aggregate_checked_batch(self._ctx, ks._h, ia.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ps,
+                                                                    soff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd,
+                                                                    ctypes.c_size_t(len(dst)), po, pr, pst))
+        return o[:64 * g].tobytes(), r[:rb * g].tobytes(), st[:g].tobytes()
+
+    def keyset_aggregate_stats(self):
+        """dict: groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified
+        individually, groups that ended in ST_SHORT"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_aggregate_stats(self._ctx, o))
+        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_signatures": int(o[2]), "short_groups": int(o[3])}
+
     def aggregate_verify_batch(self, key_sets, msg_sets, agg_sigs, dst=DEFAULT_DST):
         """Many independent aggregate signatures in one call.  key_sets: list of byte strings (each a multiple of 128 bytes: the
         keys of one group); msg_sets: one list of messages per group, as many as the group has keys; agg_sigs: 64 bytes per group.

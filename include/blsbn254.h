@@ -301,6 +301,43 @@ int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* ctx, const blsbn25
                                                 const uint8_t* msgs, const uint64_t* off /* n_groups+1 */, const uint8_t* sigs /* n_groups*64 */,
                                                 size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
 int blsbn254_keyset_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* Checked signature aggregation over a registered key set -- what the node calls that collects the committee members' individual
+ * signatures on one message and hands on what blsbn254_keyset_fast_aggregate_verify_batch consumes: per message the aggregate
+ * signature and the participation bitmap, with the bad signatures left out.  Group g is one message msgs[msg_off[g] ..
+ * msg_off[g + 1]) with the signatures received for it, the entries sig_off[g] .. sig_off[g + 1]: entry s says that key idx[s] of
+ * the key set signed with sigs[64 s ..].  sig_off / msg_off: n_groups + 1 non-decreasing element / byte offsets, host arrays,
+ * which need not start at 0 (idx, sigs and msgs are indexed by them as given); the outputs are indexed from the first group.
+ * Inside a group the indices must be STRICTLY INCREASING: no key twice, and one canonical order of a group's entries.
+ * BLSBN254_E_ARG (with a last_error text): NULL arguments, a key set of another context, decreasing offsets, n_groups above
+ * BLSBN254_CHUNK_LANES (4 Mi), more than 2^23 entries, an idx >= n_keys, indices of a group that do not strictly increase; the
+ * outputs are then untouched.  n_groups == 0 returns 0.  A bad entry or group is never an error of the call.
+ * An entry is a CANDIDATE when its key has the KeyValidate bit blsbn254_keyset_valid reports (computed once, at registration)
+ * and its signature decodes, is on the curve and is not the identity.  Other entries are left out silently: they never fail
+ * their group and never cause the fallback.
+ * Optimistic attempt, once for all groups of the call (one pass of enqueued work): A_g = the sum of the group's candidate
+ * signatures, row_g = the candidates' bits, and the equation of blsbn254_keyset_fast_aggregate_verify_batch on (row_g, msg_g,
+ * A_g).  Where it holds: status[g] = 0, out_sigs[64 g ..] = A_g, row g of out_sel (ceil(n_keys/8) bytes) = row_g.  The check is
+ * of the SUM: signatures whose errors cancel in it (sigma_a + D, sigma_b - D) are both used, and the aggregate is correct.
+ * Fallback, only for the groups that had a candidate and failed the equation (repacked into one sub-call): every candidate is
+ * verified as blsbn254_verify_batch verifies (key, msg_g, signature), the entries whose bit is set are kept and summed again,
+ * and the same single equation is run once more on the result.  It holds: status 0 with the kept set as the row.  It does not:
+ * BLSBN254_ST_SHORT.  That second check exists for the one case per-signature verification does not exclude, kept keys whose
+ * sum is the identity (P and -P both registered and both signing): such a group ends in BLSBN254_ST_SHORT, and choosing a
+ * subset of it is left to the caller.  A group without entries, without a candidate or without a kept entry is
+ * BLSBN254_ST_SHORT too.  A short group's outputs are the identity encoding (0, 1) and an all-zero row.
+ * With status 0: blsbn254_keyset_fast_aggregate_verify_batch sets the group's bit for (row of out_sel, msg, out_sigs) under the
+ * same dst, and out_sigs is byte-identical to blsbn254_aggregate_sigs on the selected entries' signatures.  A group's outcome
+ * depends on its own inputs only: not on the attempt that served it, on launch boundaries or on its neighbours.  Pending
+ * asynchronous verify calls are settled on entry and none is left pending.  The groups of this call are not counted by
+ * blsbn254_keyset_stats (its launches of the word kernel neither); blsbn254_keyset_aggregate_stats, since the context was
+ * created: out[0] groups settled by the optimistic attempt, out[1] groups sent to the fallback, out[2] signatures verified
+ * individually, out[3] groups ending in BLSBN254_ST_SHORT. */
+int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint32_t* idx /* N */, const uint8_t* sigs /* N*64 */, const uint64_t* sig_off /* n_groups+1 */,
+        const uint8_t* msgs, const uint64_t* msg_off /* n_groups+1, bytes */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len,
+        uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* n_groups*ceil(n_keys/8) */, uint8_t* status /* n_groups */);
+int blsbn254_keyset_aggregate_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Mul<Scalar> for G1Projective (g1.rs:518-534, multiply :821-841) and G2Projective (g2.rs:866-886), element-wise:
  * out_i = [k_i] P_i.  Points uncompressed, scalars 32 bytes big-endian (scalar.rs:229-233) and < r.  A point that does not
  * decode or is off the curve returns BLSBN254_ERR_G1 / BLSBN254_ERR_G2, a scalar >= r BLSBN254_ERR_SCALAR (the reference's

@@ -451,6 +451,32 @@ pub fn keyset_fast_aggregate_verify_batch(keys: &KeySet, rows: &[&[u8]], msgs: &
     bits(&bm, n)
 }
 
+/// What the node that collects a committee's individual signatures hands on (`blsbn254_keyset_aggregate_checked_batch`):
+/// `entries[g]` = the `(key index, signature)` pairs received for `msgs[g]`, sorted here by index (a repeated index panics).
+/// Element g = `Some((aggregate signature, participation row))`, which `keyset_fast_aggregate_verify_batch` accepts for the
+/// message, or `None` when nothing usable is left (`BLSBN254_ST_SHORT`).  Bad signatures are left out, never an error.
+pub fn keyset_aggregate_checked_batch(keys: &KeySet, entries: &[Vec<(u32, [u8; 64])>], msgs: &[&[u8]], dst: &[u8]) -> Vec<Option<([u8; 64], Vec<u8>)>> {
+    assert_eq!(entries.len(), msgs.len());
+    let n = msgs.len();
+    let rb = (keys.len() + 7) / 8;
+    let (mut idx, mut sg, mut soff) = (Vec::<u32>::new(), Vec::<u8>::new(), vec![0u64]);
+    for e in entries {
+        let mut e = e.clone();
+        e.sort_by_key(|p| p.0);
+        assert!(e.windows(2).all(|w| w[0].0 < w[1].0), "a key index is repeated");
+        for (k, s) in &e { idx.push(*k); sg.extend_from_slice(s); }
+        soff.push(idx.len() as u64);
+    }
+    let (data, moff) = pack(msgs);
+    let (mut out, mut sel, mut status) = (vec![0u8; 64 * n], vec![0u8; rb * n], vec![0u8; n]);
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_keyset_aggregate_checked_batch(c, keys.0, idx.as_ptr(), sg.as_ptr(), soff.as_ptr(), data.as_ptr(), moff.as_ptr(), n, dst.as_ptr(), dst.len(),
+                                                     out.as_mut_ptr(), sel.as_mut_ptr(), status.as_mut_ptr())
+    }))
+    .expect("a key index names no key of the set");
+    (0..n).map(|g| if status[g] == 0 { Some((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), sel[rb * g..rb * g + rb].to_vec())) } else { None }).collect()
+}
+
 // ---------------------------------------------------------------- N GPUs of one node
 
 /// All GPUs named in `BLSBN254_DEVICES` (comma-separated HIP ordinals, default "0"): one context and one host thread per
