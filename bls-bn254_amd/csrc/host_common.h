@@ -18,6 +18,7 @@
 #include "key_cache.h"   // the store of prepared keys: its state words and kernels
 #include "seg_plan.h"    // SegLevel, SegLaunch, the planners of the segmented reductions
 #include "keyset_agg_plan.h"   // KaRepack, the argument walk of the checked aggregation over a key set
+#include "keyset_merge_plan.h" // KmRepack, the argument walk of the checked merge over a key set
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -111,6 +112,22 @@ struct BNH KaggWs {
   std::vector<uint64_t> s_moff, s_emoff;
   std::vector<size_t> fail;
 };
+// checked merge of partial aggregates over a registered key set (host_keyset_merge.hip, k_keyset_merge.hip): the staged rows and
+// signatures, the signature test and the selection's byte per contribution, the used and candidate bitmaps over the call's
+// contributions, the signatures as points (27 x N limbs) and the groups' sums with the levels between them, the sums' encodings,
+// the groups' merged rows, their verification bits, the contribution offsets; for the fallback the bits of the per-contribution
+// verification.  Host side: what an attempt downloads, the groups that go to the fallback and their sub-call (keyset_merge_plan.h
+// KmRepack) with its messages (one per group for the equation, one per contribution for the per-contribution verification),
+// offsets and results.
+struct BNH KmWs {
+  DevBuf rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits;
+  GroupOff goff;
+  SegWs seg;
+  KmRepack sub;
+  std::vector<uint8_t> h_gbits, h_used, h_cand, s_msgs, s_emsgs, s_out, s_rows;
+  std::vector<uint64_t> s_moff, s_emoff;
+  std::vector<size_t> fail;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -189,8 +206,10 @@ struct blsbn254_ctx {
   TcWs tc;
   KsetWs kset;
   KaggWs kagg;
+  KmWs kmrg;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
   uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
+  uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
@@ -313,8 +332,9 @@ static const size_t PREP_KEY_LIMBS = (size_t)BN_NEG_G2_LINES * 162;      // a ke
 struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok; };   // pair tables (verify), raw line triples (multi_miller_loop), validity
 // a registered key set (host_keyset.hip): the keys as affine limb-major rows (36 x n limbs), the bad / skip words (keyset.h), the
 // total of the non-skipped keys (54 limbs), KeyValidate per key (bytes), the encodings as they were uploaded (128 B per key: the
-// per-signature fallback of host_keyset_agg.hip gathers its keys from them)
-struct blsbn254_keyset { blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid, enc; };
+// per-signature fallback of host_keyset_agg.hip gathers its keys from them), the KeyValidate bits packed into a word per 32 keys
+// (bits past the last key 0: the selection of host_keyset_merge.hip tests a row's words against them)
+struct blsbn254_keyset { blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid, enc, vwords; };
 
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip

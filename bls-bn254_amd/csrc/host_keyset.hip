@@ -35,6 +35,10 @@ int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, b
   const uint64_t goff[2] = {0, (uint64_t)n_keys};
   TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, goff, 1));
   HIPCHK(c, hipMemcpyAsync(k->total.p, c->gs_sum.p, 54 * 4, hipMemcpyDeviceToDevice, c->stream));
+  // the KeyValidate bits by words, for the selection of the checked merge: packed once, here
+  HIPCHK(c, k->vwords.reserve(W * 4));
+  HIPCHK(c, hipMemsetAsync(k->vwords.p, 0, W * 4, c->stream));
+  TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(n_keys), k_pack_bitmap, (const uint8_t*)k->valid.p, n_keys, (uint8_t*)k->vwords.p));
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) { (void)hipDeviceSynchronize(); }       // nothing may still be writing the buffers the owner frees
   HIPCHK(c, es);

@@ -173,6 +173,11 @@ BN_KERNEL k_ka_scan(const uint8_t* key_valid, const uint32_t* idx, const uint8_t
                     int32_t* pts);
 __global__ void __launch_bounds__(256) k_ka_rows(const uint32_t* idx, const uint8_t* cand, const uint32_t* goff, size_t m, size_t lo, uint32_t n_keys, uint8_t* rows);
 __global__ void __launch_bounds__(256) k_ka_gather_keys(const uint4* enc, const uint32_t* idx, size_t m, uint4* out);
+// checked merge of partial aggregates over a registered key set (k_keyset_merge.hip)
+BN_KERNEL k_km_sig(const uint8_t* sigs, size_t m, uint32_t lo, size_t N, uint8_t* sig_ok, int32_t* pts);
+__global__ void __launch_bounds__(256) k_km_select(const uint8_t* rows, const uint8_t* sig_ok, const uint8_t* mask, const uint32_t* goff, const uint32_t* valid,
+                                                  uint32_t n_keys, size_t g_lo, size_t m, uint8_t* flags, uint8_t* urows);
+BN_KERNEL k_km_points(const uint8_t* flags, size_t m, uint32_t lo, size_t N, int32_t* pts, uint8_t* used, uint8_t* cand);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

@@ -497,6 +497,55 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_aggregate_stats(self._ctx, o))
         return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_signatures": int(o[2]), "short_groups": int(o[3])}
 
+    def keyset_merge_checked_batch(self, ks, contributions, msgs, dst=DEFAULT_DST):
+        """The call of an intermediate node of an aggregation tree: contributions[g] = the partial aggregates received for
+        msgs[g], a list of (row, 64-byte signature) pairs in the order of their priority, a row being ceil(n_keys / 8) bytes
+        or an iterable of key indices of the registered KeySet.  The order is kept.  Returns (out_sigs, rows, used, status):
+        64 bytes, one merged row and one status byte per group, and per group the list of its contributions' used flags.
+        status 0: the sum of the used signatures, which keyset_fast_aggregate_verify_batch accepts for (row, message), the row
+        being the OR of the used rows; ST_SHORT = 5: nothing usable, the identity encoding, a zero row and no flag.  Selection
+        is greedy: a contribution is used when its signature is a curve point, its row is not empty, selects keys that pass
+        KeyValidate only and is disjoint from the rows used before it.  One pairing equation per group checks the merged sum;
+        only a group that fails it has every candidate verified on its own and is selected again.  No exception for a bad
+        contribution or group."""
+        g = len(msgs)
+        if len(contributions) != g:
+            raise ValueError("one list of contributions per message")
+        n, rb = ks.count(), (ks.count() + 7) // 8
+        rows, sigs, coff = [], [], np.zeros(g + 1, dtype=np.uint64)
+        for i, cs in enumerate(contributions):
+            for row, sig in cs:
+                if not isinstance(row, (bytes, bytearray, memoryview)):
+                    r = bytearray(rb)
+                    for k in row:
+                        k = int(k)
+                        if k < 0 or k >= n:
+                            raise ValueError("a row names no key of the set")
+                        r[k >> 3] |= 1 << (k & 7)
+                    row = r
+                if len(row) != rb or len(sig) != 64:
+                    raise ValueError("a contribution is (row of %d bytes or key indices, 64 signature bytes)" % rb)
+                rows.append(bytes(row)); sigs.append(bytes(sig))
+            coff[i + 1] = len(rows)
+        nc = len(rows)
+        data, moff = pack_messages(msgs)
+        a, pa = _inbuf(b"".join(rows)); s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
+        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        r = np.zeros(max(rb * g, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
+        u = np.zeros((nc + 7) // 8 + 1, dtype=np.uint8); pu = u.ctypes.data_as(_u8p)
+        st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_keyset_merge_checked_batch(self._ctx, ks._h, pa, ps, coff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p),
+                                                                ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po, pr, pu, pst))
+        used = [[bool((u[t >> 3] >> (t & 7)) & 1) for t in range(int(coff[i]), int(coff[i + 1]))] for i in range(g)]
+        return o[:64 * g].tobytes(), r[:rb * g].tobytes(), used, st[:g].tobytes()
+
+    def keyset_merge_stats(self):
+        """dict: groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified
+        individually, groups that ended in ST_SHORT"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_merge_stats(self._ctx, o))
+        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_contributions": int(o[2]), "short_groups": int(o[3])}
+
     def aggregate_verify_batch(self, key_sets, msg_sets, agg_sigs, dst=DEFAULT_DST):
         """Many independent aggregate signatures in one call.  key_sets: list of byte strings (each a multiple of 128 bytes: the
         keys of one group); msg_sets: one list of messages per group, as many as the group has keys; agg_sigs: 64 bytes per group.

@@ -338,6 +338,49 @@ int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* ctx, const blsbn254_ke
         const uint8_t* dst, size_t dst_len,
         uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* n_groups*ceil(n_keys/8) */, uint8_t* status /* n_groups */);
 int blsbn254_keyset_aggregate_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* Checked merge of partial aggregates over a registered key set -- what an intermediate node of an aggregation tree calls: it
+ * receives PARTIAL AGGREGATES for one message, each an aggregate signature with the bitmap of the keys that are in it, and hands
+ * on one merged (aggregate, bitmap) pair without the bad contributions.  Group g is one message msgs[msg_off[g] .. msg_off[g + 1])
+ * with the contributions con_off[g] .. con_off[g + 1]: contribution s is the row rows[s * ceil(n_keys/8) ..] (bit i = key i is in
+ * it, LSB-first, as a row of sel) and the signature sigs[64 s ..].  con_off / msg_off: n_groups + 1 non-decreasing element / byte
+ * offsets, host arrays, which need not start at 0 (rows, sigs and msgs are indexed by them as given); the outputs and the bits
+ * of `used` are indexed from the first group and the first contribution of the call.
+ * BLSBN254_E_ARG (with a last_error text): NULL arguments, a key set of another context, decreasing offsets, n_groups above
+ * BLSBN254_CHUNK_LANES (4 Mi), more than 2^23 contributions, more than 2^30 bytes of rows, a row that sets a bit at an index
+ * >= n_keys; the outputs are then untouched and nothing was enqueued.  n_groups == 0 returns 0.  A bad contribution or group is
+ * never an error of the call.
+ * A contribution is a CANDIDATE when its signature decodes, is on the curve and is not the identity, its row is not empty, and
+ * every key its row selects has the KeyValidate bit blsbn254_keyset_valid reports (so a merged key sum is always in the
+ * r-torsion).  SELECTION is greedy, in the order given: a contribution is selected when it is a candidate and its row is disjoint
+ * from the union of the rows selected before it in its group.  The caller sets the priority by the order.  Everything else --
+ * overlapping contributions, duplicates, non-candidates -- is left out silently: it never fails its group and never causes the
+ * fallback.
+ * Optimistic attempt, once for all groups of the call (one pass of enqueued work): A_g = the sum of the selected signatures,
+ * row_g = the OR of the selected rows, and the equation of blsbn254_keyset_fast_aggregate_verify_batch on (row_g, msg_g, A_g).
+ * Where it holds: status[g] = 0, out_sigs[64 g ..] = A_g, row g of out_sel = row_g, and the bits of the selected contributions
+ * in `used`.  The check is of the SUM: contributions whose errors cancel in it (sigma_a + D, sigma_b - D) are both used, and the
+ * aggregate is correct.
+ * Fallback, only for the groups that selected something and failed the equation (repacked into one sub-call): EVERY candidate
+ * of the group, not only the selected ones, is verified on its own by the same equation on (its row, msg_g, its signature); then
+ * the same selection runs again with those bits as its mask -- once a bad contribution is gone, a later one that overlapped it
+ * becomes admissible -- and the one equation decides again: status 0 with the new selection, or BLSBN254_ST_SHORT.  The second
+ * check exists for kept rows whose keys sum to the identity (P and -P both registered).  A group without contributions, without a
+ * candidate or with nothing kept is BLSBN254_ST_SHORT too.  A short group's outputs are the identity encoding (0, 1), an all-zero
+ * row and no bit of `used`.
+ * With status 0: blsbn254_keyset_fast_aggregate_verify_batch sets the group's bit for (row of out_sel, msg, out_sigs) under the
+ * same dst, out_sigs is byte-identical to blsbn254_aggregate_sigs on the used signatures in order, and the row of out_sel is the
+ * OR of the used rows.  A group's outcome depends on its own inputs only: not on the attempt that served it, on launch
+ * boundaries or on its neighbours.  Pending asynchronous verify calls are settled on entry and none is left pending.  The groups
+ * of this call count in neither blsbn254_keyset_stats nor blsbn254_keyset_aggregate_stats; blsbn254_keyset_merge_stats, since the
+ * context was created: out[0] groups settled by the optimistic attempt, out[1] groups sent to the fallback, out[2] contributions
+ * verified individually, out[3] groups ending in BLSBN254_ST_SHORT. */
+int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint8_t* rows /* N*ceil(n_keys/8) */, const uint8_t* sigs /* N*64 */, const uint64_t* con_off /* n_groups+1 */,
+        const uint8_t* msgs, const uint64_t* msg_off /* n_groups+1, bytes */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len,
+        uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* n_groups*ceil(n_keys/8) */,
+        uint8_t* used /* ceil(N/8), bit s = contribution s of the call, LSB-first */, uint8_t* status /* n_groups */);
+int blsbn254_keyset_merge_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Mul<Scalar> for G1Projective (g1.rs:518-534, multiply :821-841) and G2Projective (g2.rs:866-886), element-wise:
  * out_i = [k_i] P_i.  Points uncompressed, scalars 32 bytes big-endian (scalar.rs:229-233) and < r.  A point that does not
  * decode or is off the curve returns BLSBN254_ERR_G1 / BLSBN254_ERR_G2, a scalar >= r BLSBN254_ERR_SCALAR (the reference's

@@ -477,6 +477,37 @@ pub fn keyset_aggregate_checked_batch(keys: &KeySet, entries: &[Vec<(u32, [u8; 6
     (0..n).map(|g| if status[g] == 0 { Some((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), sel[rb * g..rb * g + rb].to_vec())) } else { None }).collect()
 }
 
+/// What an intermediate node of an aggregation tree hands on (`blsbn254_keyset_merge_checked_batch`): `contributions[g]` =
+/// the partial aggregates received for `msgs[g]`, each a `(row, signature)` pair with a row of `ceil(keys.len() / 8)` bytes,
+/// in the order of their priority (kept).  Element g = `Some((merged signature, merged row, used flag per contribution))`,
+/// which `keyset_fast_aggregate_verify_batch` accepts for the message, or `None` when nothing usable is left
+/// (`BLSBN254_ST_SHORT`).  Selection is greedy over disjoint rows; bad contributions are left out, never an error.
+pub fn keyset_merge_checked_batch(keys: &KeySet, contributions: &[Vec<(Vec<u8>, [u8; 64])>], msgs: &[&[u8]], dst: &[u8]) -> Vec<Option<([u8; 64], Vec<u8>, Vec<bool>)>> {
+    assert_eq!(contributions.len(), msgs.len());
+    let n = msgs.len();
+    let rb = (keys.len() + 7) / 8;
+    let (mut rows, mut sg, mut coff) = (Vec::<u8>::new(), Vec::<u8>::new(), vec![0u64]);
+    for cs in contributions {
+        for (r, s) in cs {
+            assert_eq!(r.len(), rb, "a row is ceil(n_keys / 8) bytes");
+            rows.extend_from_slice(r); sg.extend_from_slice(s);
+        }
+        coff.push((sg.len() / 64) as u64);
+    }
+    let total = sg.len() / 64;
+    let (data, moff) = pack(msgs);
+    let (mut out, mut sel, mut used, mut status) = (vec![0u8; 64 * n], vec![0u8; rb * n], vec![0u8; (total + 7) / 8], vec![0u8; n]);
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_keyset_merge_checked_batch(c, keys.0, rows.as_ptr(), sg.as_ptr(), coff.as_ptr(), data.as_ptr(), moff.as_ptr(), n, dst.as_ptr(), dst.len(),
+                                                 out.as_mut_ptr(), sel.as_mut_ptr(), used.as_mut_ptr(), status.as_mut_ptr())
+    }))
+    .expect("a padding bit is set");
+    (0..n).map(|g| if status[g] == 0 {
+        let flags = (coff[g] as usize..coff[g + 1] as usize).map(|s| (used[s >> 3] >> (s & 7)) & 1 == 1).collect();
+        Some((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), sel[rb * g..rb * g + rb].to_vec(), flags))
+    } else { None }).collect()
+}
+
 // ---------------------------------------------------------------- N GPUs of one node
 
 /// All GPUs named in `BLSBN254_DEVICES` (comma-separated HIP ordinals, default "0"): one context and one host thread per
