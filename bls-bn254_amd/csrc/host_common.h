@@ -19,6 +19,7 @@
 #include "seg_plan.h"    // SegLevel, SegLaunch, the planners of the segmented reductions
 #include "keyset_agg_plan.h"   // KaRepack, the argument walk of the checked aggregation over a key set
 #include "keyset_merge_plan.h" // KmRepack, the argument walk of the checked merge over a key set
+#include "keyset_weight_plan.h" // KwRepack, the column-total check and the quorum rule of the weights over a key set
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -128,6 +129,16 @@ struct BNH KmWs {
   std::vector<uint64_t> s_moff, s_emoff;
   std::vector<size_t> fail;
 };
+// stake weights by bitmap and the verify with a quorum over a registered key set (host_keyset_weight.hip, k_keyset_weight.hip):
+// the groups' weights of a call; host side the key-major table a blsbn254_keyset_set_weights uploads, the row that selects every
+// key (the totals are its weights), the groups that reach quorum and their sub-call (keyset_weight_plan.h KwRepack) with its bits
+struct BNH KwWs {
+  DevBuf out;
+  KwRepack sub;
+  std::vector<uint64_t> h_tab;
+  std::vector<uint8_t> h_ones, h_bits;
+  std::vector<size_t> reach;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -207,7 +218,9 @@ struct blsbn254_ctx {
   KsetWs kset;
   KaggWs kagg;
   KmWs kmrg;
+  KwWs kw;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
+  uint64_t stat_kw[4] = {0, 0, 0, 0};    // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
   uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
   uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
@@ -333,8 +346,15 @@ struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok;
 // a registered key set (host_keyset.hip): the keys as affine limb-major rows (36 x n limbs), the bad / skip words (keyset.h), the
 // total of the non-skipped keys (54 limbs), KeyValidate per key (bytes), the encodings as they were uploaded (128 B per key: the
 // per-signature fallback of host_keyset_agg.hip gathers its keys from them), the KeyValidate bits packed into a word per 32 keys
-// (bits past the last key 0: the selection of host_keyset_merge.hip tests a row's words against them)
-struct blsbn254_keyset { blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid, enc, vwords; };
+// (bits past the last key 0: the selection of host_keyset_merge.hip tests a row's words against them).  A set registered with
+// proofs of possession (checked): the bits of the proofs' verification, which the registration folds into bad / skip / valid.
+// The stake table (host_keyset_weight.hip; n_cols == 0: none): key-major, weff[i * n_cols + q] = column q of key i (the kernel
+// masks every row with vwords, so a key without the KeyValidate bit weighs 0), and the columns' totals of the effective weights
+struct blsbn254_keyset {
+  blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid, enc, vwords;
+  bool checked = false; DevBuf pop;
+  size_t n_cols = 0; DevBuf weff; uint64_t wtotal[BLSBN254_KS_MAX_COLS] = {};
+};
 
 // ---- internal helpers shared between the units (defined in the unit named on the right)
 BNH int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len);   // host.hip
@@ -381,6 +401,11 @@ BNH int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uin
 // the sums of n_groups rows ALREADY ON THE DEVICE (ceil(k->n / 8) bytes each) over the key set k into c->gs_sum / c->gs_sum_ok,
 // the flip bytes into c->kset.h_flip (enqueued); *launches: launches of the word kernel
 BNH int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* d_rows, size_t n_groups, size_t* launches);   // host_keyset.hip
+// the argument checks the calls over rows share (n_groups > 0): the limit, and no row may set a bit that names no key
+BNH int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups);   // host_keyset.hip
+// blsbn254_keyset_fast_aggregate_verify_batch behind its argument checks and ENTER; sel == nullptr: the rows are in c->kset.sel already
+BNH int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs,
+                       size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);   // host_keyset.hip
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip

@@ -12,7 +12,13 @@ static const size_t KS_LAUNCH_ITEMS = (size_t)1 << 20;      // word partials of 
 static const size_t KS_RUN_ITEMS = 16;                      // keyset.h KS_RUN
 static inline size_t ks_nwords(size_t n) { return (n + 31) / 32; }
 
-int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, blsbn254_keyset** out) {
+// The registration, with proofs of possession or without (proofs == nullptr: nothing below differs from a registration that
+// never heard of them).  With proofs the pipeline of blsbn254_pop_verify_batch runs FIRST, on the staged keys and proofs: it owns
+// the context's staging buffers while it runs and leaves in_a, the staged keys, as they were.  Its bits are kept on the handle
+// and make a failing key bad (k_ks_register); for the total the same kernel overwrites the STAGED copy of such a key with an
+// encoding that does not decode, after the handle's copy of the encodings was taken: enc keeps the bytes as uploaded.
+static int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
+                     blsbn254_keyset** out) {
   if (!c || !out) return BLSBN254_E_ARG;
   *out = nullptr;
   if (!pks || n_keys == 0) return BLSBN254_E_ARG;
@@ -26,9 +32,21 @@ int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, b
   HIPCHK(c, k->aff.reserve(36 * n_keys * 4)); HIPCHK(c, k->bad.reserve(W * 4)); HIPCHK(c, k->skip.reserve(W * 4));
   HIPCHK(c, k->total.reserve(54 * 4)); HIPCHK(c, k->valid.reserve(n_keys)); HIPCHK(c, c->sub_ok.reserve(n_keys)); HIPCHK(c, k->enc.reserve(128 * n_keys));
   TRY(upload(c, c->in_a, pks, 128 * n_keys));
+  if (proofs) {
+    const size_t nb = (n_keys + 7) / 8;
+    HIPCHK(c, k->pop.reserve(nb + 8)); HIPCHK(c, c->in_off.reserve(8 * (n_keys + 1))); HIPCHK(c, c->bitmap.reserve(nb + 8));
+    TRY(upload(c, c->in_b, proofs, 64 * n_keys));
+    TRY(launch(c, c->stream, "iota_off", grid_lanes(n_keys + 1), k_iota_off, (uint64_t*)c->in_off.p, n_keys, (uint64_t)128));
+    TRY(blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_a.p, (const uint64_t*)c->in_off.p,
+                                                (const uint8_t*)c->in_b.p, n_keys, pop_dst, pop_dst_len, (uint8_t*)c->bitmap.p));
+    HIPCHK(c, hipMemcpyAsync(k->pop.p, c->bitmap.p, nb, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, c->sub_ok.reserve(n_keys));                  // the pipeline above may have grown it for a size of its own
+    k->checked = true;
+  }
+  const uint8_t* mask = proofs ? (const uint8_t*)k->pop.p : nullptr;
   HIPCHK(c, hipMemcpyAsync(k->enc.p, c->in_a.p, 128 * n_keys, hipMemcpyDeviceToDevice, c->stream));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(n_keys), k_g2_check, (const uint8_t*)c->in_a.p, n_keys, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
-  TRY(launch(c, c->stream, "ks_register", grid_lanes(n_keys), k_ks_register, (const uint8_t*)c->in_a.p, (uint32_t)n_keys, (const uint8_t*)c->sub_ok.p,
+  TRY(launch(c, c->stream, "ks_register", grid_lanes(n_keys), k_ks_register, (uint8_t*)c->in_a.p, (uint32_t)n_keys, (const uint8_t*)c->sub_ok.p, mask,
              (int32_t*)k->aff.p, (uint32_t*)k->bad.p, (uint32_t*)k->skip.p, (uint8_t*)k->valid.p));
   // the total: k_g2_load stores a bad key as the identity, and adding an identity key changes nothing, so the sum of ALL the
   // encodings is the sum of the non-skipped keys (the flag of that sum is not looked at)
@@ -47,6 +65,16 @@ int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, b
   *out = k;
   return 0;
 }
+int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, blsbn254_keyset** out) {
+  return ks_create(c, pks, nullptr, n_keys, nullptr, 0, out);
+}
+int blsbn254_keyset_create_checked(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
+                                   blsbn254_keyset** out) {
+  if (out) *out = nullptr;
+  if (!proofs || (pop_dst_len && !pop_dst)) return BLSBN254_E_ARG;
+  return ks_create(c, pks, proofs, n_keys, pop_dst, pop_dst_len, out);
+}
+int blsbn254_keyset_checked(const blsbn254_keyset* k) { return k && k->checked ? 1 : 0; }
 void blsbn254_keyset_destroy(blsbn254_keyset* k) {
   if (!k) return;
   (void)hipSetDevice(k->ctx->device);
@@ -63,8 +91,8 @@ int blsbn254_keyset_valid(blsbn254_ctx* c, const blsbn254_keyset* k, uint8_t* ok
   return download(c, ok_bitmap, c->bitmap.p, (k->n + 7) / 8);
 }
 
-// the argument checks the two calls share (n_groups > 0): the limit, and no row may set a bit that names no key
-static int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups) {
+// the argument checks the calls over rows share (n_groups > 0): the limit, and no row may set a bit that names no key
+int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups) {
   if (n_groups > c->chunk) { c->last_error = "more groups than one launch chunk"; return BLSBN254_E_ARG; }
   const size_t rb = (k->n + 7) / 8;
   if (k->n & 7) {
@@ -136,13 +164,10 @@ int blsbn254_keyset_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const u
   return 0;
 }
 
-// bit g = blsbn254_fast_aggregate_verify_batch on the selected keys of row g: from the sums on, the same pipeline
-int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off,
-                                                const uint8_t* sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
-  if (!c || !k || k->ctx != c || !off || (n_groups && (!sel || !sigs || !valid_bitmap)) || (dst_len && !dst)) return BLSBN254_E_ARG;
-  if (n_groups == 0) return 0;
-  TRY(ks_args(c, k, sel, n_groups));
-  ENTER(c);
+// bit g = blsbn254_fast_aggregate_verify_batch on the selected keys of row g: from the sums on, the same pipeline.  sel == nullptr:
+// the rows are staged in c->kset.sel already (the verify with a quorum has weighed them there)
+int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n_groups,
+                   const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
   uint32_t dl;
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off, n_groups));
@@ -150,7 +175,8 @@ int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_
   HIPCHK(c, c->gs_pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve(nb + 8));
   TRY(upload(c, c->in_b, sigs, 64 * n_groups));
   size_t launches;
-  TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
+  if (sel) TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
+  else TRY(ks_enqueue_sums_dev(c, k, (const uint8_t*)c->kset.sel.p, n_groups, &launches));
   TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
              (uint8_t*)c->gs_pk.p, 1));
   TRY(verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
@@ -158,6 +184,14 @@ int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_
   TRY(download(c, valid_bitmap, c->bitmap.p, nb));
   ks_tally(c, n_groups, launches);
   return 0;
+}
+int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off,
+                                                const uint8_t* sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+  if (!c || !k || k->ctx != c || !off || (n_groups && (!sel || !sigs || !valid_bitmap)) || (dst_len && !dst)) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  TRY(ks_args(c, k, sel, n_groups));
+  ENTER(c);
+  return ks_verify_rows(c, k, sel, msgs, off, sigs, n_groups, dst, dst_len, valid_bitmap);
 }
 
 int blsbn254_keyset_stats(blsbn254_ctx* c, uint64_t out[4]) {

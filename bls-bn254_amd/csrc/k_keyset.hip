@@ -1,5 +1,8 @@
 // k_keyset.hip -- sums over a registered key set selected by bitmaps (keyset.h has the lane functions and the layout):
-//   k_ks_register    one lane per key, once per key set: affine rows, the bad / skip words (by ballot), KeyValidate bytes
+//   k_ks_register    one lane per key, once per key set: affine rows, the bad / skip words (by ballot), KeyValidate bytes; with a
+//                    mask (the bits of the proofs of possession) a key whose bit is 0 is BAD as one that does not decode, and
+//                    the lane stores an undecodable encoding over ITS key in the staged copy it read, so that the total (a
+//                    segmented sum over the staged encodings, which loads a bad key as the identity) leaves the key out
 //   k_ks_count       one lane per group: flip and ok of its row
 //   k_ks_word_sum    the hot kernel: grid (ceil(G / 256), W), a workgroup is ONE 32-key word across 256 consecutive groups.  The
 //                    word's keys are staged into LDS once (36 x 32 limbs, 4.6 KB, [limb][32]: for a fixed limb the 32 keys sit
@@ -13,12 +16,14 @@
 #include "kernels.h"
 using namespace bn;
 
-BN_KERNEL k_ks_register(const uint8_t* pks, uint32_t n_keys, const uint8_t* sub_ok, int32_t* aff, uint32_t* bad, uint32_t* skip, uint8_t* valid) {
+BN_KERNEL k_ks_register(uint8_t* pks, uint32_t n_keys, const uint8_t* sub_ok, const uint8_t* mask, int32_t* aff, uint32_t* bad, uint32_t* skip, uint8_t* valid) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool b = false, s = false;
   if (i < n_keys) {
     const KsKey k = ks_register(pks + 128 * (size_t)i);
-    b = k.bad; s = k.skip;
+    const bool pass = ks_mask_bit(mask, i);
+    b = k.bad | !pass; s = k.skip | !pass;
+    if (!pass) ks_blank_enc(pks + 128 * (size_t)i);
     ks_store_aff(aff + i, n_keys, k.p);
     valid[i] = (sub_ok[i] && !s) ? 1 : 0;
   }

@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) k_tc_select(const uint8_t* bits_a, const 
 __global__ void __launch_bounds__(256) k_tc_gather_c0(const uint32_t* commitments, const uint32_t* coff, const uint32_t* goff, size_t n_groups, uint32_t* gstat,
                                                      uint32_t* keys);
 // sums over a registered key set selected by bitmaps (k_keyset.hip)
-BN_KERNEL k_ks_register(const uint8_t* pks, uint32_t n_keys, const uint8_t* sub_ok, int32_t* aff, uint32_t* bad, uint32_t* skip, uint8_t* valid);
+BN_KERNEL k_ks_register(uint8_t* pks, uint32_t n_keys, const uint8_t* sub_ok, const uint8_t* mask, int32_t* aff, uint32_t* bad, uint32_t* skip, uint8_t* valid);
 BN_KERNEL k_ks_count(const uint8_t* sel, size_t G, uint32_t n_keys, const uint32_t* bad, uint8_t* flip, uint8_t* ok);
 BN_KERNEL k_ks_word_sum(const int32_t* aff, uint32_t n_keys, const uint32_t* skip, const uint8_t* sel, const uint8_t* flip, size_t G,
                         int32_t* out, size_t out_stride);
@@ -178,6 +178,9 @@ BN_KERNEL k_km_sig(const uint8_t* sigs, size_t m, uint32_t lo, size_t N, uint8_t
 __global__ void __launch_bounds__(256) k_km_select(const uint8_t* rows, const uint8_t* sig_ok, const uint8_t* mask, const uint32_t* goff, const uint32_t* valid,
                                                   uint32_t n_keys, size_t g_lo, size_t m, uint8_t* flags, uint8_t* urows);
 BN_KERNEL k_km_points(const uint8_t* flags, size_t m, uint32_t lo, size_t N, int32_t* pts, uint8_t* used, uint8_t* cand);
+// stake weights over a registered key set selected by bitmaps (k_keyset_weight.hip)
+__global__ void __launch_bounds__(256) k_ks_weight(const uint8_t* rows, const uint32_t* vwords, const uint64_t* tab, uint32_t n_keys, uint32_t n_cols, size_t g_lo,
+                                                  size_t m, uint64_t* out);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

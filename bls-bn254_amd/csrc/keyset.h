@@ -65,6 +65,13 @@ BN_INL KsCount ks_count(const uint8_t* row, uint32_t n_keys, const uint32_t* bad
 }
 BN_INL uint32_t ks_word_mask(uint32_t word, bool flip, uint32_t skip, uint32_t tail) { return (flip ? ~word : word) & ~skip & tail; }
 
+// registration with proofs of possession: bit i of mask (LSB-first) = the proof of key i verifies; no mask: every key passes
+BN_INL bool ks_mask_bit(const uint8_t* mask, uint32_t i) { return mask ? ((mask[i >> 3] >> (i & 7)) & 1u) != 0 : true; }
+// an encoding that does not decode (every coordinate >= p) over a staged key; the staging buffer is 16-byte aligned
+BN_INL void ks_blank_enc(uint8_t* pk) {
+  uint32_t* w = (uint32_t*)pk;
+  for (int j = 0; j < 32; ++j) w[j] = 0xffffffffu;
+}
 // registration: a key's affine coordinates and its two bits.  A skipped key's row is never read back.
 struct KsKey { G2A p; bool bad, skip; };
 BN_FUNC KsKey ks_register(const uint8_t* pk) {

@@ -458,6 +458,40 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_stats(self._ctx, o))
         return {"groups": int(o[0]), "complement_groups": int(o[1]), "launches": int(o[2]), "key_sets": int(o[3])}
 
+    def keyset_weight_batch(self, ks, sel_rows):
+        """The stake each row of bitmaps selects from a KeySet with weights (KeySet.set_weights): an (n_groups, n_cols) uint64
+        array, entry (g, q) = the sum of column q over the selected keys that have the KeyValidate bit.  Exact."""
+        sel, g = self._keyset_rows(ks, sel_rows)
+        nc = ks.n_cols
+        a, pa = _inbuf(sel); out = np.zeros(max(g * nc, 1), dtype=np.uint64)
+        self._chk(self._lib.blsbn254_keyset_weight_batch(self._ctx, ks._h, pa, ctypes.c_size_t(g), out.ctypes.data_as(_u64p)))
+        return out[:g * nc].reshape(g, nc)
+
+    def keyset_quorum_verify_batch(self, ks, sel_rows, msgs, sigs, min_weight, dst=DEFAULT_DST):
+        """keyset_fast_aggregate_verify_batch with a quorum: min_weight holds one minimum per stake column of the KeySet (0
+        switches a column off).  Returns (bitmap, weights): bit g is set when row g carries at least the minimum in every column
+        AND its aggregate verifies; weights is what keyset_weight_batch gives, for every group.  The groups are weighed first,
+        and only those that reach the quorum are summed and paired."""
+        sel, g = self._keyset_rows(ks, sel_rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        nc = ks.n_cols
+        mw = np.ascontiguousarray(min_weight, dtype=np.uint64).reshape(-1)
+        if mw.size != nc:
+            raise ValueError("one minimum per weight column")
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(sel); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        wout = np.zeros(max(g * nc, 1), dtype=np.uint64)
+        self._chk(self._lib.blsbn254_keyset_quorum_verify_batch(self._ctx, ks._h, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(g), pd,
+                                                                ctypes.c_size_t(len(dst)), mw.ctypes.data_as(_u64p), wout.ctypes.data_as(_u64p), po))
+        return o[:(g + 7) // 8].tobytes(), wout[:g * nc].reshape(g, nc)
+
+    def keyset_weight_stats(self):
+        """dict: groups weighed, groups below quorum (neither summed nor paired), launches of the weight kernel, weight tables set"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_weight_stats(self._ctx, o))
+        return {"groups": int(o[0]), "below_quorum": int(o[1]), "launches": int(o[2]), "tables": int(o[3])}
+
     def keyset_aggregate_checked_batch(self, ks, entry_sets, msgs, dst=DEFAULT_DST):
         """The collecting node's call: entry_sets[g] = the signatures received for msgs[g], a list of (key index, 64-byte
         signature) pairs or a dict {index: signature} over the registered KeySet (sorted by index here; a repeated index raises
@@ -927,15 +961,48 @@ class PreparedKeys:
 
 class KeySet:
     """blsbn254_keyset: n_keys public keys registered once on the engine's GPU (decoded, curve-checked, with their total), to be
-    summed by participation bitmaps (Engine.keyset_sum_batch, Engine.keyset_fast_aggregate_verify_batch)."""
+    summed by participation bitmaps (Engine.keyset_sum_batch, Engine.keyset_fast_aggregate_verify_batch).  With proofs (n_keys x
+    64 bytes, as pop_prove_batch makes them) every key's proof of possession is verified under pop_dst at registration, and a
+    key whose proof fails is a bad key of the set, as one that does not decode."""
 
-    def __init__(self, engine, pks, n_keys):
+    def __init__(self, engine, pks, n_keys, proofs=None, pop_dst=POP_DST):
         self._eng = engine
         self._lib = engine._lib
         self._lib.blsbn254_keyset_count.restype = ctypes.c_size_t
         self._h = ctypes.c_void_p()
+        self.n_cols = 0
         a, pa = _inbuf(pks, 128 * n_keys)
-        engine._chk(self._lib.blsbn254_keyset_create(engine._ctx, pa, ctypes.c_size_t(n_keys), ctypes.byref(self._h)))
+        if proofs is None:
+            engine._chk(self._lib.blsbn254_keyset_create(engine._ctx, pa, ctypes.c_size_t(n_keys), ctypes.byref(self._h)))
+        else:
+            b, pb = _inbuf(proofs, 64 * n_keys); d, pd = _inbuf(pop_dst)
+            engine._chk(self._lib.blsbn254_keyset_create_checked(engine._ctx, pa, pb, ctypes.c_size_t(n_keys), pd, ctypes.c_size_t(len(pop_dst)),
+                                                                 ctypes.byref(self._h)))
+
+    def checked(self):
+        """True for a set registered with proofs of possession"""
+        return bool(self._lib.blsbn254_keyset_checked(self._h))
+
+    def set_weights(self, columns):
+        """columns: 1 to 8 stake columns of n_keys unsigned 64-bit entries each (a list of sequences, or an (n_cols, n_keys)
+        array).  Replaces an earlier table.  A column whose sum does not fit 64 bits raises Bn254Error and changes nothing."""
+        cols = [[int(v) for v in col] for col in columns]
+        n = self.count()
+        if any(len(col) != n for col in cols):
+            raise ValueError("a weight column must have %d entries" % n)
+        if any(v < 0 or v >> 64 for col in cols for v in col):
+            raise ValueError("a weight must fit 64 bits")
+        w = np.array(cols, dtype=np.uint64).reshape(-1)
+        if w.size == 0:
+            w = np.zeros(1, dtype=np.uint64)
+        self._eng._chk(self._lib.blsbn254_keyset_set_weights(self._eng._ctx, self._h, w.ctypes.data_as(_u64p), ctypes.c_size_t(len(cols))))
+        self.n_cols = len(cols)
+
+    def total_weight(self):
+        """the columns' sums over the keys that have the KeyValidate bit: a list of n_cols ints"""
+        o = (ctypes.c_uint64 * 8)()
+        self._eng._chk(self._lib.blsbn254_keyset_total_weight(self._eng._ctx, self._h, o))
+        return [int(o[q]) for q in range(self.n_cols)]
 
     def count(self):
         return int(self._lib.blsbn254_keyset_count(self._h))

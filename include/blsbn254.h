@@ -381,6 +381,51 @@ int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* ctx, const blsbn254_keyset
         uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* n_groups*ceil(n_keys/8) */,
         uint8_t* used /* ceil(N/8), bit s = contribution s of the call, LSB-first */, uint8_t* status /* n_groups */);
 int blsbn254_keyset_merge_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* A key set registered WITH proofs of possession, stake weights on the handle, and FastAggregateVerify with a quorum -- what a
+ * proof-of-stake verifier decides is not "does this aggregate verify" but "does a verifying aggregate carry the quorum's stake".
+ * blsbn254_keyset_create_checked: blsbn254_keyset_create with one proof per key, proof i checked exactly as
+ * blsbn254_pop_verify_batch checks (pk_i, proof_i) under pop_dst.  A key whose proof fails becomes a BAD key of the handle, in
+ * every respect like a key that does not decode: its blsbn254_keyset_valid bit is 0, it is left out of the total, a row that
+ * selects it gets status 0 from blsbn254_keyset_sum_batch and is invalid in blsbn254_keyset_fast_aggregate_verify_batch, and it
+ * is never a candidate of the checked aggregation or merge.  A failing proof is never an error of the registration.  Argument
+ * errors: those of blsbn254_keyset_create, and NULL proofs (or a NULL pop_dst with pop_dst_len > 0).  blsbn254_keyset_checked:
+ * 1 for a handle created with proofs, else 0.  With proofs that all hold, every call on the handle gives the bytes it gives on
+ * the handle blsbn254_keyset_create makes of the same keys.
+ * blsbn254_keyset_set_weights: n_cols (1 .. BLSBN254_KS_MAX_COLS) stake columns, weights[q * n_keys + i] = column q of key i,
+ * one column per quorum.  Calling again replaces the table (a stake change per epoch needs no new registration).  A column whose
+ * sum over ALL n_keys entries does not fit 64 bits is BLSBN254_E_ARG with a last_error text, and nothing is changed: no later
+ * sum can overflow.  The EFFECTIVE weight of a key without the blsbn254_keyset_valid bit is 0 (applied on the device, from the bits):
+ * an identity key changes no key sum, so under plain arithmetic it could be selected in a verifying aggregate and lend it its
+ * stake.  blsbn254_keyset_total_weight: the columns' sums of the effective weights.  A handle without a table has no columns:
+ * blsbn254_keyset_total_weight and the two calls below return BLSBN254_E_ARG for it.
+ * blsbn254_keyset_weight_batch: rows and argument checks as blsbn254_keyset_sum_batch; out[g * n_cols + q] = the sum of the
+ * effective weights of column q over the set bits of row g, exact; an empty row gives 0.  One wave per row on the device.  The
+ * rows blsbn254_keyset_aggregate_checked_batch / blsbn254_keyset_merge_checked_batch hand out in out_sel are rows of this call.
+ * blsbn254_keyset_quorum_verify_batch: the arguments of blsbn254_keyset_fast_aggregate_verify_batch and ONE rule per call,
+ * min_weight[q] per column.  Group g REACHES QUORUM when weights_out[g * n_cols + q] >= min_weight[q] for every column (a
+ * minimum of 0 switches a column off).  Bit g of valid_bitmap is set when the group reaches quorum AND bit g of
+ * blsbn254_keyset_fast_aggregate_verify_batch on the same inputs is set.  weights_out = what blsbn254_keyset_weight_batch
+ * gives, always filled for every group: the caller reads the reason for a 0 bit from it.  The weights are computed and read
+ * back FIRST (one small synchronisation); only the groups that reach quorum are then summed and paired, repacked by the host
+ * into one sub-call where some do not; where none does, nothing more is launched.  A group's outcome depends on its own inputs
+ * only.  Argument errors as blsbn254_keyset_fast_aggregate_verify_batch, plus NULL min_weight / weights_out, decreasing message
+ * offsets and a handle without a table.  Pending asynchronous verify calls are settled on entry.  blsbn254_keyset_stats counts
+ * only the groups that were summed.  blsbn254_keyset_weight_stats, since the context was created: out[0] groups weighed (by the
+ * two calls), out[1] groups below quorum (not summed, not paired), out[2] launches of the weight kernel for them, out[3] tables
+ * set. */
+#define BLSBN254_KS_MAX_COLS 8
+int blsbn254_keyset_create_checked(blsbn254_ctx* ctx, const uint8_t* pks /* n_keys*128 */, const uint8_t* proofs /* n_keys*64 */,
+                                   size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len, blsbn254_keyset** out);
+int blsbn254_keyset_checked(const blsbn254_keyset* keys);
+int blsbn254_keyset_set_weights(blsbn254_ctx* ctx, blsbn254_keyset* keys, const uint64_t* weights /* n_cols*n_keys */, size_t n_cols);
+int blsbn254_keyset_total_weight(blsbn254_ctx* ctx, const blsbn254_keyset* keys, uint64_t* out /* n_cols */);
+int blsbn254_keyset_weight_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* sel, size_t n_groups,
+                                 uint64_t* out /* n_groups*n_cols */);
+int blsbn254_keyset_quorum_verify_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* sel,
+        const uint8_t* msgs, const uint64_t* off /* n_groups+1 */, const uint8_t* sigs /* n_groups*64 */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len, const uint64_t* min_weight /* n_cols */,
+        uint64_t* weights_out /* n_groups*n_cols */, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_keyset_weight_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Mul<Scalar> for G1Projective (g1.rs:518-534, multiply :821-841) and G2Projective (g2.rs:866-886), element-wise:
  * out_i = [k_i] P_i.  Points uncompressed, scalars 32 bytes big-endian (scalar.rs:229-233) and < r.  A point that does not
  * decode or is off the curve returns BLSBN254_ERR_G1 / BLSBN254_ERR_G2, a scalar >= r BLSBN254_ERR_SCALAR (the reference's

@@ -398,8 +398,8 @@ pub fn multi_miller_loop_prepared(keys: &PreparedKeys, terms: &[(&G1Affine, u32)
 
 /// A committee's public keys, resident on the GPU (`blsbn254_keyset`): decoded and curve-checked once, then summed per
 /// aggregate by a participation bitmap (`ceil(n/8)` bytes per row, bit i LSB-first = key i signed).  Tied to the process-wide
-/// engine context.
-pub struct KeySet(*mut ffi::KeySet);
+/// engine context.  The second field is the number of stake columns set by `set_weights` (0: none).
+pub struct KeySet(*mut ffi::KeySet, usize);
 unsafe impl Send for KeySet {}
 
 impl KeySet {
@@ -407,7 +407,36 @@ impl KeySet {
         let flat: Vec<u8> = pks.iter().flatten().copied().collect();
         let mut h: *mut ffi::KeySet = core::ptr::null_mut();
         with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_create(c, flat.as_ptr(), pks.len(), &mut h) })).expect("an empty key set, or a device error");
-        KeySet(h)
+        KeySet(h, 0)
+    }
+    /// The same with one proof of possession per key (`blsbn254_keyset_create_checked`), verified under `pop_dst` as
+    /// `pop_verify_batch` verifies it: a key whose proof fails is a bad key of the set, as one that does not decode.
+    pub fn new_checked(pks: &[[u8; 128]], proofs: &[[u8; 64]], pop_dst: &[u8]) -> Self {
+        assert_eq!(pks.len(), proofs.len());
+        let flat: Vec<u8> = pks.iter().flatten().copied().collect();
+        let pf: Vec<u8> = proofs.iter().flatten().copied().collect();
+        let mut h: *mut ffi::KeySet = core::ptr::null_mut();
+        with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_create_checked(c, flat.as_ptr(), pf.as_ptr(), pks.len(), pop_dst.as_ptr(), pop_dst.len(), &mut h) }))
+            .expect("an empty key set, or a device error");
+        KeySet(h, 0)
+    }
+    pub fn checked(&self) -> bool { unsafe { ffi::blsbn254_keyset_checked(self.0) == 1 } }
+    /// 1 to 8 stake columns of `len()` entries each (`blsbn254_keyset_set_weights`); replaces an earlier table.  `Err`: a
+    /// column whose sum does not fit 64 bits, and nothing is changed.  A key without the `valid()` bit weighs 0.
+    pub fn set_weights(&mut self, columns: &[&[u64]]) -> Result<(), Bn254Error> {
+        assert!(columns.iter().all(|col| col.len() == self.len()));
+        let flat: Vec<u64> = columns.iter().flat_map(|col| col.iter().copied()).collect();
+        with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_set_weights(c, self.0, flat.as_ptr(), columns.len()) }))?;
+        self.1 = columns.len();
+        Ok(())
+    }
+    pub fn cols(&self) -> usize { self.1 }
+    /// The columns' sums over the keys that have the `valid()` bit.
+    pub fn total_weight(&self) -> Vec<u64> {
+        let mut out = vec![0u64; 8];
+        with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_total_weight(c, self.0, out.as_mut_ptr()) })).expect("no weights set");
+        out.truncate(self.1);
+        out
     }
     pub fn len(&self) -> usize { unsafe { ffi::blsbn254_keyset_count(self.0) } }
     /// KeyValidate per registered key (decodes, not the identity, on the curve, in the r-torsion): for the registrar.
@@ -449,6 +478,36 @@ pub fn keyset_fast_aggregate_verify_batch(keys: &KeySet, rows: &[&[u8]], msgs: &
     }))
     .expect("a padding bit is set");
     bits(&bm, n)
+}
+
+/// The stake each row selects (`blsbn254_keyset_weight_batch`): element g = one sum per column of the set's table.
+pub fn keyset_weight_batch(keys: &KeySet, rows: &[&[u8]]) -> Vec<Vec<u64>> {
+    let (n, nc) = (rows.len(), keys.cols());
+    let sel: Vec<u8> = rows.iter().flat_map(|r| r.iter().copied()).collect();
+    assert_eq!(sel.len(), n * ((keys.len() + 7) / 8));
+    let mut out = vec![0u64; n * nc];
+    with_ctx(|c| check(unsafe { ffi::blsbn254_keyset_weight_batch(c, keys.0, sel.as_ptr(), n, out.as_mut_ptr()) })).expect("no weights set, or a padding bit is set");
+    out.chunks(nc.max(1)).take(n).map(|w| w.to_vec()).collect()
+}
+
+/// `keyset_fast_aggregate_verify_batch` with a quorum (`blsbn254_keyset_quorum_verify_batch`): element g = (the group carries
+/// at least `min_weight[q]` in every column AND its aggregate verifies, its weights).  Groups below the quorum are neither
+/// summed nor paired.
+pub fn keyset_quorum_verify_batch(keys: &KeySet, rows: &[&[u8]], msgs: &[&[u8]], sigs: &[[u8; 64]], dst: &[u8], min_weight: &[u64]) -> Vec<(bool, Vec<u64>)> {
+    assert!(rows.len() == msgs.len() && msgs.len() == sigs.len() && min_weight.len() == keys.cols());
+    let (n, nc) = (rows.len(), keys.cols());
+    let sel: Vec<u8> = rows.iter().flat_map(|r| r.iter().copied()).collect();
+    assert_eq!(sel.len(), n * ((keys.len() + 7) / 8));
+    let (data, off) = pack(msgs);
+    let sg: Vec<u8> = sigs.iter().flatten().copied().collect();
+    let mut bm = vec![0u8; (n + 7) / 8];
+    let mut w = vec![0u64; n * nc];
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_keyset_quorum_verify_batch(c, keys.0, sel.as_ptr(), data.as_ptr(), off.as_ptr(), sg.as_ptr(), n, dst.as_ptr(), dst.len(), min_weight.as_ptr(),
+                                                 w.as_mut_ptr(), bm.as_mut_ptr())
+    }))
+    .expect("no weights set, or a padding bit is set");
+    bits(&bm, n).into_iter().zip(w.chunks(nc.max(1))).map(|(b, x)| (b, x.to_vec())).collect()
 }
 
 /// What the node that collects a committee's individual signatures hands on (`blsbn254_keyset_aggregate_checked_batch`):
