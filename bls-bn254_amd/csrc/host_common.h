@@ -20,6 +20,7 @@
 #include "keyset_agg_plan.h"   // KaRepack, the argument walk of the checked aggregation over a key set
 #include "keyset_merge_plan.h" // KmRepack, the argument walk of the checked merge over a key set
 #include "keyset_weight_plan.h" // KwRepack, the column-total check and the quorum rule of the weights over a key set
+#include "keyset_committee_plan.h" // KcTable, KcPlan: the committee tables of a key set and the plan of a call over them
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -139,6 +140,19 @@ struct BNH KwWs {
   std::vector<uint8_t> h_ones, h_bits;
   std::vector<size_t> reach;
 };
+// committees over a registered key set (host_keyset_committee.hip, k_keyset_committee.hip): the call's rows; per sorted group its
+// committee, row offset, partial base and caller's group; the items; the flip / ok bytes; the group-major partials of a launch
+// with their (constant 1) flags; the reduced sums by sorted position with theirs; the levels between them; the committee of every
+// committee word of a table being set; the weights of a call.  Host side: the plan (its vectors are what the uploads read), the
+// flip bytes a call downloads, and the rows, offsets and committees of the call that sums a new table's totals.
+struct BNH KcWs {
+  DevBuf sel, scom, srow, spbase, order, items, flip, ok, part, part_ok, u, u_ok, wcom, wout;
+  SegWs seg;
+  KcPlan plan;
+  std::vector<uint8_t> h_flip, h_ones;
+  std::vector<uint64_t> h_off;
+  std::vector<uint32_t> h_com;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -219,8 +233,10 @@ struct blsbn254_ctx {
   KaggWs kagg;
   KmWs kmrg;
   KwWs kw;
+  KcWs kcom;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
   uint64_t stat_kw[4] = {0, 0, 0, 0};    // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
+  uint64_t stat_kc[4] = {0, 0, 0, 0};    // committee calls: groups served, groups summed through the complement, launches of the word kernel, committee tables set
   uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
   uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
@@ -350,10 +366,24 @@ struct blsbn254_g2prepared { blsbn254_ctx* ctx; size_t u; DevBuf table, raw, ok;
 // proofs of possession (checked): the bits of the proofs' verification, which the registration folds into bad / skip / valid.
 // The stake table (host_keyset_weight.hip; n_cols == 0: none): key-major, weff[i * n_cols + q] = column q of key i (the kernel
 // masks every row with vwords, so a key without the KeyValidate bit weighs 0), and the columns' totals of the effective weights
+// The committee table (host_keyset_committee.hip; no committees: none): the members' key indices, the committees as the kernels
+// read them (KcCom), per committee word the bad / skip / valid bits of its members (keyset_committee.h), per committee the total
+// of its non-skipped members (54 limbs, limb-major with stride n_com); the host mirror for argument checks and planning.
+struct BNH KcDev {
+  DevBuf members, coms, cbad, cskip, cvalid, totals;
+  KcTable tab;
+  void swap(KcDev& o) {
+    DevBuf* a[6] = {&members, &coms, &cbad, &cskip, &cvalid, &totals};
+    DevBuf* b[6] = {&o.members, &o.coms, &o.cbad, &o.cskip, &o.cvalid, &o.totals};
+    for (int i = 0; i < 6; ++i) { std::swap(a[i]->p, b[i]->p); std::swap(a[i]->cap, b[i]->cap); }
+    std::swap(tab, o.tab);
+  }
+};
 struct blsbn254_keyset {
   blsbn254_ctx* ctx; size_t n; DevBuf aff, bad, skip, total, valid, enc, vwords;
   bool checked = false; DevBuf pop;
   size_t n_cols = 0; DevBuf weff; uint64_t wtotal[BLSBN254_KS_MAX_COLS] = {};
+  KcDev cm;
 };
 
 // ---- internal helpers shared between the units (defined in the unit named on the right)
@@ -406,6 +436,9 @@ BNH int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, s
 // blsbn254_keyset_fast_aggregate_verify_batch behind its argument checks and ENTER; sel == nullptr: the rows are in c->kset.sel already
 BNH int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs,
                        size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);   // host_keyset.hip
+// the tail of ks_verify_rows: the sums in c->gs_sum / c->gs_sum_ok (enqueued) encoded and paired with the staged messages and
+// signatures (stage_msgs, c->in_b), the bits downloaded
+BNH int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid_bitmap);   // host_keyset.hip
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip

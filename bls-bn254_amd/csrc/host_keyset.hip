@@ -9,6 +9,7 @@ extern "C" {
 
 static const size_t KS_MAX_KEYS = (size_t)1 << 16;
 static const size_t KS_LAUNCH_ITEMS = (size_t)1 << 20;      // word partials of one launch: 54 x 4 B each, about 226 MB
+static_assert(KS_LAUNCH_ITEMS == KC_LAUNCH_PARTIALS, "keyset_committee_plan.h cuts its launches by the same bound");
 static const size_t KS_RUN_ITEMS = 16;                      // keyset.h KS_RUN
 static inline size_t ks_nwords(size_t n) { return (n + 31) / 32; }
 
@@ -164,6 +165,15 @@ int blsbn254_keyset_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const u
   return 0;
 }
 
+// from the groups' sums on (c->gs_sum / c->gs_sum_ok, enqueued; c->gs_pk and c->bitmap reserved by the caller): the pipeline of
+// blsbn254_fast_aggregate_verify_batch.  Shared with the committee form (host_keyset_committee.hip).
+int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid_bitmap) {
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
+             (uint8_t*)c->gs_pk.p, 1));
+  TRY(verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
+                       (uint8_t*)c->bitmap.p));
+  return download(c, valid_bitmap, c->bitmap.p, (n_groups + 7) / 8);
+}
 // bit g = blsbn254_fast_aggregate_verify_batch on the selected keys of row g: from the sums on, the same pipeline.  sel == nullptr:
 // the rows are staged in c->kset.sel already (the verify with a quorum has weighed them there)
 int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n_groups,
@@ -177,11 +187,7 @@ int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel
   size_t launches;
   if (sel) TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
   else TRY(ks_enqueue_sums_dev(c, k, (const uint8_t*)c->kset.sel.p, n_groups, &launches));
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
-             (uint8_t*)c->gs_pk.p, 1));
-  TRY(verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
-                       (uint8_t*)c->bitmap.p));
-  TRY(download(c, valid_bitmap, c->bitmap.p, nb));
+  TRY(ks_verify_sums(c, n_groups, dl, valid_bitmap));
   ks_tally(c, n_groups, launches);
   return 0;
 }

@@ -181,6 +181,17 @@ BN_KERNEL k_km_points(const uint8_t* flags, size_t m, uint32_t lo, size_t N, int
 // stake weights over a registered key set selected by bitmaps (k_keyset_weight.hip)
 __global__ void __launch_bounds__(256) k_ks_weight(const uint8_t* rows, const uint32_t* vwords, const uint64_t* tab, uint32_t n_keys, uint32_t n_cols, size_t g_lo,
                                                   size_t m, uint64_t* out);
+// committees over a registered key set (k_keyset_committee.hip)
+BN_KERNEL k_kc_words(const uint32_t* members, const uint4* coms, const uint32_t* wcom, size_t n_words, const uint32_t* bad, const uint32_t* skip,
+                     const uint32_t* vwords, uint32_t* cbad, uint32_t* cskip, uint32_t* cvalid);
+BN_KERNEL k_kc_count(const uint8_t* sel, const uint64_t* srow, const uint32_t* scom, const uint4* coms, const uint32_t* cbad, size_t lo, size_t m, int noflip,
+                     uint8_t* flip, uint8_t* ok);
+BN_KERNEL k_kc_word_sum(const int32_t* aff, uint32_t n_keys, const uint32_t* members, const uint4* coms, const uint32_t* cskip, const uint4* items, const uint8_t* sel,
+              const uint64_t* srow, const uint32_t* scom, const uint32_t* spbase, const uint8_t* flip, int32_t* out, size_t out_stride);
+BN_KERNEL k_kc_finish(const int32_t* u, size_t u_stride, size_t G, const uint32_t* scom, const uint32_t* order, const int32_t* totals, size_t n_com,
+                      const uint8_t* flip, const uint8_t* ok, int32_t* out, size_t out_stride, uint8_t* ok_out);
+__global__ void __launch_bounds__(256) k_kc_weight(const uint8_t* rows, const uint64_t* grow, const uint32_t* gcom, const uint4* coms, const uint32_t* members,
+                                                  const uint32_t* cvalid, const uint64_t* tab, uint32_t n_cols, size_t g_lo, size_t m, uint64_t* out);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

@@ -492,6 +492,58 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_weight_stats(self._ctx, o))
         return {"groups": int(o[0]), "below_quorum": int(o[1]), "launches": int(o[2]), "tables": int(o[3])}
 
+    def _committee_rows(self, com, rows):
+        """com: one committee index per group; rows: one row of ceil(size(com[g]) / 8) bytes per group -> the arguments of the C
+        calls (the arrays are kept alive by the caller's reference to the tuple)"""
+        rows = [bytes(r) for r in rows]
+        g = len(rows)
+        if len(com) != g:
+            raise ValueError("one committee index per row")
+        ca = np.zeros(max(g, 1), dtype=np.uint32)
+        ca[:g] = np.asarray(list(com), dtype=np.uint32) if g else []
+        so = np.zeros(g + 1, dtype=np.uint64)
+        if g:
+            so[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+        a, pa = _inbuf(b"".join(rows))
+        return g, ca, ca.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), a, pa, so, so.ctypes.data_as(_u64p)
+
+    def keyset_committee_sum_batch(self, ks, com, rows):
+        """keyset_sum_batch over the committees of a KeySet (KeySet.set_committees): group g names committee com[g], rows[g] has one
+        bit per MEMBER of that committee.  Returns (n_groups x 128 bytes, n_groups status bytes): what keyset_sum_batch gives on
+        the rows scattered over the registry."""
+        g, ca, pc, a, pa, so, pso = self._committee_rows(com, rows)
+        o, po = _outbuf(128 * g); st, pst = _outbuf(g)
+        self._chk(self._lib.blsbn254_keyset_committee_sum_batch(self._ctx, ks._h, pc, pa, pso, ctypes.c_size_t(g), po, pst))
+        return o[:128 * g].tobytes(), st[:g].tobytes()
+
+    def keyset_committee_fast_aggregate_verify_batch(self, ks, com, rows, msgs, sigs, dst=DEFAULT_DST):
+        """keyset_fast_aggregate_verify_batch over the committees of a KeySet: one committee index, one row over that committee's
+        members, one message and 64 signature bytes per group.  Returns the LSB-first bitmap over the groups."""
+        g, ca, pc, a, pa, so, pso = self._committee_rows(com, rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        data, off = pack_messages(msgs)
+        m, pm = _inbuf(data); s, ps = _inbuf(sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        self._chk(self._lib.blsbn254_keyset_committee_fast_aggregate_verify_batch(self._ctx, ks._h, pc, pa, pso, pm, off.ctypes.data_as(_u64p), ps,
+                                                                                  ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po))
+        return o[:(g + 7) // 8].tobytes()
+
+    def keyset_committee_weight_batch(self, ks, com, rows):
+        """keyset_weight_batch over the committees of a KeySet: an (n_groups, n_cols) uint64 array, entry (g, q) = the sum of
+        stake column q over the selected members of committee com[g] that have the KeyValidate bit."""
+        g, ca, pc, a, pa, so, pso = self._committee_rows(com, rows)
+        nc = ks.n_cols
+        out = np.zeros(max(g * nc, 1), dtype=np.uint64)
+        self._chk(self._lib.blsbn254_keyset_committee_weight_batch(self._ctx, ks._h, pc, pa, pso, ctypes.c_size_t(g), out.ctypes.data_as(_u64p)))
+        return out[:g * nc].reshape(g, nc)
+
+    def keyset_committee_stats(self):
+        """dict: groups served by the committee calls, groups summed through the complement, launches of the word kernel,
+        committee tables set"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_committee_stats(self._ctx, o))
+        return {"groups": int(o[0]), "complement_groups": int(o[1]), "launches": int(o[2]), "tables": int(o[3])}
+
     def keyset_aggregate_checked_batch(self, ks, entry_sets, msgs, dst=DEFAULT_DST):
         """The collecting node's call: entry_sets[g] = the signatures received for msgs[g], a list of (key index, 64-byte
         signature) pairs or a dict {index: signature} over the registered KeySet (sorted by index here; a repeated index raises
@@ -969,6 +1021,7 @@ class KeySet:
         self._eng = engine
         self._lib = engine._lib
         self._lib.blsbn254_keyset_count.restype = ctypes.c_size_t
+        self._lib.blsbn254_keyset_committee_count.restype = ctypes.c_size_t
         self._h = ctypes.c_void_p()
         self.n_cols = 0
         a, pa = _inbuf(pks, 128 * n_keys)
@@ -1003,6 +1056,30 @@ class KeySet:
         o = (ctypes.c_uint64 * 8)()
         self._eng._chk(self._lib.blsbn254_keyset_total_weight(self._eng._ctx, self._h, o))
         return [int(o[q]) for q in range(self.n_cols)]
+
+    def set_committees(self, committees):
+        """committees: a list of index lists into the key set (1 to 65536 of them, none empty, no index twice within one list;
+        lists may overlap).  Replaces an earlier table.  A violation raises Bn254Error and leaves the earlier table in place."""
+        lists = [[int(i) for i in com] for com in committees]
+        if any(i < 0 or i >> 32 for com in lists for i in com):
+            raise ValueError("a member index must fit 32 bits")
+        flat = np.array([i for com in lists for i in com] or [0], dtype=np.uint32)
+        off = np.zeros(len(lists) + 1, dtype=np.uint64)
+        if lists:
+            off[1:] = np.cumsum([len(com) for com in lists], dtype=np.uint64)
+        self._eng._chk(self._lib.blsbn254_keyset_set_committees(self._eng._ctx, self._h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                                off.ctypes.data_as(_u64p), ctypes.c_size_t(len(lists))))
+        self._com_sizes = [len(com) for com in lists]
+
+    def committee_count(self):
+        return int(self._lib.blsbn254_keyset_committee_count(self._h))
+
+    def committee_total_weight(self):
+        """per committee the columns' sums over its members that have the KeyValidate bit: an (n_com, n_cols) uint64 array, the
+        weights of the rows that select every member"""
+        sizes = getattr(self, "_com_sizes", [])
+        rows = [bytes([0xff] * (n // 8) + ([0xff >> (8 - n % 8)] if n % 8 else [])) for n in sizes]
+        return self._eng.keyset_committee_weight_batch(self, list(range(len(sizes))), rows)
 
     def count(self):
         return int(self._lib.blsbn254_keyset_count(self._h))

@@ -426,6 +426,41 @@ int blsbn254_keyset_quorum_verify_batch(blsbn254_ctx* ctx, const blsbn254_keyset
         const uint8_t* dst, size_t dst_len, const uint64_t* min_weight /* n_cols */,
         uint64_t* weights_out /* n_groups*n_cols */, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
 int blsbn254_keyset_weight_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* COMMITTEES over a registered key set: a node holds ONE registry of keys, and each aggregate it receives is signed by a subset
+ * of one committee -- a list of registry indices -- with participation bits that count positions in that list.
+ * blsbn254_keyset_set_committees registers n_com (1 .. 65536) committees on the handle: committee c is
+ * members[com_off[c] .. com_off[c+1]), indices into the key set.  Every committee has at least one member, com_off starts at 0
+ * and does not decrease, com_off[n_com] = M <= 4 Mi (the default BLSBN254_CHUNK_LANES), every index is < n_keys, and no index
+ * appears twice within one committee; committees may overlap one another freely.  A violation is BLSBN254_E_ARG with a last_error
+ * that names the committee, and the handle keeps the table it had.  Calling again replaces the table.  A committee may contain
+ * bad keys, identity keys and keys whose proof failed: they behave as in the full-width calls.  blsbn254_keyset_committee_count:
+ * the committees of the handle, 0 before the first successful blsbn254_keyset_set_committees.
+ * The three calls below take n_groups RAGGED groups: group g names committee com[g] and brings row
+ * sel[sel_off[g] .. sel_off[g+1]) of exactly ceil(size(com[g]) / 8) bytes, bit j (LSB-first) = member j of the committee signed.
+ * BLSBN254_E_ARG: a wrong row length, a set bit past the committee's last member, com[g] >= n_com, a handle without a table,
+ * n_groups above BLSBN254_CHUNK_LANES; n_groups == 0 returns 0.  Each gives EXACTLY what its full-width counterpart gives for the
+ * row with bit members[j] set for every set bit j:
+ * blsbn254_keyset_committee_sum_batch: out / status of blsbn254_keyset_sum_batch (the identity encoding and status 0 for a row that
+ * selects a bad key).  blsbn254_keyset_committee_fast_aggregate_verify_batch: the bits of
+ * blsbn254_keyset_fast_aggregate_verify_batch.  blsbn254_keyset_committee_weight_batch: out of blsbn254_keyset_weight_batch
+ * (effective weights: a key without the validity bit weighs 0); BLSBN254_E_ARG without a stake table.
+ * A group in which more than half of its COMMITTEE signed is summed through the complement against the committee's total (kept
+ * on the handle).  Pending asynchronous verify calls are settled on entry.  blsbn254_keyset_stats does not count these calls;
+ * blsbn254_keyset_committee_stats, since the context was created: out[0] groups served, out[1] groups summed through the
+ * complement, out[2] launches of the word kernel, out[3] committee tables set. */
+int blsbn254_keyset_set_committees(blsbn254_ctx* ctx, blsbn254_keyset* keys, const uint32_t* members /* M */,
+                                   const uint64_t* com_off /* n_com+1 */, size_t n_com);
+size_t blsbn254_keyset_committee_count(const blsbn254_keyset* keys);
+int blsbn254_keyset_committee_sum_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com /* n_groups */,
+        const uint8_t* sel, const uint64_t* sel_off /* n_groups+1, bytes */, size_t n_groups, uint8_t* out /* n_groups*128 */,
+        uint8_t* status /* n_groups */);
+int blsbn254_keyset_committee_fast_aggregate_verify_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint32_t* com /* n_groups */, const uint8_t* sel, const uint64_t* sel_off /* n_groups+1, bytes */,
+        const uint8_t* msgs, const uint64_t* off /* n_groups+1 */, const uint8_t* sigs /* n_groups*64 */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_keyset_committee_weight_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com /* n_groups */,
+        const uint8_t* sel, const uint64_t* sel_off /* n_groups+1, bytes */, size_t n_groups, uint64_t* out /* n_groups*n_cols */);
+int blsbn254_keyset_committee_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Mul<Scalar> for G1Projective (g1.rs:518-534, multiply :821-841) and G2Projective (g2.rs:866-886), element-wise:
  * out_i = [k_i] P_i.  Points uncompressed, scalars 32 bytes big-endian (scalar.rs:229-233) and < r.  A point that does not
  * decode or is off the curve returns BLSBN254_ERR_G1 / BLSBN254_ERR_G2, a scalar >= r BLSBN254_ERR_SCALAR (the reference's
