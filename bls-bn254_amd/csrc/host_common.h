@@ -21,6 +21,7 @@
 #include "keyset_merge_plan.h" // KmRepack, the argument walk of the checked merge over a key set
 #include "keyset_weight_plan.h" // KwRepack, the column-total check and the quorum rule of the weights over a key set
 #include "keyset_committee_plan.h" // KcTable, KcPlan: the committee tables of a key set and the plan of a call over them
+#include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -153,6 +154,23 @@ struct BNH KcWs {
   std::vector<uint64_t> h_off;
   std::vector<uint32_t> h_com;
 };
+// key-set FastAggregateVerify by random linear combination per message (host_keyset_rlc.hip, k_keyset_rlc.hip): the seed; per
+// group its committee and row offset (committee form), sorted position, chunk-size byte, eligibility byte and weight; per sorted
+// position its group; the weighted points A (27 x G limbs) and B (54 x G limbs) at their sorted positions with the (constant 1)
+// flags k_g2_seg_sum reads; the chunks' starts and lengths, sums (27 / 54 x M limbs, with flags nobody reads), eligible counts,
+// states and the encodings of their G1 sums; the list, points, flags, signatures, key encodings, messages, offsets and bits of a
+// sub-call of the verify pipeline (the checked chunks, then the exact list); the levels of the sums.  Host side: the plan (its
+// vectors are what the uploads read) and every copy an upload reads or a download fills.
+struct BNH KsrWs {
+  DevBuf seed, com, row_off, pos, order, multi, elig, wt, a, b, ones, cstart, clen, sa, sb, sb_ok, cnt, state, sa_bytes, list, c_pts, c_ok, c_sigs, pk, msgs,
+         moff, bits;
+  SegWs seg;
+  KsrPlan plan;
+  uint8_t h_seed[32];
+  std::vector<uint8_t> h_elig, h_state, h_bits, h_msgs;
+  std::vector<uint32_t> h_cstart, h_clen, h_list;
+  std::vector<uint64_t> h_moff, h_rowoff;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -234,9 +252,12 @@ struct blsbn254_ctx {
   KmWs kmrg;
   KwWs kw;
   KcWs kcom;
+  KsrWs ksr;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
   uint64_t stat_kw[4] = {0, 0, 0, 0};    // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
   uint64_t stat_kc[4] = {0, 0, 0, 0};    // committee calls: groups served, groups summed through the complement, launches of the word kernel, committee tables set
+  size_t ksr_group = KSR_DEFAULT_GROUP;  // groups per chunk of the key-set RLC calls (blsbn254_set_keyset_rlc_group)
+  uint64_t stat_ksr[6] = {0, 0, 0, 0, 0, 0};   // groups decided by a passed chunk, chunks checked, groups sent to the exact path after their chunk failed, groups sent there directly, message classes, calls
   uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
   uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
@@ -439,6 +460,14 @@ BNH int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t*
 // the tail of ks_verify_rows: the sums in c->gs_sum / c->gs_sum_ok (enqueued) encoded and paired with the staged messages and
 // signatures (stage_msgs, c->in_b), the bits downloaded
 BNH int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid_bitmap);   // host_keyset.hip
+// the committee form's sums: the arguments checked (n_groups > 0), then the rows staged in c->kcom.sel, the sums into c->gs_sum /
+// c->gs_sum_ok in the caller's order (enqueued); kc_tally counts the call once it has succeeded and synchronised
+BNH int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
+BNH int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
+BNH void kc_tally(blsbn254_ctx* c, size_t n_groups);   // host_keyset_committee.hip
+// the full-width form's: the rows staged in c->kset.sel, the sums enqueued; ks_tally counts the call likewise
+BNH int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches);   // host_keyset.hip
+BNH void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches);   // host_keyset.hip
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip

@@ -137,12 +137,12 @@ int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t
   return 0;
 }
 // the same for rows of the caller: staged in c->kset.sel first
-static int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches) {
+int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches) {
   TRY(upload(c, c->kset.sel, sel, (k->n + 7) / 8 * n_groups));
   return ks_enqueue_sums_dev(c, k, (const uint8_t*)c->kset.sel.p, n_groups, launches);
 }
 // counted once the call has succeeded (and synchronised: the flip bytes are on the host)
-static void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches) {
+void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches) {
   c->stat_kset[0] += n_groups; c->stat_kset[2] += launches;
   for (size_t g = 0; g < n_groups; ++g) c->stat_kset[1] += c->kset.h_flip[g] ? 1 : 0;
 }

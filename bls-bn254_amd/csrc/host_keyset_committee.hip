@@ -83,14 +83,14 @@ int blsbn254_keyset_set_committees(blsbn254_ctx* c, blsbn254_keyset* k, const ui
 size_t blsbn254_keyset_committee_count(const blsbn254_keyset* k) { return k ? k->cm.tab.com.size() : 0; }
 
 // the checks the three calls share (n_groups > 0)
-static int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups) {
+int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups) {
   if (k->cm.tab.com.empty()) { c->last_error = "the key set has no committees (blsbn254_keyset_set_committees)"; return BLSBN254_E_ARG; }
   if (n_groups > c->chunk) { c->last_error = "more groups than one launch chunk"; return BLSBN254_E_ARG; }
   return kc_check_rows(k->cm.tab, com, sel, sel_off, n_groups, c->last_error) ? 0 : BLSBN254_E_ARG;
 }
 // the call's rows staged, its plan made, its sums into c->gs_sum / c->gs_sum_ok in the caller's order (enqueued); the flip bytes
 // into c->kcom.h_flip (enqueued: read after the caller's synchronising download)
-static int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups) {
+int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups) {
   KcWs& w = c->kcom;
   if (!kc_plan(k->cm.tab, com, sel_off, n_groups, c->chunk, w.plan, w.seg.h_start, w.seg.h_len)) { c->last_error = "internal: committee sums do not converge"; return BLSBN254_E_HIP; }
   TRY(upload(c, w.sel, sel + sel_off[0], sel_off[n_groups] - sel_off[0]));
@@ -104,7 +104,7 @@ static int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint
   return 0;
 }
 // counted once the call has succeeded (and synchronised: the flip bytes are on the host)
-static void kc_tally(blsbn254_ctx* c, size_t n_groups) {
+void kc_tally(blsbn254_ctx* c, size_t n_groups) {
   c->stat_kc[0] += n_groups; c->stat_kc[2] += c->kcom.plan.launches.size();
   for (size_t i = 0; i < n_groups; ++i) c->stat_kc[1] += c->kcom.h_flip[i] ? 1 : 0;
 }

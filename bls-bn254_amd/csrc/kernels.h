@@ -192,6 +192,16 @@ BN_KERNEL k_kc_finish(const int32_t* u, size_t u_stride, size_t G, const uint32_
                       const uint8_t* flip, const uint8_t* ok, int32_t* out, size_t out_stride, uint8_t* ok_out);
 __global__ void __launch_bounds__(256) k_kc_weight(const uint8_t* rows, const uint64_t* grow, const uint32_t* gcom, const uint4* coms, const uint32_t* members,
                                                   const uint32_t* cvalid, const uint64_t* tab, uint32_t n_cols, size_t g_lo, size_t m, uint64_t* out);
+// key-set FastAggregateVerify by random linear combination per message (k_keyset_rlc.hip)
+BN_KERNEL k_ksr_elig(const uint8_t* rows, const uint64_t* row_off, uint32_t n_keys, const uint32_t* com, const uint4* coms, const uint32_t* skip,
+                     const uint32_t* valid, const int32_t* sums, const uint8_t* sum_ok, size_t G, const uint8_t* sigs, const uint8_t* seed,
+                     const uint8_t* multi, uint8_t* elig, uint64_t* wt);
+BN_KERNEL k_ksr_weigh_g1(const uint8_t* sigs, const uint8_t* elig, const uint64_t* wt, const uint32_t* pos, size_t G, int32_t* a_ws);
+BN_KERNEL k_ksr_weigh_g2(const int32_t* sums, const uint8_t* elig, const uint64_t* wt, const uint32_t* pos, size_t G, int32_t* b_ws);
+BN_KERNEL k_ksr_chunks(const int32_t* sa, const int32_t* sb, size_t M, const uint32_t* cstart, const uint32_t* clen, const uint32_t* order,
+                       const uint8_t* elig, uint32_t* cnt, uint8_t* state, uint8_t* sa_bytes);
+__global__ void __launch_bounds__(256) k_ksr_gather(const uint32_t* list, size_t m, const int32_t* pts, size_t pts_stride, const uint8_t* ok, const uint8_t* sigs,
+                                                   int32_t* c_pts, uint8_t* c_ok, uint8_t* c_sigs);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

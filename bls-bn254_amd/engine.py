@@ -544,6 +544,52 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_committee_stats(self._ctx, o))
         return {"groups": int(o[0]), "complement_groups": int(o[1]), "launches": int(o[2]), "tables": int(o[3])}
 
+    @staticmethod
+    def _seed_arg(seed):
+        if seed is None:
+            return None, ctypes.cast(None, _u8p)
+        return _inbuf(seed, 32)
+
+    def keyset_fast_aggregate_verify_batch_rlc(self, ks, sel_rows, msgs, sigs, dst=DEFAULT_DST, seed=None):
+        """Same bitmap as keyset_fast_aggregate_verify_batch, via random linear combinations per message: the groups that sign the
+        same message are checked a chunk (64 groups unless set_keyset_rlc_group says otherwise) at a time with ONE pairing
+        equation, and whatever a chunk does not decide takes the exact path.  seed = None: the library draws it from the OS
+        inside the call (production); a caller seed is for reproducible tests only."""
+        sel, g = self._keyset_rows(ks, sel_rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(sel); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        sd, psd = self._seed_arg(seed)
+        self._chk(self._lib.blsbn254_keyset_fast_aggregate_verify_batch_rlc(self._ctx, ks._h, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(g), pd,
+                                                                            ctypes.c_size_t(len(dst)), psd, po))
+        return o[:(g + 7) // 8].tobytes()
+
+    def keyset_committee_fast_aggregate_verify_batch_rlc(self, ks, com, rows, msgs, sigs, dst=DEFAULT_DST, seed=None):
+        """Same bitmap as keyset_committee_fast_aggregate_verify_batch, via random linear combinations per message (see
+        keyset_fast_aggregate_verify_batch_rlc)."""
+        g, ca, pc, a, pa, so, pso = self._committee_rows(com, rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        data, off = pack_messages(msgs)
+        m, pm = _inbuf(data); s, ps = _inbuf(sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        sd, psd = self._seed_arg(seed)
+        self._chk(self._lib.blsbn254_keyset_committee_fast_aggregate_verify_batch_rlc(self._ctx, ks._h, pc, pa, pso, pm, off.ctypes.data_as(_u64p), ps,
+                                                                                      ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), psd, po))
+        return o[:(g + 7) // 8].tobytes()
+
+    def set_keyset_rlc_group(self, group):
+        """groups per chunk of the key-set RLC calls: 2 .. 4096; 0 = the default, 64"""
+        self._chk(self._lib.blsbn254_set_keyset_rlc_group(self._ctx, ctypes.c_size_t(group)))
+
+    def keyset_rlc_stats(self):
+        """dict: groups decided by a chunk that passed, chunks checked, groups sent to the exact path after their chunk failed,
+        groups sent there directly, message classes seen, calls"""
+        o = (ctypes.c_uint64 * 6)()
+        self._chk(self._lib.blsbn254_keyset_rlc_stats(self._ctx, o))
+        return {"decided_groups": int(o[0]), "chunks": int(o[1]), "failed_chunk_groups": int(o[2]), "direct_groups": int(o[3]), "classes": int(o[4]),
+                "calls": int(o[5])}
+
     def keyset_aggregate_checked_batch(self, ks, entry_sets, msgs, dst=DEFAULT_DST):
         """The collecting node's call: entry_sets[g] = the signatures received for msgs[g], a list of (key index, 64-byte
         signature) pairs or a dict {index: signature} over the registered KeySet (sorted by index here; a repeated index raises

@@ -461,6 +461,41 @@ int blsbn254_keyset_committee_fast_aggregate_verify_batch(blsbn254_ctx* ctx, con
 int blsbn254_keyset_committee_weight_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com /* n_groups */,
         const uint8_t* sel, const uint64_t* sel_off /* n_groups+1, bytes */, size_t n_groups, uint64_t* out /* n_groups*n_cols */);
 int blsbn254_keyset_committee_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* blsbn254_keyset_fast_aggregate_verify_batch and blsbn254_keyset_committee_fast_aggregate_verify_batch by RANDOM LINEAR
+ * COMBINATION PER MESSAGE: the same arguments plus a seed, the same bitmap.  The groups of a call whose messages are
+ * byte-identical form a class; a class, in the caller's order, is cut into chunks of at most C groups (default 64,
+ * blsbn254_set_keyset_rlc_group: 2 <= group <= 4096 fixes it, 0 restores the default, anything else is BLSBN254_E_ARG), and a
+ * chunk with message m, key sums S_g and signatures sig_g is checked as ONE virtual tuple
+ *   e(sum_g r_g sig_g, -G2gen) * e(H(m), sum_g r_g S_g) == 1
+ * on the verify pipeline: 1/C as many Miller loops and final exponentiations where aggregates share their message.
+ * A group takes part in its chunk's sums only when it is ELIGIBLE: its row selects no bad key, every key it adds has the
+ * KeyValidate bit (so its sum lies in the r-torsion without a test of its own), its signature decodes, is on the curve and is
+ * not the identity, and its sum is not the identity.  An eligible group of a chunk that passes has its bit set.  Every other
+ * group -- not eligible, alone in its chunk or the only eligible member of it, in a chunk whose weighted sum is the identity, or
+ * an eligible member of a chunk that FAILED -- is decided by the exact call's own pipeline on its sum, in one sub-call.  So bit g
+ * is bit g of the exact call on the same arguments, and can differ only where an invalid group passed its chunk's check:
+ * probability at most 2^-64 per chunk checked, given a fresh secret seed.
+ * Weights: r_g = the first 8 bytes, big-endian, of SHA-256(seed || "KSRLC" || g as 8 bytes little-endian || sig_g); 0 becomes 1.
+ * seed = NULL (the production setting): the library draws 32 bytes from the OS (getrandom) inside the call, i.e. after
+ * the batch is fixed.  A caller-supplied seed exists for reproducible tests; soundness then rests on that seed being
+ * fresh and secret -- never reuse one, never derive it from public data.
+ * Argument errors and n_groups == 0 behave as in the exact calls (the offsets of the messages are checked before anything is
+ * launched; msgs == NULL with a message of non-zero length is BLSBN254_E_ARG).  Pending asynchronous verify calls are settled
+ * on entry and none is left pending.  blsbn254_keyset_stats / blsbn254_keyset_committee_stats count the sums as they do for
+ * the exact calls.  blsbn254_keyset_rlc_stats, since the context was created: out[0] groups decided by a chunk that passed,
+ * out[1] chunks checked, out[2] groups sent to the exact path because their chunk failed, out[3] groups sent there directly
+ * (not eligible, or in a chunk that was not checked), out[4] message classes seen, out[5] calls. */
+int blsbn254_keyset_fast_aggregate_verify_batch_rlc(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint8_t* sel /* n_groups*ceil(n_keys/8) */, const uint8_t* msgs, const uint64_t* off /* n_groups+1 */,
+        const uint8_t* sigs /* n_groups*64 */, size_t n_groups, const uint8_t* dst, size_t dst_len,
+        const uint8_t seed[32] /* NULL: getrandom inside the call */, uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_keyset_committee_fast_aggregate_verify_batch_rlc(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint32_t* com /* n_groups */, const uint8_t* sel, const uint64_t* sel_off /* n_groups+1, bytes */,
+        const uint8_t* msgs, const uint64_t* off /* n_groups+1 */, const uint8_t* sigs /* n_groups*64 */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len, const uint8_t seed[32] /* NULL: getrandom inside the call */,
+        uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_set_keyset_rlc_group(blsbn254_ctx* ctx, size_t group);
+int blsbn254_keyset_rlc_stats(blsbn254_ctx* ctx, uint64_t out[6]);
 /* Mul<Scalar> for G1Projective (g1.rs:518-534, multiply :821-841) and G2Projective (g2.rs:866-886), element-wise:
  * out_i = [k_i] P_i.  Points uncompressed, scalars 32 bytes big-endian (scalar.rs:229-233) and < r.  A point that does not
  * decode or is off the curve returns BLSBN254_ERR_G1 / BLSBN254_ERR_G2, a scalar >= r BLSBN254_ERR_SCALAR (the reference's
