@@ -160,18 +160,21 @@ template <class F> BN_FUNC Proj<F> proj_mul_u64(const Proj<F>& p, uint64_t k) {
   }
   return acc;
 }
-// The BN parameter x = 0x44e992b44a6909f1 as a signed-digit chain over {1, 17, 35} -- negation is free in both places the chain is
-// used: a point's inverse is (x, -y), a cyclotomic element's inverse is its conjugate --
-//   _17 = 2^4 * 1 + 1,  _35 = 2 * _17 + 1,
-//   x = (((((((((((_35 << 6 - _35) << 7 + _17) << 2 + _35) << 4 - _35) << 4 - _35) << 9 + _35) << 4 + _35) << 6 + _17) << 5 + _35) << 5 - _17) << 5 + _17
-// = 62 doublings + 13 additions (binary: 62 + 27; the unsigned chain used until round 3: 62 + 17), found by exhaustive search
-// over dictionaries of up to five odd values below 64 with an optimal signed recoding for each (tools/x_chain_search.py).
+// The BN parameter x = 0x44e992b44a6909f1 as a signed chain whose multipliers are its own early running values -- negation is free in
+// both places the chain is used (a point's inverse is (x, -y), a cyclotomic element's inverse is its conjugate) but a negative
+// takes a slot of its own --
+//   _129 = 2^7 * 1 + 1,  _517 = 2^2 * _129 + 1,  _2197 = 2^2 * _517 + _129          (parked: -1, _129, -_517, _2197)
+//   x = (((((((((_2197 << 4 + _129) << 10 + _2197) << 1 + 1) << 13 + _2197) << 2 - 1) << 5 + 1) << 4 + _129) << 11 - _517) << 1 - _517
+// = 62 doublings + 12 additions (binary: 62 + 27; the signed chain over {1, 17, 35} used before: 62 + 13), found by
+// scripts/x_chain_search.py: every prefix of up to three products with values below 2^12, each value parked as itself, its
+// negative, both or not, then a backward beam search from x over the parked values.
 // One interpreter step: r <- slot[load] if load >= 0; r <- 2^sq r; r <- r + slot[mul] if mul >= 0; slot[store] <- r and
-// slot[cstore] <- -r if >= 0.  Slot 0 holds the input.  Shared by [x]P (below, quad.h) and t^x (pairing.h, tri.h, wide.h).
+// slot[cstore] <- -r if >= 0.  Slot 0 holds the input; the first step only parks its negative.  Shared by [x]P (below, quad.h)
+// and t^x (pairing.h, tri.h, wide.h).
 struct ChainOp { int8_t load, sq, mul, store, cstore; };
 constexpr int BN_X_CHAIN_LEN = 13, BN_X_CHAIN_SLOTS = 5;
-#define BN_X_CHAIN {{-1, 4, 0, 1, 2}, {-1, 1, 0, 3, 4}, {-1, 6, 4, -1, -1}, {-1, 7, 1, -1, -1}, {-1, 2, 3, -1, -1}, {-1, 4, 4, -1, -1}, {-1, 4, 4, -1, -1}, \
-                    {-1, 9, 3, -1, -1}, {-1, 4, 3, -1, -1}, {-1, 6, 1, -1, -1}, {-1, 5, 3, -1, -1}, {-1, 5, 2, -1, -1}, {-1, 5, 1, -1, -1}}
+#define BN_X_CHAIN {{-1, 0, -1, -1, 1}, {-1, 7, 0, 2, -1}, {-1, 2, 0, -1, 3}, {-1, 2, 2, 4, -1}, {-1, 4, 2, -1, -1}, {-1, 10, 4, -1, -1}, {-1, 1, 0, -1, -1}, \
+                    {-1, 13, 4, -1, -1}, {-1, 2, 1, -1, -1}, {-1, 5, 0, -1, -1}, {-1, 4, 2, -1, -1}, {-1, 11, 3, -1, -1}, {-1, 1, 3, -1, -1}}
 // [x]P by that chain; runs of doublings are done in Jacobian coordinates.
 template <class F> BN_FUNC Proj<F> proj_mul_bn_x(const Proj<F>& p) {
   BN_CTX;
@@ -414,7 +417,7 @@ BN_FUNC SvdwFrac svdw_g1_frac(const Fp& u_in) {
   r.d = fp_select(e1 | e2, d12, d3);
   const Fp U = fp_select(e1, g1n, fp_select(e2, g2n, g3n)), V = fp_select(e1 | e2, v12, v3);
   const Fp V3 = fp_mul(fp_sqr(V), V);
-  const Fp y = fp_mul(fp_mul(U, V), fp_pow(fp_mul(U, V3), BN_EXP(EXP_PM3_4)));
+  const Fp y = fp_mul(fp_mul(U, V), fp_pow_pm3_4(fp_mul(U, V3)));
   const bool flip = fp_sgn0(u) != fp_sgn0(y);
   r.y = fp_select(flip, fp_norm(fp_neg(y)), y);
   return r;

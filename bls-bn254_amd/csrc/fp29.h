@@ -70,7 +70,7 @@ struct Fp {
 
 // ------------------------------------------------------------------ check-mode instrumentation
 #ifdef BN_CHECK
-struct CheckStats { double worst_mul = 0, worst_dot = 0, worst_vb = 0; long muls = 0, sqrs = 0, dots = 0, norms = 0, lcs = 0, lc_terms = 0; };
+struct CheckStats { double worst_mul = 0, worst_dot = 0, worst_vb = 0; long muls = 0, sqrs = 0, dots = 0, norms = 0, lcs = 0, lc_terms = 0, sha_blocks = 0; };
 inline CheckStats& check_stats() { static thread_local CheckStats s; return s; }    // per thread: tests/hostsim runs the lanes of a quad (tri.h) as threads
 inline double mag(const Fp& a) { return std::fmax(std::fabs(a.lo), std::fabs(a.hi)); }
 inline double tmag(const Fp& a) { return std::fmax(std::fabs(a.tlo), std::fabs(a.thi)); }
@@ -492,7 +492,33 @@ BN_FUNC Fp fp_pow(const Fp& a, Exp256 e) {
   }
   return r;
 }
-BN_FUNC Fp fp_inv_pow(const Fp& a) { return fp_pow(a, BN_EXP(EXP_PM2)); }             // Fermat: the reference's Fp::invert (fp.rs:207-210); inv0(0) = 0 (E15)
+// a^((p-3)/4), the one power of the hash's map (curve.h svdw_g1_frac), by an addition chain fixed for THIS exponent
+// (scripts/gen_sqrt_chain.py generates the table below and checks it against Python integers; --check re-reads it from this file):
+// the odd powers a^1 .. a^27 (one squaring + 13 products), then 39 steps of "s squarings, one product with a table entry" --
+// window width 5, odd powers up to 27: 52 products + 251 squarings against the 77 + 252 of fp_pow's 4-bit fixed windows.
+// The steps are a compile-time table, the same for every lane and every input: control flow is uniform and no exponent bit is
+// looked at while it runs.
+struct PowStep { uint8_t sq, idx; };                     // idx: table entry a^(2 idx + 1)
+constexpr int BN_PM3_4_TAB = 14, BN_PM3_4_FIRST = 1, BN_PM3_4_LEN = 39;
+#define BN_PM3_4_CHAIN {{10, 12}, {8, 9}, {5, 9}, {4, 4}, {4, 3}, {9, 9}, {7, 6}, {10, 2}, {7, 13}, {1, 0}, {7, 2}, {10, 8}, {6, 13}, {5, 6}, {8, 1}, {11, 10}, {1, 0}, {9, 11}, {6, 12}, {5, 7}, {10, 5}, {6, 10}, {7, 8}, {5, 6}, {7, 3}, {6, 3}, {7, 10}, {7, 6}, {6, 7}, {5, 0}, {10, 8}, {1, 0}, {9, 5}, {6, 13}, {8, 7}, {5, 9}, {4, 7}, {4, 2}, {4, 0}}
+BN_FUNC Fp fp_pow_pm3_4(const Fp& a) {
+  const PowStep prog[BN_PM3_4_LEN] = BN_PM3_4_CHAIN;
+  Fp tab[BN_PM3_4_TAB];
+  tab[0] = fp_norm(a);
+  const Fp a2 = fp_sqr(tab[0]);
+  for (int i = 1; i < BN_PM3_4_TAB; ++i) tab[i] = fp_mul(tab[i - 1], a2);
+  Fp r = tab[BN_PM3_4_FIRST];
+  for (int k = 0; k < BN_PM3_4_LEN; ++k) {
+    const PowStep op = prog[k];
+    // as in fp_pow: the table lives in scratch, its entry is fetched before the squarings and the barrier keeps the load there
+    Fp t = tab[op.idx];
+    BN_SCHED_BARRIER;
+    for (int q = 0; q < op.sq; ++q) r = fp_sqr(r);
+    r = fp_mul(r, t);
+  }
+  return r;
+}
+BN_FUNC Fp fp_inv_pow(const Fp& a) { return fp_pow(a, BN_EXP(EXP_PM2)); }            // Fermat: the reference's Fp::invert (fp.rs:207-210); inv0(0) = 0 (E15)
 
 // Inversion by the Bernstein-Yang divstep recurrence ("safegcd", 2019/266) in the half-delta form, 29 steps per batch so that a
 // batch shifts the operands by exactly one limb of this file's radix.  Same result as Fermat's a^(p-2) (the inverse is unique;

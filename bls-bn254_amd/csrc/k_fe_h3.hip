@@ -19,11 +19,18 @@ BN_KERNEL k_fe_h3(const int32_t* t, const int32_t* a, const int32_t* c, const in
     const Ws src[5] = {{const_cast<int32_t*>(t), stride, l4, true}, {const_cast<int32_t*>(a), stride, l4, true}, {const_cast<int32_t*>(c), stride, l4, true},
                        {const_cast<int32_t*>(b2), stride, l4, true}, {const_cast<int32_t*>(x0), stride, l4, true}};
     const Ws park = {park_lds, 256, threadIdx.x * 4u, false};
-    Fp12 r = fe_h3_loop(src, Ws{tmp, stride, l4, true}, &park);
-    if (mode == 0) bit = fp12_is_one(r) & (flags[i] == (FLAG_SIG_OK | FLAG_PK_OK)) & (sub_ok[i] != 0);
-    else if (mode == 3) *is_one = fp12_is_one(r) ? 1 : 0;
-    else if (mode == 4) gt_bytes[i] = fp12_is_one(r) ? 1 : 0;
-    else fp12_to_be(gt_bytes + 384 * (size_t)i, r);
+    // the modes that only want "== 1" stop one product early and compare the two sides (pairing.h fe_h3_verdict); the Gt modes
+    // run all eight steps.  One rolled loop either way: the step count is uniform over the launch.
+    const bool gt_out = mode == 1 || mode == 2;
+    const Ws tw = {tmp, stride, l4, true};
+    Fp12 r = fe_h3_loop(src, tw, &park, gt_out ? 8 : 7);
+    if (gt_out) fp12_to_be(gt_bytes + 384 * (size_t)i, r);
+    else {
+      const bool one = fe_h3_verdict(r, tw);
+      if (mode == 0) bit = one & (flags[i] == (FLAG_SIG_OK | FLAG_PK_OK)) & (sub_ok[i] != 0);
+      else if (mode == 3) *is_one = one ? 1 : 0;
+      else gt_bytes[i] = one ? 1 : 0;
+    }
   }
   if (mode == 0) write_ballot(bitmap, n, i, bit);
 }

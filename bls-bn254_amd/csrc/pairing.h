@@ -374,8 +374,8 @@ BN_FUNC Fp12 cyclotomic_exp_x(const Fp12& f) {
 //   easy:  t  = f^((p^6-1)(p^2+1))
 //   hard:  t^(l0 + l1 p + l2 p^2 + l3 p^3), Fuentes-Castaneda et al. arrangement with three t -> t^x
 //          exponentiations (cyclotomic_exp_x) separated by the small steps h1, h2, h3.
-// f^x by the signed chain BN_X_CHAIN (curve.h) = 62 cyclotomic squarings + 13 multiplications (binary: 27): f^-17 and f^-35 are
-// the conjugates of f^17 and f^35.  Run as a small uniform interpreter (one inlined squaring and one inlined
+// f^x by the signed chain BN_X_CHAIN (curve.h) = 62 cyclotomic squarings + 12 multiplications (binary: 27): f^-1 and f^-517 are
+// the conjugates of f and f^517.  Run as a small uniform interpreter (one inlined squaring and one inlined
 // multiply-by-memory-operand in the loop body): the five named powers live in `slots` (limb-major memory, 10 x 108 limbs per
 // lane reserved) and are read back one Fp6 half at a time.
 BN_FUNC Fp12 cyclotomic_exp_x_chain(const Fp12& f, const Ws& slots, const Ws* park = nullptr) {
@@ -553,10 +553,12 @@ BN_FUNC Fp12 fp12_load_limbs(const int32_t* in, size_t stride) {
 // them); tmp = 4 x 108 limbs for e, e^(p^2), d^p, l3^(p^3).  Same value as fe_h3:
 //   e = b2 x0, d = a e, l3 = conj(t) d = conj(t conj(d)), result = (c e t) d^p e^(p^2) l3^(p^3).
 struct H3Op { int8_t pre, mul, post; };      // pre: 1 r = b2, 2 r = conj(r), 3 r = e;  mul: operand index (5.. = tmp slots);  post: see below
-BN_FUNC Fp12 fe_h3_loop(const Ws* src, const Ws& tmp, const Ws* park) {
+// steps = 8: the value of fe_h3.  steps = 7 stops before the last product: r = l0 d^p e^(p^2), with l3^(p^3) left in tmp slot 3
+// for fe_h3_verdict below.
+BN_FUNC Fp12 fe_h3_loop(const Ws* src, const Ws& tmp, const Ws* park, int steps = 8) {
   const H3Op prog[8] = {{1, 4, 1}, {0, 1, 2}, {2, 0, 3}, {3, 2, 0}, {0, 0, 0}, {0, 7, 0}, {0, 6, 0}, {0, 8, 0}};
   Fp12 r = fp12_one();
-  for (int k = 0; k < 8; ++k) {
+  for (int k = 0; k < steps; ++k) {
     const H3Op op = prog[k];
     if (op.pre == 1) r = fp12_load_mem(src[3]);
     else if (op.pre == 2) r = fp12_conj(r);
@@ -570,6 +572,25 @@ BN_FUNC Fp12 fe_h3_loop(const Ws* src, const Ws& tmp, const Ws* park) {
     BN_MEM_FENCE;
   }
   return r;
+}
+
+// "fe_h3 == 1" without its last product, for the callers that only want the verdict.  With A = l0 d^p e^(p^2) (r after seven
+// steps of fe_h3_loop) and B = l3^(p^3) (tmp slot 3), fe_h3 = A B.  Every phase value is a product of conjugates, Frobenius
+// images and cyclotomic squares of t = fe_easy(f), and t conj(t) = 1 for every f != 0: B^-1 = conj(B), so A B == 1 exactly when
+// A == conj(B), i.e. A.c0 == B.c0 and A.c1 + B.c1 == 0, compared in canonical form (fp_is_zero canonicalises the difference).
+// f = 0 gives t = 0 and every phase value 0, where the two sides agree while fe_h3 = 0 != 1: A != 0 is part of the verdict, so
+// the all-zero tuple fails as it did.  One dense Fp12 product fewer than the eighth step.
+BN_FUNC bool fe_h3_verdict(const Fp12& r, const Ws& tmp) {
+  BN_CTX;
+  const Ws b = ws_at(tmp, 324);
+  bool eq = true, zero = true;
+  { const Fp2 x = fp2_load_mem(b); eq &= fp2_eq(r.c0.c0, x); zero &= fp2_is_zero(r.c0.c0); }
+  { const Fp2 x = fp2_load_mem(ws_at(b, 18)); eq &= fp2_eq(r.c0.c1, x); zero &= fp2_is_zero(r.c0.c1); }
+  { const Fp2 x = fp2_load_mem(ws_at(b, 36)); eq &= fp2_eq(r.c0.c2, x); zero &= fp2_is_zero(r.c0.c2); }
+  { const Fp2 x = fp2_load_mem(ws_at(b, 54)); eq &= fp2_is_zero(fp2_add(r.c1.c0, x)); zero &= fp2_is_zero(r.c1.c0); }
+  { const Fp2 x = fp2_load_mem(ws_at(b, 72)); eq &= fp2_is_zero(fp2_add(r.c1.c1, x)); zero &= fp2_is_zero(r.c1.c1); }
+  { const Fp2 x = fp2_load_mem(ws_at(b, 90)); eq &= fp2_is_zero(fp2_add(r.c1.c2, x)); zero &= fp2_is_zero(r.c1.c2); }
+  return eq & !zero;
 }
 
 // fe_h1 / fe_h2 as tails of the t^x phase kernels (k_fe_expx_tail.hip): computed right after the chain from the value

@@ -34,6 +34,7 @@ BN_SHA_FUNC void sha256_compress(uint32_t* h, const uint32_t* blk) {
       0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08,
       0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208,
       0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+  BN_TRK(++check_stats().sha_blocks;)
   uint32_t w[16];
   BN_UNROLL for (int i = 0; i < 16; ++i) w[i] = blk[i];
   uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
@@ -57,6 +58,14 @@ BN_FUNC void sha256_init(Sha256& s) {
   s.h[4] = 0x510e527f; s.h[5] = 0x9b05688c; s.h[6] = 0x1f83d9ab; s.h[7] = 0x5be0cd19;
   for (int i = 0; i < 16; ++i) s.w[i] = 0;
   s.cur = 0; s.fill = 0; s.total = 0;
+}
+// The state after ONE block of 64 zero bytes (scripts/sha256_zero_block_state.py derives it from FIPS 180-4; tests/test_op_trim.py
+// recomputes it): b_0 of expand_message_xmd always hashes Z_pad first, so it starts here, one compression of its hash saved.
+BN_FUNC void sha256_init_zpad(Sha256& s) {
+  s.h[0] = 0xda5698be; s.h[1] = 0x17b9b469; s.h[2] = 0x62335799; s.h[3] = 0x779fbeca;
+  s.h[4] = 0x8ce5d491; s.h[5] = 0xc0d26243; s.h[6] = 0xbafef9ea; s.h[7] = 0x1837a9d8;
+  for (int i = 0; i < 16; ++i) s.w[i] = 0;
+  s.cur = 0; s.fill = 0; s.total = 64;
 }
 // One byte: assembled in a register, the block array is written once per completed word (it is indexed by a
 // run-time value, so it lives in scratch: a read-modify-write per byte was an exposed scratch round trip per byte).
@@ -84,8 +93,7 @@ BN_FUNC void expand_message_xmd(uint8_t* out, uint32_t n, const uint8_t* msg, si
                                      const uint8_t* dst, uint32_t dst_len) {
   uint8_t b0[32], bi[32];
   Sha256 s;
-  sha256_init(s);
-  for (int i = 0; i < 64; ++i) sha256_byte(s, 0);                 // Z_pad
+  sha256_init_zpad(s);                                            // Z_pad: the state after its block is a constant
   sha256_update(s, msg, msg_len);
   sha256_byte(s, (uint8_t)(n >> 8)); sha256_byte(s, (uint8_t)n); sha256_byte(s, 0);
   sha256_update(s, dst, dst_len); sha256_byte(s, (uint8_t)dst_len);

@@ -304,7 +304,7 @@ BN_HD inline void wide_miller_1(const Wide& W, const G2A& q, const Ws& pt, const
   }
 #undef BN_WIDE_LINE_STEP
 }
-// out = in^x by the signed chain of cyclotomic_exp_x_chain (pairing.h, BN_X_CHAIN): 62 squarings + 13 products; R is the accumulator
+// out = in^x by the signed chain of cyclotomic_exp_x_chain (pairing.h, BN_X_CHAIN): 62 squarings + 12 products; R is the accumulator
 BN_HD inline void wide_exp_x(const Wide& W, uint32_t out, uint32_t in) {
   const ChainOp prog[BN_X_CHAIN_LEN] = BN_X_CHAIN;
   wide_exec(W, WOP_COPY, WV_SLOT0, in, 0);
