@@ -186,6 +186,7 @@ struct blsbn254_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   DevBuf in_a, in_b, in_c, in_off, dst, h_ws, f_ws, f_ws2, flags, sub_ok, status, bitmap, out, scalars, misc;
+  DevBuf wire_a, wire_b; // compressed keys / signatures as uploaded (host_compressed.hip): inflated into in_a / in_b, which the pipelines read
   DevBuf fe[6];          // final-exponentiation phase buffers (x, a, b, c, b2, d), 108 x n limbs each
   DevBuf rlc_a2, rlc_a, rlc_b, rlc_elig, rlc_f2, rlc_bytes, rlc_neg, rlc_ok, rlc_idx, rlc_cpk, rlc_csig, rlc_ch, rlc_csub, rlc_cbm;   // RLC batch verification
   // RLC over repeated keys (k_rlc2.hip): weighted points, chunk descriptions, virtual tuples, fallback list
@@ -455,8 +456,22 @@ BNH int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uin
 // the argument checks the calls over rows share (n_groups > 0): the limit, and no row may set a bit that names no key
 BNH int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups);   // host_keyset.hip
 // blsbn254_keyset_fast_aggregate_verify_batch behind its argument checks and ENTER; sel == nullptr: the rows are in c->kset.sel already
+// compressed: the signatures are 32-byte encodings (stage_g1)
 BNH int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs,
-                       size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);   // host_keyset.hip
+                       size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap, bool compressed = false);   // host_keyset.hip
+// A call's n public keys into c->in_a / its n signatures into c->in_b, where every pipeline reads them: uploaded as they are, or
+// (compressed: 64 / 32 bytes each) uploaded to c->wire_a / c->wire_b and inflated from there by k_g2_inflate / k_g1_inflate,
+// an element that does not inflate as the marker no decoder accepts (inflate.h).  Enqueued.
+BNH int stage_g2(blsbn254_ctx* c, const uint8_t* pks, size_t n, bool compressed);    // host_compressed.hip
+BNH int stage_g1(blsbn254_ctx* c, const uint8_t* sigs, size_t n, bool compressed);   // host_compressed.hip
+// the entry points that exist in both forms, behind their argument checks and ENTER
+BNH int verify_batch_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n, const uint8_t* dst,
+                          size_t dst_len, uint8_t* bm, bool compressed);   // host_verify.hip
+BNH int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n, const uint8_t* dst,
+                              size_t dst_len, const uint8_t* seed, uint8_t* bm, bool compressed);   // host_rlc.hip
+// the registration of a key set, arguments checked in here; proofs == nullptr: without proofs of possession
+BNH int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
+                  blsbn254_keyset** out, bool compressed);   // host_keyset.hip
 // the tail of ks_verify_rows: the sums in c->gs_sum / c->gs_sum_ok (enqueued) encoded and paired with the staged messages and
 // signatures (stage_msgs, c->in_b), the bits downloaded
 BNH int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid_bitmap);   // host_keyset.hip

@@ -18,8 +18,11 @@ static inline size_t ks_nwords(size_t n) { return (n + 31) / 32; }
 // the context's staging buffers while it runs and leaves in_a, the staged keys, as they were.  Its bits are kept on the handle
 // and make a failing key bad (k_ks_register); for the total the same kernel overwrites the STAGED copy of such a key with an
 // encoding that does not decode, after the handle's copy of the encodings was taken: enc keeps the bytes as uploaded.
-static int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
-                     blsbn254_keyset** out) {
+// compressed: the keys (and the proofs) are wire encodings, inflated on the way into the staging buffers (stage_g2 / stage_g1):
+// from there on nothing differs, so the handle is the one the inflated bytes would have made -- enc keeps the INFLATED bytes, a
+// proof's message is the 128-byte uncompressed key, a key that does not inflate is the marker, which does not decode.
+int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
+              blsbn254_keyset** out, bool compressed) {
   if (!c || !out) return BLSBN254_E_ARG;
   *out = nullptr;
   if (!pks || n_keys == 0) return BLSBN254_E_ARG;
@@ -32,11 +35,11 @@ static int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs,
   const size_t W = ks_nwords(n_keys);
   HIPCHK(c, k->aff.reserve(36 * n_keys * 4)); HIPCHK(c, k->bad.reserve(W * 4)); HIPCHK(c, k->skip.reserve(W * 4));
   HIPCHK(c, k->total.reserve(54 * 4)); HIPCHK(c, k->valid.reserve(n_keys)); HIPCHK(c, c->sub_ok.reserve(n_keys)); HIPCHK(c, k->enc.reserve(128 * n_keys));
-  TRY(upload(c, c->in_a, pks, 128 * n_keys));
+  TRY(stage_g2(c, pks, n_keys, compressed));
   if (proofs) {
     const size_t nb = (n_keys + 7) / 8;
     HIPCHK(c, k->pop.reserve(nb + 8)); HIPCHK(c, c->in_off.reserve(8 * (n_keys + 1))); HIPCHK(c, c->bitmap.reserve(nb + 8));
-    TRY(upload(c, c->in_b, proofs, 64 * n_keys));
+    TRY(stage_g1(c, proofs, n_keys, compressed));
     TRY(launch(c, c->stream, "iota_off", grid_lanes(n_keys + 1), k_iota_off, (uint64_t*)c->in_off.p, n_keys, (uint64_t)128));
     TRY(blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_a.p, (const uint64_t*)c->in_off.p,
                                                 (const uint8_t*)c->in_b.p, n_keys, pop_dst, pop_dst_len, (uint8_t*)c->bitmap.p));
@@ -67,13 +70,13 @@ static int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs,
   return 0;
 }
 int blsbn254_keyset_create(blsbn254_ctx* c, const uint8_t* pks, size_t n_keys, blsbn254_keyset** out) {
-  return ks_create(c, pks, nullptr, n_keys, nullptr, 0, out);
+  return ks_create(c, pks, nullptr, n_keys, nullptr, 0, out, false);
 }
 int blsbn254_keyset_create_checked(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
                                    blsbn254_keyset** out) {
   if (out) *out = nullptr;
   if (!proofs || (pop_dst_len && !pop_dst)) return BLSBN254_E_ARG;
-  return ks_create(c, pks, proofs, n_keys, pop_dst, pop_dst_len, out);
+  return ks_create(c, pks, proofs, n_keys, pop_dst, pop_dst_len, out, false);
 }
 int blsbn254_keyset_checked(const blsbn254_keyset* k) { return k && k->checked ? 1 : 0; }
 void blsbn254_keyset_destroy(blsbn254_keyset* k) {
@@ -177,13 +180,13 @@ int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid
 // bit g = blsbn254_fast_aggregate_verify_batch on the selected keys of row g: from the sums on, the same pipeline.  sel == nullptr:
 // the rows are staged in c->kset.sel already (the verify with a quorum has weighed them there)
 int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n_groups,
-                   const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+                   const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap, bool compressed) {
   uint32_t dl;
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off, n_groups));
   const size_t nb = (n_groups + 7) / 8;
   HIPCHK(c, c->gs_pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve(nb + 8));
-  TRY(upload(c, c->in_b, sigs, 64 * n_groups));
+  TRY(stage_g1(c, sigs, n_groups, compressed));
   size_t launches;
   if (sel) TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
   else TRY(ks_enqueue_sums_dev(c, k, (const uint8_t*)c->kset.sel.p, n_groups, &launches));

@@ -268,14 +268,18 @@ int blsbn254_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   if (!c || !off || (n && (!pks || !sigs || !bm)) || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
+  return verify_batch_rlc_host(c, pks, msgs, off, sigs, n, dst, dst_len, seed, bm, false);
+}
+int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n, const uint8_t* dst,
+                          size_t dst_len, const uint8_t* seed, uint8_t* bm, bool compressed) {
   uint32_t dl; int rc = stage_dst(c, dst, dst_len, &dl);
   if (rc) return rc;
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   const size_t nb = (n + 7) / 8;
   HIPCHK(c, c->bitmap.reserve(nb + 8));
-  TRY(upload(c, c->in_a, pks, 128 * n));
-  TRY(upload(c, c->in_b, sigs, 64 * n));
+  TRY(stage_g2(c, pks, n, compressed));
+  TRY(stage_g1(c, sigs, n, compressed));
   rc = stage_seed(c, seed);
   if (rc) return rc;
   // Repeated keys: per-key chunks as virtual tuples on the prepared-key path (k_rlc2.hip).  Batches beyond one launch chunk

@@ -513,12 +513,16 @@ int blsbn254_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* ms
   if (!c || !off || (n && (!pks || !sigs || !bm)) || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
+  return verify_batch_host(c, pks, msgs, off, sigs, n, dst, dst_len, bm, false);
+}
+int verify_batch_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n, const uint8_t* dst,
+                      size_t dst_len, uint8_t* bm, bool compressed) {
   int rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   size_t nb = (n + 7) / 8;
   HIPCHK(c, c->bitmap.reserve(nb + 8));
-  TRY(upload(c, c->in_a, pks, 128 * n));
-  TRY(upload(c, c->in_b, sigs, 64 * n));
+  TRY(stage_g2(c, pks, n, compressed));
+  TRY(stage_g1(c, sigs, n, compressed));
   rc = blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p,
                                  (const uint8_t*)c->in_b.p, n, dst, dst_len, (uint8_t*)c->bitmap.p);
   if (rc) return rc;

@@ -84,6 +84,9 @@ BN_KERNEL k_hash_to_scalar(const uint8_t* msgs, const uint64_t* off, size_t n, c
 BN_KERNEL k_iota_off(uint64_t* off, size_t n, uint64_t step);
 BN_KERNEL k_g1_codec(const uint8_t* in, size_t n, uint8_t* out, uint8_t* status, int mode);
 BN_KERNEL k_g2_codec(const uint8_t* in, size_t n, uint8_t* out, uint8_t* status, int mode);
+// compressed -> uncompressed per element (k_inflate.hip, inflate.h): the bytes or the marker to out, 1 / 0 to status (may be null)
+BN_KERNEL k_g1_inflate(const uint8_t* in, size_t n, uint8_t* out, uint8_t* status);
+BN_KERNEL k_g2_inflate(const uint8_t* in, size_t n, uint8_t* out, uint8_t* status);
 BN_KERNEL k_rlc_prep(const uint8_t* pks, const uint8_t* sigs, const int32_t* h_ws, const uint8_t* sub_ok, const uint8_t* seed,
                      size_t n, size_t n_pad, int32_t* a_ws, int32_t* b_ws, uint8_t* elig);
 BN_KERNEL k_fp12_mask_one(int32_t* f_ws, size_t stride, const uint8_t* elig, size_t n_pad);

@@ -230,6 +230,17 @@ class Engine:
                                                   ctypes.c_size_t(len(dst)), po))
         return o[:(n + 7) // 8].tobytes()
 
+    def verify_batch_compressed(self, pks, msgs, sigs, dst=DEFAULT_DST):
+        """verify_batch on compressed operands (64 bytes per key, 32 per signature): the bitmap verify_batch gives on the outputs
+        of g2_inflate_batch / g1_inflate_batch, inflated on the device; a key or signature that does not inflate clears its bit."""
+        n = len(msgs)
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(pks, 64 * n); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 32 * n); d, pd = _inbuf(dst)
+        o, po = _outbuf((n + 7) // 8)
+        self._chk(self._lib.blsbn254_verify_batch_compressed(self._ctx, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(n), pd,
+                                                             ctypes.c_size_t(len(dst)), po))
+        return o[:(n + 7) // 8].tobytes()
+
     def set_async_verify(self, on):
         """verify_batch_dev enqueues on the previous call's key count without reading the new one back first (default on)"""
         self._chk(self._lib.blsbn254_set_async_verify(self._ctx, ctypes.c_int(1 if on else 0)))
@@ -318,6 +329,17 @@ class Engine:
         o, po = _outbuf((n + 7) // 8)
         self._chk(self._lib.blsbn254_verify_batch_rlc(self._ctx, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(n), pd,
                                                       ctypes.c_size_t(len(dst)), psd, po))
+        return o[:(n + 7) // 8].tobytes()
+
+    def verify_batch_rlc_compressed(self, pks, msgs, sigs, dst=DEFAULT_DST, seed=None):
+        """verify_batch_rlc on compressed operands (64 bytes per key, 32 per signature); seed as there."""
+        n = len(msgs)
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(pks, 64 * n); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 32 * n); d, pd = _inbuf(dst)
+        sd, psd = self._seed_arg(seed)
+        o, po = _outbuf((n + 7) // 8)
+        self._chk(self._lib.blsbn254_verify_batch_rlc_compressed(self._ctx, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(n), pd,
+                                                                 ctypes.c_size_t(len(dst)), psd, po))
         return o[:(n + 7) // 8].tobytes()
 
     def aggregate_path_stats(self):
@@ -450,6 +472,18 @@ class Engine:
         a, pa = _inbuf(sel); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 64 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
         self._chk(self._lib.blsbn254_keyset_fast_aggregate_verify_batch(self._ctx, ks._h, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(g), pd,
                                                                         ctypes.c_size_t(len(dst)), po))
+        return o[:(g + 7) // 8].tobytes()
+
+    def keyset_fast_aggregate_verify_batch_compressed(self, ks, sel_rows, msgs, sigs, dst=DEFAULT_DST):
+        """keyset_fast_aggregate_verify_batch on compressed signatures (32 bytes per group); a signature that does not inflate
+        clears its group's bit.  ks: a KeySet of any registration."""
+        sel, g = self._keyset_rows(ks, sel_rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        data, off = pack_messages(msgs)
+        a, pa = _inbuf(sel); m, pm = _inbuf(data); s, ps = _inbuf(sigs, 32 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        self._chk(self._lib.blsbn254_keyset_fast_aggregate_verify_batch_compressed(self._ctx, ks._h, pa, pm, off.ctypes.data_as(_u64p), ps, ctypes.c_size_t(g),
+                                                                                   pd, ctypes.c_size_t(len(dst)), po))
         return o[:(g + 7) // 8].tobytes()
 
     def keyset_stats(self):
@@ -925,6 +959,20 @@ class Engine:
     def g2_compress_batch(self, g2, n): return self._codec(self._lib.blsbn254_g2_compress_batch, g2, n, 128, 64)
     def g2_decompress_batch(self, c, n): return self._codec(self._lib.blsbn254_g2_decompress_batch, c, n, 64, 128)
 
+    def _inflate(self, fn, data, n, isz):
+        a, pa = _inbuf(data, isz * n); o, po = _outbuf(2 * isz * n); st, pst = _outbuf(n)
+        self._chk(fn(self._ctx, pa, ctypes.c_size_t(n), po, pst))
+        return o[:2 * isz * n].tobytes(), st[:n].tobytes()
+
+    def g1_inflate_batch(self, c, n):
+        """The per-element form of g1_decompress_batch: (n x 64 bytes, n status bytes).  status 1: the element's uncompressed
+        bytes; status 0: it does not decode and its output is the marker, 64 bytes of 0xFF, which no entry point decodes."""
+        return self._inflate(self._lib.blsbn254_g1_inflate_batch, c, n, 32)
+
+    def g2_inflate_batch(self, c, n):
+        """As g1_inflate_batch for 64-byte compressed G2 elements: (n x 128 bytes, n status bytes)."""
+        return self._inflate(self._lib.blsbn254_g2_inflate_batch, c, n, 64)
+
     # ---- signing side (also used to generate large synthetic batches)
     def sign_batch(self, sks, msgs, dst=DEFAULT_DST):
         n = len(msgs)
@@ -1061,15 +1109,23 @@ class KeySet:
     """blsbn254_keyset: n_keys public keys registered once on the engine's GPU (decoded, curve-checked, with their total), to be
     summed by participation bitmaps (Engine.keyset_sum_batch, Engine.keyset_fast_aggregate_verify_batch).  With proofs (n_keys x
     64 bytes, as pop_prove_batch makes them) every key's proof of possession is verified under pop_dst at registration, and a
-    key whose proof fails is a bad key of the set, as one that does not decode."""
+    key whose proof fails is a bad key of the set, as one that does not decode.  compressed=True: pks are n_keys x 64 bytes and
+    proofs n_keys x 32 bytes in the compressed encodings; the set is the one their inflated bytes register (a proof still signs
+    the 128-byte uncompressed key)."""
 
-    def __init__(self, engine, pks, n_keys, proofs=None, pop_dst=POP_DST):
+    def __init__(self, engine, pks, n_keys, proofs=None, pop_dst=POP_DST, compressed=False):
         self._eng = engine
         self._lib = engine._lib
         self._lib.blsbn254_keyset_count.restype = ctypes.c_size_t
         self._lib.blsbn254_keyset_committee_count.restype = ctypes.c_size_t
         self._h = ctypes.c_void_p()
         self.n_cols = 0
+        if compressed:
+            a, pa = _inbuf(pks, 64 * n_keys); d, pd = _inbuf(pop_dst)
+            b, pb = (None, ctypes.cast(None, _u8p)) if proofs is None else _inbuf(proofs, 32 * n_keys)
+            engine._chk(self._lib.blsbn254_keyset_create_compressed(engine._ctx, pa, pb, ctypes.c_size_t(n_keys), pd, ctypes.c_size_t(len(pop_dst)),
+                                                                    ctypes.byref(self._h)))
+            return
         a, pa = _inbuf(pks, 128 * n_keys)
         if proofs is None:
             engine._chk(self._lib.blsbn254_keyset_create(engine._ctx, pa, ctypes.c_size_t(n_keys), ctypes.byref(self._h)))

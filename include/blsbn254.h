@@ -14,8 +14,11 @@
  *   Fr  32 B  big-endian (both directions; the reference's LE to_repr, E11, is not reproduced)
  *   identity: G1 = (0, 1), G2 = (0, 1); on input x == 0 means identity (g1.rs:352-353, g2.rs:377)
  *   Decoding is strict: a coordinate >= p is an error (the reference masks bit 255 of G1
- *   coordinates, g1.rs:346-347; not reproduced).  Compressed encodings are not accepted (the
- *   reference's G1 compressed codec is defective).
+ *   coordinates, g1.rs:346-347; not reproduced).
+ *   Compressed encodings (G1 32 B, G2 64 B, "compressed wire codecs" below) are accepted by exactly
+ *   the entry points whose names say so: blsbn254_g1/g2_decompress_batch, blsbn254_g1/g2_inflate_batch
+ *   and the *_compressed calls ("compressed input" below).  Every other entry point takes the
+ *   uncompressed formats above and nothing else.
  *   msgs = concatenated message bytes, off = n+1 offsets (off[i]..off[i+1] is message i).
  *   bitmaps: ceil(n/8) bytes, bit i of the batch = bit (i & 7) of byte i >> 3.
  *
@@ -654,6 +657,40 @@ int blsbn254_g1_compress_batch(blsbn254_ctx* ctx, const uint8_t* g1 /* n*64 */, 
 int blsbn254_g1_decompress_batch(blsbn254_ctx* ctx, const uint8_t* in /* n*32 */, size_t n, uint8_t* g1 /* n*64 */);
 int blsbn254_g2_compress_batch(blsbn254_ctx* ctx, const uint8_t* g2 /* n*128 */, size_t n, uint8_t* out /* n*64 */);
 int blsbn254_g2_decompress_batch(blsbn254_ctx* ctx, const uint8_t* in /* n*64 */, size_t n, uint8_t* g2 /* n*128 */);
+
+/* ---- compressed input: per-element inflation, and the verify / key-set calls on wire-format operands ---- */
+/* The per-element form of the decompress calls: a malformed element is never an error of the call.  Element i that decodes
+ * gives status[i] = 1 and the bytes blsbn254_g1/g2_decompress_batch give for it; one that does not (a coordinate >= p, or no
+ * point with that x) gives status[i] = 0 and THE MARKER, 0xFF in all of its 64 / 128 output bytes.  No entry point of this
+ * library decodes the marker (its coordinates are >= p), so the output may be fed to any of them and a malformed element is
+ * then treated as that entry point treats any undecodable one: a cleared bit in the verify calls, a bad key in a key set, its
+ * error code in the primitives.  Same rule as decompression otherwise: flag = parity of y / sgn0(y), x == 0 is the identity
+ * whatever the flag; G2 subgroup membership is not tested here.  Bad arguments (a null pointer with n > 0): BLSBN254_E_ARG, outputs untouched;
+ * n == 0: 0. */
+int blsbn254_g1_inflate_batch(blsbn254_ctx* ctx, const uint8_t* in /* n*32 */, size_t n, uint8_t* g1 /* n*64 */, uint8_t* status /* n */);
+int blsbn254_g2_inflate_batch(blsbn254_ctx* ctx, const uint8_t* in /* n*64 */, size_t n, uint8_t* g2 /* n*128 */, uint8_t* status /* n */);
+/* blsbn254_verify_batch / blsbn254_verify_batch_rlc on compressed public keys and signatures: the bitmap those calls give on
+ * the outputs of blsbn254_g2_inflate_batch(pks) and blsbn254_g1_inflate_batch(sigs) -- a key or signature that does not
+ * inflate clears its tuple's bit -- with the inflation done on the device between the upload and the pipeline: nothing but
+ * the bitmap comes back.  Chunking, size limits, argument errors and the meaning of seed are those of the uncompressed calls. */
+int blsbn254_verify_batch_compressed(blsbn254_ctx* ctx, const uint8_t* pks /* n*64 */, const uint8_t* msgs, const uint64_t* off,
+                                     const uint8_t* sigs /* n*32 */, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);
+int blsbn254_verify_batch_rlc_compressed(blsbn254_ctx* ctx, const uint8_t* pks /* n*64 */, const uint8_t* msgs, const uint64_t* off,
+                                         const uint8_t* sigs /* n*32 */, size_t n, const uint8_t* dst, size_t dst_len, const uint8_t seed[32],
+                                         uint8_t* valid_bitmap);
+/* Key-set registration from compressed keys: the handle blsbn254_keyset_create makes from the inflated keys, or, with proofs
+ * (non-null: compressed too, 32 bytes each), the handle blsbn254_keyset_create_checked makes from the inflated keys and proofs;
+ * every later call on the handle gives the bytes it gives on that one.  A key that does not inflate is a bad key of the handle,
+ * a proof that does not inflate is a failing proof.  A proof's MESSAGE stays the 128-byte UNCOMPRESSED encoding of its key, as
+ * blsbn254_pop_prove_batch signs it: compression changes how a proof travels, not what it signs.  proofs == NULL: pop_dst and
+ * pop_dst_len are ignored.  Limits and argument errors as the uncompressed registrations. */
+int blsbn254_keyset_create_compressed(blsbn254_ctx* ctx, const uint8_t* pks /* n_keys*64 */, const uint8_t* proofs /* n_keys*32 or NULL */,
+                                      size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len, blsbn254_keyset** out);
+/* blsbn254_keyset_fast_aggregate_verify_batch on compressed signatures: its bitmap on blsbn254_g1_inflate_batch(sigs).  keys:
+ * a handle of any of the three registrations. */
+int blsbn254_keyset_fast_aggregate_verify_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* sel,
+                                                           const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs /* n_groups*32 */,
+                                                           size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);
 
 /* ---- device-resident variants (plumbing for callers that already hold the batch in HBM) ----- */
 /* All d_* pointers are device pointers on ctx's GPU.  Work is enqueued on ctx's stream and is
