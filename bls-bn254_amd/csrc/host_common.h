@@ -21,6 +21,7 @@
 #include "keyset_merge_plan.h" // KmRepack, the argument walk of the checked merge over a key set
 #include "keyset_weight_plan.h" // KwRepack, the column-total check and the quorum rule of the weights over a key set
 #include "keyset_committee_plan.h" // KcTable, KcPlan: the committee tables of a key set and the plan of a call over them
+#include "keyset_committee_agg_plan.h" // KcaRepack, the argument walk of the checked aggregation per committee of a key set
 #include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
 #include "../../include/blsbn254.h"
 
@@ -154,6 +155,21 @@ struct BNH KcWs {
   std::vector<uint64_t> h_off;
   std::vector<uint32_t> h_com;
 };
+// checked signature aggregation per committee of a registered key set (host_keyset_committee_agg.hip, k_keyset_committee_agg.hip):
+// what KaggWs holds, with positions in place of indices; the groups' committees, the prefix of their row words and the byte
+// offsets of their rows (device buffers and the host copies they are uploaded from); for the fallback the registry indices the
+// positions resolve to.  Host side: the bits an attempt downloads, the groups that go to the fallback and their sub-call
+// (keyset_committee_agg_plan.h KcaRepack) with its signatures, messages, offsets and results.  The key sums run in KcWs.
+struct BNH KcaWs {
+  DevBuf com, pos, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits, ridx, wpre, roff;
+  GroupOff goff;
+  SegWs seg;
+  KcaRepack sub;
+  std::vector<uint64_t> h_wpre, h_roff;
+  std::vector<uint8_t> h_gbits, s_sigs, s_msgs, s_emsgs, s_out, s_rows;
+  std::vector<uint64_t> s_moff, s_emoff;
+  std::vector<size_t> fail;
+};
 // key-set FastAggregateVerify by random linear combination per message (host_keyset_rlc.hip, k_keyset_rlc.hip): the seed; per
 // group its committee and row offset (committee form), sorted position, chunk-size byte, eligibility byte and weight; per sorted
 // position its group; the weighted points A (27 x G limbs) and B (54 x G limbs) at their sorted positions with the (constant 1)
@@ -253,6 +269,7 @@ struct blsbn254_ctx {
   KmWs kmrg;
   KwWs kw;
   KcWs kcom;
+  KcaWs kcagg;
   KsrWs ksr;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
   uint64_t stat_kw[4] = {0, 0, 0, 0};    // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
@@ -260,6 +277,7 @@ struct blsbn254_ctx {
   size_t ksr_group = KSR_DEFAULT_GROUP;  // groups per chunk of the key-set RLC calls (blsbn254_set_keyset_rlc_group)
   uint64_t stat_ksr[6] = {0, 0, 0, 0, 0, 0};   // groups decided by a passed chunk, chunks checked, groups sent to the exact path after their chunk failed, groups sent there directly, message classes, calls
   uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
+  uint64_t stat_kcagg[4] = {0, 0, 0, 0}; // the same four counts of the checked aggregation per committee
   uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
@@ -480,6 +498,8 @@ BNH int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* v
 BNH int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
 BNH int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
 BNH void kc_tally(blsbn254_ctx* c, size_t n_groups);   // host_keyset_committee.hip
+// kc_enqueue_call behind its upload: the rows are ALREADY ON THE DEVICE at d_rows, row g at d_rows + (sel_off[g] - sel_off[0])
+BNH int kc_enqueue_call_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* d_rows, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
 // the full-width form's: the rows staged in c->kset.sel, the sums enqueued; ks_tally counts the call likewise
 BNH int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_t n_groups, size_t* launches);   // host_keyset.hip
 BNH void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches);   // host_keyset.hip

@@ -88,15 +88,20 @@ int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, cons
   if (n_groups > c->chunk) { c->last_error = "more groups than one launch chunk"; return BLSBN254_E_ARG; }
   return kc_check_rows(k->cm.tab, com, sel, sel_off, n_groups, c->last_error) ? 0 : BLSBN254_E_ARG;
 }
-// the call's rows staged, its plan made, its sums into c->gs_sum / c->gs_sum_ok in the caller's order (enqueued); the flip bytes
+// the call's rows staged (uploaded to c->kcom.sel), its plan made, its sums into c->gs_sum / c->gs_sum_ok in the caller's order (enqueued); the flip bytes
 // into c->kcom.h_flip (enqueued: read after the caller's synchronising download)
 int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups) {
   KcWs& w = c->kcom;
-  if (!kc_plan(k->cm.tab, com, sel_off, n_groups, c->chunk, w.plan, w.seg.h_start, w.seg.h_len)) { c->last_error = "internal: committee sums do not converge"; return BLSBN254_E_HIP; }
   TRY(upload(c, w.sel, sel + sel_off[0], sel_off[n_groups] - sel_off[0]));
+  return kc_enqueue_call_dev(c, k, com, (const uint8_t*)w.sel.p, sel_off, n_groups);
+}
+// the same behind the upload, for a caller whose rows are on the device already (host_keyset_committee_agg.hip)
+int kc_enqueue_call_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* d_rows, const uint64_t* sel_off, size_t n_groups) {
+  KcWs& w = c->kcom;
+  if (!kc_plan(k->cm.tab, com, sel_off, n_groups, c->chunk, w.plan, w.seg.h_start, w.seg.h_len)) { c->last_error = "internal: committee sums do not converge"; return BLSBN254_E_HIP; }
   HIPCHK(c, w.u.reserve(54 * 4 * n_groups)); HIPCHK(c, w.u_ok.reserve(n_groups));
   HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
-  TRY(kc_enqueue_sums(c, k, (const uint8_t*)w.sel.p, n_groups, false, {(int32_t*)w.u.p, n_groups, (uint8_t*)w.u_ok.p}));
+  TRY(kc_enqueue_sums(c, k, d_rows, n_groups, false, {(int32_t*)w.u.p, n_groups, (uint8_t*)w.u_ok.p}));
   TRY(launch(c, c->stream, "kc_finish", grid_lanes(n_groups), k_kc_finish, (const int32_t*)w.u.p, n_groups, n_groups, (const uint32_t*)w.scom.p, (const uint32_t*)w.order.p,
              (const int32_t*)k->cm.totals.p, k->cm.tab.com.size(), (const uint8_t*)w.flip.p, (const uint8_t*)w.ok.p, (int32_t*)c->gs_sum.p, n_groups, (uint8_t*)c->gs_sum_ok.p));
   w.h_flip.resize(n_groups);

@@ -195,6 +195,13 @@ BN_KERNEL k_kc_finish(const int32_t* u, size_t u_stride, size_t G, const uint32_
                       const uint8_t* flip, const uint8_t* ok, int32_t* out, size_t out_stride, uint8_t* ok_out);
 __global__ void __launch_bounds__(256) k_kc_weight(const uint8_t* rows, const uint64_t* grow, const uint32_t* gcom, const uint4* coms, const uint32_t* members,
                                                   const uint32_t* cvalid, const uint64_t* tab, uint32_t n_cols, size_t g_lo, size_t m, uint64_t* out);
+// checked signature aggregation per committee of a registered key set (k_keyset_committee_agg.hip)
+BN_KERNEL k_kca_scan(const uint32_t* cvalid, const uint4* coms, const uint32_t* com, const uint32_t* goff, uint32_t ng, const uint32_t* pos, const uint8_t* sigs,
+                     const uint8_t* mask, size_t m, uint32_t lo, size_t N, uint8_t* cand, int32_t* pts);
+__global__ void __launch_bounds__(256) k_kca_rows(const uint32_t* pos, const uint8_t* cand, const uint32_t* goff, const uint64_t* wpre, const uint64_t* roff,
+                                                 const uint4* coms, const uint32_t* com, uint32_t ng, size_t m, uint64_t lo, uint8_t* rows);
+__global__ void __launch_bounds__(256) k_kca_resolve(const uint32_t* members, const uint4* coms, const uint32_t* com, const uint32_t* goff, uint32_t ng,
+                                                    const uint32_t* pos, size_t m, uint32_t lo, uint32_t* idx);
 // key-set FastAggregateVerify by random linear combination per message (k_keyset_rlc.hip)
 BN_KERNEL k_ksr_elig(const uint8_t* rows, const uint64_t* row_off, uint32_t n_keys, const uint32_t* com, const uint4* coms, const uint32_t* skip,
                      const uint32_t* valid, const int32_t* sums, const uint8_t* sum_ok, size_t G, const uint8_t* sigs, const uint8_t* seed,

@@ -663,6 +663,56 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_aggregate_stats(self._ctx, o))
         return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_signatures": int(o[2]), "short_groups": int(o[3])}
 
+    def keyset_committee_aggregate_checked_batch(self, ks, com, entry_sets, msgs, dst=DEFAULT_DST):
+        """keyset_aggregate_checked_batch per committee of a KeySet (KeySet.set_committees): group g names committee com[g], and
+        entry_sets[g] = the signatures received for msgs[g], a list of (position, 64-byte signature) pairs or a dict {position:
+        signature}, a position counting in the committee's member list (sorted by position here; a repeated position raises
+        ValueError).  Returns (out_sigs, rows, status): 64 bytes and one status byte per group, and rows as a list of per-group
+        byte strings of ceil(size(com[g]) / 8) bytes each, bit j = member j is in the aggregate -- ready for
+        keyset_committee_fast_aggregate_verify_batch(ks, com, rows, msgs, out_sigs).  Signatures and statuses are those of
+        keyset_aggregate_checked_batch on the entries translated to registry indices; no exception for a bad group."""
+        g = len(msgs)
+        if len(entry_sets) != g or len(com) != g:
+            raise ValueError("one committee index and one set of entries per message")
+        sizes = getattr(ks, "_com_sizes", [])
+        com = [int(x) for x in com]
+        if any(x < 0 or x >= len(sizes) for x in com):
+            raise ValueError("a group names a committee the key set does not have")
+        pos, sigs, soff = [], [], np.zeros(g + 1, dtype=np.uint64)
+        for i, es in enumerate(entry_sets):
+            es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
+            if any(a[0] == b[0] for a, b in zip(es, es[1:])):
+                raise ValueError("entry set %d names a position twice" % i)
+            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != 64 for _, s in es):
+                raise ValueError("an entry is (position, 64 signature bytes)")
+            pos += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
+            soff[i + 1] = len(pos)
+        rbs = [(sizes[x] + 7) // 8 for x in com]
+        sel_off = np.zeros(g + 1, dtype=np.uint64)
+        if g:
+            sel_off[1:] = np.cumsum(rbs, dtype=np.uint64)
+        total = int(sel_off[g])
+        ca = np.asarray(com if com else [0], dtype=np.uint32)
+        pa = np.asarray(pos if pos else [0], dtype=np.uint32)
+        data, moff = pack_messages(msgs)
+        s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
+        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        r = np.zeros(max(total, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
+        st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._chk(self._lib.blsbn254_keyset_committee_aggregate_checked_batch(self._ctx, ks._h, ca.ctypes.data_as(u32p), pa.ctypes.data_as(u32p), ps,
+                                                                              soff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p),
+                                                                              sel_off.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)),
+                                                                              po, pr, pst))
+        raw = r[:total].tobytes()
+        return o[:64 * g].tobytes(), [raw[int(sel_off[i]):int(sel_off[i + 1])] for i in range(g)], st[:g].tobytes()
+
+    def keyset_committee_aggregate_stats(self):
+        """the counts of keyset_aggregate_stats for keyset_committee_aggregate_checked_batch"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_committee_aggregate_stats(self._ctx, o))
+        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_signatures": int(o[2]), "short_groups": int(o[3])}
+
     def keyset_merge_checked_batch(self, ks, contributions, msgs, dst=DEFAULT_DST):
         """The call of an intermediate node of an aggregation tree: contributions[g] = the partial aggregates received for
         msgs[g], a list of (row, 64-byte signature) pairs in the order of their priority, a row being ceil(n_keys / 8) bytes

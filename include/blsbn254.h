@@ -464,6 +464,40 @@ int blsbn254_keyset_committee_fast_aggregate_verify_batch(blsbn254_ctx* ctx, con
 int blsbn254_keyset_committee_weight_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com /* n_groups */,
         const uint8_t* sel, const uint64_t* sel_off /* n_groups+1, bytes */, size_t n_groups, uint64_t* out /* n_groups*n_cols */);
 int blsbn254_keyset_committee_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* Checked signature aggregation PER COMMITTEE of a registered key set -- blsbn254_keyset_aggregate_checked_batch for the collector
+ * whose signatures arrive per committee: nothing in the call is as wide as the registry.  Group g is committee com[g] of the
+ * handle's table (blsbn254_keyset_set_committees), one message msgs[msg_off[g] .. msg_off[g + 1]) and the entries sig_off[g] ..
+ * sig_off[g + 1]: entry s says that member pos[s] of the committee signed with sigs[64 s ..].  pos[s] is a POSITION in the
+ * committee's member list, not a registry index; inside a group the positions must be STRICTLY INCREASING.  sig_off / msg_off /
+ * sel_off: n_groups + 1 non-decreasing element / byte / byte offsets, host arrays, which need not start at 0 (pos, sigs and msgs
+ * are indexed by them as given; out_sigs and status are indexed from the first group).  sel_off is an INPUT: row g of out_sel is
+ * written at out_sel + (sel_off[g] - sel_off[0]) and must be exactly ceil(size(com[g]) / 8) bytes long, the row rule of the three
+ * read-side committee calls -- so (com, out_sel, sel_off) go unchanged to blsbn254_keyset_committee_fast_aggregate_verify_batch or
+ * its _rlc form.  Bit j of a row = member j of the committee is in the aggregate.
+ * For every group out_sigs[64 g ..] and status[g] are byte for byte what blsbn254_keyset_aggregate_checked_batch returns for the
+ * same group with every entry translated to idx = members[com_off[com[g]] + pos] (and the entries re-sorted by idx: members may be
+ * listed in any order, and the aggregate's affine encoding does not depend on the order of addition), and bit j of the row is set
+ * exactly when bit members[com_off[com[g]] + j] of that call's row is.  Everything said there carries over: the candidate rule
+ * (the key has the KeyValidate bit, the signature decodes, is on the curve and is not the identity), entries left out silently,
+ * the one optimistic equation per group, the fallback that verifies every candidate of a failing group and runs the one equation
+ * again, BLSBN254_ST_SHORT with the identity encoding and a zero row (P and -P both signing included), cancelling errors that
+ * are both used, a group's outcome depending on its own inputs only, pending asynchronous verifies settled on entry.
+ * BLSBN254_E_ARG (with a last_error text; the outputs are untouched and nothing was enqueued): NULL arguments, a key set of
+ * another context, a handle without a committee table, com[g] >= n_com, pos[s] >= size(com[g]) (the text names the entry),
+ * positions of a group that do not strictly increase (the text names the group), decreasing offsets, a row length other than
+ * ceil(size / 8), more than 2^23 entries, n_groups above BLSBN254_CHUNK_LANES.  n_groups == 0 returns 0.
+ * The groups of this call count in none of blsbn254_keyset_stats, blsbn254_keyset_aggregate_stats and
+ * blsbn254_keyset_committee_stats; blsbn254_keyset_committee_aggregate_stats, since the context was created: out[0] groups settled
+ * by the optimistic attempt, out[1] groups sent to the fallback, out[2] signatures verified individually, out[3] groups ending in
+ * BLSBN254_ST_SHORT. */
+int blsbn254_keyset_committee_aggregate_checked_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint32_t* com /* n_groups */,
+        const uint32_t* pos /* N */, const uint8_t* sigs /* N*64 */, const uint64_t* sig_off /* n_groups+1 */,
+        const uint8_t* msgs, const uint64_t* msg_off /* n_groups+1, bytes */,
+        const uint64_t* sel_off /* n_groups+1, bytes */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len,
+        uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* sel_off[n_groups]-sel_off[0] */, uint8_t* status /* n_groups */);
+int blsbn254_keyset_committee_aggregate_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* blsbn254_keyset_fast_aggregate_verify_batch and blsbn254_keyset_committee_fast_aggregate_verify_batch by RANDOM LINEAR
  * COMBINATION PER MESSAGE: the same arguments plus a seed, the same bitmap.  The groups of a call whose messages are
  * byte-identical form a class; a class, in the caller's order, is cut into chunks of at most C groups (default 64,

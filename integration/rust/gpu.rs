@@ -536,6 +536,37 @@ pub fn keyset_aggregate_checked_batch(keys: &KeySet, entries: &[Vec<(u32, [u8; 6
     (0..n).map(|g| if status[g] == 0 { Some((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), sel[rb * g..rb * g + rb].to_vec())) } else { None }).collect()
 }
 
+/// `keyset_aggregate_checked_batch` per committee of the handle's table (`blsbn254_keyset_committee_aggregate_checked_batch`):
+/// `groups[g]` = `(committee, its number of members, the (position in its member list, signature) pairs received for msgs[g])`,
+/// sorted here by position (a repeated position panics).  Element g = `Some((aggregate signature, participation row of
+/// ceil(members / 8) bytes))`, the row and signature the committee form of the verify accepts for the message, or `None` when
+/// nothing usable is left (`BLSBN254_ST_SHORT`).  Bad signatures are left out, never an error.
+pub fn keyset_committee_aggregate_checked_batch(keys: &KeySet, groups: &[(u32, usize, Vec<(u32, [u8; 64])>)], msgs: &[&[u8]], dst: &[u8])
+    -> Vec<Option<([u8; 64], Vec<u8>)>> {
+    assert_eq!(groups.len(), msgs.len());
+    let n = msgs.len();
+    let (mut com, mut pos, mut sg, mut soff, mut roff) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<u8>::new(), vec![0u64], vec![0u64]);
+    for (c, size, e) in groups {
+        let mut e = e.clone();
+        e.sort_by_key(|p| p.0);
+        assert!(e.windows(2).all(|w| w[0].0 < w[1].0), "a position is repeated");
+        for (k, s) in &e { pos.push(*k); sg.extend_from_slice(s); }
+        com.push(*c);
+        soff.push(pos.len() as u64);
+        roff.push(roff[roff.len() - 1] + ((size + 7) / 8) as u64);
+    }
+    let (data, moff) = pack(msgs);
+    let (mut out, mut sel, mut status) = (vec![0u8; 64 * n], vec![0u8; roff[n] as usize], vec![0u8; n]);
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_keyset_committee_aggregate_checked_batch(c, keys.0, com.as_ptr(), pos.as_ptr(), sg.as_ptr(), soff.as_ptr(), data.as_ptr(), moff.as_ptr(),
+                                                               roff.as_ptr(), n, dst.as_ptr(), dst.len(), out.as_mut_ptr(), sel.as_mut_ptr(), status.as_mut_ptr())
+    }))
+    .expect("no committee table, a committee or position out of range, or a wrong member count");
+    (0..n).map(|g| if status[g] == 0 {
+        Some((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), sel[roff[g] as usize..roff[g + 1] as usize].to_vec()))
+    } else { None }).collect()
+}
+
 /// What an intermediate node of an aggregation tree hands on (`blsbn254_keyset_merge_checked_batch`): `contributions[g]` =
 /// the partial aggregates received for `msgs[g]`, each a `(row, signature)` pair with a row of `ceil(keys.len() / 8)` bytes,
 /// in the order of their priority (kept).  Element g = `Some((merged signature, merged row, used flag per contribution))`,
