@@ -22,6 +22,7 @@
 #include "keyset_weight_plan.h" // KwRepack, the column-total check and the quorum rule of the weights over a key set
 #include "keyset_committee_plan.h" // KcTable, KcPlan: the committee tables of a key set and the plan of a call over them
 #include "keyset_committee_agg_plan.h" // KcaRepack, the argument walk of the checked aggregation per committee of a key set
+#include "keyset_committee_merge_plan.h" // KcmRepack, the argument walk of the checked merge per committee of a key set
 #include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
 #include "../../include/blsbn254.h"
 
@@ -170,6 +171,23 @@ struct BNH KcaWs {
   std::vector<uint64_t> s_moff, s_emoff;
   std::vector<size_t> fail;
 };
+// checked merge of partial aggregates per committee of a registered key set (host_keyset_committee_merge.hip,
+// k_keyset_committee_merge.hip): what KmWs holds, with ragged rows (the merged rows in urows at the caller's sel_off positions);
+// the groups' committees and the byte offsets of their contribution rows and of their merged rows (device buffers and the host
+// copies they are uploaded from); for the fallback the committee and the row offset of every contribution.  Host side: what an
+// attempt downloads, the groups that go to the fallback and their sub-call (keyset_committee_merge_plan.h KcmRepack) with its
+// messages, offsets and results.  The key sums run in KcWs.
+struct BNH KcmWs {
+  DevBuf com, rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits, rbase, roff;
+  GroupOff goff;
+  SegWs seg;
+  KcmRepack sub;
+  std::vector<uint64_t> h_rbase, h_roff, h_coff;
+  std::vector<uint32_t> h_ccom;
+  std::vector<uint8_t> h_gbits, h_used, h_cand, s_msgs, s_emsgs, s_out, s_rows;
+  std::vector<uint64_t> s_moff, s_emoff;
+  std::vector<size_t> fail;
+};
 // key-set FastAggregateVerify by random linear combination per message (host_keyset_rlc.hip, k_keyset_rlc.hip): the seed; per
 // group its committee and row offset (committee form), sorted position, chunk-size byte, eligibility byte and weight; per sorted
 // position its group; the weighted points A (27 x G limbs) and B (54 x G limbs) at their sorted positions with the (constant 1)
@@ -270,6 +288,7 @@ struct blsbn254_ctx {
   KwWs kw;
   KcWs kcom;
   KcaWs kcagg;
+  KcmWs kcmrg;
   KsrWs ksr;
   uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
   uint64_t stat_kw[4] = {0, 0, 0, 0};    // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
@@ -279,6 +298,7 @@ struct blsbn254_ctx {
   uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
   uint64_t stat_kcagg[4] = {0, 0, 0, 0}; // the same four counts of the checked aggregation per committee
   uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
+  uint64_t stat_kcmrg[4] = {0, 0, 0, 0}; // the same four counts of the checked merge per committee
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches

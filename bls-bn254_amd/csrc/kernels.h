@@ -202,6 +202,10 @@ __global__ void __launch_bounds__(256) k_kca_rows(const uint32_t* pos, const uin
                                                  const uint4* coms, const uint32_t* com, uint32_t ng, size_t m, uint64_t lo, uint8_t* rows);
 __global__ void __launch_bounds__(256) k_kca_resolve(const uint32_t* members, const uint4* coms, const uint32_t* com, const uint32_t* goff, uint32_t ng,
                                                     const uint32_t* pos, size_t m, uint32_t lo, uint32_t* idx);
+// checked merge of partial aggregates per committee of a registered key set (k_keyset_committee_merge.hip)
+__global__ void __launch_bounds__(256) k_kcm_select(const uint8_t* rows, const uint8_t* sig_ok, const uint8_t* mask, const uint32_t* goff, const uint32_t* com,
+                                                   const uint4* coms, const uint32_t* cvalid, const uint64_t* rbase, const uint64_t* roff, size_t g_lo, size_t m,
+                                                   uint8_t* flags, uint8_t* urows);
 // key-set FastAggregateVerify by random linear combination per message (k_keyset_rlc.hip)
 BN_KERNEL k_ksr_elig(const uint8_t* rows, const uint64_t* row_off, uint32_t n_keys, const uint32_t* com, const uint4* coms, const uint32_t* skip,
                      const uint32_t* valid, const int32_t* sums, const uint8_t* sum_ok, size_t G, const uint8_t* sigs, const uint8_t* seed,

@@ -762,6 +762,64 @@ class Engine:
         self._chk(self._lib.blsbn254_keyset_merge_stats(self._ctx, o))
         return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_contributions": int(o[2]), "short_groups": int(o[3])}
 
+    def keyset_committee_merge_checked_batch(self, ks, com, groups, msgs, dst=DEFAULT_DST):
+        """keyset_merge_checked_batch per committee of a KeySet (KeySet.set_committees): group g names committee com[g], and
+        groups[g] = the partial aggregates received for msgs[g], a list of (row, 64-byte signature) pairs in the order of their
+        priority, a row being ceil(size(com[g]) / 8) bytes, bit j = member j of the committee is in it, or an iterable of
+        positions in the committee's member list.  The order is kept.  Returns (out_sigs, rows, used, status): 64 bytes and one
+        status byte per group, per group the list of its contributions' used flags, and rows as a list of per-group byte strings
+        of ceil(size(com[g]) / 8) bytes each -- ready for keyset_committee_fast_aggregate_verify_batch(ks, com, rows, msgs,
+        out_sigs), and the (rows, out_sigs) of keyset_committee_aggregate_checked_batch are contributions of this call as they
+        are.  Signatures, statuses and used flags are those of keyset_merge_checked_batch on the rows scattered over the
+        registry; no exception for a bad contribution or group."""
+        g = len(msgs)
+        if len(groups) != g or len(com) != g:
+            raise ValueError("one committee index and one list of contributions per message")
+        sizes = getattr(ks, "_com_sizes", [])
+        com = [int(x) for x in com]
+        if any(x < 0 or x >= len(sizes) for x in com):
+            raise ValueError("a group names a committee the key set does not have")
+        rows, sigs = [], []
+        coff, roff, sel_off = (np.zeros(g + 1, dtype=np.uint64) for _ in range(3))
+        for i, cs in enumerate(groups):
+            n, rb = sizes[com[i]], (sizes[com[i]] + 7) // 8
+            for row, sig in cs:
+                if not isinstance(row, (bytes, bytearray, memoryview)):
+                    r = bytearray(rb)
+                    for k in row:
+                        k = int(k)
+                        if k < 0 or k >= n:
+                            raise ValueError("a row names no member of the committee")
+                        r[k >> 3] |= 1 << (k & 7)
+                    row = r
+                if len(row) != rb or len(sig) != 64:
+                    raise ValueError("a contribution is (row of %d bytes or positions, 64 signature bytes)" % rb)
+                rows.append(bytes(row)); sigs.append(bytes(sig))
+            coff[i + 1] = len(rows)
+            roff[i + 1] = int(roff[i]) + rb * (len(rows) - int(coff[i]))
+            sel_off[i + 1] = int(sel_off[i]) + rb
+        nc, total = len(rows), int(sel_off[g])
+        ca = np.asarray(com if com else [0], dtype=np.uint32)
+        data, moff = pack_messages(msgs)
+        a, pa = _inbuf(b"".join(rows)); s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
+        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        r = np.zeros(max(total, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
+        u = np.zeros((nc + 7) // 8 + 1, dtype=np.uint8); pu = u.ctypes.data_as(_u8p)
+        st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_keyset_committee_merge_checked_batch(self._ctx, ks._h, ca.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pa,
+                                                                          roff.ctypes.data_as(_u64p), ps, coff.ctypes.data_as(_u64p), pm,
+                                                                          moff.ctypes.data_as(_u64p), sel_off.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd,
+                                                                          ctypes.c_size_t(len(dst)), po, pr, pu, pst))
+        used = [[bool((u[t >> 3] >> (t & 7)) & 1) for t in range(int(coff[i]), int(coff[i + 1]))] for i in range(g)]
+        raw = r[:total].tobytes()
+        return o[:64 * g].tobytes(), [raw[int(sel_off[i]):int(sel_off[i + 1])] for i in range(g)], used, st[:g].tobytes()
+
+    def keyset_committee_merge_stats(self):
+        """the counts of keyset_merge_stats for keyset_committee_merge_checked_batch"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_keyset_committee_merge_stats(self._ctx, o))
+        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_contributions": int(o[2]), "short_groups": int(o[3])}
+
     def aggregate_verify_batch(self, key_sets, msg_sets, agg_sigs, dst=DEFAULT_DST):
         """Many independent aggregate signatures in one call.  key_sets: list of byte strings (each a multiple of 128 bytes: the
         keys of one group); msg_sets: one list of messages per group, as many as the group has keys; agg_sigs: 64 bytes per group.

@@ -498,6 +498,48 @@ int blsbn254_keyset_committee_aggregate_checked_batch(blsbn254_ctx* ctx, const b
         const uint8_t* dst, size_t dst_len,
         uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* sel_off[n_groups]-sel_off[0] */, uint8_t* status /* n_groups */);
 int blsbn254_keyset_committee_aggregate_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* Checked merge of partial aggregates PER COMMITTEE of a registered key set -- blsbn254_keyset_merge_checked_batch for the
+ * intermediate node whose partial aggregates arrive per committee: nothing in the call is as wide as the registry.  Group g is
+ * committee com[g] of the handle's table (blsbn254_keyset_set_committees), one message msgs[msg_off[g] .. msg_off[g + 1]) and the
+ * contributions con_off[g] .. con_off[g + 1]: contribution s brings the signature sigs[64 s ..] and a row of exactly
+ * rb_g = ceil(size(com[g]) / 8) bytes, bit j (LSB-first) = member j of the committee is in the contribution.  The rows of a
+ * group lie back to back from rows + row_off[g], in contribution order: row_off[g + 1] - row_off[g] must equal
+ * (con_off[g + 1] - con_off[g]) * rb_g.  con_off / row_off / msg_off / sel_off: n_groups + 1 non-decreasing element / byte /
+ * byte / byte offsets, host arrays, none of which needs to start at 0 (rows, sigs and msgs are indexed by them as given);
+ * out_sigs and status are indexed from the first group of the call, the bits of `used` from its first contribution.  sel_off
+ * is an INPUT, exactly as in blsbn254_keyset_committee_aggregate_checked_batch: row g of out_sel is written at
+ * out_sel + (sel_off[g] - sel_off[0]) and is rb_g bytes long -- so the outputs of that call from several collectors,
+ * concatenated, are the input of this one, and (com, out_sel, sel_off) go unchanged to
+ * blsbn254_keyset_committee_fast_aggregate_verify_batch, its _rlc form and blsbn254_keyset_committee_weight_batch.
+ * The call behaves as blsbn254_keyset_merge_checked_batch on the same handle with every contribution row replaced by its
+ * SCATTERED row, the row with bit members[com_off[com[g]] + j] set for every set bit j (members of one committee are distinct:
+ * disjoint in positions is disjoint in registry indices, and the greedy selection is the same): out_sigs[64 g ..] and status[g]
+ * are byte for byte what that call returns, the bits of `used` are the same bits, and bit j of the row of out_sel is set exactly
+ * when bit members[com_off[com[g]] + j] of that call's row is.  Everything said there carries over: the candidate rule (the
+ * signature decodes, is on the curve and is not the identity, the row is not empty, every selected key has the KeyValidate
+ * bit), greedy selection in the order given, what is left out silently, the one optimistic equation per group, the fallback
+ * that verifies EVERY candidate of a failing group on its own and then selects again with those bits as the mask,
+ * BLSBN254_ST_SHORT with the identity encoding, a zero row and no bit of `used` (kept keys that sum to the identity included),
+ * cancelling errors that are both used, a group's outcome depending on its own inputs only, pending asynchronous verifies
+ * settled on entry.
+ * BLSBN254_E_ARG (with a last_error text; the outputs are untouched and nothing was enqueued): NULL arguments, a key set of
+ * another context, a handle without a committee table, com[g] >= n_com (the text names the group), a row_off span that is not
+ * count * rb_g or a sel_off span that is not rb_g (the text names the group), a row that sets a bit past the committee's last
+ * member (the text names the contribution, counted from the first of the call), decreasing offsets in any of the four arrays,
+ * more than 2^23 contributions, more than 2^30 bytes of rows, n_groups above BLSBN254_CHUNK_LANES.  n_groups == 0 returns 0.
+ * The groups of this call count in none of the other stats calls; blsbn254_keyset_committee_merge_stats, since the context was
+ * created: out[0] groups settled by the optimistic attempt, out[1] groups sent to the fallback, out[2] contributions verified
+ * individually, out[3] groups ending in BLSBN254_ST_SHORT. */
+int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* ctx, const blsbn254_keyset* keys,
+        const uint32_t* com /* n_groups */,
+        const uint8_t* rows, const uint64_t* row_off /* n_groups+1, bytes */,
+        const uint8_t* sigs /* N*64 */, const uint64_t* con_off /* n_groups+1 */,
+        const uint8_t* msgs, const uint64_t* msg_off /* n_groups+1, bytes */,
+        const uint64_t* sel_off /* n_groups+1, bytes */, size_t n_groups,
+        const uint8_t* dst, size_t dst_len,
+        uint8_t* out_sigs /* n_groups*64 */, uint8_t* out_sel /* sel_off[n_groups]-sel_off[0] */,
+        uint8_t* used /* ceil(N/8) */, uint8_t* status /* n_groups */);
+int blsbn254_keyset_committee_merge_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* blsbn254_keyset_fast_aggregate_verify_batch and blsbn254_keyset_committee_fast_aggregate_verify_batch by RANDOM LINEAR
  * COMBINATION PER MESSAGE: the same arguments plus a seed, the same bitmap.  The groups of a call whose messages are
  * byte-identical form a class; a class, in the caller's order, is cut into chunks of at most C groups (default 64,

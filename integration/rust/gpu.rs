@@ -598,6 +598,45 @@ pub fn keyset_merge_checked_batch(keys: &KeySet, contributions: &[Vec<(Vec<u8>, 
     } else { None }).collect()
 }
 
+/// `keyset_merge_checked_batch` per committee of the handle's table (`blsbn254_keyset_committee_merge_checked_batch`):
+/// `groups[g]` = `(committee, its number of members, the (row, signature) pairs received for msgs[g])`, a row being
+/// `ceil(members / 8)` bytes with bit j = member j of the committee, in the order of their priority (kept).  The pairs
+/// `keyset_committee_aggregate_checked_batch` hands out are contributions of this call as they are.  Element g =
+/// `Some((merged signature, merged row of ceil(members / 8) bytes, used flag per contribution))`, the row and signature the
+/// committee form of the verify accepts for the message, or `None` when nothing usable is left (`BLSBN254_ST_SHORT`).
+/// Selection is greedy over disjoint rows; bad contributions are left out, never an error.
+pub fn keyset_committee_merge_checked_batch(keys: &KeySet, groups: &[(u32, usize, Vec<(Vec<u8>, [u8; 64])>)], msgs: &[&[u8]], dst: &[u8])
+    -> Vec<Option<([u8; 64], Vec<u8>, Vec<bool>)>> {
+    assert_eq!(groups.len(), msgs.len());
+    let n = msgs.len();
+    let (mut com, mut rows, mut sg) = (Vec::<u32>::new(), Vec::<u8>::new(), Vec::<u8>::new());
+    let (mut coff, mut roff, mut soff) = (vec![0u64], vec![0u64], vec![0u64]);
+    for (c, size, cs) in groups {
+        let rb = (size + 7) / 8;
+        for (r, s) in cs {
+            assert_eq!(r.len(), rb, "a row is ceil(members / 8) bytes");
+            rows.extend_from_slice(r); sg.extend_from_slice(s);
+        }
+        com.push(*c);
+        coff.push((sg.len() / 64) as u64);
+        roff.push(rows.len() as u64);
+        soff.push(soff[soff.len() - 1] + rb as u64);
+    }
+    let total = sg.len() / 64;
+    let (data, moff) = pack(msgs);
+    let (mut out, mut sel, mut used, mut status) = (vec![0u8; 64 * n], vec![0u8; soff[n] as usize], vec![0u8; (total + 7) / 8], vec![0u8; n]);
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_keyset_committee_merge_checked_batch(c, keys.0, com.as_ptr(), rows.as_ptr(), roff.as_ptr(), sg.as_ptr(), coff.as_ptr(), data.as_ptr(),
+                                                           moff.as_ptr(), soff.as_ptr(), n, dst.as_ptr(), dst.len(), out.as_mut_ptr(), sel.as_mut_ptr(),
+                                                           used.as_mut_ptr(), status.as_mut_ptr())
+    }))
+    .expect("no committee table, a committee out of range, a wrong member count, or a padding bit is set");
+    (0..n).map(|g| if status[g] == 0 {
+        let flags = (coff[g] as usize..coff[g + 1] as usize).map(|s| (used[s >> 3] >> (s & 7)) & 1 == 1).collect();
+        Some((out[64 * g..64 * g + 64].try_into().expect("64 bytes"), sel[soff[g] as usize..soff[g + 1] as usize].to_vec(), flags))
+    } else { None }).collect()
+}
+
 // ---------------------------------------------------------------- N GPUs of one node
 
 /// All GPUs named in `BLSBN254_DEVICES` (comma-separated HIP ordinals, default "0"): one context and one host thread per
