@@ -107,9 +107,11 @@ struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; 
 // the levels between them, the sums' encodings, the groups' rows, their verification bits, the entry offsets; for the fallback
 // the gathered keys and the bits of the per-signature verification.  Host side: the bits and rows an attempt downloads, the
 // groups that go to the fallback and their sub-call (keyset_agg.h KaRepack) with its signatures, messages (one per group for the
-// equation, one per entry for the per-signature verification), offsets and results.
+// equation, one per entry for the per-signature verification), offsets and results.  The wire-format form: the
+// 32-byte signatures as uploaded (wire; the optimistic attempt reads them where they are, the fallback inflates them into sigs)
+// and the sums' compressed encodings (wout).
 struct BNH KaggWs {
-  DevBuf idx, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits;
+  DevBuf idx, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits, wire, wout;
   GroupOff goff;
   SegWs seg;
   KaRepack sub;
@@ -123,9 +125,10 @@ struct BNH KaggWs {
 // the groups' merged rows, their verification bits, the contribution offsets; for the fallback the bits of the per-contribution
 // verification.  Host side: what an attempt downloads, the groups that go to the fallback and their sub-call (keyset_merge_plan.h
 // KmRepack) with its messages (one per group for the equation, one per contribution for the per-contribution verification),
-// offsets and results.
+// offsets and results.  The wire-format form: the 32-byte signatures as uploaded (wire, inflated into sigs) and the
+// sums' compressed encodings (wout).
 struct BNH KmWs {
-  DevBuf rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits;
+  DevBuf rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits, wire, wout;
   GroupOff goff;
   SegWs seg;
   KmRepack sub;
@@ -160,9 +163,10 @@ struct BNH KcWs {
 // what KaggWs holds, with positions in place of indices; the groups' committees, the prefix of their row words and the byte
 // offsets of their rows (device buffers and the host copies they are uploaded from); for the fallback the registry indices the
 // positions resolve to.  Host side: the bits an attempt downloads, the groups that go to the fallback and their sub-call
-// (keyset_committee_agg_plan.h KcaRepack) with its signatures, messages, offsets and results.  The key sums run in KcWs.
+// (keyset_committee_agg_plan.h KcaRepack) with its signatures, messages, offsets and results.  The key sums run in KcWs.  wire /
+// wout: as in KaggWs.
 struct BNH KcaWs {
-  DevBuf com, pos, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits, ridx, wpre, roff;
+  DevBuf com, pos, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits, ridx, wpre, roff, wire, wout;
   GroupOff goff;
   SegWs seg;
   KcaRepack sub;
@@ -176,9 +180,9 @@ struct BNH KcaWs {
 // the groups' committees and the byte offsets of their contribution rows and of their merged rows (device buffers and the host
 // copies they are uploaded from); for the fallback the committee and the row offset of every contribution.  Host side: what an
 // attempt downloads, the groups that go to the fallback and their sub-call (keyset_committee_merge_plan.h KcmRepack) with its
-// messages, offsets and results.  The key sums run in KcWs.
+// messages, offsets and results.  The key sums run in KcWs.  wire / wout: as in KmWs.
 struct BNH KcmWs {
-  DevBuf com, rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits, rbase, roff;
+  DevBuf com, rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits, rbase, roff, wire, wout;
   GroupOff goff;
   SegWs seg;
   KcmRepack sub;
@@ -379,6 +383,10 @@ static inline int seg_run_levels(const SegWs& w, const std::vector<SegLevel>& le
 }
 // G1Affine::identity on the wire: x = 0, y = 1
 static inline void g1_identity_bytes(uint8_t o[64]) { std::memset(o, 0, 64); o[63] = 1; }
+// ... and compressed (g1_compress of it): x = 0 with the parity of y = 1 as the flag
+static inline void g1_identity_wire(uint8_t o[32]) { std::memset(o, 0, 32); o[0] = 0x80; }
+// the identity in the encoding a call hands out: 32 bytes for the wire-format forms, 64 otherwise
+static inline void g1_identity_out(uint8_t* o, bool wire) { if (wire) g1_identity_wire(o); else g1_identity_bytes(o); }
 
 // Work forked onto stream2 must never outlive a failing call: a function that forks holds one of these, and an early
 // error return (before the main stream has waited for ev_join) then waits for stream2 on the way out, so nothing is
@@ -502,6 +510,9 @@ BNH int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t*
 // an element that does not inflate as the marker no decoder accepts (inflate.h).  Enqueued.
 BNH int stage_g2(blsbn254_ctx* c, const uint8_t* pks, size_t n, bool compressed);    // host_compressed.hip
 BNH int stage_g1(blsbn254_ctx* c, const uint8_t* sigs, size_t n, bool compressed);   // host_compressed.hip
+// n 32-byte signatures ALREADY ON THE DEVICE at d_in inflated into the 64 n bytes at d_out (k_g1_inflate, launch chunk by launch
+// chunk; enqueued): for the callers that stage signatures in buffers of their own
+BNH int g1_inflate_dev(blsbn254_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_out);   // host_compressed.hip
 // the entry points that exist in both forms, behind their argument checks and ENTER
 BNH int verify_batch_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n, const uint8_t* dst,
                           size_t dst_len, uint8_t* bm, bool compressed);   // host_verify.hip

@@ -30,6 +30,8 @@ int stage_g1(blsbn254_ctx* c, const uint8_t* sigs, size_t n, bool compressed) {
   return inflate_dev(c, (const uint8_t*)c->wire_b.p, n, (uint8_t*)c->in_b.p, nullptr, false);
 }
 
+int g1_inflate_dev(blsbn254_ctx* c, const uint8_t* d_in, size_t n, uint8_t* d_out) { return inflate_dev(c, d_in, n, d_out, nullptr, false); }
+
 // ---------------- the inflate primitives: the per-element form of blsbn254_g1/g2_decompress_batch
 static int inflate_common(blsbn254_ctx* c, const uint8_t* in, size_t n, uint8_t* out, uint8_t* status, bool g2) {
   if (!c || (n && (!in || !out || !status))) return BLSBN254_E_ARG;

@@ -15,6 +15,12 @@
 //                is launched.
 // A group's outcome depends on its own inputs only: which attempt served it, where a launch ended and how many groups shared
 // the call do not change a byte.
+//
+// The wire-format form (blsbn254_keyset_aggregate_checked_batch_compressed) shares this body behind KaCall::wire:
+// 32-byte signatures in, 32-byte sums out.  Its optimistic attempt uploads the 32 N bytes to w.wire and scans them where they
+// are (k_ka_scan_wire inflates its own entry; no 64 N buffer exists); its sums leave in both encodings (k_g1p_to_wire: 64 bytes
+// for the equation, 32 for the caller).  Its fallback repacks 32-byte entries, inflates them into w.sigs (k_g1_inflate) and goes
+// on as above: the per-signature verification reads the 64-byte form.
 #include "host_common.h"
 
 extern "C" {
@@ -27,20 +33,28 @@ struct KaCall {
   const uint8_t* msgs; const uint64_t* msg_off;
   size_t n_groups;
   const uint8_t* dst; size_t dst_len;
+  bool wire;                                                           // sigs holds 32 bytes per entry, the sums leave compressed too
 };
 }
 
 // One attempt over the groups of A, enqueued: the signature sums' encodings into c->kagg.out, the rows into c->kagg.rows, the
-// bits of the groups' equation into c->kagg.gbits.
+// bits of the groups' equation into c->kagg.gbits; A.wire: the sums' compressed encodings into c->kagg.wout as well.
 static int ka_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KaCall& A, bool fallback) {
   KaggWs& w = c->kagg;
   const size_t ng = A.n_groups, rb = (k->n + 7) / 8, W = (k->n + 31) / 32;
   TRY(stage_group_offsets(c, w.goff, A.sig_off, ng));
   const size_t N = w.goff.h[ng], N1 = N ? N : 1, nb = (N + 7) / 8;
-  HIPCHK(c, w.idx.reserve(4 * N1)); HIPCHK(c, w.sigs.reserve(64 * N1));
+  const bool scan_wire = A.wire && !fallback;                          // the scan inflates: no 64-byte form of the entries
+  HIPCHK(c, w.idx.reserve(4 * N1));
+  if (!scan_wire) HIPCHK(c, w.sigs.reserve(64 * N1));
+  if (A.wire) HIPCHK(c, w.wire.reserve(32 * N1));
   if (N) {
     TRY(upload(c, w.idx, A.idx + A.sig_off[0], 4 * N));
-    TRY(upload(c, w.sigs, A.sigs + 64 * A.sig_off[0], 64 * N));
+    if (!A.wire) TRY(upload(c, w.sigs, A.sigs + 64 * A.sig_off[0], 64 * N));
+    else {
+      TRY(upload(c, w.wire, A.sigs + 32 * A.sig_off[0], 32 * N));
+      if (fallback) TRY(g1_inflate_dev(c, (const uint8_t*)w.wire.p, N, (uint8_t*)w.sigs.p));
+    }
   }
   if (fallback && N) {
     // every entry as the tuple (its key, the group's message, its signature): the keys by index from the handle, the group's
@@ -62,7 +76,11 @@ static int ka_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KaCall& A
   HIPCHK(c, w.cand.reserve(nb + 8)); HIPCHK(c, w.pts.reserve(27 * N1 * 4)); HIPCHK(c, w.rows.reserve(rb * ng));
   HIPCHK(c, w.gsum.reserve(27 * ng * 4)); HIPCHK(c, w.out.reserve(64 * ng)); HIPCHK(c, w.gbits.reserve((ng + 7) / 8 + 8));
   const uint32_t* goff = (const uint32_t*)w.goff.d.p;
+  if (A.wire) HIPCHK(c, w.wout.reserve(32 * ng));
   TRY(for_chunks(c, N, [&](size_t lo, size_t m) {
+    if (scan_wire)
+      return launch(c, c->stream, "ka_scan_wire", grid_lanes(m), k_ka_scan_wire, (const uint8_t*)k->valid.p, (const uint32_t*)w.idx.p, (const uint8_t*)w.wire.p,
+                    (const uint8_t*)nullptr, m, (uint32_t)lo, N, (uint8_t*)w.cand.p, (int32_t*)w.pts.p);
     return launch(c, c->stream, "ka_scan", grid_lanes(m), k_ka_scan, (const uint8_t*)k->valid.p, (const uint32_t*)w.idx.p, (const uint8_t*)w.sigs.p,
                   fallback ? (const uint8_t*)w.vbits.p : (const uint8_t*)nullptr, m, (uint32_t)lo, N, (uint8_t*)w.cand.p, (int32_t*)w.pts.p);
   }));
@@ -84,7 +102,8 @@ static int ka_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KaCall& A
                        [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
       return launch(c, c->stream, "g1_seg_sum", grid_lanes(runs), k_g1_seg_sum, in.v, in.stride, (const uint32_t*)nullptr, start, len, runs, out.v, out.stride);
     }));
-  TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
+  if (A.wire) TRY(launch(c, c->stream, "g1p_to_wire", grid_lanes(ng), k_g1p_to_wire, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p, (uint8_t*)w.wout.p));
+  else TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
   // the key sums from the rows where they are, then the equation of blsbn254_keyset_fast_aggregate_verify_batch
   size_t word_launches;
   TRY(ks_enqueue_sums_dev(c, k, (const uint8_t*)w.rows.p, ng, &word_launches));
@@ -96,9 +115,9 @@ static int ka_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KaCall& A
   return verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)w.out.p, ng, dl, (uint8_t*)w.gbits.p);
 }
 
-int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* idx, const uint8_t* sigs, const uint64_t* sig_off,
-                                            const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
-                                            uint8_t* out_sigs, uint8_t* out_sel, uint8_t* status) {
+// both forms of the entry point; wire: sigs and out_sigs hold 32 bytes per signature
+static int ka_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* idx, const uint8_t* sigs, const uint64_t* sig_off, const uint8_t* msgs,
+                      const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* out_sigs, uint8_t* out_sel, uint8_t* status, bool wire) {
   if (!c || !k || k->ctx != c) return BLSBN254_E_ARG;
   if (n_groups == 0) return 0;
   if (!sig_off || !msg_off || !out_sigs || !out_sel || !status || (dst_len && !dst)) return BLSBN254_E_ARG;
@@ -117,11 +136,12 @@ int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* c, const blsbn254_keys
   }
   ENTER(c);
   KaggWs& w = c->kagg;
-  const size_t rb = (k->n + 7) / 8, gb = (n_groups + 7) / 8;
-  const KaCall A{idx, sigs, sig_off, msgs, msg_off, n_groups, dst, dst_len};
+  const size_t rb = (k->n + 7) / 8, gb = (n_groups + 7) / 8, sb = wire ? 32 : 64;
+  const DevBuf& d_out = wire ? w.wout : w.out;                         // the sums as the caller gets them
+  const KaCall A{idx, sigs, sig_off, msgs, msg_off, n_groups, dst, dst_len, wire};
   TRY(ka_attempt(c, k, A, false));
   w.h_gbits.assign(gb, 0);
-  HIPCHK(c, hipMemcpyAsync(out_sigs, w.out.p, 64 * n_groups, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_sigs, d_out.p, sb * n_groups, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(out_sel, w.rows.p, rb * n_groups, hipMemcpyDeviceToHost, c->stream));
   TRY(download(c, w.h_gbits.data(), w.gbits.p, gb));
   // a group whose equation does not hold: the identity and, once the repack has read its candidates off the row, a zero row
@@ -129,7 +149,7 @@ int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* c, const blsbn254_keys
   for (size_t g = 0; g < n_groups; ++g) {
     if ((w.h_gbits[g >> 3] >> (g & 7)) & 1) { status[g] = 0; ++c->stat_kagg[0]; continue; }
     status[g] = BLSBN254_ST_SHORT;
-    g1_identity_bytes(out_sigs + 64 * g);
+    g1_identity_out(out_sigs + sb * g, wire);
     const uint8_t* row = out_sel + g * rb;
     if (std::any_of(row, row + rb, [](uint8_t b) { return b != 0; })) w.fail.push_back(g);
     else ++c->stat_kagg[3];
@@ -139,8 +159,8 @@ int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* c, const blsbn254_keys
   const size_t nf = w.fail.size();
   ka_repack(w.fail, idx, sig_off, out_sel, rb, w.sub);
   const size_t Ns = w.sub.idx.size();
-  w.s_sigs.resize(64 * Ns);
-  for (size_t i = 0; i < Ns; ++i) std::memcpy(w.s_sigs.data() + 64 * i, sigs + 64 * w.sub.pos[i], 64);
+  w.s_sigs.resize(sb * Ns);
+  for (size_t i = 0; i < Ns; ++i) std::memcpy(w.s_sigs.data() + sb * i, sigs + sb * w.sub.pos[i], sb);
   w.s_msgs.clear(); w.s_moff.assign(1, 0);
   for (size_t g : w.fail) {
     std::memset(out_sel + g * rb, 0, rb);
@@ -148,20 +168,31 @@ int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* c, const blsbn254_keys
     w.s_moff.push_back(w.s_msgs.size());
   }
   c->stat_kagg[1] += nf; c->stat_kagg[2] += Ns;
-  const KaCall B{w.sub.idx.data(), w.s_sigs.data(), w.sub.off.data(), w.s_msgs.data(), w.s_moff.data(), nf, dst, dst_len};
+  const KaCall B{w.sub.idx.data(), w.s_sigs.data(), w.sub.off.data(), w.s_msgs.data(), w.s_moff.data(), nf, dst, dst_len, wire};
   TRY(ka_attempt(c, k, B, true));
-  w.s_out.resize(64 * nf); w.s_rows.resize(rb * nf); w.h_gbits.assign((nf + 7) / 8, 0);
-  HIPCHK(c, hipMemcpyAsync(w.s_out.data(), w.out.p, 64 * nf, hipMemcpyDeviceToHost, c->stream));
+  w.s_out.resize(sb * nf); w.s_rows.resize(rb * nf); w.h_gbits.assign((nf + 7) / 8, 0);
+  HIPCHK(c, hipMemcpyAsync(w.s_out.data(), d_out.p, sb * nf, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(w.s_rows.data(), w.rows.p, rb * nf, hipMemcpyDeviceToHost, c->stream));
   TRY(download(c, w.h_gbits.data(), w.gbits.p, (nf + 7) / 8));
   for (size_t j = 0; j < nf; ++j) {
     const size_t g = w.fail[j];
     if (!((w.h_gbits[j >> 3] >> (j & 7)) & 1)) { ++c->stat_kagg[3]; continue; }
     status[g] = 0;
-    std::memcpy(out_sigs + 64 * g, w.s_out.data() + 64 * j, 64);
+    std::memcpy(out_sigs + sb * g, w.s_out.data() + sb * j, sb);
     std::memcpy(out_sel + g * rb, w.s_rows.data() + rb * j, rb);
   }
   return 0;
+}
+
+int blsbn254_keyset_aggregate_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* idx, const uint8_t* sigs, const uint64_t* sig_off,
+                                            const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                            uint8_t* out_sigs, uint8_t* out_sel, uint8_t* status) {
+  return ka_checked(c, k, idx, sigs, sig_off, msgs, msg_off, n_groups, dst, dst_len, out_sigs, out_sel, status, false);
+}
+int blsbn254_keyset_aggregate_checked_batch_compressed(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* idx, const uint8_t* sigs, const uint64_t* sig_off,
+                                                       const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                       uint8_t* out_sigs, uint8_t* out_sel, uint8_t* status) {
+  return ka_checked(c, k, idx, sigs, sig_off, msgs, msg_off, n_groups, dst, dst_len, out_sigs, out_sel, status, true);
 }
 
 int blsbn254_keyset_aggregate_stats(blsbn254_ctx* c, uint64_t out[4]) {

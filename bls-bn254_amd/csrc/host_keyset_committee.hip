@@ -130,9 +130,9 @@ int blsbn254_keyset_committee_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* 
   return 0;
 }
 
-int blsbn254_keyset_committee_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off,
-                                                          const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n_groups, const uint8_t* dst,
-                                                          size_t dst_len, uint8_t* valid_bitmap) {
+// both forms of the entry point; compressed: sigs holds 32 bytes per group (stage_g1)
+static int kc_verify(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, const uint8_t* msgs,
+                     const uint64_t* off, const uint8_t* sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap, bool compressed) {
   if (!c || !k || k->ctx != c || !off || (n_groups && (!com || !sel || !sel_off || !sigs || !valid_bitmap)) || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (n_groups == 0) return 0;
   TRY(kc_args(c, k, com, sel, sel_off, n_groups));
@@ -141,11 +141,21 @@ int blsbn254_keyset_committee_fast_aggregate_verify_batch(blsbn254_ctx* c, const
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off, n_groups));
   HIPCHK(c, c->gs_pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve((n_groups + 7) / 8 + 8));
-  TRY(upload(c, c->in_b, sigs, 64 * n_groups));
+  TRY(stage_g1(c, sigs, n_groups, compressed));
   TRY(kc_enqueue_call(c, k, com, sel, sel_off, n_groups));
   TRY(ks_verify_sums(c, n_groups, dl, valid_bitmap));
   kc_tally(c, n_groups);
   return 0;
+}
+int blsbn254_keyset_committee_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off,
+                                                          const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n_groups, const uint8_t* dst,
+                                                          size_t dst_len, uint8_t* valid_bitmap) {
+  return kc_verify(c, k, com, sel, sel_off, msgs, off, sigs, n_groups, dst, dst_len, valid_bitmap, false);
+}
+int blsbn254_keyset_committee_fast_aggregate_verify_batch_compressed(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel,
+                                                                     const uint64_t* sel_off, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs,
+                                                                     size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+  return kc_verify(c, k, com, sel, sel_off, msgs, off, sigs, n_groups, dst, dst_len, valid_bitmap, true);
 }
 
 int blsbn254_keyset_committee_weight_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups,

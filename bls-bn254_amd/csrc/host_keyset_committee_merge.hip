@@ -20,6 +20,10 @@
 //                group: nothing is launched.
 // A group's outcome depends on its own inputs only: which attempt served it, where a launch ended and how many groups shared
 // the call do not change a byte.
+//
+// The wire-format form (blsbn254_keyset_committee_merge_checked_batch_compressed) shares this body behind
+// KcmCall::wire exactly as host_keyset_merge.hip does: 32-byte signatures uploaded to w.wire and inflated into w.sigs, the sums
+// out in both encodings (k_g1p_to_wire), 32-byte signatures in the fallback's repack.
 #include "host_common.h"
 
 extern "C" {
@@ -34,12 +38,13 @@ struct KcmCall {
   const uint8_t* msgs; const uint64_t* msg_off; const uint64_t* sel_off;
   size_t n_groups;
   const uint8_t* dst; size_t dst_len;
+  bool wire;                                                           // sigs holds 32 bytes per contribution, the sums leave compressed too
 };
 }
 
 // One attempt over the groups of A, enqueued: the signature sums' encodings into c->kcmrg.out, the merged rows into c->kcmrg.urows
 // (row g at sel_off[g] - sel_off[0]), the used / candidate bitmaps into c->kcmrg.used / cand, the bits of the groups' equation
-// into c->kcmrg.gbits.
+// into c->kcmrg.gbits; A.wire: the sums' compressed encodings into c->kcmrg.wout as well.
 static int kcm_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KcmCall& A, bool fallback) {
   KcmWs& w = c->kcmrg;
   const size_t ng = A.n_groups;
@@ -52,7 +57,11 @@ static int kcm_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KcmCall&
   HIPCHK(c, w.rows.reserve(in_bytes ? in_bytes : 1)); HIPCHK(c, w.sigs.reserve(64 * N1));
   if (N) {
     TRY(upload(c, w.rows, A.rows + A.row_off[0], in_bytes));
-    TRY(upload(c, w.sigs, A.sigs + 64 * A.con_off[0], 64 * N));
+    if (!A.wire) TRY(upload(c, w.sigs, A.sigs + 64 * A.con_off[0], 64 * N));
+    else {
+      TRY(upload(c, w.wire, A.sigs + 32 * A.con_off[0], 32 * N));
+      TRY(g1_inflate_dev(c, (const uint8_t*)w.wire.p, N, (uint8_t*)w.sigs.p));
+    }
   }
   const size_t n_pk = fallback ? std::max(std::min(N, c->chunk), ng) : ng;
   HIPCHK(c, c->gs_pk.reserve(128 * n_pk)); HIPCHK(c, c->gs_sum.reserve(n_pk * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_pk));
@@ -115,7 +124,10 @@ static int kcm_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KcmCall&
                        [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
       return launch(c, c->stream, "g1_seg_sum", grid_lanes(runs), k_g1_seg_sum, in.v, in.stride, (const uint32_t*)nullptr, start, len, runs, out.v, out.stride);
     }));
-  TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
+  if (A.wire) {
+    HIPCHK(c, w.wout.reserve(32 * ng));
+    TRY(launch(c, c->stream, "g1p_to_wire", grid_lanes(ng), k_g1p_to_wire, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p, (uint8_t*)w.wout.p));
+  } else TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
   // the key sums from the merged rows where they are, by the committee path, then the equation of the committee verify
   TRY(kc_enqueue_call_dev(c, k, A.com, (const uint8_t*)w.urows.p, A.sel_off, ng));
   TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(ng), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, ng, (const uint8_t*)c->gs_sum_ok.p, ng, (uint8_t*)c->gs_pk.p, 1));
@@ -125,10 +137,10 @@ static int kcm_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KcmCall&
 
 static inline bool kcm_bit(const std::vector<uint8_t>& bm, size_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
 
-int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* rows, const uint64_t* row_off,
-                                                  const uint8_t* sigs, const uint64_t* con_off, const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* sel_off,
-                                                  size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used,
-                                                  uint8_t* status) {
+// both forms of the entry point; wire: sigs and out_sigs hold 32 bytes per signature
+static int kcm_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* rows, const uint64_t* row_off, const uint8_t* sigs,
+                       const uint64_t* con_off, const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* sel_off, size_t n_groups, const uint8_t* dst,
+                       size_t dst_len, uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used, uint8_t* status, bool wire) {
   if (!c) return BLSBN254_E_ARG;
   if (!k) { c->last_error = "a NULL argument"; return BLSBN254_E_ARG; }
   if (k->ctx != c) { c->last_error = "the key set belongs to another context"; return BLSBN254_E_ARG; }
@@ -159,12 +171,13 @@ int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn25
   }
   ENTER(c);
   KcmWs& w = c->kcmrg;
-  const size_t gb = (n_groups + 7) / 8, total = sel_off[n_groups] - sel_off[0];
+  const size_t gb = (n_groups + 7) / 8, total = sel_off[n_groups] - sel_off[0], sb = wire ? 32 : 64;
   const size_t N = (size_t)(con_off[n_groups] - con_off[0]), nb = (N + 7) / 8;
-  const KcmCall A{com, rows, row_off, sigs, con_off, msgs, msg_off, sel_off, n_groups, dst, dst_len};
+  const DevBuf& d_out = wire ? w.wout : w.out;                         // the sums as the caller gets them
+  const KcmCall A{com, rows, row_off, sigs, con_off, msgs, msg_off, sel_off, n_groups, dst, dst_len, wire};
   TRY(kcm_attempt(c, k, A, false));
   w.h_gbits.assign(gb, 0); w.h_used.assign(nb + 1, 0); w.h_cand.assign(nb + 1, 0);
-  HIPCHK(c, hipMemcpyAsync(out_sigs, w.out.p, 64 * n_groups, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_sigs, d_out.p, sb * n_groups, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(out_sel, w.urows.p, total, hipMemcpyDeviceToHost, c->stream));
   if (nb) {
     HIPCHK(c, hipMemcpyAsync(w.h_used.data(), w.used.p, nb, hipMemcpyDeviceToHost, c->stream));
@@ -183,7 +196,7 @@ int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn25
       continue;
     }
     status[g] = BLSBN254_ST_SHORT;
-    g1_identity_bytes(out_sigs + 64 * g);
+    g1_identity_out(out_sigs + sb * g, wire);
     uint8_t *row = out_sel + (sel_off[g] - sel_off[0]), *end = out_sel + (sel_off[g + 1] - sel_off[0]);
     if (std::any_of(row, end, [](uint8_t b) { return b != 0; })) w.fail.push_back(g);
     else ++c->stat_kcmrg[3];
@@ -192,7 +205,7 @@ int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn25
   if (w.fail.empty()) return 0;
   // the sub-call over the failing groups' candidates, repacked (ctx-owned: the arrays outlive the asynchronous uploads)
   const size_t nf = w.fail.size();
-  kcm_repack(T, w.fail, com, rows, row_off, sigs, con_off, w.h_cand.data(), w.sub);
+  kcm_repack(T, w.fail, com, rows, row_off, sigs, con_off, w.h_cand.data(), w.sub, sb);
   const size_t Ns = w.sub.pos.size();
   w.s_msgs.clear(); w.s_moff.assign(1, 0);
   for (size_t g : w.fail) {
@@ -201,11 +214,11 @@ int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn25
   }
   c->stat_kcmrg[1] += nf; c->stat_kcmrg[2] += Ns;
   const KcmCall B{w.sub.com.data(), w.sub.rows.data(), w.sub.row_off.data(), w.sub.sigs.data(), w.sub.off.data(), w.s_msgs.data(), w.s_moff.data(),
-                  w.sub.sel_off.data(), nf, dst, dst_len};
+                  w.sub.sel_off.data(), nf, dst, dst_len, wire};
   TRY(kcm_attempt(c, k, B, true));
   const size_t nbs = (Ns + 7) / 8, sub_total = w.sub.sel_off[nf];
-  w.s_out.resize(64 * nf); w.s_rows.resize(sub_total); w.h_gbits.assign((nf + 7) / 8, 0); w.h_used.assign(nbs + 1, 0);
-  HIPCHK(c, hipMemcpyAsync(w.s_out.data(), w.out.p, 64 * nf, hipMemcpyDeviceToHost, c->stream));
+  w.s_out.resize(sb * nf); w.s_rows.resize(sub_total); w.h_gbits.assign((nf + 7) / 8, 0); w.h_used.assign(nbs + 1, 0);
+  HIPCHK(c, hipMemcpyAsync(w.s_out.data(), d_out.p, sb * nf, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(w.s_rows.data(), w.urows.p, sub_total, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(w.h_used.data(), w.used.p, nbs, hipMemcpyDeviceToHost, c->stream));
   TRY(download(c, w.h_gbits.data(), w.gbits.p, (nf + 7) / 8));
@@ -213,12 +226,25 @@ int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn25
     const size_t g = w.fail[j];
     if (!kcm_bit(w.h_gbits, j)) { ++c->stat_kcmrg[3]; continue; }
     status[g] = 0;
-    std::memcpy(out_sigs + 64 * g, w.s_out.data() + 64 * j, 64);
+    std::memcpy(out_sigs + sb * g, w.s_out.data() + sb * j, sb);
     std::memcpy(out_sel + (sel_off[g] - sel_off[0]), w.s_rows.data() + w.sub.sel_off[j], sel_off[g + 1] - sel_off[g]);
     for (uint64_t i = w.sub.off[j]; i < w.sub.off[j + 1]; ++i)
       if (kcm_bit(w.h_used, i)) { const uint64_t s = w.sub.pos[i] - con_off[0]; used[s >> 3] |= (uint8_t)(1u << (s & 7)); }
   }
   return 0;
+}
+
+int blsbn254_keyset_committee_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* rows, const uint64_t* row_off,
+                                                  const uint8_t* sigs, const uint64_t* con_off, const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* sel_off,
+                                                  size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used,
+                                                  uint8_t* status) {
+  return kcm_checked(c, k, com, rows, row_off, sigs, con_off, msgs, msg_off, sel_off, n_groups, dst, dst_len, out_sigs, out_sel, used, status, false);
+}
+int blsbn254_keyset_committee_merge_checked_batch_compressed(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* rows,
+                                                             const uint64_t* row_off, const uint8_t* sigs, const uint64_t* con_off, const uint8_t* msgs,
+                                                             const uint64_t* msg_off, const uint64_t* sel_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                             uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used, uint8_t* status) {
+  return kcm_checked(c, k, com, rows, row_off, sigs, con_off, msgs, msg_off, sel_off, n_groups, dst, dst_len, out_sigs, out_sel, used, status, true);
 }
 
 int blsbn254_keyset_committee_merge_stats(blsbn254_ctx* c, uint64_t out[4]) {

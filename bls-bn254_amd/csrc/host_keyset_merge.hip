@@ -19,6 +19,11 @@
 // two uses apart, and both are reserved for the larger use before the first kernel is enqueued.
 // A group's outcome depends on its own inputs only: which attempt served it, where a launch ended and how many groups shared
 // the call do not change a byte.
+//
+// The wire-format form (blsbn254_keyset_merge_checked_batch_compressed) shares this body behind KmCall::wire: the
+// contributions' 32-byte signatures are uploaded to w.wire and inflated into w.sigs (k_g1_inflate), where k_km_sig reads them as
+// ever -- a contribution that does not inflate is the marker no decoder accepts; the sums leave in both encodings
+// (k_g1p_to_wire); the fallback's repack carries 32-byte signatures.
 #include "host_common.h"
 
 extern "C" {
@@ -32,11 +37,13 @@ struct KmCall {
   const uint8_t* msgs; const uint64_t* msg_off;
   size_t n_groups;
   const uint8_t* dst; size_t dst_len;
+  bool wire;                                                           // sigs holds 32 bytes per contribution, the sums leave compressed too
 };
 }
 
 // One attempt over the groups of A, enqueued: the signature sums' encodings into c->kmrg.out, the merged rows into c->kmrg.urows,
-// the used / candidate bitmaps into c->kmrg.used / cand, the bits of the groups' equation into c->kmrg.gbits.
+// the used / candidate bitmaps into c->kmrg.used / cand, the bits of the groups' equation into c->kmrg.gbits; A.wire: the sums'
+// compressed encodings into c->kmrg.wout as well.
 static int km_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KmCall& A, bool fallback) {
   KmWs& w = c->kmrg;
   const size_t ng = A.n_groups, rb = (k->n + 7) / 8;
@@ -45,7 +52,11 @@ static int km_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KmCall& A
   HIPCHK(c, w.rows.reserve(rb * N1)); HIPCHK(c, w.sigs.reserve(64 * N1));
   if (N) {
     TRY(upload(c, w.rows, A.rows + rb * A.con_off[0], rb * N));
-    TRY(upload(c, w.sigs, A.sigs + 64 * A.con_off[0], 64 * N));
+    if (!A.wire) TRY(upload(c, w.sigs, A.sigs + 64 * A.con_off[0], 64 * N));
+    else {
+      TRY(upload(c, w.wire, A.sigs + 32 * A.con_off[0], 32 * N));
+      TRY(g1_inflate_dev(c, (const uint8_t*)w.wire.p, N, (uint8_t*)w.sigs.p));
+    }
   }
   const size_t n_pk = fallback ? std::max(std::min(N, c->chunk), ng) : ng;
   HIPCHK(c, c->gs_pk.reserve(128 * n_pk)); HIPCHK(c, c->gs_sum.reserve(n_pk * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_pk));
@@ -104,7 +115,10 @@ static int km_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KmCall& A
                        [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
       return launch(c, c->stream, "g1_seg_sum", grid_lanes(runs), k_g1_seg_sum, in.v, in.stride, (const uint32_t*)nullptr, start, len, runs, out.v, out.stride);
     }));
-  TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
+  if (A.wire) {
+    HIPCHK(c, w.wout.reserve(32 * ng));
+    TRY(launch(c, c->stream, "g1p_to_wire", grid_lanes(ng), k_g1p_to_wire, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p, (uint8_t*)w.wout.p));
+  } else TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
   // the key sums from the merged rows where they are, then the equation of blsbn254_keyset_fast_aggregate_verify_batch
   TRY(ks_enqueue_sums_dev(c, k, (const uint8_t*)w.urows.p, ng, &word_launches));
   TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(ng), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, ng, (const uint8_t*)c->gs_sum_ok.p, ng, (uint8_t*)c->gs_pk.p, 1));
@@ -114,9 +128,10 @@ static int km_attempt(blsbn254_ctx* c, const blsbn254_keyset* k, const KmCall& A
 
 static inline bool km_bit(const std::vector<uint8_t>& bm, size_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
 
-int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* rows, const uint8_t* sigs, const uint64_t* con_off,
-                                        const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
-                                        uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used, uint8_t* status) {
+// both forms of the entry point; wire: sigs and out_sigs hold 32 bytes per signature
+static int km_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* rows, const uint8_t* sigs, const uint64_t* con_off, const uint8_t* msgs,
+                      const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used,
+                      uint8_t* status, bool wire) {
   if (!c) return BLSBN254_E_ARG;
   if (!k) { c->last_error = "a NULL argument"; return BLSBN254_E_ARG; }
   if (k->ctx != c) { c->last_error = "the key set belongs to another context"; return BLSBN254_E_ARG; }
@@ -137,12 +152,13 @@ int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* 
   }
   ENTER(c);
   KmWs& w = c->kmrg;
-  const size_t rb = (k->n + 7) / 8, gb = (n_groups + 7) / 8;
+  const size_t rb = (k->n + 7) / 8, gb = (n_groups + 7) / 8, sb = wire ? 32 : 64;
   const size_t N = (size_t)(con_off[n_groups] - con_off[0]), nb = (N + 7) / 8;
-  const KmCall A{rows, sigs, con_off, msgs, msg_off, n_groups, dst, dst_len};
+  const DevBuf& d_out = wire ? w.wout : w.out;                         // the sums as the caller gets them
+  const KmCall A{rows, sigs, con_off, msgs, msg_off, n_groups, dst, dst_len, wire};
   TRY(km_attempt(c, k, A, false));
   w.h_gbits.assign(gb, 0); w.h_used.assign(nb + 1, 0); w.h_cand.assign(nb + 1, 0);
-  HIPCHK(c, hipMemcpyAsync(out_sigs, w.out.p, 64 * n_groups, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_sigs, d_out.p, sb * n_groups, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(out_sel, w.urows.p, rb * n_groups, hipMemcpyDeviceToHost, c->stream));
   if (nb) {
     HIPCHK(c, hipMemcpyAsync(w.h_used.data(), w.used.p, nb, hipMemcpyDeviceToHost, c->stream));
@@ -161,7 +177,7 @@ int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* 
       continue;
     }
     status[g] = BLSBN254_ST_SHORT;
-    g1_identity_bytes(out_sigs + 64 * g);
+    g1_identity_out(out_sigs + sb * g, wire);
     uint8_t* row = out_sel + g * rb;
     if (std::any_of(row, row + rb, [](uint8_t b) { return b != 0; })) w.fail.push_back(g);
     else ++c->stat_kmrg[3];
@@ -170,7 +186,7 @@ int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* 
   if (w.fail.empty()) return 0;
   // the sub-call over the failing groups' candidates, repacked (ctx-owned: the arrays outlive the asynchronous uploads)
   const size_t nf = w.fail.size();
-  km_repack(w.fail, rows, sigs, con_off, w.h_cand.data(), rb, w.sub);
+  km_repack(w.fail, rows, sigs, con_off, w.h_cand.data(), rb, w.sub, sb);
   const size_t Ns = w.sub.pos.size();
   w.s_msgs.clear(); w.s_moff.assign(1, 0);
   for (size_t g : w.fail) {
@@ -178,11 +194,11 @@ int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* 
     w.s_moff.push_back(w.s_msgs.size());
   }
   c->stat_kmrg[1] += nf; c->stat_kmrg[2] += Ns;
-  const KmCall B{w.sub.rows.data(), w.sub.sigs.data(), w.sub.off.data(), w.s_msgs.data(), w.s_moff.data(), nf, dst, dst_len};
+  const KmCall B{w.sub.rows.data(), w.sub.sigs.data(), w.sub.off.data(), w.s_msgs.data(), w.s_moff.data(), nf, dst, dst_len, wire};
   TRY(km_attempt(c, k, B, true));
   const size_t nbs = (Ns + 7) / 8;
-  w.s_out.resize(64 * nf); w.s_rows.resize(rb * nf); w.h_gbits.assign((nf + 7) / 8, 0); w.h_used.assign(nbs + 1, 0);
-  HIPCHK(c, hipMemcpyAsync(w.s_out.data(), w.out.p, 64 * nf, hipMemcpyDeviceToHost, c->stream));
+  w.s_out.resize(sb * nf); w.s_rows.resize(rb * nf); w.h_gbits.assign((nf + 7) / 8, 0); w.h_used.assign(nbs + 1, 0);
+  HIPCHK(c, hipMemcpyAsync(w.s_out.data(), d_out.p, sb * nf, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(w.s_rows.data(), w.urows.p, rb * nf, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(w.h_used.data(), w.used.p, nbs, hipMemcpyDeviceToHost, c->stream));
   TRY(download(c, w.h_gbits.data(), w.gbits.p, (nf + 7) / 8));
@@ -190,12 +206,23 @@ int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* 
     const size_t g = w.fail[j];
     if (!km_bit(w.h_gbits, j)) { ++c->stat_kmrg[3]; continue; }
     status[g] = 0;
-    std::memcpy(out_sigs + 64 * g, w.s_out.data() + 64 * j, 64);
+    std::memcpy(out_sigs + sb * g, w.s_out.data() + sb * j, sb);
     std::memcpy(out_sel + g * rb, w.s_rows.data() + rb * j, rb);
     for (uint64_t i = w.sub.off[j]; i < w.sub.off[j + 1]; ++i)
       if (km_bit(w.h_used, i)) { const uint64_t s = w.sub.pos[i] - con_off[0]; used[s >> 3] |= (uint8_t)(1u << (s & 7)); }
   }
   return 0;
+}
+
+int blsbn254_keyset_merge_checked_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* rows, const uint8_t* sigs, const uint64_t* con_off,
+                                        const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                        uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used, uint8_t* status) {
+  return km_checked(c, k, rows, sigs, con_off, msgs, msg_off, n_groups, dst, dst_len, out_sigs, out_sel, used, status, false);
+}
+int blsbn254_keyset_merge_checked_batch_compressed(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* rows, const uint8_t* sigs, const uint64_t* con_off,
+                                                   const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                   uint8_t* out_sigs, uint8_t* out_sel, uint8_t* used, uint8_t* status) {
+  return km_checked(c, k, rows, sigs, con_off, msgs, msg_off, n_groups, dst, dst_len, out_sigs, out_sel, used, status, true);
 }
 
 int blsbn254_keyset_merge_stats(blsbn254_ctx* c, uint64_t out[4]) {

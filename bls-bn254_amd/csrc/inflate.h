@@ -3,7 +3,8 @@
 // g1_decompress / g2_decompress (curve.h: flag = parity of y / sgn0(y), x == 0 is the identity whatever the flag, a coordinate
 // >= p does not decode) and give the same bytes for every element that decodes.  An element that does not decode becomes THE
 // MARKER, 0xFF in every output byte: g1_decode / g2_decode reject it (coordinate >= p), so every pipeline behind treats it as it
-// treats any undecodable point and none of their kernels has to know where its input came from.
+// treats any undecodable point and none of their kernels has to know where its input came from.  g1_inflate_point is g1_inflate
+// for a lane that computes on with the point (the wire-format scans of keyset_agg.h): no bytes, no marker, a verdict.
 //
 // Both square roots come from fp_pow_pm3_4, the fixed addition chain for (p-3)/4 (fp29.h: 251 squarings + 52 products, uniform
 // control flow, no exponent bit looked at), not from fp_pow's windows and not from an Fp2 ladder:
@@ -69,6 +70,31 @@ BN_FUNC bool g1_inflate(const uint8_t* in, uint8_t* out) {
   fp_to_be_fill(out, fp_select(inf, fp_zero(), x), fill);             // the identity is (0, 1), as g1_encode writes it
   fp_to_be_fill(out + 32, fp_select(inf, fp_one(), ys), fill);
   return ok;
+}
+
+// g1_inflate for a lane that goes on computing with the point instead of storing it: the same decoding, the same chain and the
+// same selects, no bytes written.  The point comes back as th_point (threshold_batch.h) gives it on g1_inflate's bytes: x and y
+// in the form fp_from_be leaves, the stand-in (1, 2) and ok = false where the encoding does not inflate, inf for x == 0.  The
+// square test of the root IS the curve equation, so a caller has no second curve test to run.
+BN_FUNC G1A g1_inflate_point(const uint8_t in[32], bool& ok) {
+  BN_CTX;
+  uint8_t xb[32];
+  for (int i = 0; i < 32; ++i) xb[i] = in[i];
+  const int flag = xb[0] >> 7; xb[0] &= 0x7f;
+  bool okx;
+  const Fp x = fp_from_be(xb, okx);
+  const bool inf = okx & fp_is_zero(x);
+  const Fp rhs = fp_norm(fp_add(fp_mul(fp_sqr(x), x), fp_const(bnc::THREE)));
+  const Fp y = fp_mul(rhs, fp_pow_pm3_4(rhs));
+  const bool sq = fp_eq(fp_sqr(y), rhs);
+  const bool flip = fp_sgn0(y) != flag;
+  const Fp ys = fp_select(flip, fp_norm(fp_neg(y)), y);
+  ok = okx & (inf | sq);
+  G1A p;
+  p.x = fp_select(ok, x, fp_one());
+  p.y = fp_select(ok, ys, fp_norm(fp_add(fp_one(), fp_one())));
+  p.inf = inf;                                                         // (inf implies okx, so ok)
+  return p;
 }
 
 // in: 64 bytes (g2_compress).  out: the 128 bytes g2_decompress + g2_encode give, and true; or the marker, and false.  The

@@ -206,6 +206,12 @@ __global__ void __launch_bounds__(256) k_kca_resolve(const uint32_t* members, co
 __global__ void __launch_bounds__(256) k_kcm_select(const uint8_t* rows, const uint8_t* sig_ok, const uint8_t* mask, const uint32_t* goff, const uint32_t* com,
                                                    const uint4* coms, const uint32_t* cvalid, const uint64_t* rbase, const uint64_t* roff, size_t g_lo, size_t m,
                                                    uint8_t* flags, uint8_t* urows);
+// the checked aggregation and merge calls in wire format (k_keyset_wire.hip): the scans for 32-byte entries, a sum in both encodings
+BN_KERNEL k_ka_scan_wire(const uint8_t* key_valid, const uint32_t* idx, const uint8_t* sigs, const uint8_t* mask, size_t m, uint32_t lo, size_t N, uint8_t* cand,
+                         int32_t* pts);
+BN_KERNEL k_kca_scan_wire(const uint32_t* cvalid, const uint4* coms, const uint32_t* com, const uint32_t* goff, uint32_t ng, const uint32_t* pos, const uint8_t* sigs,
+                          const uint8_t* mask, size_t m, uint32_t lo, size_t N, uint8_t* cand, int32_t* pts);
+BN_KERNEL k_g1p_to_wire(const int32_t* ws, size_t stride, size_t m, uint8_t* full, uint8_t* wire);
 // key-set FastAggregateVerify by random linear combination per message (k_keyset_rlc.hip)
 BN_KERNEL k_ksr_elig(const uint8_t* rows, const uint64_t* row_off, uint32_t n_keys, const uint32_t* com, const uint4* coms, const uint32_t* skip,
                      const uint32_t* valid, const int32_t* sums, const uint8_t* sum_ok, size_t G, const uint8_t* sigs, const uint8_t* seed,

@@ -4,6 +4,7 @@
 //   ka_scan         one lane per entry: the candidate bit (the key's KeyValidate byte, tc_candidate of the signature, and the
 //                   bit of an optional mask bitmap over the call's entries) and the signature as a projective point for the
 //                   segmented G1 sum, the identity for a non-candidate
+//   ka_scan_wire    the same for 32-byte entries (g1_inflate_point of inflate.h); ka_wire_out: a group's sum in both encodings
 //   ka_row_word     one lane per (group, 32-key word): the word of the group's participation row, found by binary search in
 //                   the group's sorted indices and ORed from the candidate bits of the entries that fall into the word
 //   ka_row_store    the word's bytes into a row of ceil(n_keys / 8) bytes (rows need no alignment: bytes, not words)
@@ -14,6 +15,7 @@
 // The lane functions are not a CPU fallback: nothing in the product's host path calls them.
 #pragma once
 #include "threshold_checked.h"
+#include "inflate.h"
 #include "keyset.h"
 #include "keyset_agg_plan.h"
 
@@ -31,9 +33,38 @@ BN_FUNC KaScan ka_scan(const uint8_t* key_valid, const uint32_t* idx, const uint
   r.p = proj_select(r.cand, proj_from_affine(a), proj_identity<Fp>());
   return r;
 }
+// ka_scan for entries that arrive in wire format: sigs holds 32 bytes per entry, the point comes from
+// g1_inflate_point, whose square test of the root is the curve test th_point runs.  The candidate bit and the point are those of
+// ka_scan on g1_inflate's bytes: an entry that does not inflate is the marker there and no candidate here.
+BN_FUNC KaScan ka_scan_wire(const uint8_t* key_valid, const uint32_t* idx, const uint8_t* sigs, const uint8_t* mask, size_t s) {
+  BN_CTX;
+  bool ok;
+  const G1A a = g1_inflate_point(sigs + 32 * s, ok);     // the stand-in (1, 2) where it does not inflate
+  KaScan r;
+  r.cand = ok & !a.inf & (key_valid[idx[s]] != 0) & (mask ? tc_bit(mask, s) : true);
+  r.p = proj_select(r.cand, proj_from_affine(a), proj_identity<Fp>());
+  return r;
+}
 // the layout k_g1_seg_sum reads: x, y, z limb-major
 BN_FUNC void ka_store_point(int32_t* ws, size_t stride, const G1P& p) {
   store_fp(ws, stride, p.x); store_fp(ws + NL * stride, stride, p.y); store_fp(ws + 2 * NL * stride, stride, p.z);
+}
+BN_FUNC G1P ka_load_point(const int32_t* ws, size_t stride) {
+  return {load_fp(ws, stride), load_fp(ws + NL * stride, stride), load_fp(ws + 2 * NL * stride, stride)};
+}
+// A group's sum in both encodings from ONE conversion to affine and one pass out of Montgomery form per coordinate: full = the 64
+// bytes g1_encode writes (what the verify pipeline reads), wire = the 32 bytes g1_compress writes (what the caller gets), the
+// parity of the canonical y as the flag; the identity is (0, 1) in both.
+BN_FUNC void ka_wire_out(const G1P& p, uint8_t* full, uint8_t* wire) {
+  BN_CTX;
+  const G1A a = g1_to_affine(p);
+  const Fp x = fp_from_mont(fp_select(a.inf, fp_zero(), a.x)), y = fp_from_mont(fp_select(a.inf, fp_one(), a.y));
+  uint32_t wx[8], wy[8];
+  limbs_to_words(wx, x.l); limbs_to_words(wy, y.l);
+  BN_UNROLL for (int j = 0; j < 8; ++j) {
+    store_be32(full + 4 * (7 - j), wx[j]); store_be32(full + 32 + 4 * (7 - j), wy[j]);
+    store_be32(wire + 4 * (7 - j), j == 7 ? wx[j] | ((wy[0] & 1u) << 31) : wx[j]);
+  }
 }
 
 // the first s in [a, b) with idx[s] >= key (b if none); idx strictly increasing over [a, b)

@@ -48,6 +48,16 @@ BN_FUNC KaScan kca_scan(const uint32_t* cvalid, const uint32_t* pos, const uint8
   r.p = proj_select(r.cand, proj_from_affine(a), proj_identity<Fp>());
   return r;
 }
+// kca_scan for 32-byte entries, as ka_scan_wire is ka_scan for them (keyset_agg.h)
+BN_FUNC KaScan kca_scan_wire(const uint32_t* cvalid, const uint32_t* pos, const uint8_t* sigs, const uint8_t* mask, size_t s) {
+  BN_CTX;
+  bool ok;
+  const G1A a = g1_inflate_point(sigs + 32 * s, ok);     // the stand-in (1, 2) where it does not inflate
+  KaScan r;
+  r.cand = ok & !a.inf & (kc_bit(cvalid, pos[s]) != 0) & (mask ? tc_bit(mask, s) : true);
+  r.p = proj_select(r.cand, proj_from_affine(a), proj_identity<Fp>());
+  return r;
+}
 // members: the committee's (at its first member)
 BN_INL uint32_t kca_resolve(const uint32_t* members, const uint32_t* pos, size_t s) { return members[pos[s]]; }
 

@@ -71,10 +71,11 @@ static inline void kcm_layout_contributions(const KcTable& t, const uint32_t* co
 // The sub-call of the groups in `fail` (ascending group numbers of the call): of each group the CANDIDATE contributions only,
 // in the order given.  cand: the candidate bitmap over the call's contributions (bit s - con_off[0], LSB-first).  pos: the call
 // position (as con_off counts) each one came from; com / off / row_off / sel_off: the sub-call's committees and offsets, the
-// offsets from 0; rows / sigs: the candidates' rows and signatures, contiguous.
+// offsets from 0; rows / sigs: the candidates' rows and signatures, contiguous.  sig_bytes: the size of one signature as the
+// caller holds it (64, or 32 in wire format).
 struct KcmRepack { std::vector<uint32_t> com; std::vector<uint64_t> pos, off, row_off, sel_off; std::vector<uint8_t> rows, sigs; };
 static inline void kcm_repack(const KcTable& t, const std::vector<size_t>& fail, const uint32_t* com, const uint8_t* rows, const uint64_t* row_off,
-                              const uint8_t* sigs, const uint64_t* con_off, const uint8_t* cand, KcmRepack& out) {
+                              const uint8_t* sigs, const uint64_t* con_off, const uint8_t* cand, KcmRepack& out, size_t sig_bytes = 64) {
   out.com.clear(); out.pos.clear(); out.rows.clear(); out.sigs.clear();
   out.off.assign(1, 0); out.row_off.assign(1, 0); out.sel_off.assign(1, 0);
   for (size_t g : fail) {
@@ -85,7 +86,7 @@ static inline void kcm_repack(const KcTable& t, const std::vector<size_t>& fail,
       const uint8_t* row = rows + row_off[g] + (s - con_off[g]) * rb;
       out.pos.push_back(s);
       out.rows.insert(out.rows.end(), row, row + rb);
-      out.sigs.insert(out.sigs.end(), sigs + 64 * s, sigs + 64 * s + 64);
+      out.sigs.insert(out.sigs.end(), sigs + sig_bytes * s, sigs + sig_bytes * s + sig_bytes);
     }
     out.com.push_back(com[g]);
     out.off.push_back(out.pos.size());

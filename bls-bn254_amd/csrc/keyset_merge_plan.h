@@ -31,10 +31,10 @@ static inline KmWalk km_walk(const uint8_t* rows, const uint64_t* con_off, size_
 // The sub-call of the groups in `fail` (ascending group numbers of the call): of each group the CANDIDATE contributions only,
 // in the order given.  cand: the candidate bitmap over the call's contributions (bit s - con_off[0], LSB-first).  pos: the call
 // position (an index into the caller's rows / sigs) each one came from; off: the sub-call's offsets, from 0; rows / sigs: their
-// rows and signatures, contiguous.
+// rows and signatures, contiguous.  sig_bytes: the size of one signature as the caller holds it (64, or 32 in wire format).
 struct KmRepack { std::vector<uint64_t> pos, off; std::vector<uint8_t> rows, sigs; };
 static inline void km_repack(const std::vector<size_t>& fail, const uint8_t* rows, const uint8_t* sigs, const uint64_t* con_off, const uint8_t* cand,
-                             size_t row_bytes, KmRepack& out) {
+                             size_t row_bytes, KmRepack& out, size_t sig_bytes = 64) {
   out.pos.clear(); out.off.assign(1, 0);
   for (size_t g : fail) {
     for (uint64_t s = con_off[g]; s < con_off[g + 1]; ++s) {
@@ -44,9 +44,9 @@ static inline void km_repack(const std::vector<size_t>& fail, const uint8_t* row
     out.off.push_back(out.pos.size());
   }
   const size_t n = out.pos.size();
-  out.rows.resize(n * row_bytes); out.sigs.resize(64 * n);
+  out.rows.resize(n * row_bytes); out.sigs.resize(sig_bytes * n);
   for (size_t i = 0; i < n; ++i) {
     std::memcpy(out.rows.data() + i * row_bytes, rows + out.pos[i] * row_bytes, row_bytes);
-    std::memcpy(out.sigs.data() + 64 * i, sigs + 64 * out.pos[i], 64);
+    std::memcpy(out.sigs.data() + sig_bytes * i, sigs + sig_bytes * out.pos[i], sig_bytes);
   }
 }

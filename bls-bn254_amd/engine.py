@@ -562,6 +562,18 @@ class Engine:
                                                                                   ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po))
         return o[:(g + 7) // 8].tobytes()
 
+    def keyset_committee_fast_aggregate_verify_batch_compressed(self, ks, com, rows, msgs, sigs, dst=DEFAULT_DST):
+        """keyset_committee_fast_aggregate_verify_batch on compressed signatures (32 bytes per group); a signature that does not
+        inflate clears its group's bit."""
+        g, ca, pc, a, pa, so, pso = self._committee_rows(com, rows)
+        if len(msgs) != g:
+            raise ValueError("one row per message")
+        data, off = pack_messages(msgs)
+        m, pm = _inbuf(data); s, ps = _inbuf(sigs, 32 * g); d, pd = _inbuf(dst); o, po = _outbuf((g + 7) // 8)
+        self._chk(self._lib.blsbn254_keyset_committee_fast_aggregate_verify_batch_compressed(self._ctx, ks._h, pc, pa, pso, pm, off.ctypes.data_as(_u64p), ps,
+                                                                                             ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po))
+        return o[:(g + 7) // 8].tobytes()
+
     def keyset_committee_weight_batch(self, ks, com, rows):
         """keyset_weight_batch over the committees of a KeySet: an (n_groups, n_cols) uint64 array, entry (g, q) = the sum of
         stake column q over the selected members of committee com[g] that have the KeyValidate bit."""
@@ -632,6 +644,16 @@ class Engine:
         for (row, message); ST_SHORT = 5: nothing usable, the identity encoding and a zero row.  Entries on a key that fails
         KeyValidate or with a signature that is no curve point are left out; all candidates are checked with one pairing
         equation per group, and only a group that fails it has every signature verified.  No exception for a bad group."""
+        return self._keyset_aggregate_checked(ks, entry_sets, msgs, dst, 64)
+
+    def keyset_aggregate_checked_batch_compressed(self, ks, entry_sets, msgs, dst=DEFAULT_DST):
+        """keyset_aggregate_checked_batch in wire format: 32-byte compressed signatures in the entries, 32 bytes per group in
+        out_sigs.  Rows and statuses are those of keyset_aggregate_checked_batch on g1_inflate_batch of the signatures, out_sigs
+        is g1_compress_batch of its out_sigs; a signature that does not inflate is left out like any undecodable one."""
+        return self._keyset_aggregate_checked(ks, entry_sets, msgs, dst, 32)
+
+    def _keyset_aggregate_checked(self, ks, entry_sets, msgs, dst, sb):
+        fn = self._lib.blsbn254_keyset_aggregate_checked_batch if sb == 64 else self._lib.blsbn254_keyset_aggregate_checked_batch_compressed
         g = len(msgs)
         if len(entry_sets) != g:
             raise ValueError("one set of entries per message")
@@ -640,21 +662,20 @@ class Engine:
             es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
             if any(a[0] == b[0] for a, b in zip(es, es[1:])):
                 raise ValueError("entry set %d names a key twice" % i)
-            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != 64 for _, s in es):
-                raise ValueError("an entry is (key index, 64 signature bytes)")
+            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != sb for _, s in es):
+                raise ValueError("an entry is (key index, %d signature bytes)" % sb)
             idx += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
             soff[i + 1] = len(idx)
         rb = (ks.count() + 7) // 8
         ia = np.asarray(idx if idx else [0], dtype=np.uint32)
         data, moff = pack_messages(msgs)
         s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
-        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        o, po = _outbuf(sb * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
         r = np.zeros(max(rb * g, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
         st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
-        self._chk(self._lib.blsbn254_keyset_aggregate_checked_batch(self._ctx, ks._h, ia.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ps,
-                                                                    soff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd,
-                                                                    ctypes.c_size_t(len(dst)), po, pr, pst))
-        return o[:64 * g].tobytes(), r[:rb * g].tobytes(), st[:g].tobytes()
+        self._chk(fn(self._ctx, ks._h, ia.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ps, soff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p),
+                     ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po, pr, pst))
+        return o[:sb * g].tobytes(), r[:rb * g].tobytes(), st[:g].tobytes()
 
     def keyset_aggregate_stats(self):
         """dict: groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified
@@ -671,6 +692,18 @@ class Engine:
         byte strings of ceil(size(com[g]) / 8) bytes each, bit j = member j is in the aggregate -- ready for
         keyset_committee_fast_aggregate_verify_batch(ks, com, rows, msgs, out_sigs).  Signatures and statuses are those of
         keyset_aggregate_checked_batch on the entries translated to registry indices; no exception for a bad group."""
+        return self._keyset_committee_aggregate_checked(ks, com, entry_sets, msgs, dst, 64)
+
+    def keyset_committee_aggregate_checked_batch_compressed(self, ks, com, entry_sets, msgs, dst=DEFAULT_DST):
+        """keyset_committee_aggregate_checked_batch in wire format: 32-byte compressed signatures in the entries, 32 bytes per
+        group in out_sigs -- ready for keyset_committee_fast_aggregate_verify_batch_compressed(ks, com, rows, msgs, out_sigs).
+        Rows and statuses are those of the uncompressed call on g1_inflate_batch of the signatures, out_sigs is g1_compress_batch
+        of its out_sigs."""
+        return self._keyset_committee_aggregate_checked(ks, com, entry_sets, msgs, dst, 32)
+
+    def _keyset_committee_aggregate_checked(self, ks, com, entry_sets, msgs, dst, sb):
+        fn = (self._lib.blsbn254_keyset_committee_aggregate_checked_batch if sb == 64
+              else self._lib.blsbn254_keyset_committee_aggregate_checked_batch_compressed)
         g = len(msgs)
         if len(entry_sets) != g or len(com) != g:
             raise ValueError("one committee index and one set of entries per message")
@@ -683,8 +716,8 @@ class Engine:
             es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
             if any(a[0] == b[0] for a, b in zip(es, es[1:])):
                 raise ValueError("entry set %d names a position twice" % i)
-            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != 64 for _, s in es):
-                raise ValueError("an entry is (position, 64 signature bytes)")
+            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != sb for _, s in es):
+                raise ValueError("an entry is (position, %d signature bytes)" % sb)
             pos += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
             soff[i + 1] = len(pos)
         rbs = [(sizes[x] + 7) // 8 for x in com]
@@ -696,16 +729,14 @@ class Engine:
         pa = np.asarray(pos if pos else [0], dtype=np.uint32)
         data, moff = pack_messages(msgs)
         s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
-        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        o, po = _outbuf(sb * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
         r = np.zeros(max(total, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
         st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
         u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._chk(self._lib.blsbn254_keyset_committee_aggregate_checked_batch(self._ctx, ks._h, ca.ctypes.data_as(u32p), pa.ctypes.data_as(u32p), ps,
-                                                                              soff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p),
-                                                                              sel_off.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)),
-                                                                              po, pr, pst))
+        self._chk(fn(self._ctx, ks._h, ca.ctypes.data_as(u32p), pa.ctypes.data_as(u32p), ps, soff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p),
+                     sel_off.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po, pr, pst))
         raw = r[:total].tobytes()
-        return o[:64 * g].tobytes(), [raw[int(sel_off[i]):int(sel_off[i + 1])] for i in range(g)], st[:g].tobytes()
+        return o[:sb * g].tobytes(), [raw[int(sel_off[i]):int(sel_off[i + 1])] for i in range(g)], st[:g].tobytes()
 
     def keyset_committee_aggregate_stats(self):
         """the counts of keyset_aggregate_stats for keyset_committee_aggregate_checked_batch"""
@@ -724,6 +755,16 @@ class Engine:
         KeyValidate only and is disjoint from the rows used before it.  One pairing equation per group checks the merged sum;
         only a group that fails it has every candidate verified on its own and is selected again.  No exception for a bad
         contribution or group."""
+        return self._keyset_merge_checked(ks, contributions, msgs, dst, 64)
+
+    def keyset_merge_checked_batch_compressed(self, ks, contributions, msgs, dst=DEFAULT_DST):
+        """keyset_merge_checked_batch in wire format: 32-byte compressed signatures in the contributions, 32 bytes per group in
+        out_sigs.  Rows, used flags and statuses are those of keyset_merge_checked_batch on g1_inflate_batch of the signatures,
+        out_sigs is g1_compress_batch of its out_sigs; a contribution whose signature does not inflate is never used."""
+        return self._keyset_merge_checked(ks, contributions, msgs, dst, 32)
+
+    def _keyset_merge_checked(self, ks, contributions, msgs, dst, sb):
+        fn = self._lib.blsbn254_keyset_merge_checked_batch if sb == 64 else self._lib.blsbn254_keyset_merge_checked_batch_compressed
         g = len(msgs)
         if len(contributions) != g:
             raise ValueError("one list of contributions per message")
@@ -739,21 +780,21 @@ class Engine:
                             raise ValueError("a row names no key of the set")
                         r[k >> 3] |= 1 << (k & 7)
                     row = r
-                if len(row) != rb or len(sig) != 64:
-                    raise ValueError("a contribution is (row of %d bytes or key indices, 64 signature bytes)" % rb)
+                if len(row) != rb or len(sig) != sb:
+                    raise ValueError("a contribution is (row of %d bytes or key indices, %d signature bytes)" % (rb, sb))
                 rows.append(bytes(row)); sigs.append(bytes(sig))
             coff[i + 1] = len(rows)
         nc = len(rows)
         data, moff = pack_messages(msgs)
         a, pa = _inbuf(b"".join(rows)); s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
-        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        o, po = _outbuf(sb * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
         r = np.zeros(max(rb * g, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
         u = np.zeros((nc + 7) // 8 + 1, dtype=np.uint8); pu = u.ctypes.data_as(_u8p)
         st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
-        self._chk(self._lib.blsbn254_keyset_merge_checked_batch(self._ctx, ks._h, pa, ps, coff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p),
-                                                                ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po, pr, pu, pst))
+        self._chk(fn(self._ctx, ks._h, pa, ps, coff.ctypes.data_as(_u64p), pm, moff.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)),
+                     po, pr, pu, pst))
         used = [[bool((u[t >> 3] >> (t & 7)) & 1) for t in range(int(coff[i]), int(coff[i + 1]))] for i in range(g)]
-        return o[:64 * g].tobytes(), r[:rb * g].tobytes(), used, st[:g].tobytes()
+        return o[:sb * g].tobytes(), r[:rb * g].tobytes(), used, st[:g].tobytes()
 
     def keyset_merge_stats(self):
         """dict: groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified
@@ -772,6 +813,19 @@ class Engine:
         out_sigs), and the (rows, out_sigs) of keyset_committee_aggregate_checked_batch are contributions of this call as they
         are.  Signatures, statuses and used flags are those of keyset_merge_checked_batch on the rows scattered over the
         registry; no exception for a bad contribution or group."""
+        return self._keyset_committee_merge_checked(ks, com, groups, msgs, dst, 64)
+
+    def keyset_committee_merge_checked_batch_compressed(self, ks, com, groups, msgs, dst=DEFAULT_DST):
+        """keyset_committee_merge_checked_batch in wire format: 32-byte compressed signatures in the contributions, 32 bytes per
+        group in out_sigs; the (rows, out_sigs) of keyset_committee_aggregate_checked_batch_compressed are contributions of this
+        call as they are, and its own go to keyset_committee_fast_aggregate_verify_batch_compressed.  Rows, used flags and
+        statuses are those of the uncompressed call on g1_inflate_batch of the signatures, out_sigs is g1_compress_batch of its
+        out_sigs."""
+        return self._keyset_committee_merge_checked(ks, com, groups, msgs, dst, 32)
+
+    def _keyset_committee_merge_checked(self, ks, com, groups, msgs, dst, sb):
+        fn = (self._lib.blsbn254_keyset_committee_merge_checked_batch if sb == 64
+              else self._lib.blsbn254_keyset_committee_merge_checked_batch_compressed)
         g = len(msgs)
         if len(groups) != g or len(com) != g:
             raise ValueError("one committee index and one list of contributions per message")
@@ -792,8 +846,8 @@ class Engine:
                             raise ValueError("a row names no member of the committee")
                         r[k >> 3] |= 1 << (k & 7)
                     row = r
-                if len(row) != rb or len(sig) != 64:
-                    raise ValueError("a contribution is (row of %d bytes or positions, 64 signature bytes)" % rb)
+                if len(row) != rb or len(sig) != sb:
+                    raise ValueError("a contribution is (row of %d bytes or positions, %d signature bytes)" % (rb, sb))
                 rows.append(bytes(row)); sigs.append(bytes(sig))
             coff[i + 1] = len(rows)
             roff[i + 1] = int(roff[i]) + rb * (len(rows) - int(coff[i]))
@@ -802,17 +856,15 @@ class Engine:
         ca = np.asarray(com if com else [0], dtype=np.uint32)
         data, moff = pack_messages(msgs)
         a, pa = _inbuf(b"".join(rows)); s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
-        o, po = _outbuf(64 * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
+        o, po = _outbuf(sb * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
         r = np.zeros(max(total, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
         u = np.zeros((nc + 7) // 8 + 1, dtype=np.uint8); pu = u.ctypes.data_as(_u8p)
         st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
-        self._chk(self._lib.blsbn254_keyset_committee_merge_checked_batch(self._ctx, ks._h, ca.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pa,
-                                                                          roff.ctypes.data_as(_u64p), ps, coff.ctypes.data_as(_u64p), pm,
-                                                                          moff.ctypes.data_as(_u64p), sel_off.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd,
-                                                                          ctypes.c_size_t(len(dst)), po, pr, pu, pst))
+        self._chk(fn(self._ctx, ks._h, ca.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pa, roff.ctypes.data_as(_u64p), ps, coff.ctypes.data_as(_u64p), pm,
+                     moff.ctypes.data_as(_u64p), sel_off.ctypes.data_as(_u64p), ctypes.c_size_t(g), pd, ctypes.c_size_t(len(dst)), po, pr, pu, pst))
         used = [[bool((u[t >> 3] >> (t & 7)) & 1) for t in range(int(coff[i]), int(coff[i + 1]))] for i in range(g)]
         raw = r[:total].tobytes()
-        return o[:64 * g].tobytes(), [raw[int(sel_off[i]):int(sel_off[i + 1])] for i in range(g)], used, st[:g].tobytes()
+        return o[:sb * g].tobytes(), [raw[int(sel_off[i]):int(sel_off[i + 1])] for i in range(g)], used, st[:g].tobytes()
 
     def keyset_committee_merge_stats(self):
         """the counts of keyset_merge_stats for keyset_committee_merge_checked_batch"""

@@ -767,6 +767,42 @@ int blsbn254_keyset_create_compressed(blsbn254_ctx* ctx, const uint8_t* pks /* n
 int blsbn254_keyset_fast_aggregate_verify_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* sel,
                                                            const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs /* n_groups*32 */,
                                                            size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);
+/* The write side on wire bytes: a collector, a merger and a verifier that hold 32-byte signatures run on them end to end.
+ * blsbn254_keyset_aggregate_checked_batch and blsbn254_keyset_committee_aggregate_checked_batch on compressed signatures in
+ * and out: status and out_sel are byte for byte what the uncompressed call gives on blsbn254_g1_inflate_batch(sigs), and
+ * out_sigs is blsbn254_g1_compress_batch of that call's out_sigs (a group that ends BLSBN254_ST_SHORT: the compressed
+ * identity).  A signature that does not inflate is left out as any undecodable one is -- never an error of the call, never a
+ * reason for the fallback.  Every other rule (arguments, limits, offsets, sel_off, the stats arrays, which are shared with the
+ * uncompressed forms) is the uncompressed call's. */
+int blsbn254_keyset_aggregate_checked_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* idx,
+                                                       const uint8_t* sigs /* N*32 */, const uint64_t* sig_off, const uint8_t* msgs,
+                                                       const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                       uint8_t* out_sigs /* n_groups*32 */, uint8_t* out_sel, uint8_t* status);
+int blsbn254_keyset_committee_aggregate_checked_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com,
+                                                                 const uint32_t* pos, const uint8_t* sigs /* N*32 */, const uint64_t* sig_off,
+                                                                 const uint8_t* msgs, const uint64_t* msg_off, const uint64_t* sel_off,
+                                                                 size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                                 uint8_t* out_sigs /* n_groups*32 */, uint8_t* out_sel, uint8_t* status);
+/* blsbn254_keyset_merge_checked_batch and blsbn254_keyset_committee_merge_checked_batch likewise: the partial aggregates
+ * arrive compressed, the merged aggregates leave compressed; status, out_sel and used are those of the uncompressed call on
+ * blsbn254_g1_inflate_batch(sigs), out_sigs is blsbn254_g1_compress_batch of its out_sigs. */
+int blsbn254_keyset_merge_checked_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint8_t* rows,
+                                                   const uint8_t* sigs /* N*32 */, const uint64_t* con_off, const uint8_t* msgs,
+                                                   const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                   uint8_t* out_sigs /* n_groups*32 */, uint8_t* out_sel, uint8_t* used, uint8_t* status);
+int blsbn254_keyset_committee_merge_checked_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com,
+                                                             const uint8_t* rows, const uint64_t* row_off, const uint8_t* sigs /* N*32 */,
+                                                             const uint64_t* con_off, const uint8_t* msgs, const uint64_t* msg_off,
+                                                             const uint64_t* sel_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                             uint8_t* out_sigs /* n_groups*32 */, uint8_t* out_sel, uint8_t* used,
+                                                             uint8_t* status);
+/* blsbn254_keyset_committee_fast_aggregate_verify_batch on compressed signatures: its bitmap on
+ * blsbn254_g1_inflate_batch(sigs), as blsbn254_keyset_fast_aggregate_verify_batch_compressed is for the full-width call. */
+int blsbn254_keyset_committee_fast_aggregate_verify_batch_compressed(blsbn254_ctx* ctx, const blsbn254_keyset* keys, const uint32_t* com,
+                                                                     const uint8_t* sel, const uint64_t* sel_off, const uint8_t* msgs,
+                                                                     const uint64_t* off, const uint8_t* sigs /* n_groups*32 */,
+                                                                     size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                                     uint8_t* valid_bitmap);
 
 /* ---- device-resident variants (plumbing for callers that already hold the batch in HBM) ----- */
 /* All d_* pointers are device pointers on ctx's GPU.  Work is enqueued on ctx's stream and is
