@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -102,40 +103,30 @@ struct BNH TcWs {
 // sums over a registered key set selected by bitmaps (host_keyset.hip, k_keyset.hip): the call's rows, the groups' flip / ok bytes,
 // the word-major partials of a launch and of its reduction passes (ping-pong); the host copy the flip bytes are downloaded to
 struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; };
-// checked signature aggregation over a registered key set (host_keyset_agg.hip, k_keyset_agg.hip): the staged indices and
-// signatures, the candidate bitmap over the call's entries, the signatures as points (27 x N limbs) and the groups' sums with
-// the levels between them, the sums' encodings, the groups' rows, their verification bits, the entry offsets; for the fallback
-// the gathered keys and the bits of the per-signature verification.  Host side: the bits and rows an attempt downloads, the
-// groups that go to the fallback and their sub-call (keyset_agg.h KaRepack) with its signatures, messages (one per group for the
-// equation, one per entry for the per-signature verification), offsets and results.  The wire-format form: the
-// 32-byte signatures as uploaded (wire; the optimistic attempt reads them where they are, the fallback inflates them into sigs)
-// and the sums' compressed encodings (wout).
-struct BNH KaggWs {
-  DevBuf idx, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits, wire, wout;
+// What the four checked calls over a registered key set hold alike (host_keyset_checked.hip; aggregation and merge, full-width and
+// per committee: DESIGN.md 6i, 6j, 6o, 6p, 6q).  An "entry" is a signature of the aggregation forms, a contribution of the merge
+// forms.  On the device: the entries' signatures as 64-byte encodings (sigs) and, wire-format forms, as the 32 bytes uploaded
+// (wire); the candidate bitmap over the entries and (merge forms) the used one; the signatures as points (27 x N limbs), the
+// groups' sums with the levels between them (seg), the sums' encodings (out: 64 bytes, wout: 32 bytes, wire-format forms), the
+// groups' rows as they leave (orows), the bits of the groups' equation (gbits), the entry offsets (goff); for the fallback the
+// bits of the per-entry verification (vbits).  Host side: what an attempt downloads (h_*), the groups that go to the fallback
+// (fail), the sub-call's messages (s_msgs / s_moff: one per group for the equation; s_emsgs / s_emoff: one per entry for the
+// per-entry verification) and results (s_out, s_rows); the row offsets g * row_bytes the full-width forms address their rows by.
+struct BNH CkWs {
+  DevBuf sigs, wire, cand, used, pts, gsum, out, wout, orows, gbits, vbits;
   GroupOff goff;
   SegWs seg;
-  KaRepack sub;
-  std::vector<uint8_t> h_gbits, s_sigs, s_msgs, s_emsgs, s_out, s_rows;
-  std::vector<uint64_t> s_moff, s_emoff;
-  std::vector<size_t> fail;
-};
-// checked merge of partial aggregates over a registered key set (host_keyset_merge.hip, k_keyset_merge.hip): the staged rows and
-// signatures, the signature test and the selection's byte per contribution, the used and candidate bitmaps over the call's
-// contributions, the signatures as points (27 x N limbs) and the groups' sums with the levels between them, the sums' encodings,
-// the groups' merged rows, their verification bits, the contribution offsets; for the fallback the bits of the per-contribution
-// verification.  Host side: what an attempt downloads, the groups that go to the fallback and their sub-call (keyset_merge_plan.h
-// KmRepack) with its messages (one per group for the equation, one per contribution for the per-contribution verification),
-// offsets and results.  The wire-format form: the 32-byte signatures as uploaded (wire, inflated into sigs) and the
-// sums' compressed encodings (wout).
-struct BNH KmWs {
-  DevBuf rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits, wire, wout;
-  GroupOff goff;
-  SegWs seg;
-  KmRepack sub;
   std::vector<uint8_t> h_gbits, h_used, h_cand, s_msgs, s_emsgs, s_out, s_rows;
-  std::vector<uint64_t> s_moff, s_emoff;
+  std::vector<uint64_t> s_moff, s_emoff, even_off;
   std::vector<size_t> fail;
 };
+// ... and each form's own (KcaWs, KcmWs: behind KcWs).  Aggregation (host_keyset_agg.hip): the staged indices, the keys the
+// fallback gathers, the sub-call (keyset_agg_plan.h KaRepack) and its signatures
+struct BNH KaggWs : CkWs { DevBuf idx, pks; KaRepack sub; std::vector<uint8_t> s_sigs; };
+// the merge forms (ck_select, ck_verify_contributions): the contributions' rows as staged, the signature test and the selection's
+// byte per contribution; merge (host_keyset_merge.hip): the sub-call (keyset_merge_plan.h KmRepack)
+struct BNH KmStage : CkWs { DevBuf rows, sig_ok, flags; };
+struct BNH KmWs : KmStage { KmRepack sub; };
 // stake weights by bitmap and the verify with a quorum over a registered key set (host_keyset_weight.hip, k_keyset_weight.hip):
 // the groups' weights of a call; host side the key-major table a blsbn254_keyset_set_weights uploads, the row that selects every
 // key (the totals are its weights), the groups that reach quorum and their sub-call (keyset_weight_plan.h KwRepack) with its bits
@@ -159,38 +150,25 @@ struct BNH KcWs {
   std::vector<uint64_t> h_off;
   std::vector<uint32_t> h_com;
 };
-// checked signature aggregation per committee of a registered key set (host_keyset_committee_agg.hip, k_keyset_committee_agg.hip):
-// what KaggWs holds, with positions in place of indices; the groups' committees, the prefix of their row words and the byte
-// offsets of their rows (device buffers and the host copies they are uploaded from); for the fallback the registry indices the
-// positions resolve to.  Host side: the bits an attempt downloads, the groups that go to the fallback and their sub-call
-// (keyset_committee_agg_plan.h KcaRepack) with its signatures, messages, offsets and results.  The key sums run in KcWs.  wire /
-// wout: as in KaggWs.
-struct BNH KcaWs {
-  DevBuf com, pos, sigs, cand, pts, gsum, out, rows, gbits, pks, vbits, ridx, wpre, roff, wire, wout;
-  GroupOff goff;
-  SegWs seg;
+// aggregation per committee (host_keyset_committee_agg.hip; the key sums run in KcWs): positions in place of indices; the
+// groups' committees, the prefix of their row words and the byte offsets of their rows (device buffers and the host copies they
+// are uploaded from); for the fallback the registry indices the positions resolve to and the gathered keys; the sub-call
+// (keyset_committee_agg_plan.h KcaRepack) and its signatures
+struct BNH KcaWs : CkWs {
+  DevBuf com, pos, pks, ridx, wpre, roff;
   KcaRepack sub;
   std::vector<uint64_t> h_wpre, h_roff;
-  std::vector<uint8_t> h_gbits, s_sigs, s_msgs, s_emsgs, s_out, s_rows;
-  std::vector<uint64_t> s_moff, s_emoff;
-  std::vector<size_t> fail;
+  std::vector<uint8_t> s_sigs;
 };
-// checked merge of partial aggregates per committee of a registered key set (host_keyset_committee_merge.hip,
-// k_keyset_committee_merge.hip): what KmWs holds, with ragged rows (the merged rows in urows at the caller's sel_off positions);
-// the groups' committees and the byte offsets of their contribution rows and of their merged rows (device buffers and the host
-// copies they are uploaded from); for the fallback the committee and the row offset of every contribution.  Host side: what an
-// attempt downloads, the groups that go to the fallback and their sub-call (keyset_committee_merge_plan.h KcmRepack) with its
-// messages, offsets and results.  The key sums run in KcWs.  wire / wout: as in KmWs.
-struct BNH KcmWs {
-  DevBuf com, rows, sigs, sig_ok, flags, used, cand, pts, gsum, out, urows, gbits, vbits, rbase, roff, wire, wout;
-  GroupOff goff;
-  SegWs seg;
+// merge per committee (host_keyset_committee_merge.hip): ragged rows (the merged rows in orows at the caller's sel_off
+// positions); the groups' committees and the byte offsets of their contribution rows and of their merged rows (device buffers
+// and the host copies they are uploaded from); for the fallback the committee and the row offset of every contribution; the
+// sub-call (keyset_committee_merge_plan.h KcmRepack)
+struct BNH KcmWs : KmStage {
+  DevBuf com, rbase, roff;
   KcmRepack sub;
   std::vector<uint64_t> h_rbase, h_roff, h_coff;
   std::vector<uint32_t> h_ccom;
-  std::vector<uint8_t> h_gbits, h_used, h_cand, s_msgs, s_emsgs, s_out, s_rows;
-  std::vector<uint64_t> s_moff, s_emoff;
-  std::vector<size_t> fail;
 };
 // key-set FastAggregateVerify by random linear combination per message (host_keyset_rlc.hip, k_keyset_rlc.hip): the seed; per
 // group its committee and row offset (committee form), sorted position, chunk-size byte, eligibility byte and weight; per sorted
@@ -568,6 +546,55 @@ BNH int td_msg_args(blsbn254_ctx* c, const uint8_t* partial_sigs, const uint64_t
 BNH int td_stage_commitments(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, size_t n_groups);   // host_threshold_deal.hip
 BNH int td_verify_shares_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint8_t* partial_sigs,
                                  const uint64_t* id_off, const uint8_t* msgs, const uint64_t* msg_off, size_t n_groups, const uint8_t* dst, size_t dst_len);   // host_threshold_deal.hip
+// The checked calls over a registered key set (host_keyset_agg / _merge / _committee_agg / _committee_merge.hip): the steps all
+// four share, each written once in host_keyset_checked.hip.  CkArgs: the arguments they share, sigs indexed by ent_off as given
+// (wire: 32 bytes per signature in and per sum out); CkOut: the caller's outputs (used: merge forms, else NULL).
+static const size_t CK_SUM_GROUP = 16;      // signatures per lane and level of the group sums
+static inline bool bit_at(const uint8_t* bm, size_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
+struct CkArgs {
+  const uint8_t* sigs; const uint64_t* ent_off; const uint8_t* msgs; const uint64_t* msg_off;
+  size_t n_groups;
+  const uint8_t* dst; size_t dst_len;
+  bool wire;
+};
+struct CkOut { uint8_t *sigs, *rows, *used, *status; };
+// the sub-call a form's repack leaves: its entries, the byte offsets of its groups' rows and (merge forms, else NULL) per entry
+// its index in the caller's arrays with the groups' entry offsets
+struct CkSub { size_t n; const uint64_t* row_off; const uint64_t *pos, *off; };
+// The argument checks: context and handle, n_groups == 0 (CK_NOTHING: the caller returns 0), NULL pointers (missing: one of the
+// form's own or of its outputs is; ent_missing: one that a call with entries needs is), committees: the handle needs a table,
+// the chunk limit, the offsets ("<noun> offsets decrease")
+static const int CK_NOTHING = 1;
+BNH int ck_args(blsbn254_ctx* c, const blsbn254_keyset* k, const CkArgs& A, bool missing, bool ent_missing, bool committees, const char* noun);
+// the call's N signatures into w.sigs, through w.wire and g1_inflate_dev when compressed; inflate = false: compressed entries stay
+// in w.wire, where the caller's scan reads them, and no 64 N buffer is reserved
+BNH int ck_stage_sigs(blsbn254_ctx* c, CkWs& w, const CkArgs& A, size_t N, bool inflate);
+// c->gs_pk / gs_sum / gs_sum_ok for n key sums: a call that uses them twice reserves for the larger use BEFORE the first kernel
+// that touches them is enqueued (a later reserve that grows them would free what that kernel still reads)
+BNH int ck_reserve_key_sums(blsbn254_ctx* c, size_t n);
+// the group's message once per entry of w.goff into w.s_emsgs / w.s_emoff (ctx-owned: they outlive the upload)
+BNH void ck_expand_msgs(CkWs& w, const CkArgs& A);
+// the tail of an attempt, behind the kernels that left the entries' points in w.pts and the rows in w.orows: the signature sums by
+// levels, their encodings into w.out (wire: w.wout too), the key sums by key_sums() into c->gs_sum / c->gs_sum_ok, then ONE
+// verification per group of (key sum, message, signature sum), its bits into w.gbits.  Enqueued.
+BNH int ck_tail(blsbn254_ctx* c, CkWs& w, const CkArgs& A, uint32_t dl, const std::function<int()>& key_sums);
+// The two attempts of a call: attempt(false) over the caller's groups, the download, the groups marked; for those that had a
+// candidate and failed the sub-call's messages (w.s_msgs / w.s_moff, final before the repack runs, so it may point its call at
+// them), the form's repack(fail), their rows zeroed, attempt(true) and what passes copied back.  row_off: the
+// byte offsets of the groups' rows in O.rows (rebased here; ck_even_rows for rows of one width); stat: the form's four counts.
+BNH int ck_two_attempts(blsbn254_ctx* c, CkWs& w, const CkArgs& A, const uint64_t* row_off, const CkOut& O, uint64_t stat[4],
+                        const std::function<int(bool)>& attempt, const std::function<CkSub(const std::vector<size_t>&)>& repack);
+BNH const uint64_t* ck_even_rows(CkWs& w, size_t n_groups, size_t row_bytes);
+// the aggregation pair's per-signature verification: the keys d_idx names gathered from the handle's encodings into pks, the
+// group's message once per entry, the bits into w.vbits (synchronises)
+BNH int ck_verify_entries(blsbn254_ctx* c, const blsbn254_keyset* k, CkWs& w, DevBuf& pks, const uint32_t* d_idx, const CkArgs& A, size_t N);
+// the merge pair's selection: the signature test (k_km_sig), select(lo, m) for every launch of a wave per group, the points of
+// what was not selected cleared and the used / candidate bitmaps (k_km_points)
+BNH int ck_select(blsbn254_ctx* c, KmStage& w, size_t n_groups, size_t N, const std::function<int(size_t, size_t)>& select);
+// ... and its per-contribution verification: key_sums(lo, m) for every launch chunk, the group's message once per contribution,
+// the bits into w.vbits; settle: wait for each launch before the next is planned
+BNH int ck_verify_contributions(blsbn254_ctx* c, KmStage& w, const CkArgs& A, size_t N, uint32_t dl, bool settle,
+                                const std::function<int(size_t, size_t)>& key_sums);
 
 // A launch of n tuples is small enough that the prepared-key path wins whatever its keys: with line tables the Miller loop (and
 // the final exponentiation) can run one WAVE per tuple (wide.h) or, up to tri_max, three lanes per tuple (k_tri.hip) instead of

@@ -636,6 +636,40 @@ class Engine:
         return {"decided_groups": int(o[0]), "chunks": int(o[1]), "failed_chunk_groups": int(o[2]), "direct_groups": int(o[3]), "classes": int(o[4]),
                 "calls": int(o[5])}
 
+    def _stats4(self, fn, names):
+        """the four counts of a stats call as a dict"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(fn(self._ctx, o))
+        return {name: int(o[i]) for i, name in enumerate(names)}
+
+    @staticmethod
+    def _entry_sets(entry_sets, sb, noun):
+        """entry_sets[g]: (key index or position, signature) pairs or a dict, sorted here -> (uint32 array, signature bytes, offsets);
+        noun: what the first element of an entry is called in the errors"""
+        ids, sigs, soff = [], [], np.zeros(len(entry_sets) + 1, dtype=np.uint64)
+        for i, es in enumerate(entry_sets):
+            es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
+            if any(a[0] == b[0] for a, b in zip(es, es[1:])):
+                raise ValueError("entry set %d names a %s twice" % (i, noun.split()[0]))
+            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != sb for _, s in es):
+                raise ValueError("an entry is (%s, %d signature bytes)" % (noun, sb))
+            ids += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
+            soff[i + 1] = len(ids)
+        return np.asarray(ids if ids else [0], dtype=np.uint32), b"".join(sigs), soff
+
+    @staticmethod
+    def _bit_row(row, n, err):
+        """a row of ceil(n / 8) bytes: as it is when given as bytes, else from an iterable of the indices below n it sets"""
+        if isinstance(row, (bytes, bytearray, memoryview)):
+            return row
+        r = bytearray((n + 7) // 8)
+        for k in row:
+            k = int(k)
+            if k < 0 or k >= n:
+                raise ValueError(err)
+            r[k >> 3] |= 1 << (k & 7)
+        return r
+
     def keyset_aggregate_checked_batch(self, ks, entry_sets, msgs, dst=DEFAULT_DST):
         """The collecting node's call: entry_sets[g] = the signatures received for msgs[g], a list of (key index, 64-byte
         signature) pairs or a dict {index: signature} over the registered KeySet (sorted by index here; a repeated index raises
@@ -657,19 +691,10 @@ class Engine:
         g = len(msgs)
         if len(entry_sets) != g:
             raise ValueError("one set of entries per message")
-        idx, sigs, soff = [], [], np.zeros(g + 1, dtype=np.uint64)
-        for i, es in enumerate(entry_sets):
-            es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
-            if any(a[0] == b[0] for a, b in zip(es, es[1:])):
-                raise ValueError("entry set %d names a key twice" % i)
-            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != sb for _, s in es):
-                raise ValueError("an entry is (key index, %d signature bytes)" % sb)
-            idx += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
-            soff[i + 1] = len(idx)
+        ia, sigs, soff = self._entry_sets(entry_sets, sb, "key index")
         rb = (ks.count() + 7) // 8
-        ia = np.asarray(idx if idx else [0], dtype=np.uint32)
         data, moff = pack_messages(msgs)
-        s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
+        s, ps = _inbuf(sigs); m, pm = _inbuf(data); d, pd = _inbuf(dst)
         o, po = _outbuf(sb * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
         r = np.zeros(max(rb * g, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
         st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
@@ -680,9 +705,7 @@ class Engine:
     def keyset_aggregate_stats(self):
         """dict: groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified
         individually, groups that ended in ST_SHORT"""
-        o = (ctypes.c_uint64 * 4)()
-        self._chk(self._lib.blsbn254_keyset_aggregate_stats(self._ctx, o))
-        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_signatures": int(o[2]), "short_groups": int(o[3])}
+        return self._stats4(self._lib.blsbn254_keyset_aggregate_stats, ("optimistic_groups", "fallback_groups", "verified_signatures", "short_groups"))
 
     def keyset_committee_aggregate_checked_batch(self, ks, com, entry_sets, msgs, dst=DEFAULT_DST):
         """keyset_aggregate_checked_batch per committee of a KeySet (KeySet.set_committees): group g names committee com[g], and
@@ -711,24 +734,15 @@ class Engine:
         com = [int(x) for x in com]
         if any(x < 0 or x >= len(sizes) for x in com):
             raise ValueError("a group names a committee the key set does not have")
-        pos, sigs, soff = [], [], np.zeros(g + 1, dtype=np.uint64)
-        for i, es in enumerate(entry_sets):
-            es = sorted(es.items() if isinstance(es, dict) else ((int(k), s) for k, s in es))
-            if any(a[0] == b[0] for a, b in zip(es, es[1:])):
-                raise ValueError("entry set %d names a position twice" % i)
-            if any(k < 0 or k >= 1 << 32 for k, _ in es) or any(len(s) != sb for _, s in es):
-                raise ValueError("an entry is (position, %d signature bytes)" % sb)
-            pos += [k for k, _ in es]; sigs += [bytes(s) for _, s in es]
-            soff[i + 1] = len(pos)
+        pa, sigs, soff = self._entry_sets(entry_sets, sb, "position")
         rbs = [(sizes[x] + 7) // 8 for x in com]
         sel_off = np.zeros(g + 1, dtype=np.uint64)
         if g:
             sel_off[1:] = np.cumsum(rbs, dtype=np.uint64)
         total = int(sel_off[g])
         ca = np.asarray(com if com else [0], dtype=np.uint32)
-        pa = np.asarray(pos if pos else [0], dtype=np.uint32)
         data, moff = pack_messages(msgs)
-        s, ps = _inbuf(b"".join(sigs)); m, pm = _inbuf(data); d, pd = _inbuf(dst)
+        s, ps = _inbuf(sigs); m, pm = _inbuf(data); d, pd = _inbuf(dst)
         o, po = _outbuf(sb * g)                                 # (large outputs of _outbuf share one buffer: only one per call)
         r = np.zeros(max(total, 1), dtype=np.uint8); pr = r.ctypes.data_as(_u8p)
         st = np.zeros(g + 1, dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
@@ -740,9 +754,7 @@ class Engine:
 
     def keyset_committee_aggregate_stats(self):
         """the counts of keyset_aggregate_stats for keyset_committee_aggregate_checked_batch"""
-        o = (ctypes.c_uint64 * 4)()
-        self._chk(self._lib.blsbn254_keyset_committee_aggregate_stats(self._ctx, o))
-        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_signatures": int(o[2]), "short_groups": int(o[3])}
+        return self._stats4(self._lib.blsbn254_keyset_committee_aggregate_stats, ("optimistic_groups", "fallback_groups", "verified_signatures", "short_groups"))
 
     def keyset_merge_checked_batch(self, ks, contributions, msgs, dst=DEFAULT_DST):
         """The call of an intermediate node of an aggregation tree: contributions[g] = the partial aggregates received for
@@ -772,14 +784,7 @@ class Engine:
         rows, sigs, coff = [], [], np.zeros(g + 1, dtype=np.uint64)
         for i, cs in enumerate(contributions):
             for row, sig in cs:
-                if not isinstance(row, (bytes, bytearray, memoryview)):
-                    r = bytearray(rb)
-                    for k in row:
-                        k = int(k)
-                        if k < 0 or k >= n:
-                            raise ValueError("a row names no key of the set")
-                        r[k >> 3] |= 1 << (k & 7)
-                    row = r
+                row = self._bit_row(row, n, "a row names no key of the set")
                 if len(row) != rb or len(sig) != sb:
                     raise ValueError("a contribution is (row of %d bytes or key indices, %d signature bytes)" % (rb, sb))
                 rows.append(bytes(row)); sigs.append(bytes(sig))
@@ -799,9 +804,7 @@ class Engine:
     def keyset_merge_stats(self):
         """dict: groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified
         individually, groups that ended in ST_SHORT"""
-        o = (ctypes.c_uint64 * 4)()
-        self._chk(self._lib.blsbn254_keyset_merge_stats(self._ctx, o))
-        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_contributions": int(o[2]), "short_groups": int(o[3])}
+        return self._stats4(self._lib.blsbn254_keyset_merge_stats, ("optimistic_groups", "fallback_groups", "verified_contributions", "short_groups"))
 
     def keyset_committee_merge_checked_batch(self, ks, com, groups, msgs, dst=DEFAULT_DST):
         """keyset_merge_checked_batch per committee of a KeySet (KeySet.set_committees): group g names committee com[g], and
@@ -838,14 +841,7 @@ class Engine:
         for i, cs in enumerate(groups):
             n, rb = sizes[com[i]], (sizes[com[i]] + 7) // 8
             for row, sig in cs:
-                if not isinstance(row, (bytes, bytearray, memoryview)):
-                    r = bytearray(rb)
-                    for k in row:
-                        k = int(k)
-                        if k < 0 or k >= n:
-                            raise ValueError("a row names no member of the committee")
-                        r[k >> 3] |= 1 << (k & 7)
-                    row = r
+                row = self._bit_row(row, n, "a row names no member of the committee")
                 if len(row) != rb or len(sig) != sb:
                     raise ValueError("a contribution is (row of %d bytes or positions, %d signature bytes)" % (rb, sb))
                 rows.append(bytes(row)); sigs.append(bytes(sig))
@@ -868,9 +864,7 @@ class Engine:
 
     def keyset_committee_merge_stats(self):
         """the counts of keyset_merge_stats for keyset_committee_merge_checked_batch"""
-        o = (ctypes.c_uint64 * 4)()
-        self._chk(self._lib.blsbn254_keyset_committee_merge_stats(self._ctx, o))
-        return {"optimistic_groups": int(o[0]), "fallback_groups": int(o[1]), "verified_contributions": int(o[2]), "short_groups": int(o[3])}
+        return self._stats4(self._lib.blsbn254_keyset_committee_merge_stats, ("optimistic_groups", "fallback_groups", "verified_contributions", "short_groups"))
 
     def aggregate_verify_batch(self, key_sets, msg_sets, agg_sigs, dst=DEFAULT_DST):
         """Many independent aggregate signatures in one call.  key_sets: list of byte strings (each a multiple of 128 bytes: the
