@@ -6,28 +6,25 @@ scratch bytes per lane (spilled registers) and the instruction count.  Usage: py
 import collections
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from kernel_resources import code_objects
+from kernel_resources import cached, demangled, disassembly
 
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def lint(path):
     """{symbol: Counter(total, readfirstlane, waterfall_loops, flat)} for every function symbol of the gfx950 code objects"""
+    return cached("lint", path, _lint)
+
+
+def _lint(path):
     out = {}
-    tmp = tempfile.mkdtemp()
-    for idx, (data, off, size) in enumerate(code_objects(path)):
-        co = os.path.join(tmp, "co_%d.o" % idx)
-        open(co, "wb").write(data[off:off + size])
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
+    for dis in disassembly(path):
         cur = None
         prev = ""
-        for line in dis.splitlines():
+        for line in open(dis):
             m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
             if m:
                 cur = out.setdefault(m.group(1), collections.Counter())
@@ -51,9 +48,10 @@ def main():
     paths = sys.argv[1:] or [os.path.join(ROOT, "bls-bn254_amd", "libblsbn254_hip.so")]
     print("%-44s %8s %8s %8s %6s" % ("symbol", "instrs", "rfl", "wf-loops", "flat"))
     for p in paths:
-        for name, c in sorted(lint(p).items()):
-            short = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.split("(")[0].strip() if name.startswith("_Z") else name
-            print("%-44s %8d %8d %8d %6d" % (short[:44], c["total"], c["readfirstlane"], c["waterfall_loops"], c["flat"]))
+        counts = lint(p)
+        short = demangled(counts)
+        for name, c in sorted(counts.items()):
+            print("%-44s %8d %8d %8d %6d" % (short[name][:44], c["total"], c["readfirstlane"], c["waterfall_loops"], c["flat"]))
 
 
 if __name__ == "__main__":

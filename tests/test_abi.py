@@ -6,19 +6,9 @@ import re
 
 import pytest
 
+from tests.library_support import M, declared_symbols, library_path_built  # noqa: F401 (M is a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "blsbn254.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(blsbn254_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_header_declares_the_surveyed_entry_points():
@@ -45,11 +35,7 @@ def test_rust_shim_extern_block_matches_the_header():
 
 
 def test_library_exports_every_declared_symbol(M):
-    path = M.library_path()
-    if not os.path.exists(path):
-        bld = __import__("bls_bn254_amd.build", fromlist=["x"])
-        bld.build()
-    lib = ctypes.CDLL(path)
+    lib = ctypes.CDLL(library_path_built())
     for s in declared_symbols():
         assert hasattr(lib, s), "missing export " + s
 

@@ -5,12 +5,10 @@ and the flag fold keep everything in registers."""
 import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
-from tests.test_msm_kernels import _scratch
+from tests.library_support import M, library_path_built, lint_by_name, scratch_bytes  # noqa: F401 (M is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("blsbn254_aggregate_verify_batch", "blsbn254_aggregate_batch_stats")
@@ -18,14 +16,8 @@ KERNELS = ("k_agb_place_sigs", "k_miller_hpk2r", "k_agb_fold")
 
 
 @pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
 def scratch():
-    return _scratch()
+    return scratch_bytes()
 
 
 def test_header_declares_and_library_exports_both_symbols(M):
@@ -33,10 +25,7 @@ def test_header_declares_and_library_exports_both_symbols(M):
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for s in SYMBOLS:
         assert re.search(r"\bint\s+%s\s*\(" % s, text), "not declared: " + s
-    path = M.library_path()
-    if not os.path.exists(path):
-        __import__("bls_bn254_amd.build", fromlist=["x"]).build()
-    lib = ctypes.CDLL(path)
+    lib = ctypes.CDLL(library_path_built())
     for s in SYMBOLS:
         assert hasattr(lib, s), "missing export " + s
 
@@ -62,12 +51,7 @@ def test_placement_and_fold_without_scratch(scratch):
 
 
 def test_ragged_miller_kernel_has_no_flat_or_serialised_accesses_beyond_the_dense_one(M):
-    sys.path.insert(0, os.path.join(ROOT, "scripts"))
-    from isa_lint import lint
-    by_name = {}
-    for sym, c in lint(M.library_path()).items():
-        name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.split("(")[0].strip() if sym.startswith("_Z") else sym
-        by_name[name] = c
+    by_name = lint_by_name(M.library_path())
     r, d = by_name["k_miller_hpk2r"], by_name["k_miller_hpk2"]
     print("k_miller_hpk2r: %s; k_miller_hpk2: %s" % (dict(r), dict(d)))
     assert r["flat"] <= d["flat"]

@@ -10,33 +10,12 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import bits_of, IDENT1, IDENT2, offsets_u64
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
-IDENT2 = bytes(64) + bytes(32) + bytes(31) + b"\x01"
 E_ARG = -1
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def bits_of(bm, n):
-    return [bool(bm[i >> 3] >> (i & 7) & 1) for i in range(n)]
-
-
-def offsets(sizes):
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
 
 
 def oracle_verify(oracle, pks, msgs, sig, dst):
@@ -134,7 +113,7 @@ def test_group_offsets_need_not_start_at_zero(eng, oracle, M):
     G = Groups(oracle, [2, 2, 0, 3, 1], dst)
     G.flip_message(3, 0)
     keys = b"".join(G.key_sets()); msgs = [m for ms in G.msgs for m in ms]
-    goff = offsets(G.sizes)[1:]                                       # the first group's two pairs belong to no group
+    goff = offsets_u64(G.sizes)[1:]                                       # the first group's two pairs belong to no group
     sigs = b"".join(G.sigs[1:])
     want = [True, False, False, True]
     assert bits_of(eng.aggregate_verify_batch_flat(keys, msgs, goff, sigs, dst), 4) == want
@@ -164,7 +143,7 @@ def test_equals_hash_and_pairing_check_composition(eng, oracle, M):
         P.append(G.sigs[g] + H[64 * pos:64 * (pos + k)])
         Q.append(neg_g2 + b"".join(G.keys[g]))
         pos += k
-    comp = eng.pairing_check_batch(b"".join(P), b"".join(Q), offsets([k + 1 for k in sizes]))
+    comp = eng.pairing_check_batch(b"".join(P), b"".join(Q), offsets_u64([k + 1 for k in sizes]))
     got = G.run(eng)
     assert got == comp
     assert bits_of(got, len(sizes)) == want

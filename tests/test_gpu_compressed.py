@@ -9,34 +9,14 @@ import pytest
 
 from tests import compressed_cases as cc
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, IDENT1
 
 pytestmark = pytest.mark.gpu
 E_ARG = -1
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 SEED = bytes(range(32))
 u8 = ctypes.POINTER(ctypes.c_uint8)
 u64 = ctypes.POINTER(ctypes.c_uint64)
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(v):
-    return v.to_bytes(32, "big")
-
-
-def bits_of(bm, n):
-    return [bool(bm[i >> 3] & (1 << (i & 7))) for i in range(n)]
 
 
 def split(b, w):

@@ -18,27 +18,12 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32
 
 pytestmark = pytest.mark.gpu
 ONE_GT = (1).to_bytes(32, "big") + bytes(352)
 R = synth.R
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback.  Generates inputs only:
-    yield e                   # every context under test is created by the test that uses it
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
 
 
 def popcount(bm):

@@ -7,21 +7,9 @@ a capacity of 64 keys is set where the store has to be emptied.  Expected values
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback.  Generates inputs only
-    yield e
-    e.close()
 
 
 _BATCHES = {}

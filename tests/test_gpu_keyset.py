@@ -9,108 +9,15 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, IDENT1, IDENT2, row_of
+from tests.keyset_support import Committee, edge_rows, sign_rows
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT2 = bytes(127) + b"\x01"
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 E_ARG = -1
 u8 = ctypes.POINTER(ctypes.c_uint8)
 u64 = ctypes.POINTER(ctypes.c_uint64)
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def row_of(sel, n):
-    r = bytearray((n + 7) // 8)
-    for i in sel:
-        r[i >> 3] |= 1 << (i & 7)
-    return bytes(r)
-
-
-def bits_of(bitmap, n):
-    return [(bitmap[i >> 3] >> (i & 7)) & 1 == 1 for i in range(n)]
-
-
-class Committee:
-    """n keys [sk_i] G2gen made on the GPU.  special (n >= 33): an identity key, an off-curve key, an undecodable key, P and -P,
-    one key at two indices and a key outside the r-torsion.  sk[i]: what key i adds to a group's secret key (None: no
-    signature can verify with it selected)."""
-
-    def __init__(self, eng, n, seed, special=True):
-        self.n = n
-        self.sk = [synth.sk_of(1000 * seed + k) for k in range(n)]
-        pk = eng.sk_to_pk_batch(b"".join(map(b32, self.sk)), n)
-        self.keys = [pk[128 * i:128 * i + 128] for i in range(n)]
-        self.bad, self.at = set(), {}
-        if special and n >= 33:
-            at = self.at = {"ident": 3, "off": 5, "undec": n - 2, "p": 7, "negp": n // 2, "dup_a": 1, "dup_b": n - 1, "nonsub": 9}
-            self.keys[at["ident"]] = IDENT2; self.sk[at["ident"]] = 0
-            off = bytearray(self.keys[at["off"]]); off[127] ^= 1
-            self.keys[at["off"]] = bytes(off)
-            self.keys[at["undec"]] = b"\xff" * 32 + self.keys[at["undec"]][32:]
-            self.bad = {at["off"], at["undec"]}
-            p = self.keys[at["p"]]
-            self.keys[at["negp"]] = p[:64] + b32(synth.P - int.from_bytes(p[64:96], "big")) + b32(synth.P - int.from_bytes(p[96:], "big"))
-            self.sk[at["negp"]] = R - self.sk[at["p"]]
-            self.keys[at["dup_b"]] = self.keys[at["dup_a"]]; self.sk[at["dup_b"]] = self.sk[at["dup_a"]]
-            self.keys[at["nonsub"]] = synth.NON_SUBGROUP_PK
-            for i in self.bad | {at["nonsub"]}:
-                self.sk[i] = None
-        self.pks = b"".join(self.keys)
-        self.unsignable = {i for i in range(n) if self.sk[i] is None}
-
-    def gather(self, sel):
-        return b"".join(self.keys[i] for i in sorted(sel))
-
-    def group_sk(self, sel):
-        s = sum(self.sk[i] for i in sel if self.sk[i] is not None) % R
-        return s or 1                                                  # (no signature verifies under the identity key anyway)
-
-
-def sign_rows(eng, com, rows, msgs, dst):
-    return bytearray(eng.sign_batch(b"".join(b32(com.group_sk(r)) for r in rows), msgs, dst))
-
-
-def edge_rows(com, rnd):
-    """about 24 rows (sets of indices) and the names of the ones later tests refer to"""
-    n, named = com.n, {}
-    good = [i for i in range(n) if i not in com.unsignable]
-    rows = [set(), set(range(n)), {n - 1}]
-    for w in range(min((n + 31) // 32, 3)):
-        rows.append({32 * w}); rows.append({min(32 * w + 31, n - 1)})
-    rows.append(set(rnd.sample(range(n), n // 2)))                      # exactly n/2 bits: not flipped
-    named["boundary"] = len(rows); rows.append(set(rnd.sample(good, min(len(good), n // 2 + 1))))      # n/2 + 1 bits: the flip boundary, verifies
-    rows.append(set(good))                                              # flipped, the bad keys left unselected: stays valid
-    for dens in (0.1, 0.5, 0.9):
-        rows.append({i for i in good if rnd.random() < dens})
-        rows.append({i for i in range(n) if rnd.random() < dens})
-    if com.at:
-        at = com.at
-        named["flipped_with_bad"] = len(rows); rows.append(set(range(n)) - {at["undec"], at["nonsub"]})     # flipped and selects the off-curve key
-        named["p_negp"] = len(rows); rows.append({at["p"], at["negp"]})
-        named["nonsub"] = len(rows); rows.append({0, at["nonsub"]})
-        named["dup"] = len(rows); rows.append({at["dup_a"], at["dup_b"]})
-        named["ident"] = len(rows); rows.append({0, 2, at["ident"]})
-        rows.append({at["undec"]}); rows.append({0, at["off"]})
-    named["tampered"] = len(rows); rows.append(set(good[:max(1, len(good) // 3)]))
-    named["ident_sig"] = len(rows); rows.append(set(good[:max(1, len(good) // 4)]))
-    return rows, named
 
 
 @pytest.mark.parametrize("n", [1, 33, 70, 513])

@@ -10,45 +10,17 @@ import numpy as np
 import pytest
 
 from tests import synth
-from tests.test_gpu_keyset import Committee, row_of
+from tests.gpu_support import eng, M
+from tests.helpers import IDENT1, row_of
+from tests.keyset_support import Committee, delta, good_keys, sign_sets, ST_SHORT
+from tests.threshold_support import checked_flow
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 E_ARG = -1
-ST_SHORT = 5
 u8 = ctypes.POINTER(ctypes.c_uint8)
 u32 = ctypes.POINTER(ctypes.c_uint32)
 u64 = ctypes.POINTER(ctypes.c_uint64)
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def sign_sets(eng, com, sets, msgs, dst, sk=None):
-    """one dict {key index: signature of that key on msgs[g]} per set of indices; sk(g, i) overrides the signing key"""
-    pairs = [(g, i) for g, s in enumerate(sets) for i in sorted(s)]
-    out = [dict() for _ in sets]
-    if pairs:
-        sks = b"".join(b32((sk(g, i) if sk else None) or com.sk[i] or 1) for g, i in pairs)
-        sig = bytes(eng.sign_batch(sks, [msgs[g] for g, _ in pairs], dst))
-        for k, (g, i) in enumerate(pairs):
-            out[g][i] = sig[64 * k:64 * k + 64]
-    return out
 
 
 def agg(oracle, entries, kept):
@@ -72,14 +44,6 @@ def check_groups(oracle, com, entries, kept, msgs, res, dst, honest_sums=True):
         if honest_sums:
             assert sigs[g] == agg(oracle, entries[g], k), g
         assert oracle.fast_aggregate_verify(com.gather(k), len(k), msgs[g], sigs[g], dst), g
-
-
-def good_keys(com):
-    return [i for i in range(com.n) if i not in com.unsignable and i != com.at.get("ident")]
-
-
-def delta(st1, st0):
-    return {k: st1[k] - st0[k] for k in st1}
 
 
 @pytest.mark.parametrize("n", [1, 33, 70])
@@ -253,7 +217,6 @@ def test_launch_boundaries(eng, oracle, M, monkeypatch):
 
 
 def test_other_call_families_on_one_context(eng, oracle, M):
-    from tests.test_gpu_threshold_checked import _flow
     dst, dst2 = M.DEFAULT_DST, b"KEYSET-AGGREGATE-SECOND-DST"
     coms = [Committee(eng, 70, 91), Committee(eng, 33, 92)]
     entries, kept, msgs = boundary_case(eng, coms[0], dst)              # needs the fallback
@@ -262,7 +225,7 @@ def test_other_call_families_on_one_context(eng, oracle, M):
     msgs1 = [b"second set %d" % g for g in range(3)]
     entries1 = sign_sets(eng, coms[1], sets1, msgs1, dst2)              # all honest, another tag
     vb = synth.make_batch_gpu(eng, oracle, 300, dst, pool=20, invalid_every=7, spot=2)
-    deal = _flow(eng, 8, 4, 93, dst).args()
+    deal = checked_flow(eng, 8, 4, 93, dst).args()
     fav_rows = [row_of(k, 70) for k in kept if k]
     fav_msgs = [m for m, k in zip(msgs, kept) if k]
     fav_sigs = b"".join(agg(oracle, entries[g], k) for g, k in enumerate(kept) if k)

@@ -8,23 +8,12 @@ import random
 import pytest
 
 from tests import synth
-from tests.test_gpu_keyset import Committee, IDENT1, IDENT2, b32, bits_of, edge_rows, row_of, sign_rows
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, IDENT1, IDENT2, row_of
+from tests.keyset_support import Committee, edge_rows, sign_rows
 
 pytestmark = pytest.mark.gpu
 UNDEC2 = b"\xff" * 128
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
 
 
 def proofs_of(eng, com, seed):

@@ -6,15 +6,10 @@ small, then large again -- must give what the same call gives on a fresh context
 four counts, the siblings' counts untouched.  The calls themselves are pinned to the oracle by their own test files."""
 import pytest
 
-import blsbn254_loader
-from tests.test_gpu_keyset_aggregate import ST_SHORT, delta
-from tests.test_gpu_keyset_committee_aggregate import World, fresh_engine, sign_positions
-from tests.test_gpu_keyset_committee_merge import com_args, keys_of
-from tests.test_gpu_keyset_merge import Con, as_args, chunks, sign_all
-from tests.test_gpu_keyset_wire import compress_entries, compressed
+from tests.gpu_support import eng, fresh_engine, M
+from tests.keyset_support import as_args, chunks, com_args, compress_entries, compressed, Con, delta, keys_of, sign_all, sign_positions, ST_SHORT, World
 
 pytestmark = pytest.mark.gpu
-_M = blsbn254_loader.load()
 CALLS = {"agg": "keyset_aggregate", "cagg": "keyset_committee_aggregate", "mrg": "keyset_merge", "cmrg": "keyset_committee_merge"}
 # per size: the groups' committees (0: one member, a row of one byte; 1, 3, 5: rows of 4, 5 and 17 bytes over a registry of 140
 # keys, 17.5 bytes) and their entries.  Every size has a group that takes the fallback and succeeds (one wrong entry among honest
@@ -24,18 +19,6 @@ SHAPES = {"large": ([5, 3, 0, 1, 1], [12, 6, 1, 0, 4]), "small": ([3, 0, 1, 5], 
 WRONG = {"large": {(0, 4), (1, 1), (2, 0)}, "small": {(0, 2), (1, 0)}}      # (group, entry) signed with another secret key
 STATUS = {"large": bytes([0, 0, ST_SHORT, ST_SHORT, 0]), "small": bytes([0, ST_SHORT, ST_SHORT, 0])}
 COUNTS = {"large": (1, 3, 19, 2), "small": (1, 2, 4, 2)}      # optimistic groups, fallback groups, entries verified there, short groups
-
-
-@pytest.fixture(scope="module")
-def M():
-    return _M
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")

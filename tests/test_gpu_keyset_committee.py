@@ -9,32 +9,14 @@ import pytest
 
 import blsbn254_loader
 from tests import synth
-from tests.test_gpu_keyset import Committee, IDENT1, IDENT2, b32, bits_of, row_of, sign_rows
-from tests.test_keyset_committee_host import model_plan
+from tests.gpu_support import eng, fresh_engine, M
+from tests.helpers import b32, bits_of, IDENT1, IDENT2, row_of
+from tests.keyset_support import Committee, committee_model_plan, sign_rows
 
 pytestmark = pytest.mark.gpu
 E_ARG = -1
 _M = blsbn254_loader.load()
 _M.KeySet.set_committees, _M.Engine.keyset_committee_sum_batch          # the feature is there, or this module does not import
-
-
-@pytest.fixture(scope="module")
-def M():
-    return _M
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def fresh_engine(M, monkeypatch, chunk):
-    with monkeypatch.context() as mp:
-        if chunk:
-            mp.setenv("BLSBN254_CHUNK_LANES", chunk)
-        return M.Engine(0)
 
 
 def scatter(members, positions):
@@ -238,7 +220,7 @@ def test_launch_boundaries(eng, M, W, handles, monkeypatch):
         want = (eng.keyset_committee_sum_batch(ks0, com, rows), eng.keyset_committee_fast_aggregate_verify_batch(ks0, com, rows, msgs, sigs, W.dst),
                 eng.keyset_committee_weight_batch(ks0, com, rows).tolist())
         assert want[0] == eng.keyset_sum_batch(ks0, [W.wide[g] for g in groups])
-        launches = len(model_plan(W.coms, com, int(chunk))[1])
+        launches = len(committee_model_plan(W.coms, com, int(chunk))[1])
         assert launches >= min_launches and len(groups) <= int(chunk)
         e = fresh_engine(M, monkeypatch, chunk)
         try:

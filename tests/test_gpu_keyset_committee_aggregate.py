@@ -11,8 +11,9 @@ import pytest
 
 import blsbn254_loader
 from tests import synth
-from tests.test_gpu_keyset import Committee, IDENT1, b32, bits_of, row_of
-from tests.test_gpu_keyset_aggregate import ST_SHORT, delta, sign_sets
+from tests.gpu_support import eng, fresh_engine, M
+from tests.helpers import bits_of, IDENT1, row_of
+from tests.keyset_support import compact, delta, sign_positions, sign_sets, ST_SHORT, World
 
 pytestmark = pytest.mark.gpu
 E_ARG = -1
@@ -20,51 +21,6 @@ R = synth.R
 _M = blsbn254_loader.load()
 _M.Engine.keyset_committee_aggregate_checked_batch          # the feature is there, or this module does not import
 ZERO = {"optimistic_groups": 0, "fallback_groups": 0, "verified_signatures": 0, "short_groups": 0}
-
-
-@pytest.fixture(scope="module")
-def M():
-    return _M
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-class World:
-    """140 keys with an identity key (3), an off-curve key (5), a key outside the r-torsion (9), an undecodable key (138), P and
-    -P (7, 70), one key at two indices (1, 139) and, on the checked handle, a key whose proof fails (12).  Committees of 1, 31,
-    32, 33, 65 and 129 members: 1 and 2 overlap, 3 lists its members in descending order, 4 contains every special key."""
-
-    def __init__(self, eng, M):
-        self.dst = M.DEFAULT_DST
-        self.n = n = 140
-        rnd = random.Random(2027)
-        self.reg = reg = Committee(eng, n, 64)
-        at = reg.at
-        first = [reg.sk[i] if reg.sk[i] else 1000 + i for i in range(n)]
-        p = eng.pop_prove_batch(b"".join(b32(s) for s in first), n)
-        self.proofs = p[:64 * 12] + IDENT1 + p[64 * 13:]
-        self.special = set(at.values()) | {12}
-        plain = [i for i in range(n) if i not in self.special]
-        bad_com = sorted(self.special) + plain[20:20 + 65 - len(self.special)]
-        rnd.shuffle(bad_com)
-        self.coms = [[20], list(range(30, 61)), list(range(50, 82)), list(range(132, 99, -1)), bad_com, rnd.sample(plain, 129)]
-        assert [len(c) for c in self.coms] == [1, 31, 32, 33, 65, 129]
-        assert set(self.coms[1]) & set(self.coms[2]) and self.special <= set(self.coms[4]) and len(self.special) == 9
-        # members whose entry is a candidate on both handles when its signature is honest
-        self.clean = [[j for j, i in enumerate(mem) if i not in self.special or i in (at["p"], at["dup_a"], at["dup_b"])] for mem in self.coms]
-
-    def keyset(self, M, e, checked, table=None):
-        ks = M.KeySet(e, self.reg.pks, self.n, proofs=self.proofs if checked else None)
-        ks.set_committees(self.coms if table is None else table)
-        return ks
-
-    def pos_of(self, c, key):
-        return self.coms[c].index(key)
 
 
 @pytest.fixture(scope="module")
@@ -78,22 +34,6 @@ def handles(eng, M, W):
     yield hs
     for ks in hs.values():
         ks.close()
-
-
-def sign_positions(eng, W, com, pos_sets, msgs, sk=None, coms=None):
-    """one dict {position: signature of that member on msgs[g]} per group; sk(g, position) overrides the signing key"""
-    coms = coms or W.coms
-    sets = [{coms[c][p] for p in ps} for c, ps in zip(com, pos_sets)]
-    by_key = sign_sets(eng, W.reg, sets, msgs, W.dst, sk=(lambda g, i: sk(g, coms[com[g]].index(i))) if sk else None)
-    return [{p: by_key[g][coms[c][p]] for p in ps} for g, (c, ps) in enumerate(zip(com, pos_sets))]
-
-
-def compact(mem, wide_row):
-    r = bytearray((len(mem) + 7) // 8)
-    for j, i in enumerate(mem):
-        if (wide_row[i >> 3] >> (i & 7)) & 1:
-            r[j >> 3] |= 1 << (j & 7)
-    return bytes(r)
 
 
 def yardstick(e, ks, W, com, entries, msgs, coms=None):
@@ -236,13 +176,6 @@ def test_one_wrong_signature(eng, oracle, W, handles):
     # a group's outcome depends on its own inputs only: the honest neighbours alone
     alone = eng.keyset_committee_aggregate_checked_batch(ks, com[4:6], entries[4:6], msgs[4:6], W.dst)
     assert alone == (res[0][256:384], res[1][4:6], res[2][4:6])
-
-
-def fresh_engine(M, monkeypatch, chunk):
-    with monkeypatch.context() as mp:
-        if chunk:
-            mp.setenv("BLSBN254_CHUNK_LANES", chunk)
-        return M.Engine(0)
 
 
 def test_launch_boundaries(eng, M, W, handles, monkeypatch):

@@ -12,9 +12,9 @@ import pytest
 
 import blsbn254_loader
 from tests import synth
-from tests.test_gpu_keyset import Committee, IDENT1, bits_of, row_of
-from tests.test_gpu_keyset_committee_aggregate import World, compact, fresh_engine, sign_positions
-from tests.test_gpu_keyset_merge import Con, ST_SHORT, STATS, as_args, chunks, delta, expect, sign_all
+from tests.gpu_support import eng, fresh_engine, M
+from tests.helpers import bits_of, IDENT1, row_of
+from tests.keyset_support import as_args, chunks, com_args, Committee, compact, Con, delta, expect, keys_of, sign_all, sign_positions, ST_SHORT, STATS, World
 
 pytestmark = pytest.mark.gpu
 E_ARG = -1
@@ -22,18 +22,6 @@ R = synth.R
 _M = blsbn254_loader.load()
 _M.Engine.keyset_committee_merge_checked_batch              # the feature is there, or this module does not import
 ZERO = dict.fromkeys(STATS, 0)
-
-
-@pytest.fixture(scope="module")
-def M():
-    return _M
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -51,16 +39,6 @@ def handles(eng, M, W):
 
 def siblings(e):
     return e.keyset_stats(), e.keyset_aggregate_stats(), e.keyset_committee_stats(), e.keyset_committee_aggregate_stats(), e.keyset_merge_stats()
-
-
-def com_args(coms, com, groups, as_rows=False):
-    """what the wrapper takes: a contribution's keys as positions in its group's committee, or as a committee-wide row"""
-    out = []
-    for c, cs in zip(com, groups):
-        at = {k: j for j, k in enumerate(coms[c])}
-        pos = [sorted(at[k] for k in x.keys) for x in cs]
-        out.append([(row_of(p, len(coms[c])) if as_rows else p, x.sig) for p, x in zip(pos, cs)])
-    return out
 
 
 def yardstick(e, ks, n, coms, com, groups, msgs, dst):
@@ -105,10 +83,6 @@ def run_both(e, oracle, ks, W, com, groups, msgs, kinds=None):
     bits = bits_of(e.keyset_committee_fast_aggregate_verify_batch(ks, com, res[1], msgs, res[0], W.dst), len(com))
     assert [bool(b) for b in bits] == [s == 0 for s in res[3]]             # the committee verify accepts exactly the status-0 groups
     return res, tally
-
-
-def keys_of(W, c, positions=None):
-    return [W.coms[c][j] for j in (W.clean[c] if positions is None else positions)]
 
 
 def cut(keys, parts):

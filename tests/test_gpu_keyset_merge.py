@@ -12,85 +12,15 @@ import numpy as np
 import pytest
 
 from tests import synth
-from tests.test_gpu_keyset import Committee, row_of
+from tests.gpu_support import eng, M
+from tests.helpers import IDENT1, row_of
+from tests.keyset_support import as_args, chunks, Committee, Con, delta, expect, good_keys, sign_all, ST_SHORT, STATS
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 E_ARG = -1
-ST_SHORT = 5
 u8 = ctypes.POINTER(ctypes.c_uint8)
 u64 = ctypes.POINTER(ctypes.c_uint64)
-STATS = ("optimistic_groups", "fallback_groups", "verified_contributions", "short_groups")
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-class Con:
-    """one contribution: the keys its row names, the keys whose secrets sign it (signed, default the same; sk_delta is added to
-    their sum), and what the test made of it: cand = the call may select it, good = it verifies on its own"""
-
-    def __init__(self, keys, signed=None, sk_delta=0, cand=True, good=True):
-        self.keys, self.signed, self.sk_delta, self.cand, self.good, self.sig = set(keys), signed, sk_delta, cand, good, None
-
-    def broken(self, sig):
-        self.sig, self.cand, self.good = sig, False, False
-        return self
-
-
-def sign_all(eng, com, groups, msgs, dst):
-    flat = [(g, c) for g, cs in enumerate(groups) for c in cs]
-    if flat:
-        sks = b"".join(b32((com.group_sk(c.keys if c.signed is None else c.signed) + c.sk_delta) % R or 1) for _, c in flat)
-        sig = bytes(eng.sign_batch(sks, [msgs[g] for g, _ in flat], dst))
-        for k, (_, c) in enumerate(flat):
-            c.sig = sig[64 * k:64 * k + 64]
-    return groups
-
-
-def as_args(groups, n=None):
-    """what the wrapper takes: key indices, or row bytes where n is given"""
-    return [[(row_of(c.keys, n) if n else sorted(c.keys), c.sig) for c in cs] for cs in groups]
-
-
-def greedy(cs, admit):
-    union, used = set(), []
-    for c in cs:
-        u = bool(admit(c)) and not (c.keys & union)
-        if u:
-            union |= c.keys
-        used.append(u)
-    return used, union
-
-
-def expect(cs, kind=None):
-    """the model: (used flags, union or None for a short group, went to the fallback, contributions verified there).
-    kind: "cancel" = the selected errors cancel in the sum, "zero_sum" = the kept keys sum to the identity"""
-    used, union = greedy(cs, lambda c: c.cand)
-    if not any(used):
-        return [False] * len(cs), None, False, 0
-    if kind != "zero_sum" and (kind == "cancel" or all(c.good for c, u in zip(cs, used) if u)):
-        return used, union, False, 0
-    verified = sum(1 for c in cs if c.cand)
-    used, union = greedy(cs, lambda c: c.cand and c.good)
-    if not any(used) or kind == "zero_sum":
-        return [False] * len(cs), None, True, verified
-    return used, union, True, verified
 
 
 def check_groups(oracle, com, groups, msgs, res, dst, kinds=None, gather=True):
@@ -114,22 +44,6 @@ def check_groups(oracle, com, groups, msgs, res, dst, kinds=None, gather=True):
         if gather:
             assert oracle.fast_aggregate_verify(com.gather(union), len(union), msgs[g], sig, dst), g
     return tally
-
-
-def good_keys(com):
-    return [i for i in range(com.n) if i not in com.unsignable and i != com.at.get("ident")]
-
-
-def delta(st1, st0):
-    return {k: st1[k] - st0[k] for k in st1}
-
-
-def chunks(keys, sizes):
-    out, at = [], 0
-    for s in sizes:
-        out.append(keys[at:at + s]); at += s
-    assert all(len(c) == s for c, s in zip(out, sizes))
-    return out
 
 
 @pytest.mark.parametrize("n", [1, 33, 70])

@@ -12,8 +12,9 @@ import pytest
 
 import blsbn254_loader
 from tests import synth
-from tests.test_gpu_keyset import Committee, IDENT1, b32, bits_of, row_of, sign_rows
-from tests.test_keyset_rlc_host import model_plan
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, IDENT1, row_of
+from tests.keyset_support import Committee, rlc_model_plan, sign_rows
 
 pytestmark = pytest.mark.gpu
 E_ARG = -1
@@ -22,18 +23,6 @@ _M.Engine.keyset_fast_aggregate_verify_batch_rlc, _M.Engine.keyset_rlc_stats    
 DST = _M.DEFAULT_DST
 SEEDS = [b"\x01" * 32, bytes(range(32)), hashlib.sha256(b"key-set rlc").digest(), None]
 N = 70
-
-
-@pytest.fixture(scope="module")
-def M():
-    return _M
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -72,7 +61,7 @@ def neg_g1(p):
 
 def chunk_model(msgs, C):
     """(chunks worth checking when every group is eligible, groups in them, groups alone in their chunk)"""
-    _, chunks, rep = model_plan(msgs, C)
+    _, chunks, rep = rlc_model_plan(msgs, C)
     multi = [l for _, l, _ in chunks if l >= 2]
     return len(multi), sum(multi), sum(1 for _, l, _ in chunks if l == 1), len(rep)
 

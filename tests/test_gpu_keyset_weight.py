@@ -9,24 +9,13 @@ import numpy as np
 import pytest
 
 from tests import synth
-from tests.test_gpu_keyset import Committee, IDENT1, b32, bits_of, edge_rows, row_of, sign_rows
+from tests.gpu_support import eng, fresh_engine, M
+from tests.helpers import b32, bits_of, IDENT1, row_of
+from tests.keyset_support import Committee, edge_rows, sign_rows
 
 pytestmark = pytest.mark.gpu
 M64 = (1 << 64) - 1
 E_ARG = -1
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
 
 
 def table(rnd, n, nc):
@@ -37,13 +26,6 @@ def table(rnd, n, nc):
 
 def expect(cols, rows, valid):
     return [[sum(col[i] for i in r if valid[i]) for col in cols] for r in rows]
-
-
-def fresh_engine(M, monkeypatch, chunk):
-    with monkeypatch.context() as mp:
-        if chunk:
-            mp.setenv("BLSBN254_CHUNK_LANES", chunk)
-        return M.Engine(0)
 
 
 @pytest.mark.parametrize("n", [1, 33, 70, 513, 2081])

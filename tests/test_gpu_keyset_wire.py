@@ -11,8 +11,9 @@ import pytest
 
 import blsbn254_loader
 from tests import synth
-from tests.test_gpu_keyset import Committee, b32, bits_of, row_of
-from tests.test_gpu_keyset_aggregate import ST_SHORT, delta, good_keys, sign_sets
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, row_of
+from tests.keyset_support import Committee, compress_entries, compressed, delta, good_keys, sign_sets, ST_SHORT
 
 pytestmark = pytest.mark.gpu
 E_ARG = -1
@@ -25,30 +26,8 @@ IDENT_W = (bytes(32), bytes([0x80]) + bytes(31))             # the identity with
 NO_POINT = next(b32(x) for x in range(2, 99) if pow(x ** 3 + 3, (P - 1) // 2, P) == P - 1)     # x^3 + 3 is no square
 
 
-@pytest.fixture(scope="module")
-def M():
-    return _M
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
 def flip_flag(c):
     return bytes([c[0] ^ 0x80]) + c[1:]
-
-
-def compress_entries(e, entries):
-    """[{slot: 64 bytes}] -> [{slot: 32 bytes}]"""
-    flat = [(g, k) for g, es in enumerate(entries) for k in sorted(es)]
-    c = e.g1_compress_batch(b"".join(entries[g][k] for g, k in flat), len(flat)) if flat else b""
-    out = [dict() for _ in entries]
-    for j, (g, k) in enumerate(flat):
-        out[g][k] = c[32 * j:32 * j + 32]
-    return out
 
 
 def inflate_entries(e, wire):
@@ -59,10 +38,6 @@ def inflate_entries(e, wire):
     for j, (g, k) in enumerate(flat):
         out[g][k] = f[64 * j:64 * j + 64]
     return out
-
-
-def compressed(e, sigs64):
-    return e.g1_compress_batch(sigs64, len(sigs64) // 64) if sigs64 else b""
 
 
 # ------------------------------------------------------------------ the collector, key-set form

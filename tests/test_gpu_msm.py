@@ -2,43 +2,15 @@
 the oracle's Mul<Scalar> and Add folded in Python, every window width, the GLV split boundaries, identities and cancellations,
 points outside the G2 r-torsion, the error mapping, and large cases (2^20 G1 terms, 2^18 G2 terms) in closed form:
 with P_i = [a_i] G, sum_i [k_i] P_i = [sum_i k_i a_i mod r] G."""
-import os
 import random
-import re
 
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, glv_lambda, IDENT1, IDENT2
 
 pytestmark = pytest.mark.gpu
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
-IDENT2 = bytes(64) + bytes(32) + bytes(31) + b"\x01"        # x = 0, y = (c1 = 0, c0 = 1)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import blsbn254_loader
-    M = blsbn254_loader.load()
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-def glv_lambda():
-    src = open(os.path.join(ROOT, "bls-bn254_amd", "csrc", "bn254_consts.h")).read()
-    words = re.search(r"GLV_LAMBDA\[4\]\s*=\s*\{([^}]*)\}", src).group(1).split(",")
-    return sum(int(w.strip().rstrip("uUlL"), 16) << (64 * i) for i, w in enumerate(words))
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
 
 
 def fold(oracle, pts, ks, g2=False):

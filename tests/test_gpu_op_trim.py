@@ -5,16 +5,11 @@ fixed square-root chain, and the Gt-returning path, which keeps the full last st
 import pytest
 
 from tests import synth
+from tests.gpu_support import M
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 257)
 POOL = 3
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
 
 
 @pytest.fixture(scope="module")

@@ -10,38 +10,13 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, IDENT1, IDENT2, offsets_u64
 
 pytestmark = pytest.mark.gpu
 R = synth.R
 ONE = (1).to_bytes(32, "big") + bytes(352)                       # Fp12::ONE
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
-IDENT2 = bytes(64) + bytes(32) + bytes(31) + b"\x01"
 E_ARG = -1
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def offsets(sizes):
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-
-
-def bits_of(bm, n):
-    return [bool(bm[i >> 3] >> (i & 7) & 1) for i in range(n)]
 
 
 def closed_form_scalars(rnd, sizes, holds, zero=()):
@@ -110,7 +85,7 @@ def test_small_ragged_vs_oracle(eng, oracle):
     Q = bytearray(Q)
     Q[128 * 4:128 * 5] = IDENT2                                  # an identity Q in the 3-pair group (its equation no longer holds)
     Q = bytes(Q)
-    off = offsets(sizes)
+    off = offsets_u64(sizes)
     mls, bits = truth(oracle, P, Q, off)
     got = eng.multi_miller_loop_batch(P, Q, off)
     assert len(got) == 384 * len(sizes)
@@ -128,7 +103,7 @@ def test_offsets_need_not_start_at_zero(eng, oracle):
     sizes = [2, 0, 3]
     a, b, _ = closed_form_scalars(rnd, [1] + sizes, [False, True, True, False])
     P, Q = points_gpu(eng, oracle, a, b)
-    off = offsets([1] + sizes)[1:]                                  # the first pair belongs to no equation
+    off = offsets_u64([1] + sizes)[1:]                                  # the first pair belongs to no equation
     out = np.zeros(1, dtype=np.uint8)
     o = np.ascontiguousarray(off)
     g1 = np.frombuffer(P, dtype=np.uint8); g2 = np.frombuffer(Q, dtype=np.uint8)
@@ -146,7 +121,7 @@ def test_closed_form_shapes(eng, oracle):
     holds = [True, False, True, False] * 8
     a, b, _ = closed_form_scalars(rnd, sizes, holds)
     P, Q = points_gpu(eng, oracle, a, b)
-    assert bits_of(eng.pairing_check_batch(P, Q, offsets(sizes)), len(sizes)) == holds
+    assert bits_of(eng.pairing_check_batch(P, Q, offsets_u64(sizes)), len(sizes)) == holds
 
 
 def test_identity_members(eng, oracle):
@@ -162,7 +137,7 @@ def test_identity_members(eng, oracle):
     ]
     P = b"".join(p for eq, _ in eqs for p, _ in eq)
     Q = b"".join(q for eq, _ in eqs for _, q in eq)
-    off = offsets([len(eq) for eq, _ in eqs])
+    off = offsets_u64([len(eq) for eq, _ in eqs])
     want = [h for _, h in eqs]
     assert bits_of(eng.pairing_check_batch(P, Q, off), len(eqs)) == want
     assert truth(oracle, P, Q, off)[1] == want
@@ -186,7 +161,7 @@ def test_invalid_members(eng, oracle, M):
     Q[128 * 11:128 * 12] = IDENT2
     Q[128 * 14:128 * 14 + 32] = b"\xff" * 32                        # eq 7: Q does not decode (x.c1 >= p)
     P, Q = bytes(P), bytes(Q)
-    off = offsets([2] * n_eq)
+    off = offsets_u64([2] * n_eq)
     want = [g not in (1, 2, 3, 5, 7) for g in range(n_eq)]
     mls, tb = truth(oracle, P, Q, off)
     assert tb == want
@@ -216,7 +191,7 @@ def test_bls_verify_equivalence(eng, oracle, M):
     neg_g2 = oracle.g2_mul(oracle.g2_generator(), R - 1)
     P = b"".join(sigs[64 * i:64 * i + 64] + H[64 * i:64 * i + 64] for i in range(n))
     Q = b"".join(neg_g2 + pks[128 * i:128 * i + 128] for i in range(n))
-    got = eng.pairing_check_batch(P, Q, offsets([2] * n))
+    got = eng.pairing_check_batch(P, Q, offsets_u64([2] * n))
     assert got == eng.verify_batch(pks, msgs, sigs, dst) == synth.bitmap_of(exp)
 
 
@@ -231,7 +206,7 @@ def _run_forms(M, eng, oracle, monkeypatch, sizes, holds, seed, envs):
     rnd = random.Random(seed)
     a, b, holds = closed_form_scalars(rnd, sizes, holds, zero=[i for i in range(sum(sizes)) if i % 37 == 5])
     P, Q = points_gpu(eng, oracle, a, b)
-    off = offsets(sizes)
+    off = offsets_u64(sizes)
     bm = eng.pairing_check_batch(P, Q, off)
     ml = eng.multi_miller_loop_batch(P, Q, off)
     assert bits_of(bm, len(sizes)) == holds
@@ -297,7 +272,7 @@ def test_large_two_pair_equations(eng, oracle):
         holds[g] = False
     a = [v for pair in zip(a0, a1) for v in pair]; b = [v for pair in zip(b0, b1) for v in pair]
     P, Q = points_gpu(eng, oracle, a, b)
-    got = eng.pairing_check_batch(P, Q, offsets([2] * n_eq))
+    got = eng.pairing_check_batch(P, Q, offsets_u64([2] * n_eq))
     assert got == synth.bitmap_of(holds)
 
 

@@ -9,27 +9,12 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import IDENT1, IDENT2
 
 pytestmark = pytest.mark.gpu
 H = lambda s: int(s, 16)
 ONE_GT = (1).to_bytes(32, "big") + bytes(352)
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
-IDENT2 = bytes(64) + bytes(32) + bytes(31) + b"\x01"        # x = 0, y = (c1 = 0, c0 = 1): G2Affine::identity, g2.rs
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import blsbn254_loader
-    M = blsbn254_loader.load()
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
 
 
 def test_pairing_golden(eng, oracle, kats):

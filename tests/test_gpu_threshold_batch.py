@@ -9,29 +9,13 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, IDENT1, poly_eval
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 E_ARG = -1
 ERR_SCALAR, ERR_G1 = 1, 2
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
 
 
 def random_groups(eng, oracle, rnd, sizes):
@@ -48,13 +32,6 @@ def random_groups(eng, oracle, rnd, sizes):
         sig_sets.append(pts[64 * pos:64 * (pos + t)])
         pos += t
     return id_sets, sig_sets
-
-
-def poly_eval(coeffs, x):
-    acc = 0
-    for c in reversed(coeffs):
-        acc = (acc * x + c) % R
-    return acc
 
 
 def closed_form_groups(eng, oracle, rnd, sizes, dst, pool_extra=3, spot=16):

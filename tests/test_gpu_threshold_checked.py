@@ -9,101 +9,18 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, bits_of, IDENT1, poly_eval
+from tests.threshold_support import checked_flow, Deal, NEIGHBOUR_KEY, OTHER_MSG, pack
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 E_ARG = -1
 ERR_SCALAR, ERR_G2, ST_SHORT = 1, 3, 5
 SIZES_N = [1, 2, 5, 7, 64, 65, 3, 0]
 SIZES_T = [1, 2, 3, 5, 33, 4, 5, 2]          # the last two groups are short by size
-OTHER_MSG, NEIGHBOUR_KEY, IDENTITY, OFF_CURVE, UNDECODABLE = range(5)
 u8 = ctypes.POINTER(ctypes.c_uint8)
 u64 = ctypes.POINTER(ctypes.c_uint64)
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def pack(sets):
-    return [b"".join(map(b32, s)) for s in sets]
-
-
-def poly_eval(coeffs, x):
-    acc = 0
-    for c in reversed(coeffs):
-        acc = (acc * x + c) % R
-    return acc
-
-
-def bits_of(bitmap, n):
-    return [(bitmap[i >> 3] >> (i & 7)) & 1 == 1 for i in range(n)]
-
-
-class Deal:
-    """groups of sizes ns with thresholds ts: coefficients, ids (random in [1, r) in the even groups, 1 .. n in the odd ones
-    unless small_ids), commitments, one message per group, and every share's partial signature, all of them good"""
-
-    def __init__(self, eng, ns, ts, seed, dst, small_ids=False):
-        rnd = random.Random(seed)
-        self.ns, self.ts, self.dst, self.ng = list(ns), list(ts), dst, len(ns)
-        self.coefs = [[rnd.randrange(1, R) for _ in range(t)] for t in ts]
-        self.ids = [list(range(1, n + 1)) if (g & 1 or small_ids) else [rnd.randrange(1, R) for _ in range(n)] for g, n in enumerate(ns)]
-        flat = [c for s in self.coefs for c in s]
-        pks = eng.sk_to_pk_batch(b"".join(map(b32, flat)), len(flat))
-        self.commits, pos = [], 0
-        for t in ts:
-            self.commits.append(pks[128 * pos:128 * (pos + t)]); pos += t
-        self.msgs = [b"checked combine %d/%d" % (seed, g) for g in range(self.ng)]
-        self.start = [0]
-        for n in ns:
-            self.start.append(self.start[-1] + n)
-        self.N = self.start[-1]
-        self.shares = [poly_eval(self.coefs[g], x) for g in range(self.ng) for x in self.ids[g]]
-        self.sigs = bytearray(self.sign(eng, self.shares, [self.msgs[g] for g in range(self.ng) for _ in range(ns[g])]))
-
-    def sign(self, eng, sks, msgs):
-        return eng.sign_batch(b"".join(map(b32, sks)), msgs, self.dst) if sks else b""
-
-    def spoil(self, eng, g, i, kind):
-        """share i of group g becomes a bad partial of the given kind"""
-        p = self.start[g] + i
-        if kind == OTHER_MSG:
-            s = self.sign(eng, [self.shares[p]], [self.msgs[g] + b" (another message)"])
-        elif kind == NEIGHBOUR_KEY:
-            j = p + 1 if i + 1 < self.ns[g] else p - 1
-            s = self.sign(eng, [self.shares[j]], [self.msgs[g]])
-        elif kind == IDENTITY:
-            s = IDENT1
-        elif kind == OFF_CURVE:
-            s = bytearray(self.sigs[64 * p:64 * p + 64]); s[63] ^= 1
-        else:
-            s = b"\xff" * 32 + bytes(self.sigs[64 * p + 32:64 * p + 64])
-        self.sigs[64 * p:64 * p + 64] = s
-
-    def sig_sets(self, groups=None):
-        return [bytes(self.sigs[64 * self.start[g]:64 * self.start[g + 1]]) for g in (range(self.ng) if groups is None else groups)]
-
-    def args(self, groups=None):
-        gs = list(range(self.ng)) if groups is None else list(groups)
-        return ([self.commits[g] for g in gs], pack([self.ids[g] for g in gs]), self.sig_sets(gs), [self.msgs[g] for g in gs], self.dst)
-
-    def group_bits(self, bitmap, g):
-        return bits_of(bitmap, self.N)[self.start[g]:self.start[g + 1]]
 
 
 def composition(eng, deal):
@@ -250,22 +167,10 @@ def test_bad_groups_stay_local(eng, M):
         assert d.group_bits(used, g) == [True, True, True, False, False], g
 
 
-# ---------------------------------------------------------------- 6. several launches
-def _flow(eng, n_groups, bad_every, seed, dst):
-    """n_groups x (n = 5, t = 3, ids 1 .. 5); every bad_every-th group holds one partial over another message among its first 3"""
-    d = Deal(eng, [5] * n_groups, [3] * n_groups, seed, dst, small_ids=True)
-    wrong = d.sign(eng, [d.shares[5 * g + (g // bad_every) % 3] for g in range(0, n_groups, bad_every)],
-                   [d.msgs[g] + b" (another message)" for g in range(0, n_groups, bad_every)])
-    for k, g in enumerate(range(0, n_groups, bad_every)):
-        p = 5 * g + (g // bad_every) % 3
-        d.sigs[64 * p:64 * p + 64] = wrong[64 * k:64 * k + 64]
-    return d
-
-
 def test_several_launches(eng, M, monkeypatch):
     dst = M.DEFAULT_DST
     ng = 1 << 10
-    d = _flow(eng, ng, 16, 6, dst)
+    d = checked_flow(eng, ng, 16, 6, dst)
     s0 = eng.threshold_checked_stats()
     got = eng.threshold_combine_checked_batch(*d.args())
     s1 = eng.threshold_checked_stats()
@@ -338,7 +243,7 @@ def test_argument_errors(eng, M):
 def test_call_sequences_on_one_context(M, eng, oracle):
     dst, dst2 = M.DEFAULT_DST, b"CHECKED-COMBINE-SECOND-DST"
     vb = synth.make_batch_gpu(eng, oracle, 600, dst, pool=40, invalid_every=7, spot=4)          # repeated keys: the prepared path
-    d1, d2 = _flow(eng, 96, 8, 8, dst), _flow(eng, 40, 4, 9, dst2)
+    d1, d2 = checked_flow(eng, 96, 8, 8, dst), checked_flow(eng, 40, 4, 9, dst2)
     a1, a2 = d1.args(), d2.args()
     ids3 = [b32(1) + b32(3) + b32(5)] * 96
     sigs3 = [s[:64] + s[128:192] + s[256:320] for s in a1[2]]

@@ -10,41 +10,17 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.gpu_support import eng, M
+from tests.helpers import b32, IDENT1, IDENT2, poly_eval
 
 pytestmark = pytest.mark.gpu
 R = synth.R
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
-IDENT2 = bytes(127) + b"\x01"
 E_ARG = -1
 ERR_SCALAR, ERR_G2 = 1, 3
 OP_FP_MUL = 0
 OP_FR_MUL, OP_FR_SQR, OP_FR_INV, OP_FR_ADD, OP_FR_SUB, OP_FR_NEG = 64, 65, 66, 67, 68, 69
 SIZES_N = [1, 2, 0, 7, 63, 64, 65, 257]
 SIZES_T = [1, 2, 3, 8, 33, 0, 5, 4]
-
-
-@pytest.fixture(scope="module")
-def M():
-    import blsbn254_loader
-    return blsbn254_loader.load()
-
-
-@pytest.fixture(scope="module")
-def eng(M):
-    e = M.Engine(0)           # raises when the HIP extension or the GPU is missing: no fallback
-    yield e
-    e.close()
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def poly_eval(coeffs, x):
-    acc = 0
-    for c in reversed(coeffs):
-        acc = (acc * x + c) % R
-    return acc
 
 
 def pack(sets):

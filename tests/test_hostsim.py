@@ -8,26 +8,17 @@ import ctypes
 import json
 import os
 import random
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+from tests.helpers import b32
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libhostsim.so")
-    src = [os.path.join(SIM, "hostsim.cpp")] + [os.path.join(ROOT, "bls-bn254_amd", "csrc", f)
-                                               for f in os.listdir(os.path.join(ROOT, "bls-bn254_amd", "csrc")) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-DBN_VERIFY_PARK_T", "-fPIC", "-shared", "-pthread", "-o", so, os.path.join(SIM, "hostsim.cpp")])
+    so = hostsim_build.build("hostsim.cpp", "libhostsim.so")
     return ctypes.CDLL(so)
-
-
-def b32(x):
-    return x.to_bytes(32, "big")
 
 
 def test_fp_arithmetic(hs, pyref):

@@ -3,26 +3,19 @@ lazy-limb interval discipline: the square root against Python integers, the elem
 decompression byte for byte, and the counted cost of g2_inflate against g2_decompress.  A test tool; the product has no CPU
 path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import pytest
 
 from tests import compressed_cases as cc
+from tests import hostsim_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
 P = cc.P
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libinflate.so")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [os.path.join(SIM, "inflate_host.cpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-o", so, os.path.join(SIM, "inflate_host.cpp")])
+    so = hostsim_build.build("inflate_host.cpp", "libinflate.so")
     return ctypes.CDLL(so)
 
 

@@ -1,39 +1,16 @@
 """CPU-only: every kernel in the built library has a real body.  A kernel whose source hits undefined behaviour (an accidental
 self-recursion turned k_miller_tri_prepared into a 15-instruction endless loop during round 3) still compiles and links; only
 its size gives it away before a GPU run hangs on it."""
-import os
 import re
-import subprocess
-import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+from tests.library_support import instruction_counts, library_path_built, lint_by_name, scratch_bytes
+
 # kernels that are legitimately tiny (index fills, flag reductions, scans) -- everything else does field arithmetic
 SMALL_OK = ("k_iota", "k_pack_bitmap", "k_prep_unsort", "k_status_reduce", "k_and_reduce", "k_kd_", "k_scan_excl", "k_rlc2_", "k_fp12_mask_one", "k_valu_peak", "k_place_bitmap")
 
 
 def test_no_degenerate_kernels():
-    import blsbn254_loader
-    M = blsbn254_loader.load()
-    path = M.library_path()
-    if not os.path.exists(path):
-        __import__("bls_bn254_amd.build", fromlist=["x"]).build()
-    from kernel_resources import code_objects
-    tmp = tempfile.mkdtemp()
-    sizes = {}
-    for idx, (data, off, size) in enumerate(code_objects(path)):
-        co = os.path.join(tmp, "co_%d.o" % idx)
-        open(co, "wb").write(data[off:off + size])
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
-        cur = None
-        for line in dis.splitlines():
-            m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-            if m:
-                cur = m.group(1); sizes.setdefault(cur, 0)
-            elif cur and re.match(r"^\s+[a-z_0-9]+", line):
-                sizes[cur] += 1
+    sizes = instruction_counts(library_path_built())
     kernels = {k: v for k, v in sizes.items() if re.search(r"\dk_[a-z]", k) or k.startswith("k_")}
     assert len(kernels) >= 60, sorted(kernels)
     bad = [(k, v) for k, v in kernels.items() if v < 200 and not any(s in k for s in SMALL_OK)]
@@ -50,23 +27,7 @@ SCRATCH_LIMIT = {"k_miller_prepared": 0, "k_fe_expx": 0, "k_fe_expx_h1": 0, "k_f
 
 
 def test_throughput_kernels_do_not_spill_to_memory():
-    import blsbn254_loader
-    M = blsbn254_loader.load()
-    path = M.library_path()
-    if not os.path.exists(path):
-        __import__("bls_bn254_amd.build", fromlist=["x"]).build()
-    from kernel_resources import code_objects
-    tmp = tempfile.mkdtemp()
-    scratch = {}
-    for idx, (data, off, size) in enumerate(code_objects(path)):
-        co = os.path.join(tmp, "co_%d.o" % idx)
-        open(co, "wb").write(data[off:off + size])
-        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s*(\S+)", blk).group(1)
-            if name.startswith("_Z"):
-                name = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.split("(")[0].strip()
-            scratch[name] = int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1))
+    scratch = scratch_bytes()
     missing = [k for k in SCRATCH_LIMIT if k not in scratch]
     assert not missing, missing
     bad = {k: scratch[k] for k, lim in SCRATCH_LIMIT.items() if scratch[k] > lim}
@@ -83,15 +44,8 @@ SERIALISED_LIMITS = {"k_miller_prepared": (8, 0), "k_fe_expx": (8, 0), "k_fe_exp
 
 
 def test_hot_kernels_have_no_serialised_accesses():
-    import blsbn254_loader
-    M = blsbn254_loader.load()
-    path = M.library_path()
-    if not os.path.exists(path):
-        __import__("bls_bn254_amd.build", fromlist=["x"]).build()
-    from isa_lint import lint
     found = {}
-    for sym, c in lint(path).items():
-        name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.split("(")[0].strip() if sym.startswith("_Z") else sym
+    for name, c in lint_by_name(library_path_built()).items():
         if name in SERIALISED_LIMITS:
             found[name] = (c["readfirstlane"], c["flat"])
     missing = [k for k in SERIALISED_LIMITS if k not in found]

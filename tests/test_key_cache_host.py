@@ -3,14 +3,13 @@ code the kernels of k_keycache.hip run) driven by the stand-alone program tests/
 sequences of batches and compared, step by step, with a Python dict model.  The program is built twice -- plain, and with
 -fsanitize=address,undefined -fno-sanitize-recover, every buffer exactly as large as the kernels' -- and both are run as
 ordinary programs.  Capacity 8, slot table 16: collisions and wrap-around occur.  A test tool; the product has no CPU path."""
-import os
 import random
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "hostsim", "key_cache_host.cpp")
+from tests import hostsim_build
+
 C, M = 8, 16
 U32 = 0xffffffff
 
@@ -30,10 +29,8 @@ def key_hash(pk, seed):
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def prog(request, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("key_cache_" + request.param) / "key_cache_host")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover", "-g"] if request.param == "sanitized" else []
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, SRC])
-    return exe
+    exe = tmp_path_factory.mktemp("key_cache_" + request.param) / "key_cache_host"
+    return hostsim_build.build("key_cache_host.cpp", exe, shared=False, extra=hostsim_build.SANITIZED if request.param == "sanitized" else ())
 
 
 def keys_of(rnd, k):

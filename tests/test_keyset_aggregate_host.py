@@ -3,15 +3,14 @@ compiled for the host with -DBN_CHECK, and the plain C++ of its host side (keyse
 argument walk and the repack of failing groups against a Python model, each over launch cuts at several positions.  A test
 tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+from tests.helpers import b32, bitmap, launches, model_candidate, u32, u64
+
 u32p = ctypes.POINTER(ctypes.c_uint32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 KA_OK, KA_OFF_DECREASE, KA_TOO_MANY, KA_IDX_RANGE, KA_IDX_ORDER = range(5)
@@ -21,41 +20,10 @@ EDGE = [0, 31, 32, 63, 64, 69]                   # first and last key of every 3
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libkeysetaggregatehost.so")
-    main = os.path.join(SIM, "keyset_aggregate_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("keyset_aggregate_host.cpp", "libkeysetaggregatehost.so")
     lib = ctypes.CDLL(so)
     lib.hs_ka_repack.restype = ctypes.c_size_t
     return lib
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def bitmap(bools):
-    out = bytearray((len(bools) + 7) // 8 + 1)
-    for i, b in enumerate(bools):
-        if b:
-            out[i >> 3] |= 1 << (i & 7)
-    return bytes(out)
-
-
-def launches(n, cuts):
-    """[lo, hi) pieces of 0 .. n cut at the given positions"""
-    edges = [0] + [c for c in cuts if 0 < c < n] + [n]
-    return [(a, b) for a, b in zip(edges, edges[1:]) if b > a]
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32)
-
-
-def u64(a):
-    return np.ascontiguousarray(a, dtype=np.uint64)
 
 
 def scan(hs, key_valid, idx, sigs, mask, cuts):
@@ -65,12 +33,6 @@ def scan(hs, key_valid, idx, sigs, mask, cuts):
         hs.hs_ka_scan(bytes(key_valid), idx.ctypes.data_as(u32p), sigs, mask, lo, hi - lo, c, z)
         cand += list(c.raw); ident += list(z.raw)
     return cand, ident
-
-
-def model_candidate(sig, p):
-    """decodes (both coordinates below p), not the identity (x == 0 reads as it), on y^2 = x^3 + 3"""
-    x, y = int.from_bytes(sig[:32], "big"), int.from_bytes(sig[32:], "big")
-    return x < p and y < p and x != 0 and (y * y - x * x * x - 3) % p == 0
 
 
 def test_candidate_bits(hs, oracle, pyref):

@@ -4,17 +4,15 @@
 and the whole optimistic selection against a Python model, each over launch cuts at several positions.  A test tool; the product
 has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests.test_keyset_aggregate_host import b32, bitmap, launches, model_candidate, u32, u64
+from tests import hostsim_build
+from tests.helpers import b32, bitmap, launches, model_candidate, u32, u64
+from tests.keyset_support import words
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
 u8p = ctypes.POINTER(ctypes.c_uint8)
 u32p = ctypes.POINTER(ctypes.c_uint32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -30,18 +28,9 @@ def rb(size):
     return (size + 7) // 8
 
 
-def words(size):
-    return (size + 31) // 32
-
-
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libkeysetcommitteeaggregatehost.so")
-    main = os.path.join(SIM, "keyset_committee_aggregate_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("keyset_committee_aggregate_host.cpp", "libkeysetcommitteeaggregatehost.so")
     lib = ctypes.CDLL(so)
     lib.hs_kca_repack.restype = ctypes.c_size_t
     members = u32([i for c in COMS for i in c])

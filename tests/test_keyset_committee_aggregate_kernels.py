@@ -5,15 +5,14 @@ the same build.  The library still exports exactly what include/blsbn254.h decla
 the new symbols)."""
 import ctypes
 
-from tests.test_abi import declared_symbols
-from tests.test_msm_kernels import _scratch
+from tests.library_support import declared_symbols, scratch_bytes
 
 KCA_KERNELS = ("k_kca_scan", "k_kca_rows", "k_kca_resolve")
 KCA_SYMBOLS = ("blsbn254_keyset_committee_aggregate_checked_batch", "blsbn254_keyset_committee_aggregate_stats")
 
 
 def test_keyset_committee_aggregate_kernels_built_and_their_scratch():
-    scratch = _scratch()
+    scratch = scratch_bytes()
     missing = [k for k in KCA_KERNELS + ("k_ka_scan", "k_ka_gather_keys") if k not in scratch]
     assert not missing, missing
     for k in ("k_kca_rows", "k_kca_resolve", "k_ka_gather_keys"):

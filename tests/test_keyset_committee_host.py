@@ -9,20 +9,15 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT2 = bytes(127) + b"\x01"
-ITEM_GROUPS, PART_MAX = 64, 1 << 20
+from tests import hostsim_build
+from tests.helpers import IDENT2, row_of
+from tests.keyset_support import ITEM_GROUPS, PART_MAX, committee_model_plan, words
+
 
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
-    exe = os.path.join(SIM, "keyset_committee_host")
-    main = os.path.join(SIM, "keyset_committee_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(p) > os.path.getmtime(exe) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-pthread", "-o", exe, main])
+    exe = hostsim_build.build("keyset_committee_host.cpp", "keyset_committee_host", shared=False)
     d = tmp_path_factory.mktemp("kc")
 
     def f(commands):
@@ -45,48 +40,6 @@ def set_cmd(n_keys, coms):
     for c in coms:
         off.append(off[-1] + len(c))
     return ["set", n_keys, len(coms)] + off + [i for c in coms for i in c]
-
-
-def row_of(bits, size):
-    r = bytearray((size + 7) // 8)
-    for j in bits:
-        r[j >> 3] |= 1 << (j & 7)
-    return bytes(r)
-
-
-def words(size):
-    return (size + 31) // 32
-
-
-def model_plan(coms, com, chunk):
-    """the plan in Python: (order, launches as (lo, hi, partials), items as (cword, mbase, first, count))"""
-    sizes = [len(c) for c in coms]
-    off, wbase = [0], [0]
-    for s in sizes:
-        off.append(off[-1] + s); wbase.append(wbase[-1] + words(s))
-    order = sorted(range(len(com)), key=lambda g: com[g])               # Python's sort is stable
-    part_max = min(PART_MAX, chunk)
-    launches, items, lo = [], [], 0
-    while lo < len(order):
-        hi, part = lo, 0
-        while hi < len(order) and hi - lo < chunk:
-            w = words(sizes[com[order[hi]]])
-            if hi > lo and part + w > part_max:
-                break
-            part += w; hi += 1
-        a = lo
-        while a < hi:
-            c = com[order[a]]
-            b = a
-            while b < hi and com[order[b]] == c:
-                b += 1
-            for f in range(a, b, ITEM_GROUPS):
-                for w in range(words(sizes[c])):
-                    items.append((wbase[c] + w, off[c] + 32 * w, f, min(ITEM_GROUPS, b - f)))
-            a = b
-        launches.append((lo, hi, part))
-        lo = hi
-    return order, launches, items
 
 
 def parse_plan(tok, G):
@@ -115,7 +68,7 @@ def test_plan_against_the_model_and_its_invariants(run, chunk):
     assert res[0][:2] == ["ok", str(len(COMS))]
     order, spbase, srow, launches, items = parse_plan(res[1], G)
     sizes = [len(c) for c in COMS]
-    m_order, m_launches, m_items = model_plan(COMS, com, chunk)
+    m_order, m_launches, m_items = committee_model_plan(COMS, com, chunk)
     assert order == m_order and items == m_items
     assert [(lo, hi, p) for lo, hi, _, _, p, _ in launches] == m_launches
     # the permutation is stable

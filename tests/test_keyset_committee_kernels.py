@@ -5,8 +5,7 @@ build.  The library still exports exactly what include/blsbn254.h declares (test
 symbols)."""
 import ctypes
 
-from tests.test_abi import declared_symbols
-from tests.test_msm_kernels import _scratch
+from tests.library_support import declared_symbols, scratch_bytes
 
 KC_KERNELS = ("k_kc_words", "k_kc_count", "k_kc_word_sum", "k_kc_finish", "k_kc_weight")
 KC_SYMBOLS = ("blsbn254_keyset_set_committees", "blsbn254_keyset_committee_count", "blsbn254_keyset_committee_sum_batch",
@@ -14,7 +13,7 @@ KC_SYMBOLS = ("blsbn254_keyset_set_committees", "blsbn254_keyset_committee_count
 
 
 def test_keyset_committee_kernels_built_and_their_scratch():
-    scratch = _scratch()
+    scratch = scratch_bytes()
     missing = [k for k in KC_KERNELS + ("k_g2_seg_sum",) if k not in scratch]
     assert not missing, missing
     for k in ("k_kc_count", "k_kc_words", "k_kc_weight"):

@@ -5,15 +5,14 @@ ragged selection against a sequential Python model over committees of every widt
 launch cuts at several positions, the bytes a launch leaves alone, the argument walk, the layout prefixes and the repack of
 failing groups.  A test tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+from tests.helpers import bitmap, row_of, u32, u64
+
 u8p = ctypes.POINTER(ctypes.c_uint8)
 u32p = ctypes.POINTER(ctypes.c_uint32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -33,12 +32,7 @@ def table():
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libkeysetcommitteemergehost.so")
-    main = os.path.join(SIM, "keyset_committee_merge_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("keyset_committee_merge_host.cpp", "libkeysetcommitteemergehost.so")
     lib = ctypes.CDLL(so)
     lib.hs_kcm_repack.restype = ctypes.c_size_t
     lib.hs_kcm_layout_contributions.restype = ctypes.c_size_t
@@ -52,29 +46,6 @@ def hs():
     lib.wbase = list(wbase)
     assert lib.wbase == [int(x) for x in np.concatenate([[0], np.cumsum([(s + 31) // 32 for s in SIZES])])[:-1]]
     return lib
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32)
-
-
-def u64(a):
-    return np.ascontiguousarray(a, dtype=np.uint64)
-
-
-def bitmap(bools):
-    out = bytearray((len(bools) + 7) // 8 + 1)
-    for i, b in enumerate(bools):
-        if b:
-            out[i >> 3] |= 1 << (i & 7)
-    return bytes(out)
-
-
-def row_of(pos, size):
-    r = bytearray((size + 7) // 8)
-    for j in pos:
-        r[j >> 3] |= 1 << (j & 7)
-    return bytes(r)
 
 
 def rb_of(c):

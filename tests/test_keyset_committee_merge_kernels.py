@@ -4,14 +4,13 @@ does.  The library still exports exactly what include/blsbn254.h declares (tests
 symbols)."""
 import ctypes
 
-from tests.test_abi import declared_symbols
-from tests.test_msm_kernels import _scratch
+from tests.library_support import declared_symbols, scratch_bytes
 
 KCM_SYMBOLS = ("blsbn254_keyset_committee_merge_checked_batch", "blsbn254_keyset_committee_merge_stats")
 
 
 def test_keyset_committee_merge_kernel_built_and_its_scratch():
-    scratch = _scratch()
+    scratch = scratch_bytes()
     missing = [k for k in ("k_kcm_select", "k_km_select", "k_km_sig", "k_km_points") if k not in scratch]
     assert not missing, missing
     assert scratch["k_kcm_select"] == 0, "scratch bytes per lane in k_kcm_select: %d" % scratch["k_kcm_select"]

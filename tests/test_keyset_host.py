@@ -4,28 +4,20 @@ on every call: the mixed addition against the full one and against the pure-Pyth
 registration, flip / ok, the per-word masks, the word sums, the reduction passes over word-major partials, the complement --
 against a Python model for key sets that cross word and pass boundaries.  A test tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import pytest
 
+from tests import hostsim_build
 from tests import synth
+from tests.helpers import IDENT2, row_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT2 = bytes(127) + b"\x01"
 N_KEYS = [1, 31, 32, 33, 70, 513]           # 513: W = 17 words, two reduction passes
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libkeysethost.so")
-    main = os.path.join(SIM, "keyset_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("keyset_host.cpp", "libkeysethost.so")
     return ctypes.CDLL(so)
 
 
@@ -57,13 +49,6 @@ def test_mixed_addition_equals_the_full_one(hs, pyref):
     for a, ident, q, want in cases:
         mixed, full = add_mixed(hs, enc(a), ident, enc(q))
         assert mixed == full == enc(want)
-
-
-def row_of(bits_set, n):
-    r = bytearray((n + 7) // 8)
-    for i in bits_set:
-        r[i >> 3] |= 1 << (i & 7)
-    return bytes(r)
 
 
 def key_set(B, n, rnd):

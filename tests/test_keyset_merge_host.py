@@ -4,15 +4,14 @@ votes formed by the harness, and the plain C++ of its host side (keyset_merge_pl
 against a sequential Python model at every row width at which the code takes another path, the argument walk and the repack of
 failing groups.  A test tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+from tests.helpers import b32, bitmap, model_candidate, row_of, u32, u64
+
 u32p = ctypes.POINTER(ctypes.c_uint32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 KM_OK, KM_OFF_DECREASE, KM_TOO_MANY, KM_ROWS_TOO_LARGE, KM_ROW_PAD = range(5)
@@ -24,42 +23,10 @@ WIDTHS = {13: (1, 2), 70: (3, 9), 2035: (64, 255), 2050: (65, 257), 4133: (130, 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libkeysetmergehost.so")
-    main = os.path.join(SIM, "keyset_merge_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("keyset_merge_host.cpp", "libkeysetmergehost.so")
     lib = ctypes.CDLL(so)
     lib.hs_km_repack.restype = ctypes.c_size_t
     return lib
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def bitmap(bools):
-    out = bytearray((len(bools) + 7) // 8 + 1)
-    for i, b in enumerate(bools):
-        if b:
-            out[i >> 3] |= 1 << (i & 7)
-    return bytes(out)
-
-
-def row_of(keys, n):
-    r = bytearray((n + 7) // 8)
-    for i in keys:
-        r[i >> 3] |= 1 << (i & 7)
-    return bytes(r)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32)
-
-
-def u64(a):
-    return np.ascontiguousarray(a, dtype=np.uint64)
 
 
 def model_select(groups, sig_ok, mask, valid, n):
@@ -160,11 +127,6 @@ def test_admissible_once_an_earlier_one_is_masked_out(hs, n):
     assert flags == [CAND, CAND | USED, CAND] and unions == [row_of(B, n)]
     flags, unions = run_select(hs, [[A, B, C]], [0, 1, 1], None, valid, n, [])            # the same through the signature byte
     assert flags == [0, CAND | USED, CAND] and unions == [row_of(B, n)]
-
-
-def model_candidate(sig, p):
-    x, y = int.from_bytes(sig[:32], "big"), int.from_bytes(sig[32:], "big")
-    return x < p and y < p and x != 0 and (y * y - x * x * x - 3) % p == 0
 
 
 def test_signature_bytes_and_dropped_points(hs, oracle, pyref):

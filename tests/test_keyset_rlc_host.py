@@ -10,19 +10,18 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT2 = bytes(127) + b"\x01"
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
+from tests import hostsim_build
+from tests.helpers import IDENT1, IDENT2
+from tests.keyset_support import rlc_model_plan
+
 RUN = 16                                                                # keyset_rlc_plan.h KSR_RUN
 
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     d = tmp_path_factory.mktemp("ksr")
-    exe = os.path.join(str(d), "keyset_rlc_host")                       # built where the test may write: nothing is left in the tree
-    main = os.path.join(SIM, "keyset_rlc_host.cpp")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-pthread", "-o", exe, main])
+    # built where the test may write: nothing is left in the tree
+    exe = hostsim_build.build("keyset_rlc_host.cpp", os.path.join(str(d), "keyset_rlc_host"), shared=False)
 
     def f(commands):
         """commands: lists of tokens -> per command the result line's tokens (without the command's name)"""
@@ -37,24 +36,6 @@ def run(tmp_path_factory):
 
 def hexs(b):
     return bytes(b).hex() or "-"
-
-
-def model_plan(msgs, C):
-    """the plan in Python: (order, chunks as (start, len, class), representatives)"""
-    ids, rep = {}, []
-    cls = []
-    for g, m in enumerate(msgs):
-        m = bytes(m)
-        if m not in ids:
-            ids[m] = len(ids); rep.append(g)
-        cls.append(ids[m])
-    order = sorted(range(len(msgs)), key=lambda g: cls[g])              # Python's sort is stable
-    chunks, at = [], 0
-    for k in range(len(rep)):
-        size = cls.count(k)
-        chunks += [(at + s, min(C, size - s), k) for s in range(0, size, C)]
-        at += size
-    return order, chunks, rep
 
 
 def model_levels(chunks):
@@ -100,7 +81,7 @@ def test_plan_against_the_model_and_its_invariants(run, C):
     rnd.shuffle(msgs)
     G = len(msgs)
     p = parse_plan(run([["plan", C, G] + [hexs(m) for m in msgs]])[0], G)
-    order, chunks, rep = model_plan(msgs, C)
+    order, chunks, rep = rlc_model_plan(msgs, C)
     assert p["order"] == order and p["chunks"] == chunks and p["rep"] == rep
     assert len(rep) == len(set(msgs)) == len(sizes) + 5
     # a stable permutation and its inverse

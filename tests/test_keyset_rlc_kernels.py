@@ -6,8 +6,7 @@ import ctypes
 import os
 import re
 
-from tests.test_abi import declared_symbols
-from tests.test_msm_kernels import _scratch
+from tests.library_support import declared_symbols, scratch_bytes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KSR_KERNELS = ("k_ksr_elig", "k_ksr_weigh_g1", "k_ksr_weigh_g2", "k_ksr_chunks", "k_ksr_gather")
@@ -17,7 +16,7 @@ G2_WEIGHT_SCRATCH = 0                                                   # bytes 
 
 
 def test_keyset_rlc_kernels_built_and_their_scratch():
-    scratch = _scratch()
+    scratch = scratch_bytes()
     missing = [k for k in KSR_KERNELS + ("k_g1_seg_sum", "k_g2_seg_sum", "k_g2p_to_bytes") if k not in scratch]
     assert not missing, missing
     assert scratch["k_ksr_weigh_g2"] == G2_WEIGHT_SCRATCH, "scratch bytes per lane in k_ksr_weigh_g2: %d" % scratch["k_ksr_weigh_g2"]

@@ -10,8 +10,9 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+from tests.helpers import row_of
+
 M64 = (1 << 64) - 1
 # n_keys -> (words, row bytes): one key; one word and a bit; three words and 9-byte rows; 64 words, every lane one word; 66
 # words, lanes 0 and 1 own two (261-byte rows); 130 words, lanes 0 and 1 own three
@@ -20,12 +21,7 @@ WIDTHS = {1: (1, 1), 33: (2, 5), 70: (3, 9), 2035: (64, 255), 2081: (66, 261), 4
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
-    exe = os.path.join(SIM, "keyset_weight_host")
-    main = os.path.join(SIM, "keyset_weight_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(p) > os.path.getmtime(exe) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-pthread", "-o", exe, main])
+    exe = hostsim_build.build("keyset_weight_host.cpp", "keyset_weight_host", shared=False)
     d = tmp_path_factory.mktemp("kw")
 
     def f(commands):
@@ -45,13 +41,6 @@ def hexs(b):
 
 def unhex(t):
     return b"" if t == "-" else bytes.fromhex(t)
-
-
-def row_of(keys, n):
-    r = bytearray((n + 7) // 8)
-    for i in keys:
-        r[i >> 3] |= 1 << (i & 7)
-    return bytes(r)
 
 
 def table(rnd, n, nc):

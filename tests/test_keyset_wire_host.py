@@ -3,28 +3,20 @@ ka_scan_wire / ka_wire_out of keyset_agg.h, kca_scan_wire of keyset_committee_ag
 against the function it has to agree with: g1_inflate, ka_scan / kca_scan on the inflated bytes, the oracle's g1_compress.  A
 test tool; the product has no CPU path."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import compressed_cases as cc
+from tests import hostsim_build
+from tests.helpers import bitmap, IDENT1
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
 u32p = ctypes.POINTER(ctypes.c_uint32)
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libkeysetwirehost.so")
-    main = os.path.join(SIM, "keyset_wire_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("keyset_wire_host.cpp", "libkeysetwirehost.so")
     return ctypes.CDLL(so)
 
 
@@ -81,14 +73,6 @@ def test_identical_operation_counts(hs, cases):
         hs.hs_kw_scan_wire(valid, idx.ctypes.data_as(u32p), wire, None, s, pt, cn)
         scans.append([int(v) for v in cn])
     assert all(v == scans[0] for v in scans), scans
-
-
-def bitmap(bools):
-    out = bytearray((len(bools) + 7) // 8 + 1)
-    for i, b in enumerate(bools):
-        if b:
-            out[i >> 3] |= 1 << (i & 7)
-    return bytes(out)
 
 
 def test_scans_agree_with_the_uncompressed_scans_on_the_inflated_bytes(hs, cases):

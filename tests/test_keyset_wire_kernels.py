@@ -2,51 +2,22 @@
 count that tests/test_kernel_sanity.py::test_no_degenerate_kernels applies to every kernel, and the scratch of the two scans
 (the table of the square-root chain and nothing else), read from the gfx950 code objects through scripts/kernel_resources.py.
 No GPU needed."""
-import os
 import re
-import subprocess
-import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+from tests.library_support import instruction_counts, kernel_table, library_path_built
 KERNELS = ("k_ka_scan_wire", "k_kca_scan_wire", "k_g1p_to_wire")
 
 
 def library():
     import blsbn254_loader
-    M = blsbn254_loader.load()
-    path = M.library_path()
-    if not os.path.exists(path):
-        __import__("bls_bn254_amd.build", fromlist=["x"]).build()
-    return M, path
+    return blsbn254_loader.load(), library_path_built()
 
 
 def test_wire_kernels_are_in_the_library_and_not_degenerate():
     _, path = library()
-    from kernel_resources import code_objects
-    tmp = tempfile.mkdtemp()
-    sizes, scratch, spills = {}, {}, {}
-    for idx, (data, off, size) in enumerate(code_objects(path)):
-        co = os.path.join(tmp, "co_%d.o" % idx)
-        open(co, "wb").write(data[off:off + size])
-        notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True).stdout
-        if not any(k in notes for k in KERNELS):
-            continue
-        for blk in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s*(\S+)", blk).group(1)
-            scratch[name] = int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", blk).group(1))
-            spills[name] = int(re.search(r"\.vgpr_spill_count:\s*(\d+)", blk).group(1)) + int(re.search(r"\.sgpr_spill_count:\s*(\d+)", blk).group(1))
-        dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
-        cur = None
-        for line in dis.splitlines():
-            m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-            if m:
-                cur = m.group(1); sizes.setdefault(cur, 0)
-            elif cur and re.match(r"^\s+[a-z_0-9]+", line):
-                sizes[cur] += 1
+    sizes = instruction_counts(path)                                      # by symbol: the mangled names
+    scratch = {r["symbol"]: r["scratch"] for r in kernel_table(path)}
+    spills = {r["symbol"]: r["vgpr_spills"] + r["sgpr_spills"] for r in kernel_table(path)}
     for k in KERNELS:
         names = [s for s in sizes if re.search(r"\d%s(?![a-z_0-9])" % k, s)]          # the mangled name: <length><name><parameters>
         assert len(names) == 1, (k, sorted(sizes))

@@ -4,7 +4,8 @@ arithmetic (9 x 29-bit limbs, tower.h) is not touched by this experiment."""
 import ctypes
 import os
 import random
-import subprocess
+
+from tests import hostsim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
@@ -12,9 +13,7 @@ R = 1 << 260
 
 
 def _lib(tmp_path):
-    so = str(tmp_path / "liblazy_tower.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "bench_micro", "lazy_tower_host.cpp")])
-    return ctypes.CDLL(so)
+    return ctypes.CDLL(hostsim_build.build(os.path.join(ROOT, "bench_micro", "lazy_tower_host.cpp"), tmp_path / "liblazy_tower.so"))
 
 
 def limbs(x):

@@ -2,37 +2,18 @@
 every field operation asserts the lazy-limb interval discipline: signed-digit recoding, the complete mixed addition, and the
 recode -> sort -> bucket levels -> reduce -> Horner pipeline against the oracle.  A test tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
-IDENT2 = bytes(64) + bytes(32) + bytes(31) + b"\x01"
+from tests import hostsim_build
+from tests.helpers import b32, glv_lambda, IDENT1, IDENT2
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libmsmhost.so")
-    src = [os.path.join(SIM, "msm_host.cpp")] + [os.path.join(ROOT, "bls-bn254_amd", "csrc", f)
-                                                for f in os.listdir(os.path.join(ROOT, "bls-bn254_amd", "csrc")) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, os.path.join(SIM, "msm_host.cpp")])
+    so = hostsim_build.build("msm_host.cpp", "libmsmhost.so")
     return ctypes.CDLL(so)
-
-
-def glv_lambda():
-    src = open(os.path.join(ROOT, "bls-bn254_amd", "csrc", "bn254_consts.h")).read()
-    words = re.search(r"GLV_LAMBDA\[4\]\s*=\s*\{([^}]*)\}", src).group(1).split(",")
-    return sum(int(w.strip().rstrip("uUlL"), 16) << (64 * i) for i, w in enumerate(words))
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
 
 
 def digits(hs, k, c, half):

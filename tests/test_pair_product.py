@@ -6,15 +6,13 @@ field elements, and limb patterns at the ends of the intervals the checker carri
 step and of the whole loop.  A test tool; the product has no CPU path."""
 import ctypes
 import math
-import os
 import random
-import subprocess
 from fractions import Fraction
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+
 NL, RB = 9, 29
 L = 1 << RB
 RBITS = 261                                  # Montgomery R = 2^261
@@ -26,11 +24,7 @@ ENTRY_TRK = (-4e-6, 1.0 + 4e-6, -0.02, 0.02, 1.2)      # the declared range of a
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libpairproduct.so")
-    src = [os.path.join(SIM, "pair_product_host.cpp")] + [os.path.join(ROOT, "bls-bn254_amd", "csrc", f)
-                                                         for f in os.listdir(os.path.join(ROOT, "bls-bn254_amd", "csrc")) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-o", so, os.path.join(SIM, "pair_product_host.cpp")])
+    so = hostsim_build.build("pair_product_host.cpp", "libpairproduct.so")
     return ctypes.CDLL(so)
 
 

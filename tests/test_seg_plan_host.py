@@ -3,15 +3,13 @@ header the library compiles, against a model written here and against the proper
 launch takes, which groups it serves, and the (start, len) run descriptors of every level.  The start of an empty run is not
 compared: no kernel reads an item of one."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+
 T_BIG = 4096                # the library's hand-over size (host_threshold_batch.hip)
 SIZES = (0, 1, 2, 3, 7, 8, 9, 16, 17, 40, 100)
 NAMED = ([0], [0, 0, 0], [1], [8, 8], [9, 0, 7], [3, 100, 0, 2], [100], [5, 0, 0])
@@ -19,10 +17,7 @@ NAMED = ([0], [0, 0, 0], [1], [8, 8], [9, 0, 7], [3, 100, 0, 2], [100], [5, 0, 0
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libsegplanhost.so")
-    src = [os.path.join(SIM, "seg_plan_host.cpp"), os.path.join(ROOT, "bls-bn254_amd", "csrc", "seg_plan.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", so, src[0]])
+    so = hostsim_build.build("seg_plan_host.cpp", "libsegplanhost.so")
     lib = ctypes.CDLL(so)
     for f in (lib.hs_seg_levels, lib.hs_seg_cut, lib.hs_seg_whole):
         f.restype = ctypes.c_long
@@ -34,7 +29,7 @@ def hs():
     return lib
 
 
-def offsets(sizes):
+def offsets_list(sizes):
     return [0] + [int(x) for x in np.cumsum(sizes)]
 
 
@@ -222,7 +217,7 @@ def check_whole(rel, chunk, G, t_big, start, ln, plan):
 
 
 def cut_case(hs, sizes, chunk, G):
-    rel = offsets(sizes)
+    rel = offsets_list(sizes)
     got = run_cut(hs, rel, chunk, G)
     check_cut(rel, chunk, G, *got)
     assert_same(got, model_cut(rel, chunk, G))
@@ -230,7 +225,7 @@ def cut_case(hs, sizes, chunk, G):
 
 
 def whole_case(hs, sizes, chunk, G, t_big):
-    rel = offsets(sizes)
+    rel = offsets_list(sizes)
     got = run_whole(hs, rel, chunk, G, t_big)
     check_whole(rel, chunk, G, t_big, *got)
     assert_same(got, model_whole(rel, chunk, G, t_big))

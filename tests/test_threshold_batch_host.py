@@ -3,38 +3,24 @@ host with -DBN_CHECK, so every field operation asserts the lazy-limb interval di
 the GLV scalar multiplication on one doubling chain, and a whole small batch against the oracle.  A test tool; the product has
 no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
-import numpy as np
 import pytest
 
-from tests.test_msm_host import b32, glv_lambda
+from tests import hostsim_build
+from tests.helpers import b32, glv_lambda, IDENT1, offsets_u32
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
 u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libthresholdbatchhost.so")
-    main = os.path.join(SIM, "threshold_batch_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("threshold_batch_host.cpp", "libthresholdbatchhost.so")
     return ctypes.CDLL(so)
 
 
-def offsets(sizes):
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
-
-
 def lagrange(hs, id_sets):
-    off = offsets([len(s) for s in id_sets])
+    off = offsets_u32([len(s) for s in id_sets])
     n = int(off[-1])
     out = ctypes.create_string_buffer(32 * max(n, 1))
     bad = ctypes.create_string_buffer(len(id_sets))
@@ -111,7 +97,7 @@ def test_whole_small_batch_matches_threshold_combine_per_group(hs, oracle, pyref
     sig_sets[6][1] = bytes(bad_pt)                                   # group 6: off the curve
     sig_sets[7][0] = b"\xff" * 64                                    # group 7: does not decode
     id_sets[8][0] = b32(0); sig_sets[8][1] = b"\xff" * 64            # group 8: both; the scalar error wins
-    off = offsets(sizes)
+    off = offsets_u32(sizes)
     ng = len(sizes)
     out = ctypes.create_string_buffer(64 * ng)
     st = ctypes.create_string_buffer(ng)

@@ -3,15 +3,14 @@ with -DBN_CHECK: candidate bits, repeated ids, ranks, used bits, short marks and
 ragged groups with an empty group, a group cut by a launch boundary, all-zero and all-one bitmaps and t_g == n_g.  A test tool;
 the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
+from tests import hostsim_build
+from tests.helpers import b32, bitmap, launches, offsets_u32
+
 u32p = ctypes.POINTER(ctypes.c_uint32)
 MARK_SCALAR, MARK_POINT, MARK_SHORT = 1, 2, 4
 SIZES_N = [3, 0, 7, 5, 1, 6, 4, 9]
@@ -20,35 +19,8 @@ SIZES_T = [2, 2, 7, 3, 0, 4, 5, 1]          # t == n (group 2), t == 0 (group 4)
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libthresholdcheckedhost.so")
-    main = os.path.join(SIM, "threshold_checked_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("threshold_checked_host.cpp", "libthresholdcheckedhost.so")
     return ctypes.CDLL(so)
-
-
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def offsets(sizes):
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
-
-
-def bitmap(bools):
-    out = bytearray((len(bools) + 7) // 8 + 1)
-    for i, b in enumerate(bools):
-        if b:
-            out[i >> 3] |= 1 << (i & 7)
-    return bytes(out)
-
-
-def launches(n, cuts):
-    """[lo, hi) pieces of 0 .. n cut at the given positions"""
-    edges = [0] + [c for c in cuts if 0 < c < n] + [n]
-    return [(a, b) for a, b in zip(edges, edges[1:]) if b > a]
 
 
 def scan(hs, ids, sigs, goff, cuts):
@@ -108,7 +80,7 @@ def test_candidate_bits(hs, oracle, pyref):
     sigs = pts + [bytes(off), big_x, big_y, ident, bytes(64), b"\xff" * 64, bytes(32) + b"\xff" * 32]
     want = [1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]                          # (x == 0 reads as the identity whatever y holds)
     n = len(sigs)
-    goff = offsets([4, 0, n - 4])
+    goff = offsets_u32([4, 0, n - 4])
     ids = b"".join(b32(i + 1) for i in range(n))
     for cuts in ([], [3], [5, 6]):
         cand, rep = scan(hs, ids, b"".join(sigs), goff, cuts)
@@ -118,7 +90,7 @@ def test_candidate_bits(hs, oracle, pyref):
 def test_repeat_detection(hs, pyref):
     R = pyref.R
     sizes = [4, 0, 6, 3, 2]
-    goff = offsets(sizes)
+    goff = offsets_u32(sizes)
     id_sets = [[1, 2, 3, 1], [], [9, 8, 9, 7, 9, 8], [7, 6, 7], [R + 5, R + 5]]
     id_sets[3][1] = 1                                                 # the same id as group 0's: other groups are never looked at
     ids = b"".join(b32(x) for s in id_sets for x in s)
@@ -134,7 +106,7 @@ def test_repeat_detection(hs, pyref):
 @pytest.mark.parametrize("cuts", [[], [5], [8, 16, 24], list(range(1, 35))])
 def test_ranks_and_compacted_slots(hs, cuts):
     rnd = random.Random(7)
-    goff, coff = offsets(SIZES_N), offsets(SIZES_T)
+    goff, coff = offsets_u32(SIZES_N), offsets_u32(SIZES_T)
     n = int(goff[-1])
     ids = rnd.randbytes(32 * n); sigs = rnd.randbytes(64 * n)
     patterns = {"random": [rnd.random() < 0.7 for _ in range(n)], "zeros": [False] * n, "ones": [True] * n}

@@ -3,39 +3,23 @@
 in Fr against Python integers, and "in the exponent" of G2 against the oracle's g2_mul / g2_add composed the same way and
 against sk_to_pk(f(id)), at the bit counts a launch can have.  A test tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
-import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT2 = bytes(127) + b"\x01"
+from tests import hostsim_build
+from tests.helpers import b32, IDENT2, offsets_u32
+
 u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libthresholddealhost.so")
-    main = os.path.join(SIM, "threshold_deal_host.cpp")
-    csrc = os.path.join(ROOT, "bls-bn254_amd", "csrc")
-    src = [main] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, main])
+    so = hostsim_build.build("threshold_deal_host.cpp", "libthresholddealhost.so")
     return ctypes.CDLL(so)
 
 
-def b32(k):
-    return int(k).to_bytes(32, "big")
-
-
-def offsets(sizes):
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
-
-
-def poly_eval(coeffs, x, R):
+def poly_eval_mod(coeffs, x, R):
     acc = 0
     for c in reversed(coeffs):
         acc = (acc * x + c) % R
@@ -43,7 +27,7 @@ def poly_eval(coeffs, x, R):
 
 
 def fr_eval(hs, coef_sets, id_sets):
-    coff, goff = offsets([len(s) for s in coef_sets]), offsets([len(s) for s in id_sets])
+    coff, goff = offsets_u32([len(s) for s in coef_sets]), offsets_u32([len(s) for s in id_sets])
     n = int(goff[-1])
     out = ctypes.create_string_buffer(32 * max(n, 1))
     st = ctypes.create_string_buffer(len(id_sets))
@@ -53,7 +37,7 @@ def fr_eval(hs, coef_sets, id_sets):
 
 
 def g2_eval(hs, commit_sets, id_sets, nbits):
-    coff, goff = offsets([len(s) for s in commit_sets]), offsets([len(s) for s in id_sets])
+    coff, goff = offsets_u32([len(s) for s in commit_sets]), offsets_u32([len(s) for s in id_sets])
     n = int(goff[-1])
     out = ctypes.create_string_buffer(128 * max(n, 1))
     st = ctypes.create_string_buffer(len(id_sets))
@@ -75,7 +59,7 @@ def test_fr_horner_matches_python_integers(hs, pyref):
     for g, (cs, xs) in enumerate(zip(coef_sets, id_sets)):
         for i, x in enumerate(xs):
             p = int(goff[g]) + i
-            assert got[32 * p:32 * p + 32] == b32(poly_eval(cs, x, R)), (g, i)
+            assert got[32 * p:32 * p + 32] == b32(poly_eval_mod(cs, x, R)), (g, i)
 
 
 def test_fr_bad_scalars_mark_their_group_only(hs, pyref):
@@ -105,7 +89,7 @@ def test_g2_horner_matches_the_oracle(hs, oracle, pyref):
                 for c in reversed(cm[:-1]):
                     acc = oracle.g2_add(oracle.g2_mul(acc, x), c)
                 assert got[128 * p:128 * p + 128] == acc, (nbits, g, i)
-                assert acc == oracle.sk_to_pk(poly_eval(cs, x, R)), (nbits, g, i)
+                assert acc == oracle.sk_to_pk(poly_eval_mod(cs, x, R)), (nbits, g, i)
         if nbits < 254:                                              # the same ids under a larger bit count: the same bytes
             for wider in (nbits + 1, 64, 254):
                 assert g2_eval(hs, commit_sets, id_sets, wider)[0] == got, (nbits, wider)

@@ -3,15 +3,13 @@ miller_unit_coords, miller_loop_prepared_unit), compiled for the host with -DBN_
 lazy-limb interval discipline, against the oracle; the integer argument that the key's x-coefficient b3 never vanishes; and
 the executed-MAD count of the new loop.  A test tool; the product has no CPU path."""
 import ctypes
-import os
 import random
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = os.path.join(ROOT, "tests", "hostsim")
-IDENT1 = bytes(32) + (1).to_bytes(32, "big")
+from tests import hostsim_build
+from tests.helpers import IDENT1
+
 GT_ONE = (1).to_bytes(32, "big") + bytes(352)
 PARENT_LOOP_MADS = 1371816          # miller_loop_prepared, profiles/r03_executed_mads.json
 PAIR_SAVING = 88 * 810              # 324 (the scaling of T2) + 486 (one Fp2 product of the sparse multiplication) per line pair
@@ -19,11 +17,7 @@ PAIR_SAVING = 88 * 810              # 324 (the scaling of T2) + 486 (one Fp2 pro
 
 @pytest.fixture(scope="module")
 def hs():
-    so = os.path.join(SIM, "libunitpairs.so")
-    src = [os.path.join(SIM, "unit_pairs_host.cpp")] + [os.path.join(ROOT, "bls-bn254_amd", "csrc", f)
-                                                       for f in os.listdir(os.path.join(ROOT, "bls-bn254_amd", "csrc")) if f.endswith(".h")]
-    if not os.path.exists(so) or any(os.path.getmtime(p) > os.path.getmtime(so) for p in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-DBN_CHECK", "-fPIC", "-shared", "-pthread", "-o", so, os.path.join(SIM, "unit_pairs_host.cpp")])
+    so = hostsim_build.build("unit_pairs_host.cpp", "libunitpairs.so")
     return ctypes.CDLL(so)
 
 
