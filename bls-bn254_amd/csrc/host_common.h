@@ -80,9 +80,10 @@ struct BNH AgbWs {
 // key shares and their public keys over groups (host_threshold_deal.hip, k_threshold_deal.hip): the staged coefficients /
 // commitments and ids, the decoded coefficients (9 x T limbs) / loaded commitments (54 x T limbs) with their validity bytes, the
 // shares before their encoding (9 x N / 54 x N limbs), the groups' id and coefficient offsets, the per-group marks and statuses,
-// the public key shares in wire format; the host copies the per-share messages are uploaded from
+// the public key shares in wire format; the host copies the per-share messages are uploaded from.  The check of dealt key shares
+// (k_threshold_keycheck.hip): the staged shares and the byte per share its lanes leave
 struct BNH TdlWs {
-  DevBuf coef, ids, cf_ws, c_ws, c_ok, c_sub, r_ws, gstat, st, pks;
+  DevBuf coef, ids, cf_ws, c_ws, c_ok, c_sub, r_ws, gstat, st, pks, shares, share_ok;
   GroupOff goff, coff;
   std::vector<uint8_t> h_msgs;
   std::vector<uint64_t> h_moff;
@@ -283,6 +284,8 @@ struct blsbn254_ctx {
   uint64_t stat_kcmrg[4] = {0, 0, 0, 0}; // the same four counts of the checked merge per committee
   uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
   uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
+  DevBuf kc_tab;                         // the generator's multiples (threshold_keycheck.h): built at the first key-share check, no workspace aliases it
+  uint64_t stat_kchk[3] = {0, 0, 0};     // launches of the key-share check kernel, shares checked, builds of kc_tab (0: not built yet)
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
   uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)

@@ -9,12 +9,12 @@
 // call's workspace of shares (Montgomery limbs / homogeneous points).  After the last launch the marks the lanes left and the
 // validity bytes of the coefficients become statuses (k_td_finish), the shares are encoded -- those of a marked group as
 // zero bytes / the identity -- again by chunks, then ONE download and synchronisation.
+// The check of dealt key shares (blsbn254_threshold_verify_key_shares_batch) runs the G2 evaluation up to and including
+// k_td_finish, leaves the key shares homogeneous in the workspace and compares them there (k_threshold_keycheck.hip).
 #include "host_common.h"
+#include "threshold_keycheck.h"   // TD_MAX_BITS, the bits of a group's mark word, the shape of the generator table
 
 extern "C" {
-
-static const int TD_MAX_BITS = 254;                               // threshold_deal.h: the bit length of r - 1
-static const uint32_t TD_MARK_SCALAR = 1u, TD_MARK_POINT = 2u;     // threshold_deal.h: the bits of a group's mark word
 
 // the largest bit length among the m ids at `ids` (32 B big-endian each), at least 1 and capped at TD_MAX_BITS: ids that the
 // kernels will reject (>= r) are counted like any other
@@ -60,9 +60,9 @@ int td_msg_args(blsbn254_ctx* c, const uint8_t* partial_sigs, const uint64_t* id
   return 0;
 }
 
-// The device part of the G2 evaluation for all groups: the N public key shares in wire format into d_pks (device), the
-// per-group statuses into c->tdl.st.  Everything is enqueued; the caller downloads and synchronises.
-static int td_g2_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, uint8_t* d_pks) {
+// The G2 evaluation for all groups up to and including k_td_finish: the N key shares homogeneous in c->tdl.r_ws (limb-major,
+// stride N), the groups' marks complete in c->tdl.gstat, the per-group statuses in c->tdl.st.  Enqueued.
+static int td_g2_eval_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups) {
   TdlWs& w = c->tdl;
   TRY(stage_group_offsets(c, w.goff, id_off, n_groups)); TRY(stage_group_offsets(c, w.coff, coef_off, n_groups));
   HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
@@ -83,11 +83,18 @@ static int td_g2_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint
                     (uint32_t)n_groups, (const int32_t*)w.c_ws.p, T, nbits, (int32_t*)w.r_ws.p, N, gstat);
     }));
   }
-  TRY(launch(c, c->stream, "td_finish", grid_lanes(n_groups), k_td_finish, gstat, n_groups, coff, (const uint8_t*)w.c_ok.p, (const uint8_t*)w.c_sub.p, (uint32_t)TD_MARK_POINT,
-             (uint8_t*)w.st.p));
+  return launch(c, c->stream, "td_finish", grid_lanes(n_groups), k_td_finish, gstat, n_groups, coff, (const uint8_t*)w.c_ok.p, (const uint8_t*)w.c_sub.p, (uint32_t)TD_MARK_POINT,
+                (uint8_t*)w.st.p);
+}
+// The device part of the G2 evaluation for all groups: the N public key shares in wire format into d_pks (device), the
+// per-group statuses into c->tdl.st.  Everything is enqueued; the caller downloads and synchronises.
+static int td_g2_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint64_t* id_off, size_t n_groups, uint8_t* d_pks) {
+  TRY(td_g2_eval_enqueue(c, commitments, coef_off, ids, id_off, n_groups));
+  TdlWs& w = c->tdl;
+  const size_t N = w.goff.h[n_groups];
   return for_chunks(c, N, [&](size_t lo, size_t m) {
-    return launch(c, c->stream, "td_g2_encode", grid_lanes(m), k_td_g2_encode, (const int32_t*)w.r_ws.p, N, m, (uint32_t)lo, goff, (uint32_t)n_groups, (const uint32_t*)gstat,
-                  d_pks + 128 * lo);
+    return launch(c, c->stream, "td_g2_encode", grid_lanes(m), k_td_g2_encode, (const int32_t*)w.r_ws.p, N, m, (uint32_t)lo, (const uint32_t*)w.goff.d.p, (uint32_t)n_groups,
+                  (const uint32_t*)w.gstat.p, d_pks + 128 * lo);
   });
 }
 
@@ -194,6 +201,53 @@ int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* c, const uint8_t* commi
   TRY(td_verify_shares_enqueue(c, commitments, coef_off, ids, partial_sigs, id_off, msgs, msg_off, n_groups, dst, dst_len));
   if (N) HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, (N + 7) / 8, hipMemcpyDeviceToHost, c->stream));
   return download(c, status, c->tdl.st.p, n_groups);
+}
+
+// the table of the generator's multiples, built on the device at the first call that needs it and kept for the context's life
+static int kc_table(blsbn254_ctx* c) {
+  if (c->stat_kchk[2]) return 0;
+  HIPCHK(c, c->kc_tab.reserve(KC_TABLE_LIMBS * 4));
+  TRY(launch(c, c->stream, "g2gen_table", Shape{dim3((KC_WINDOWS + 63) / 64), dim3(64)}, k_g2gen_table, (int32_t*)c->kc_tab.p));
+  ++c->stat_kchk[2];
+  return 0;
+}
+
+int blsbn254_threshold_verify_key_shares_batch(blsbn254_ctx* c, const uint8_t* commitments, const uint64_t* coef_off, const uint8_t* ids, const uint8_t* shares,
+                                               const uint64_t* id_off, size_t n_groups, uint8_t* valid_bitmap, uint8_t* status) {
+  if (!c) return BLSBN254_E_ARG;
+  if (n_groups == 0) return 0;
+  int rc = td_args(c, commitments, coef_off, ids, id_off, n_groups, valid_bitmap, status);
+  if (rc) return rc;
+  const size_t N = (size_t)(id_off[n_groups] - id_off[0]);
+  if (N && !shares) return BLSBN254_E_ARG;
+  ENTER(c);
+  TdlWs& w = c->tdl;
+  if (N) {
+    TRY(kc_table(c));
+    HIPCHK(c, w.share_ok.reserve(N)); HIPCHK(c, c->bitmap.reserve((N + 7) / 8));
+    TRY(upload(c, w.shares, shares + 32 * id_off[0], 32 * N));
+  }
+  TRY(td_g2_eval_enqueue(c, commitments, coef_off, ids, id_off, n_groups));
+  if (N) {
+    TRY(for_chunks(c, N, [&](size_t lo, size_t m) {
+      ++c->stat_kchk[0]; c->stat_kchk[1] += m;
+      return launch(c, c->stream, "td_key_check", grid_lanes(m), k_td_key_check, (const uint8_t*)w.shares.p, m, (uint32_t)lo, (const int32_t*)c->kc_tab.p,
+                    (const int32_t*)w.r_ws.p, N, (uint8_t*)w.share_ok.p);
+    }));
+    // a share's bit needs its group's marks, complete only behind the last launch and k_td_finish
+    TRY(launch(c, c->stream, "td_key_bits", grid_lanes((N + 7) / 8), k_td_key_bits, (const uint8_t*)w.share_ok.p, N, (const uint32_t*)w.goff.d.p, (uint32_t)n_groups,
+               (const uint32_t*)w.gstat.p, (uint8_t*)c->bitmap.p));
+    HIPCHK(c, hipMemcpyAsync(valid_bitmap, c->bitmap.p, (N + 7) / 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(w.shares.p, 0, 32 * N, c->stream));      // the staged shares do not outlive the call
+  }
+  return download(c, status, w.st.p, n_groups);
+}
+
+int blsbn254_threshold_key_check_stats(blsbn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BLSBN254_E_ARG;
+  for (int k = 0; k < 3; ++k) out[k] = c->stat_kchk[k];
+  out[3] = (uint64_t)KC_WINDOW_BITS;
+  return 0;
 }
 
 int blsbn254_threshold_deal_stats(blsbn254_ctx* c, uint64_t out[4]) {

@@ -157,6 +157,9 @@ BN_KERNEL k_td_fr_encode(const int32_t* r_ws, size_t N, size_t m, uint32_t lo, c
 BN_KERNEL k_td_g2_encode(const int32_t* r_ws, size_t N, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, const uint32_t* gstat, uint8_t* out);
 __global__ void __launch_bounds__(256) k_td_finish(uint32_t* gstat, size_t n_groups, const uint32_t* coff, const uint8_t* ok_a, const uint8_t* ok_b, uint32_t mark,
                                                   uint8_t* status);
+__global__ void __launch_bounds__(64) k_g2gen_table(int32_t* tab);
+BN_KERNEL k_td_key_check(const uint8_t* shares, size_t m, uint32_t lo, const int32_t* tab, const int32_t* r_ws, size_t N, uint8_t* share_ok);
+__global__ void __launch_bounds__(256) k_td_key_bits(const uint8_t* share_ok, size_t N, const uint32_t* goff, uint32_t ng, const uint32_t* gstat, uint8_t* bitmap);
 BN_KERNEL k_tc_scan(const uint8_t* ids, const uint8_t* sigs, const uint8_t* id_ok, size_t m, uint32_t lo, const uint32_t* goff, uint32_t ng, uint32_t* gstat,
                     uint8_t* cand);
 __global__ void __launch_bounds__(256) k_tc_select(const uint8_t* bits_a, const uint8_t* bits_b, size_t m, uint32_t lo, const uint32_t* goff, const uint32_t* coff,

@@ -1044,6 +1044,31 @@ class Engine:
         self._chk(self._lib.blsbn254_threshold_deal_stats(self._ctx, o))
         return {"g2_launches": int(o[0]), "g2_shares": int(o[1]), "fr_shares": int(o[2]), "id_bits": int(o[3])}
 
+    def threshold_verify_key_shares_batch(self, commit_sets, id_sets, share_sets):
+        """Dealt key shares checked against their group's Feldman commitments: share_sets[g] holds 32 bytes per id of id_sets[g].
+        Returns (bitmap, status): bit i (LSB-first, in the order given) = [share_i] G2gen equals sum_j [id_i^j] C_j, share_i is
+        below r and its group's status is 0; status as g2_poly_eval_batch, every bit of a bad group 0.  A zero share is valid
+        exactly where the polynomial is zero.  Not constant time: the generator table is indexed by the share's digits."""
+        coff, goff, n = self._deal_args(commit_sets, 128, id_sets)
+        g = len(id_sets)
+        if len(share_sets) != g:
+            raise ValueError("one set of shares per set of ids")
+        if not np.array_equal(goff, self._group_offsets(share_sets, 32, "a set of shares")):
+            raise ValueError("a group needs as many shares as ids")
+        a, pa = _inbuf(b"".join(commit_sets)); x, px = _inbuf(b"".join(id_sets)); s, ps = _inbuf(b"".join(share_sets))
+        o, po = _outbuf((n + 7) // 8)
+        st = np.zeros(max(g, 1), dtype=np.uint8); pst = st.ctypes.data_as(_u8p)
+        self._chk(self._lib.blsbn254_threshold_verify_key_shares_batch(self._ctx, pa, coff.ctypes.data_as(_u64p), px, ps, goff.ctypes.data_as(_u64p),
+                                                                       ctypes.c_size_t(g), po, pst))
+        return o[:(n + 7) // 8].tobytes(), st[:g].tobytes()
+
+    def threshold_key_check_stats(self):
+        """dict: launches of the key-share check kernel, shares checked, times this context built the generator table (1 after the
+        first call with a share), and the window width of the table in bits"""
+        o = (ctypes.c_uint64 * 4)()
+        self._chk(self._lib.blsbn254_threshold_key_check_stats(self._ctx, o))
+        return {"launches": int(o[0]), "shares": int(o[1]), "table_builds": int(o[2]), "window_bits": int(o[3])}
+
     def threshold_combine_checked_batch(self, commit_sets, id_sets, sig_sets, msgs, dst=DEFAULT_DST):
         """The combiner's call: from group g's Feldman commitments (commit_sets[g], 128 bytes each; their number is the threshold
         t_g), the ids and partial signatures it received (id_sets[g], sig_sets[g]) and its message msgs[g], the group signature

@@ -662,6 +662,31 @@ int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* ctx, const uint8_t* com
 /* since context creation: out[0] launches of the G2 evaluation kernel, out[1] shares evaluated in G2, out[2] shares evaluated
  * in Fr, out[3] the bit count the last G2 launch looped over */
 int blsbn254_threshold_deal_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* What a receiver, an auditor or a complaint round does first: dealt key shares checked against their group's Feldman
+ * commitments, [share_i] G2gen == sum_j [id_i^j] C_j, one equation in G2 per share and no pairing.  Groups, offsets and argument
+ * errors are those of blsbn254_g2_poly_eval_batch (host arrays that need not start at 0; BLSBN254_E_ARG for NULL arguments,
+ * decreasing offsets, more than 2^23 ids, coefficients or groups; n_groups == 0 -> 0); shares (32 B big-endian each, in the order
+ * of the ids) == NULL with N > 0 is BLSBN254_E_ARG too.  status[g] is exactly what blsbn254_g2_poly_eval_batch writes for the
+ * same commitments and ids (BLSBN254_ERR_SCALAR first, then BLSBN254_ERR_G2, else 0).  Bit i of valid_bitmap (LSB-first, in the
+ * order of the ids; the pad bits of the last byte are 0) is 1 exactly when its group's status is 0, shares[i] is canonical
+ * (< r), and [share_i] G2gen and sum_j [id_i^j] C_j are the same group element.  Equality includes the identity: a zero share is
+ * valid exactly when f_g(id_i) = 0, and a group without commitments accepts zero shares only.  A share >= r clears its own bit
+ * and never fails its group.  A bad group or share is never an error of the call.
+ * The right-hand side is the evaluation of blsbn254_g2_poly_eval_batch (same kernels, left homogeneous; its launches go on
+ * counting in blsbn254_threshold_deal_stats out[0], out[1], out[3]); the left one is a fixed-base multiplication out of a table
+ * of the generator's multiples [d 2^(B w)] G2gen, B = blsbn254_threshold_key_check_stats out[3], which the context computes
+ * on the device at the first call with N > 0 and keeps: 256 / B - 1 additions per share, no doubling; the comparison is
+ * cross-multiplied, no inversion.  Nothing but the bitmap and the statuses leaves the device.
+ * A share may be a secret (a receiver checks what it was sent).  The call is NOT constant time: the table is indexed by the
+ * share's digits.  The staged shares are zeroed in device memory before the call returns, as blsbn254_fr_poly_eval_batch does
+ * with its own; their decoded form (the digits) lives in registers only and is never written to memory.
+ * Pending asynchronous verify calls are settled on entry; the result is final on return. */
+int blsbn254_threshold_verify_key_shares_batch(blsbn254_ctx* ctx, const uint8_t* commitments /* T*128 */, const uint64_t* coef_off,
+                                               const uint8_t* ids /* N*32 */, const uint8_t* shares /* N*32 */, const uint64_t* id_off,
+                                               size_t n_groups, uint8_t* valid_bitmap /* ceil(N/8) */, uint8_t* status /* n_groups */);
+/* since context creation: out[0] launches of the check kernel, out[1] shares checked, out[2] times this context built the
+ * generator table (1 after the first call with N > 0, and it stays 1), out[3] the window width in bits (a constant of the build) */
+int blsbn254_threshold_key_check_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* The combiner's call, over ragged groups: from a group's commitments, its message and the n_g >= t_g partial signatures it
  * received, the group signature sum_i lambda_i sigma_i over t_g good ones.  Arguments, offsets and argument errors are those of
  * blsbn254_threshold_verify_shares_batch (host arrays that need not start at 0; BLSBN254_E_ARG for NULL arguments, decreasing
