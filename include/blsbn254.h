@@ -89,7 +89,11 @@ int blsbn254_pairing_check_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uin
                                  size_t n_eq, uint8_t* valid_bitmap /* ceil(n_eq/8) */);
 /* per-pair Miller loops (no product): n outputs of 384 B */
 int blsbn254_miller_loop_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* ml_out);
-/* MillerLoopResult::final_exponentiation, pairings.rs:50-178 (pairing::MillerLoopResult :698-704) */
+/* MillerLoopResult::final_exponentiation, pairings.rs:50-178 (pairing::MillerLoopResult :698-704).  The input need not be a Miller
+ * value: any twelve canonical coefficients (each below p, Gt::to_repr order) are accepted, and every size runs the same function
+ * whichever device form it takes.  0 maps to 0 (384 zero bytes: the inversion's inv0 convention); an element of a proper
+ * subfield (Fp, Fp2, Fp6) or of w Fp6 maps to the identity.  A coefficient >= p anywhere in the batch is BLSBN254_ERR_GT.
+ * Pinned by tests/test_gpu_final_exp_forms.py. */
 int blsbn254_final_exponentiation(blsbn254_ctx* ctx, const uint8_t* ml, size_t n, uint8_t* gt);
 /* G1Projective::hash::<ExpandMsgXmd<Sha256>>(msg, dst), g1.rs:910-919; ::encode g1.rs:922-928 */
 int blsbn254_hash_to_g1_batch(blsbn254_ctx* ctx, const uint8_t* msgs, const uint64_t* off, size_t n,

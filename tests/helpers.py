@@ -79,6 +79,22 @@ def glv_lambda():
     return sum(int(w.strip().rstrip("uUlL"), 16) << (64 * i) for i, w in enumerate(words))
 
 
+# coefficients where the 9 x 29-bit limb form and its carries can go wrong: the ends of the range, limb boundaries, long carry runs
+EDGE_COEFFS = (0, 1, synth.P - 1, 2, synth.P - 2, (synth.P + 1) // 2, (synth.P - 1) // 2, 1 << 29, (1 << 29) - 1, 1 << 58, 1 << 232, (1 << 232) - 1,
+               1 << 253, (1 << 253) - 1, synth.P // 3, 3)
+
+
+def rand_coeffs(seed, n, per):
+    """n elements of `per` canonical 32-byte big-endian coefficients (top byte < 0x30 keeps every value below p); the first
+    coefficients carry EDGE_COEFFS."""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 256, size=(n * per, 32), dtype=np.uint8)
+    a[:, 0] %= 0x30
+    for k, v in enumerate(EDGE_COEFFS[:min(len(EDGE_COEFFS), n * per)]):
+        a[k] = np.frombuffer(v.to_bytes(32, "big"), dtype=np.uint8)
+    return a.tobytes()
+
+
 def offsets_u32(sizes):
     """group offsets as the host-side lane functions take them"""
     return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from tests import synth
-from tests.gpu_support import eng, M
-from tests.helpers import IDENT1, IDENT2
+from tests.gpu_support import eng, fe_form, fe_forms_set_by_environment, fe_launches, fresh_engine, M
+from tests.helpers import IDENT1, IDENT2, rand_coeffs
 
 pytestmark = pytest.mark.gpu
 H = lambda s: int(s, 16)
@@ -679,37 +679,54 @@ def test_verify_batch_rlc_edge_cases(eng, oracle, pyref, M, monkeypatch):
 
 
 def test_wide_final_exponentiation_equals_serial(eng, oracle, pyref, M, monkeypatch):
-    """Launches of at most 2048 tuples run the hard part of the final exponentiation with one WAVE per tuple
-    (k_fe_wide.hip); larger ones three lanes per tuple, or with BLSBN254_WIDE_FE=0 one lane per tuple: same Gt bytes, same bitmaps, at the
-    switch-over sizes and through every mode of the finishing step (Gt bytes, verify bitmap, single flag)."""
+    """Launches of at most 2048 tuples run the hard part of the final exponentiation with one WAVE per tuple (k_fe_wide.hip); larger
+    ones, up to tri_max, three lanes per tuple (k_tri.hip).  With BLSBN254_WIDE_FE=0 the three-lane kernels take the small launches
+    too, and with BLSBN254_TRI_MAX=0 besides, every launch runs one lane per tuple (k_fe_expx* / k_fe_h3): same Gt bytes, same
+    bitmaps, at the switch-over sizes and through every mode of the finishing step (Gt bytes, verify bitmap, single flag).  The
+    launch record of each engine says which form ran (asserted unless the environment moves the forms' sizes itself)."""
     rnd = random.Random(4096)
     G1, G2 = oracle.g1_generator(), oracle.g2_generator()
     base = 24
     p1 = [oracle.g1_mul(G1, rnd.randrange(1, pyref.R)) for _ in range(base)]
     p2 = [oracle.g2_mul(G2, rnd.randrange(1, pyref.R)) for _ in range(base)]
     want = oracle.pairing_batch(b"".join(p1), b"".join(p2), base)
-    monkeypatch.setenv("BLSBN254_WIDE_FE", "0")
-    serial = M.Engine(0)
-    monkeypatch.delenv("BLSBN254_WIDE_FE")
+    tri = fresh_engine(M, monkeypatch, None, {"BLSBN254_WIDE_FE": "0"})
+    serial = fresh_engine(M, monkeypatch, None, {"BLSBN254_WIDE_FE": "0", "BLSBN254_TRI_MAX": "0"})
+    forms = not fe_forms_set_by_environment()
+    tri_max = 0
+    if forms:
+        import torch
+        tri_max = torch.cuda.get_device_properties(0).multi_processor_count * 64
+
+    def run(e, hard, call):
+        """call() on e; the hard part that ran is `hard`, with the one-launch easy part, once"""
+        out, ran = fe_launches(e, call)
+        if forms:
+            assert ran == fe_form("one", hard), (hard, ran)
+        return out
     try:
         for n in (1, 63, 2048, 2049, 4097):
             g1 = b"".join(p1[i % base] for i in range(n)); g2 = b"".join(p2[i % base] for i in range(n))
             exp = b"".join(want[384 * (i % base):384 * (i % base) + 384] for i in range(n))
-            assert eng.pairing_batch(g1, g2, n) == exp                   # wide up to 2048, three lanes per tuple beyond
+            # wide up to 2048, three lanes per tuple beyond
+            assert run(eng, "wide" if n <= 2048 else "tri" if n <= tri_max else "lane", lambda: eng.pairing_batch(g1, g2, n)) == exp
             if n <= 63:
-                assert serial.pairing_batch(g1, g2, n) == exp            # serial kernels on the small sizes too
+                assert run(tri, "tri", lambda: tri.pairing_batch(g1, g2, n)) == exp              # three lanes per tuple on the small sizes too
+                assert run(serial, "lane", lambda: serial.pairing_batch(g1, g2, n)) == exp       # and one lane per tuple
         dst = M.DEFAULT_DST
         for n in (5, 300):
             pks, msgs, sigs, e = synth.make_batch(oracle, n, dst, invalid_every=4, uniq=20)
-            assert eng.verify_batch(pks, msgs, sigs, dst) == serial.verify_batch(pks, msgs, sigs, dst) == synth.bitmap_of(e)
+            assert run(eng, "wide", lambda: eng.verify_batch(pks, msgs, sigs, dst)) == synth.bitmap_of(e)
+            assert run(tri, "tri", lambda: tri.verify_batch(pks, msgs, sigs, dst)) == synth.bitmap_of(e)
+            assert run(serial, "lane", lambda: serial.verify_batch(pks, msgs, sigs, dst)) == synth.bitmap_of(e)
         sks = [synth.sk_of(k) for k in range(5)]
         pk5 = b"".join(oracle.sk_to_pk(s) for s in sks); m5 = [synth.msg_of(i) for i in range(5)]
         agg = oracle.aggregate_sigs(b"".join(oracle.sign(s, m, dst) for s, m in zip(sks, m5)), 5)
-        for e_ in (eng, serial):
-            assert e_.aggregate_verify(pk5, m5, agg, dst) is True
-            assert e_.aggregate_verify(pk5, m5[:4] + [b"x"], agg, dst) is False
+        for e_, hard in ((eng, "wide"), (tri, "tri"), (serial, "lane")):
+            assert run(e_, hard, lambda: e_.aggregate_verify(pk5, m5, agg, dst)) is True
+            assert run(e_, hard, lambda: e_.aggregate_verify(pk5, m5[:4] + [b"x"], agg, dst)) is False
     finally:
-        serial.close()
+        tri.close(); serial.close()
 
 
 def test_chunked_entry_points(oracle, pyref, M, monkeypatch):
@@ -766,19 +783,6 @@ def test_chunked_prepared_paths(oracle, M, monkeypatch):
         e.close()
 
 
-def _rand_coeffs(seed, n, per):
-    """n elements of `per` canonical 32-byte big-endian coefficients (top byte < 0x30 keeps every value below p); the first
-    elements carry the edge values 0, 1, p - 1."""
-    rng = np.random.default_rng(seed)
-    a = rng.integers(0, 256, size=(n * per, 32), dtype=np.uint8)
-    a[:, 0] %= 0x30
-    edge = [0, 1, synth.P - 1, 2, synth.P - 2, (synth.P + 1) // 2, (synth.P - 1) // 2, 1 << 29, (1 << 29) - 1, 1 << 58, 1 << 232, (1 << 232) - 1,
-            1 << 253, (1 << 253) - 1, synth.P // 3, 3]            # limb boundaries of the 9 x 29-bit form, long carry runs
-    for k, v in enumerate(edge[:min(len(edge), n * per)]):
-        a[k] = np.frombuffer(v.to_bytes(32, "big"), dtype=np.uint8)
-    return a.tobytes()
-
-
 @pytest.mark.parametrize("op,per,n", [
     (0, 1, 1 << 20), (1, 1, 1 << 20), (3, 1, 1 << 20), (4, 1, 1 << 20), (5, 1, 1 << 20), (8, 1, 1 << 20),       # Fp mul sqr add sub neg x9
     (2, 1, 1 << 17), (6, 1, 20000), (7, 1, 20000),                                                                 # Fp inv (divstep recurrence: 609 steps must do for every input) sqrt is_square
@@ -790,8 +794,8 @@ def test_field_primitives_fuzz_vs_oracle(eng, oracle, op, per, n):
     """Primitive-level parity: every Fp / Fp2 / Fp6 / Fp12 operation of the device arithmetic,
     element-wise on random operands (up to 2^20 wide), bit-exact against the CPU oracle.  fp6.rs / fp12.rs hold no reference
     vectors, so this -- with the oracle itself checked against the independent Python model on CPU -- is their isolated pin."""
-    a = _rand_coeffs(1000 + op, n, per)
-    b = _rand_coeffs(2000 + op, n, per) if op in eng.FIELD_OP_BINARY else None
+    a = rand_coeffs(1000 + op, n, per)
+    b = rand_coeffs(2000 + op, n, per) if op in eng.FIELD_OP_BINARY else None
     got = eng.field_op_batch(op, a, b, n)
     want = oracle.field_op_batch(op, a, b, n)
     if got != want:

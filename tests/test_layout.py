@@ -1,5 +1,5 @@
 """CPU-only: the test modules stay readable on their own.  What two of them share lives in a support module (hostsim_build,
-library_support, gpu_support, helpers, keyset_support, threshold_support), never in another test module, and only the support
+library_support, gpu_support, helpers, fp12_cases, keyset_support, threshold_support), never in another test module, and only the support
 modules run the compiler of the host-side programs or the binary tools that read the library's code objects."""
 import glob
 import os
