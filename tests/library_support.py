@@ -2,7 +2,6 @@
 kernels' metadata and disassembly counts, read once per run through scripts/kernel_resources.py and scripts/isa_lint.py.
 No GPU needed.  Nothing else under tests/ runs the binary tools itself."""
 import os
-import re
 import sys
 
 import pytest
@@ -11,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if os.path.join(ROOT, "scripts") not in sys.path:
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
+from abi_header import prototypes                                                                    # noqa: E402
 from isa_lint import lint                                                                            # noqa: E402
 from kernel_resources import demangled, instruction_counts, kernel_table, library_path_built, scratch_bytes       # noqa: E402,F401
 
@@ -22,9 +22,7 @@ def M():
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "blsbn254.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(blsbn254_[a-z0-9_]+)\s*\(", text)))
+    return sorted(p.name for p in prototypes())
 
 
 def lint_by_name(path):

@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from tests.library_support import M, declared_symbols, library_path_built  # noqa: F401 (M is a fixture)
+from tests.library_support import M, declared_symbols, library_path_built, prototypes  # noqa: F401 (M is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,6 +32,55 @@ def test_rust_shim_extern_block_matches_the_header():
     shim = open(os.path.join(ROOT, "integration", "rust", "gpu.rs")).read()
     for used in set(re.findall(r"ffi::(blsbn254_[a-z0-9_]+)", shim)):
         assert used in declared_symbols()
+
+
+def test_python_prototype_table_matches_the_header():
+    """bls-bn254_amd/_abi.py is generated from include/blsbn254.h; the committed copy must be current."""
+    import subprocess
+    import sys
+    gen = os.path.join(ROOT, "scripts", "gen_abi.py")
+    assert subprocess.call([sys.executable, gen, "--check"]) == 0, "run python scripts/gen_abi.py"
+
+
+def test_generator_refuses_a_type_it_does_not_know():
+    import gen_abi                                           # scripts/ is on the path through tests.library_support
+    assert gen_abi.arg_type("const uint8_t* const*", False) == gen_abi.arg_type("uint64_t", True) == "c_void_p"
+    assert gen_abi.ret_type("blsbn254_ctx*") == "c_void_p" and gen_abi.ret_type("void") is None
+    for bad in (lambda: gen_abi.arg_type("double", False), lambda: gen_abi.arg_type("uint64_t", False), lambda: gen_abi.ret_type("double")):
+        with pytest.raises(SystemExit):
+            bad()
+
+
+def test_every_entry_point_has_the_headers_prototype(M):
+    """load_library() sets argtypes and restype of every declared entry point, and nothing else has to: the calls below run
+    with no restype or wrapper of their own."""
+    lib = M.load_library()
+    by_value = {"size_t": ctypes.c_size_t, "int": ctypes.c_int}
+    returns = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p, "void": None}
+    protos = prototypes()
+    assert sorted(p.name for p in protos) == declared_symbols()
+    for p in protos:
+        fn = getattr(lib, p.name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(p.params), p.name
+        for t, q in zip(fn.argtypes, p.params):
+            assert t is (ctypes.c_void_p if q.is_array or q.ctype.endswith("*") else by_value[q.ctype]), (p.name, q.name)
+        assert fn.restype is (returns[p.ret] if p.ret in returns else ctypes.c_void_p), p.name
+    for count in (lib.blsbn254_keyset_count, lib.blsbn254_g2prepared_count, lib.blsbn254_keyset_committee_count):
+        got = count(None)
+        assert type(got) is int and got == 0
+    assert type(lib.blsbn254_strerror(1)) is bytes
+    with pytest.raises(TypeError):
+        lib.blsbn254_g1_check_batch(None, None, 0)           # one argument too few
+
+
+def test_a_library_without_a_declared_entry_point_is_refused_by_name(M, oracle, monkeypatch):
+    """BLSBN254_LIB selects another build of the library; one that lacks an entry point of the header does not load (the
+    oracle's shared library stands in for such a build)."""
+    oracle.lib()
+    monkeypatch.setattr(M.engine, "_lib", None)
+    monkeypatch.setenv("BLSBN254_LIB", oracle._SO)
+    with pytest.raises(RuntimeError, match="blsbn254_ctx_create"):
+        M.load_library()
 
 
 def test_library_exports_every_declared_symbol(M):

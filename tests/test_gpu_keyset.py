@@ -232,7 +232,6 @@ def test_argument_errors(eng, M):
     sg = np.frombuffer(sigs, dtype=np.uint8)
     out = np.zeros(128 * 3, dtype=np.uint8); st = np.zeros(3, dtype=np.uint8); bm = np.zeros(1, dtype=np.uint8)
     P = lambda a: a.ctypes.data_as(u8)
-    lib.blsbn254_keyset_count.restype = ctypes.c_size_t
 
     def create(c=ctx, p=P(pks), k=n, out_h=True):
         h = ctypes.c_void_p()

@@ -106,6 +106,18 @@ def test_point_checks(eng, oracle, pyref, kats):
     assert oracle.g1_check_batch(buf, len(pts1))[0] & 0x1f == 0b00011
 
 
+def test_raw_call_takes_its_prototype_from_the_header(eng, oracle):
+    """The prototypes load_library() sets from the header are live on a real call: g1_check_batch called raw, its size_t a
+    plain Python 9 and no wrapper anywhere.  Eight valid points and one off the curve, so that the bitmap spans two bytes."""
+    G1 = oracle.g1_generator()
+    pts = [oracle.g1_mul(G1, k) for k in range(1, 9)]
+    pts.insert(6, G1[:32] + (3).to_bytes(32, "big"))
+    buf = np.frombuffer(b"".join(pts), dtype=np.uint8)
+    out = np.zeros(2, dtype=np.uint8)
+    assert eng._lib.blsbn254_g1_check_batch(eng._ctx, buf.ctypes, 9, out.ctypes) == 0
+    assert out.tobytes() == eng.g1_check_batch(buf, 9) == oracle.g1_check_batch(buf.tobytes(), 9) == bytes([0b10111111, 0b1])
+
+
 @pytest.mark.parametrize("n,invalid_every", [(1, 0), (63, 4), (64, 0), (65, 5), (1000, 8)])
 def test_verify_batch(eng, oracle, M, n, invalid_every):
     dst = M.DEFAULT_DST
