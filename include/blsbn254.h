@@ -67,11 +67,18 @@ const char* blsbn254_last_error(blsbn254_ctx* ctx); /* text of the last HIP erro
  * verify_batch*, pop_verify_batch) accept any n and process it in chunks of 4 Mi elements; the product-type ones
  * (multi_miller_loop, aggregate_*, verify_batch_rlc) take at most 2^23 elements per call (BLSBN254_E_ARG beyond). */
 /* pairing(&G1Affine, &G2Affine) -> Gt, pairings.rs:760-802 (pairing::Engine::pairing :685-696).
- * Identity in either slot gives Gt::IDENTITY. */
+ * Identity in either slot gives Gt::IDENTITY.  The operands are decoded, not checked: any canonical coordinates (each below p)
+ * are accepted -- every point of E(Fp), points of the twist outside the r-torsion, coordinates on no curve at all -- and every
+ * size runs the same function of those coordinates whichever device form it takes (one wave, a quad of lanes or one lane per
+ * pair): same values, same bytes.  A point that is the identity by its encoding (x = 0, whatever y is) gives the identity.  A
+ * coordinate >= p anywhere in the batch is BLSBN254_ERR_G1 / _G2.  Pinned by tests/test_gpu_miller_forms.py. */
 int blsbn254_pairing_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* gt);
 /* multi_miller_loop(&[(&G1Affine, &G2Prepared)]) -> MillerLoopResult, pairings.rs:808-857
  * (pairing::MultiMillerLoop :706-713).  Pairs with an identity member are skipped.  Output = the
- * 384-byte Fp12 Miller-loop value (before final exponentiation). */
+ * 384-byte Fp12 Miller-loop value (before final exponentiation).  The operands are decoded, not checked, as for
+ * blsbn254_pairing_batch: any canonical coordinates are accepted, every size runs the same function whichever device form it
+ * takes, and a member that is the identity by its encoding (x = 0) has its pair skipped.  Pinned by
+ * tests/test_gpu_miller_forms.py. */
 int blsbn254_multi_miller_loop(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t ml_out[384]);
 /* n_eq independent multi_miller_loop products (pairings.rs:808-857): equation g owns the pairs
  * g1[64*off[g] .. 64*off[g+1]) / g2[128*off[g] .. 128*off[g+1]) (off: n_eq + 1 non-decreasing element offsets, host array).
@@ -87,7 +94,10 @@ int blsbn254_multi_miller_loop_batch(blsbn254_ctx* ctx, const uint8_t* g1, const
  * clears its equation's bit; it is never an error.  An empty group holds.  Same size limits. */
 int blsbn254_pairing_check_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint64_t* off,
                                  size_t n_eq, uint8_t* valid_bitmap /* ceil(n_eq/8) */);
-/* per-pair Miller loops (no product): n outputs of 384 B */
+/* per-pair Miller loops (no product): n outputs of 384 B.  The operands are decoded, not checked, as for
+ * blsbn254_pairing_batch: any canonical coordinates are accepted, every size runs the same function whichever device form it
+ * takes, and a pair with a member that is the identity by its encoding (x = 0) gives Fp12::ONE.  Pinned by
+ * tests/test_gpu_miller_forms.py. */
 int blsbn254_miller_loop_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* ml_out);
 /* MillerLoopResult::final_exponentiation, pairings.rs:50-178 (pairing::MillerLoopResult :698-704).  The input need not be a Miller
  * value: any twelve canonical coefficients (each below p, Gt::to_repr order) are accepted, and every size runs the same function

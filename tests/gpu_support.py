@@ -30,22 +30,41 @@ FE_FORM_KNOBS = ("BLSBN254_WIDE_FE", "BLSBN254_WIDE_FE_MAX", "BLSBN254_TRI_MAX",
 FE_KERNELS = ("fe_easy", "fe_easy_head", "fe_inv4", "fe_easy_tail", "fe_hard_wide", "fe_tri_hard", "fe_expx_h1", "fe_expx_h2", "fe_expx", "fe_h3")
 
 
+# ... and of the Miller loop and of the key preparation (miller_to_ws, host.hip; launch_g2_prepare, launch_miller_prepared,
+# verify_chunk_dev and blsbn254_multi_miller_loop_prepared, host_verify.hip): the same sizes, and three switches of their own
+MILLER_FORM_KNOBS = FE_FORM_KNOBS + ("BLSBN254_TRI_MILLER", "BLSBN254_QUAD_PREP", "BLSBN254_AUTO_PREPARE")
+# every Miller-loop kernel the host code launches, under the name its launch is recorded by
+MILLER_KERNELS = ("miller_wide_1", "miller_tri_1", "miller_1", "miller_wide_1p", "miller_tri_1p", "miller_hpk1p", "miller_hpk2p", "miller_hpk2", "miller_hpk2r",
+                  "miller_hpk", "miller_wide_prepared", "miller_tri_prepared", "miller_prepared", "miller_verify")
+PREP_KERNELS = ("g2_prepare", "g2_expand")          # g2_prepare: k_g2_prepare_quad or k_g2_prepare, one name for both
+
+
 def fe_forms_set_by_environment():
     """the names among FE_FORM_KNOBS that the environment sets: with any of them the sizes at which a form runs are not the
     production ones"""
     return [k for k in FE_FORM_KNOBS if k in os.environ]
 
 
-def fe_launches(e, call):
-    """call() with the engine's launch record on: (its result, {kernel name: launches} of the final-exponentiation kernels that
-    ran, absent ones left out)"""
+def miller_forms_set_by_environment():
+    """the same for MILLER_FORM_KNOBS"""
+    return [k for k in MILLER_FORM_KNOBS if k in os.environ]
+
+
+def launches(e, call, kernels):
+    """call() with the engine's launch record on: (its result, {kernel name: launches} of those of `kernels` that ran, absent
+    ones left out).  The record is switched off again whether call() returns or raises."""
     e.profile_enable(True); e.profile_reset()
     try:
         out = call()
         rec = e.profile_read()
     finally:
         e.profile_enable(False); e.profile_reset()
-    return out, {k: rec[k]["launches"] for k in FE_KERNELS if k in rec and rec[k]["launches"]}
+    return out, {k: rec[k]["launches"] for k in kernels if k in rec and rec[k]["launches"]}
+
+
+def fe_launches(e, call):
+    """launches() of the final-exponentiation kernels"""
+    return launches(e, call, FE_KERNELS)
 
 
 def fe_form(easy, hard):
