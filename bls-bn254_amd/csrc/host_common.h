@@ -25,6 +25,7 @@
 #include "keyset_committee_agg_plan.h" // KcaRepack, the argument walk of the checked aggregation per committee of a key set
 #include "keyset_committee_merge_plan.h" // KcmRepack, the argument walk of the checked merge per committee of a key set
 #include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
+#include "aggregate_rlc_plan.h" // the segments and exact ranges of the aggregate verify over groups by random linear combination
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -188,6 +189,21 @@ struct BNH KsrWs {
   std::vector<uint32_t> h_cstart, h_clen, h_list;
   std::vector<uint64_t> h_moff, h_rowoff;
 };
+// aggregate verify over groups by random linear combination (host_aggregate_rlc.hip, k_aggregate_rlc.hip): the seed; per pair its
+// group; the groups' pair offsets, segments, signature flags, eligibility bytes and weights; the weighted points
+// (27 x W limbs: pairs, signatures, one identity per virtual key); per item its virtual key id; per virtual key the table it pairs
+// with, its sum as an affine H point and the status of that; the segments' products and their is-one bytes; the groups' validity
+// bytes; the levels of the segmented product.  Host side: the plan's vectors (what the uploads read), what a round downloads, and
+// the bits of an exact sub-call.
+struct BNH AgrWs {
+  DevBuf seed, gidx, seg_of, sig_ok, elig, wt, w, vkid, mkid, h2, st, prod, isone, valid;
+  GroupOff goff;
+  SegWs seg;
+  uint8_t h_seed[32];
+  std::vector<uint32_t> h_gidx, h_bound, h_seg_of;
+  std::vector<uint8_t> h_elig, h_pass, h_bits;
+  std::vector<std::pair<size_t, size_t>> ranges;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -288,6 +304,11 @@ struct blsbn254_ctx {
   uint64_t stat_kchk[3] = {0, 0, 0};     // launches of the key-share check kernel, shares checked, builds of kc_tab (0: not built yet)
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
   uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
+  AgrWs agr;
+  size_t agr_segments = 0;               // blsbn254_set_aggregate_rlc_segments: 0 = the default rule, 1 = no second round, else S
+  // calls, groups decided by round 1, by round 2, groups sent to the exact pipeline, ineligible groups, equations checked, calls that
+  // did not take round 1, segments that failed
+  uint64_t stat_agr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
   uint64_t stat_msm[4] = {0, 0, 0, 0};   // bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
   bool profiling = false;

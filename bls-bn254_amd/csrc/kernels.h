@@ -225,6 +225,13 @@ BN_KERNEL k_ksr_chunks(const int32_t* sa, const int32_t* sb, size_t M, const uin
                        const uint8_t* elig, uint32_t* cnt, uint8_t* state, uint8_t* sa_bytes);
 __global__ void __launch_bounds__(256) k_ksr_gather(const uint32_t* list, size_t m, const int32_t* pts, size_t pts_stride, const uint8_t* ok, const uint8_t* sigs,
                                                    int32_t* c_pts, uint8_t* c_ok, uint8_t* c_sigs);
+// aggregate verify over ragged groups by random linear combination (k_aggregate_rlc.hip)
+BN_KERNEL k_agr_group(const uint8_t* sigs, const uint32_t* goff, const uint32_t* kid, const uint8_t* key_ok, const uint8_t* seed, size_t G, uint8_t* sig_ok,
+                      uint8_t* elig, uint2* wt, int32_t* w_ws, size_t W, size_t col0);
+BN_KERNEL k_agr_weigh(const int32_t* h_ws, size_t N, const uint32_t* gidx, const uint8_t* elig, const uint2* wt, int32_t* w_ws, size_t W);
+__global__ void __launch_bounds__(256) k_agr_items(const uint32_t* gidx, const uint32_t* kid, const uint32_t* seg_of, size_t N, size_t G, uint32_t u, uint32_t S,
+                                                  int32_t* w_ws, size_t W, uint32_t* vkid, uint32_t* mkid);
+__global__ void __launch_bounds__(256) k_agr_bits(const uint8_t* elig, const uint32_t* seg_of, const uint8_t* isone, size_t G, uint8_t* valid);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

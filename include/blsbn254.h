@@ -150,6 +150,47 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* ctx, const uint8_t* pks, const
                                     size_t n_groups, const uint8_t* dst, size_t dst_len,
                                     uint8_t* valid_bitmap /* ceil(n_groups/8) */);
 int blsbn254_aggregate_batch_stats(blsbn254_ctx* ctx, uint64_t out[4]);
+/* blsbn254_aggregate_verify_batch by RANDOM LINEAR COMBINATION ACROSS GROUPS: the same arguments plus a seed, the same bitmap.
+ * Arguments, layout, argument errors and the n_groups == 0 and all-empty cases are exactly those of
+ * blsbn254_aggregate_verify_batch.  For a range R of groups with secret weights r_g
+ *   prod_{g in R} [ e(sig_g, -G2gen) prod_i e(H_gi, pk_gi) ]^(r_g)
+ *     = e(sum_g r_g sig_g, -G2gen) * prod_{distinct pk} e(sum_{(g,i): pk_gi = pk} r_g H_gi, pk)
+ * so a call over a pool of u keys is decided by u + 1 table-only Miller loops and ONE final exponentiation, after N weighted
+ * hash points and N G1 additions, where the exact call runs a variable-Q Miller slot per pair and per signature and a final
+ * exponentiation per group.
+ * A group takes part only when it is ELIGIBLE: it has at least one pair, its signature decodes, is on the curve and is not the
+ * identity, and every key of it is valid by the checks of the key preparation (decodes, not the identity, on the curve, in the
+ * r-torsion).  An ineligible group has bit 0 -- the exact call's bit -- and costs no equation and no exact sub-call.
+ * Round 1: when the keys repeat (u distinct keys among the N pairs of the call, 2 u <= N and u < 65536) all eligible groups of the
+ * call form one virtual aggregate; if its equation holds, every eligible group has its bit set.  When the keys do not repeat the
+ * call IS the exact call (counted in out[6]).  Round 2, only when round 1 fails: the groups are cut into S segments of consecutive
+ * groups, each checked as its own virtual aggregate in one batched pass over the weighted points of round 1 (nothing is hashed or
+ * weighed twice); S = min(16, N / (2 u)) unless blsbn254_set_aggregate_rlc_segments fixes it (0 restores that rule, 1 = no second
+ * round, 2 .. 4096 = S, never more segments than groups; anything else is BLSBN254_E_ARG), and the round is skipped when S < 2.
+ * The eligible groups of a segment that passes have their bits set.  The eligible groups of the segments that FAILED (all of them
+ * when round 2 is skipped) are decided by blsbn254_aggregate_verify_batch's own pipeline on their contiguous group ranges, adjacent
+ * failed segments merged, and ranges with fewer than 2^16 pairs and signatures between them made one; only the bits of eligible groups are taken from it.  So bit g is bit g of the exact call on the same arguments, and can
+ * differ only where an invalid range passed its equation: probability at most 2^-64 per equation checked, given a fresh secret seed.
+ * Weights: r_g = a_g + b_g lambda (lambda the eigenvalue of phi(x, y) = (beta x, y) on G1) with the 32-bit a_g = the first 4 bytes
+ * and b_g = the next 4 bytes, each big-endian, of SHA-256(seed || "AGRLC" || g as 8 bytes little-endian || sig_g); (0, 0) becomes
+ * (1, 0).  The 2^64 pairs give 2^64 distinct weights mod r, as for blsbn254_verify_batch_rlc.
+ * seed = NULL (the production setting): the library draws 32 bytes from the OS (getrandom) inside the call, i.e. after
+ * the batch is fixed.  A caller-supplied seed exists for reproducible tests; soundness then rests on that seed being
+ * fresh and secret -- never reuse one, never derive it from public data.
+ * The PRECONDITION of blsbn254_aggregate_verify (rogue keys / repeated messages) holds per group, unchanged.
+ * Pending asynchronous verify calls are settled on entry and none is left pending.
+ * blsbn254_aggregate_rlc_stats, since the context was created: out[0] calls, out[1] groups decided by round 1, out[2] groups decided
+ * by round 2, out[3] groups sent to the exact pipeline (the eligible groups inside the ranges of the sub-calls: those of failed
+ * segments, and those between two ranges made one; every group of a call that did not take round 1), out[4] ineligible groups, out[5] equations checked, out[6] calls that did not take round 1 (keys do not repeat),
+ * out[7] segments that failed.  blsbn254_aggregate_batch_stats keeps counting whatever the exact sub-calls serve (the groups of
+ * their ranges, ineligible ones between eligible ones included).  NULL out: BLSBN254_E_ARG. */
+int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
+                                        const uint64_t* grp_off /* n_groups+1 */, const uint8_t* agg_sigs /* n_groups*64 */,
+                                        size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                        const uint8_t seed[32] /* NULL: getrandom inside the call */,
+                                        uint8_t* valid_bitmap /* ceil(n_groups/8) */);
+int blsbn254_set_aggregate_rlc_segments(blsbn254_ctx* ctx, size_t segments);
+int blsbn254_aggregate_rlc_stats(blsbn254_ctx* ctx, uint64_t out[8]);
 /* Repeated signers.  blsbn254_verify_batch (and _dev) de-duplicates the public keys of a batch on the GPU (hash table over
  * the 128-byte encodings, full comparison on every hit) and, when at most half of them are distinct (and at most 65536),
  * validates each DISTINCT key once and turns it into its table of 88 line-coefficient triples -- G2Prepared::from,

@@ -351,6 +351,32 @@ pub fn aggregate_verify_batch(groups: &[&[([u8; 128], &[u8])]], sigs: &[[u8; 64]
     bits(&bm, n)
 }
 
+/// `aggregate_verify_batch` by random linear combination across groups (`blsbn254_aggregate_verify_batch_rlc`): the same answers
+/// (an invalid range of groups passes its equation with probability at most 2^-64), one Miller loop per DISTINCT key of the call
+/// and one final exponentiation where the keys repeat.  The weights are drawn inside the library (OS randomness, after the batch
+/// is fixed).
+pub fn aggregate_verify_batch_rlc(groups: &[&[([u8; 128], &[u8])]], sigs: &[[u8; 64]], dst: &[u8]) -> Vec<bool> {
+    assert!(groups.len() == sigs.len());
+    let n = groups.len();
+    let mut goff = Vec::with_capacity(n + 1);
+    goff.push(0u64);
+    let mut flat: Vec<u8> = Vec::new();
+    let mut msgs: Vec<&[u8]> = Vec::new();
+    for g in groups {
+        for (k, m) in g.iter() { flat.extend_from_slice(k); msgs.push(m); }
+        goff.push(msgs.len() as u64);
+    }
+    let (data, off) = pack(&msgs);
+    let sg: Vec<u8> = sigs.iter().flatten().copied().collect();
+    let mut bm = vec![0u8; (n + 7) / 8];
+    with_ctx(|c| check(unsafe {
+        ffi::blsbn254_aggregate_verify_batch_rlc(c, flat.as_ptr(), data.as_ptr(), off.as_ptr(), goff.as_ptr(), sg.as_ptr(), n, dst.as_ptr(), dst.len(),
+                                                 std::ptr::null(), bm.as_mut_ptr())
+    }))
+    .expect("per-group failures are reported in the bitmap");
+    bits(&bm, n)
+}
+
 // ---------------------------------------------------------------- repeated signers: keys prepared once (G2Prepared, batched)
 
 /// The line tables of a set of public keys, resident on the GPU (`blsbn254_g2prepared`): what `G2Prepared::from`
