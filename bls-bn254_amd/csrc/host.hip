@@ -167,12 +167,27 @@ int blsbn254_valu_peak(blsbn254_ctx* c, double* mads_per_s) {
   return 0;
 }
 
-// DST handling: RFC 9380 5.3.3 (oversize DSTs are pre-hashed); staged into device memory once per call
+// The message expander of every hashing launch (host_common.h launch_hash_to_g1 and its siblings).  Settles the context FIRST: a
+// pending asynchronous verify call whose guess fails is re-run by resolve_pending from its saved DST, and that re-run must hash under
+// the expander the call was made with -- so the pending calls are resolved (ENTER) before the new id is stored.  The resident
+// tag is dropped: the staged bytes of an oversize DST depend on the expander.
+static_assert(BLSBN254_EXPAND_XMD_SHA256 == EXPAND_XMD_SHA256 && BLSBN254_EXPAND_XMD_KECCAK256 == EXPAND_XMD_KECCAK256 && BLSBN254_EXPAND_XMD_SHA3_256 == EXPAND_XMD_SHA3_256 &&
+              BLSBN254_EXPAND_XOF_SHAKE128 == EXPAND_XOF_SHAKE128 && BLSBN254_EXPAND_XOF_SHAKE256 == EXPAND_XOF_SHAKE256, "the header's ids are keccak.h's");
+int blsbn254_set_expander(blsbn254_ctx* c, int id) {
+  if (!c || id < 0 || id >= (int)EXPAND_COUNT) return BLSBN254_E_ARG;
+  ENTER(c);
+  c->expander = (uint32_t)id;
+  c->dst_host_len = -1;
+  return 0;
+}
+int blsbn254_get_expander(const blsbn254_ctx* c) { return c ? (int)c->expander : BLSBN254_E_ARG; }
+
+// DST handling: RFC 9380 5.3.3 (an oversize DST is pre-hashed with the context's expander, keccak.h oversize_dst); staged into
+// device memory once per call
 int stage_dst(blsbn254_ctx* c, const uint8_t* dst, size_t dst_len, uint32_t* out_len) {
   uint8_t tmp[256];
   if (dst_len > 255) {
-    Sha256 s; sha256_init(s);
-    sha256_update(s, (const uint8_t*)"H2C-OVERSIZE-DST-", 17); sha256_update(s, dst, dst_len); sha256_final(s, tmp);
+    oversize_dst(c->expander, tmp, dst, dst_len);
     dst_len = 32;
   } else if (dst_len) std::memcpy(tmp, dst, dst_len);
   *out_len = (uint32_t)dst_len;
@@ -384,9 +399,8 @@ static int h2c_common(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off,
   if (rc) return rc;
   size_t sz = g2 ? 128 : 64;
   HIPCHK(c, c->out.reserve(sz * n));
-  if (g2) TRY(launch(c, c->stream, "hash_to_g2", grid_lanes(n), k_hash_to_g2, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-                     (uint8_t*)c->out.p, ro));
-  else TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)nullptr,
+  if (g2) TRY(launch_hash_to_g2(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (uint8_t*)c->out.p, ro));
+  else TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)nullptr,
                   n, (uint8_t*)c->out.p, ro ? 1 : 2));
   return download(c, out, c->out.p, sz * n);
 }

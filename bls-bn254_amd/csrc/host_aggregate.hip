@@ -70,7 +70,7 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
   }
   // hash (and, on the exact path, key checks) over the caller's n pairs; their H points land in slots 0..n-1 of a stride-np workspace
   if (n) {
-    TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p,
+    TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p,
                np, (uint8_t*)nullptr, 0));
     if (!prepared) TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
   }
@@ -197,7 +197,7 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(dedup_key_ids(c, n, u, true));
   TRY(key_sorted_order(c, (const uint32_t*)c->kd_kid.p, n, u));                 // cursor[k] is now the END of run k
   const uint32_t *hist = (const uint32_t*)c->kd_hist.p, *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p, *kid = (const uint32_t*)c->kd_kid.p;
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n,
+  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, n,
              (uint8_t*)nullptr, 3));
   // sums per key: the tuples in sorted order (columns perm[s] of h_ws) -> one sum per key (key_sums)
   const int32_t* pts = nullptr; size_t pts_stride = u;

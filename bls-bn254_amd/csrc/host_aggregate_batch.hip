@@ -75,7 +75,7 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const u
 
   const uint8_t* d_pks = (const uint8_t*)c->in_a.p;
   int32_t* h = (int32_t*)c->h_ws.p;
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(N), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, (const uint8_t*)c->dst.p, dl, h, S,
+  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, dl, h, S,
              (uint8_t*)nullptr, 0));
   TRY(launch(c, c->stream, "agb_place_sigs", grid_lanes(G), k_agb_place_sigs, (const uint8_t*)c->in_b.p, G, h, N, S, (uint8_t*)a.sig_ok.p));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(N), k_g2_check, d_pks, N, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));   // the caller's keys only: never -G2gen

@@ -150,7 +150,7 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
   HIPCHK(c, c->h_ws.reserve(N * 27 * 4)); HIPCHK(c, w.w.reserve(W * 27 * 4)); HIPCHK(c, w.vkid.reserve(4 * W));
   HIPCHK(c, w.sig_ok.reserve(G)); HIPCHK(c, w.elig.reserve(G)); HIPCHK(c, w.wt.reserve(8 * G));
   TRY(dedup_key_ids(c, N, u, false));
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(N), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, N,
+  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, dl, (int32_t*)c->h_ws.p, N,
              (uint8_t*)nullptr, 3));
   HIPCHK(c, join_stream2(c));                           // the keys' validity bytes are final
   TRY(launch(c, c->stream, "agr_group", grid_lanes(G), k_agr_group, (const uint8_t*)c->in_b.p, (const uint32_t*)w.goff.d.p, (const uint32_t*)c->kd_kid.p, (const uint8_t*)c->prep_ok.p, (const uint8_t*)w.seed.p, G,

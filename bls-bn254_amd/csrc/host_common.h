@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "sha256.h"      // host-side use: pre-hashing an oversize DST only (RFC 9380 5.3.3)
+#include "keccak.h"      // (with sha256.h) host-side use: pre-hashing an oversize DST only (RFC 9380 5.3.3); the expander ids
 #include "lane_ops.h"    // flag constants
 #include "kernels.h"
 #include "key_cache.h"   // the store of prepared keys: its state words and kernels
@@ -274,6 +274,7 @@ struct blsbn254_ctx {
   DevBuf fe_slots;       // the ten named powers of the t -> t^x addition chain, 10 x 108 x n limbs
   uint8_t dst_host[256];  // the (pre-hashed if oversize) DST currently resident in `dst`, and its length; -1 = none
   int dst_host_len = -1;
+  uint32_t expander = BLSBN254_EXPAND_XMD_SHA256;   // the message expander every hashing launch runs under (blsbn254_set_expander; keccak.h EXPAND_*)
   size_t chunk = (size_t)1 << 22;   // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
   MsmWs msm;
   PcWs pc;
@@ -346,6 +347,31 @@ static inline int launch(blsbn254_ctx* c, hipStream_t s, const char* name, Shape
   { ProfScope ps(c, s, name); hipLaunchKernelGGL(kernel, g.grid, g.block, 0, s, args...); }
   HIPCHK(c, hipGetLastError());
   return 0;
+}
+// THE launches of the four hashing kernels, on the tag resident in c->dst (stage_dst: dl): the XMD-SHA-256 kernel under the
+// default expander, its sibling of k_hash_keccak.hip under any other.  No host unit names those kernels but these four helpers,
+// so every call that hashes follows blsbn254_set_expander.  Counted under one name whatever the expander.
+static inline int launch_hash_to_g1(blsbn254_ctx* c, hipStream_t s, const uint8_t* msgs, const uint64_t* off, size_t n, uint32_t dl, int32_t* ws, size_t stride,
+                                    uint8_t* out, int mode) {
+  const uint8_t* dst = (const uint8_t*)c->dst.p;
+  if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "hash_to_g1", grid_lanes(n), k_hash_to_g1, msgs, off, n, dst, dl, ws, stride, out, mode);
+  return launch(c, s, "hash_to_g1", grid_lanes(n), k_hash_to_g1_x, c->expander, msgs, off, n, dst, dl, ws, stride, out, mode);
+}
+static inline int launch_hash_to_g2(blsbn254_ctx* c, hipStream_t s, const uint8_t* msgs, const uint64_t* off, size_t n, uint32_t dl, uint8_t* out, int ro) {
+  const uint8_t* dst = (const uint8_t*)c->dst.p;
+  if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "hash_to_g2", grid_lanes(n), k_hash_to_g2, msgs, off, n, dst, dl, out, ro);
+  return launch(c, s, "hash_to_g2", grid_lanes(n), k_hash_to_g2_x, c->expander, msgs, off, n, dst, dl, out, ro);
+}
+static inline int launch_sign(blsbn254_ctx* c, hipStream_t s, const uint8_t* sks, const uint8_t* msgs, const uint64_t* off, size_t n, uint32_t dl, uint8_t* sigs,
+                              uint8_t* status) {
+  const uint8_t* dst = (const uint8_t*)c->dst.p;
+  if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "sign", grid_lanes(n), k_sign, sks, msgs, off, n, dst, dl, sigs, status);
+  return launch(c, s, "sign", grid_lanes(n), k_sign_x, c->expander, sks, msgs, off, n, dst, dl, sigs, status);
+}
+static inline int launch_hash_to_scalar(blsbn254_ctx* c, hipStream_t s, const uint8_t* msgs, const uint64_t* off, size_t n, uint32_t dl, uint8_t* out) {
+  const uint8_t* dst = (const uint8_t*)c->dst.p;
+  if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "hash_to_scalar", grid_lanes(n), k_hash_to_scalar, msgs, off, n, dst, dl, out);
+  return launch(c, s, "hash_to_scalar", grid_lanes(n), k_hash_to_scalar_x, c->expander, msgs, off, n, dst, dl, out);
 }
 // reserve, then copy host -> device on the main stream (the source must outlive the copy: the caller's, or ctx-owned / static)
 static inline int upload(blsbn254_ctx* c, DevBuf& b, const void* src, size_t bytes) {

@@ -74,8 +74,7 @@ int blsbn254_sign_batch(blsbn254_ctx* c, const uint8_t* sks, const uint8_t* msgs
   if (rc) return rc;
   HIPCHK(c, c->out.reserve(64 * n)); HIPCHK(c, c->status.reserve(n));
   TRY(upload(c, c->in_a, sks, 32 * n));
-  TRY(launch(c, c->stream, "sign", grid_lanes(n), k_sign, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-             (uint8_t*)c->out.p, (uint8_t*)c->status.p));
+  TRY(launch_sign(c, c->stream, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_SCALAR;
@@ -131,8 +130,7 @@ int blsbn254_hash_to_scalar_batch(blsbn254_ctx* c, const uint8_t* msgs, const ui
   rc = stage_msgs(c, msgs, off, n);
   if (rc) return rc;
   HIPCHK(c, c->out.reserve(32 * n));
-  TRY(launch(c, c->stream, "hash_to_scalar", grid_lanes(n), k_hash_to_scalar, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-             (uint8_t*)c->out.p));
+  TRY(launch_hash_to_scalar(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (uint8_t*)c->out.p));
   return download(c, out, c->out.p, 32 * n);
 }
 int blsbn254_pop_prove_batch(blsbn254_ctx* c, const uint8_t* sks, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* proofs_out) {
@@ -146,8 +144,7 @@ int blsbn254_pop_prove_batch(blsbn254_ctx* c, const uint8_t* sks, size_t n, cons
   TRY(upload(c, c->in_a, sks, 32 * n));
   TRY(launch(c, c->stream, "sk_to_pk", grid_lanes(n), k_sk_to_pk, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->in_c.p, (uint8_t*)c->status.p));
   TRY(launch(c, c->stream, "iota_off", grid_lanes(n + 1), k_iota_off, (uint64_t*)c->in_off.p, n, (uint64_t)128));
-  TRY(launch(c, c->stream, "sign", grid_lanes(n), k_sign, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl,
-             (uint8_t*)c->out.p, (uint8_t*)c->status.p));
+  TRY(launch_sign(c, c->stream, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (uint8_t*)c->out.p, (uint8_t*)c->status.p));
   int bad; rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
   if (rc) return rc;
   if (bad >= 0) return BLSBN254_ERR_SCALAR;

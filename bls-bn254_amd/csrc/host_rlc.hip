@@ -114,7 +114,7 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   uint32_t m32 = 0;
   HIPCHK(c, hipMemcpyAsync(&m32, cbase + u, 4, hipMemcpyDeviceToHost, c->stream));
   // the hash points and the weighted points r_i sig_i, r_i H_i (the host learns the chunk count while these run)
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 3));
+  TRY(launch_hash_to_g1(c, c->stream, d_msgs, d_off, n, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 3));
   TRY(launch(c, c->stream, "rlc2_prep", grid_lanes(n), k_rlc2_prep, (const uint32_t*)perm, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, d_seed, (int32_t*)c->r2_a.p, (int32_t*)c->r2_b.p,
              (uint8_t*)c->r2_sigok.p));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -313,7 +313,7 @@ int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* ms
     HIPCHK(c, hipStreamSynchronize(c->stream)); }
   const uint8_t* d_pks = (const uint8_t*)c->in_a.p; const uint8_t* d_sigs = (const uint8_t*)c->in_b.p;
   int32_t* f = (int32_t*)c->f_ws.p;
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n,
+  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, n,
              (uint8_t*)nullptr, 0));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, d_pks, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
   TRY(launch(c, c->stream, "rlc_prep", grid_lanes(n_pad), k_rlc_prep, d_pks, d_sigs, (const int32_t*)c->h_ws.p, (const uint8_t*)c->sub_ok.p, (const uint8_t*)c->misc.p,

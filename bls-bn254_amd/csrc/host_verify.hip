@@ -143,7 +143,7 @@ int verify_prepared_dev(blsbn254_ctx* c, const KeyTables& kt, size_t u, const ui
                         const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap) {
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
   HIPCHK(c, c->kd_hist.reserve(4 * (u + 1))); HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n));
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr,
+  TRY(launch_hash_to_g1(c, c->stream, d_msgs, d_off, n, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr,
              3));   // homogeneous H: no inversion
   if (!deduped) TRY(check_key_indices(c, d_kid, n, u, (uint32_t*)c->kd_hist.p, "tuple", false));
   TRY(key_sorted_order(c, d_kid, n, u));
@@ -191,7 +191,7 @@ int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
   ++c->stat_exact_chunks;
   HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
   HIPCHK(c, c->flags.reserve(n)); HIPCHK(c, c->sub_ok.reserve(n));
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, d_msgs, d_off, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 0));
+  TRY(launch_hash_to_g1(c, c->stream, d_msgs, d_off, n, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 0));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, d_pks, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
   TRY(launch(c, c->stream, "miller_verify", grid_lanes(n), k_miller_verify, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p));
   return run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 0, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p, d_bitmap, nullptr, nullptr);
@@ -478,7 +478,7 @@ int blsbn254_aggregate_verify_prepared(blsbn254_ctx* c, const blsbn254_g2prepare
   static const int init[3] = {NO_INDEX, 1, 1};         // the armed index shares its upload with the two validity words
   HIPCHK(c, hipMemcpyAsync(d_ok, init, 12, hipMemcpyHostToDevice, c->stream));
   TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", true));   // its read-back also waits for the copy of sig_key (on the stack)
-  TRY(launch(c, c->stream, "hash_to_g1", grid_lanes(n), k_hash_to_g1, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, (const uint8_t*)c->dst.p, dl, (int32_t*)c->h_ws.p, np,
+  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, np,
              (uint8_t*)nullptr, 0));
   TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 2)));
   TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,

@@ -25,6 +25,16 @@ BN_KERNEL k_hash_to_g1(const uint8_t* msgs, const uint64_t* off, size_t n, const
                        int32_t* h_ws, size_t h_stride, uint8_t* out_bytes, int mode);
 BN_KERNEL k_hash_to_g2(const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
                        uint8_t* out_bytes, int ro);
+// the four hashing kernels under the expander xid != 0 (k_hash_keccak.hip, keccak.h EXPAND_*): k_hash_to_g1 / k_hash_to_g2 above,
+// k_sign / k_hash_to_scalar below, with xid in front of their arguments.  BN_KERNEL_1: one wave per SIMD whatever the unit's policy
+#define BN_KERNEL_1 __global__ void __launch_bounds__(256, 1)
+BN_KERNEL k_hash_to_g1_x(uint32_t xid, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
+                         int32_t* h_ws, size_t h_stride, uint8_t* out_bytes, int mode);
+BN_KERNEL_1 k_hash_to_g2_x(uint32_t xid, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
+                           uint8_t* out_bytes, int ro);
+BN_KERNEL_1 k_sign_x(uint32_t xid, const uint8_t* sks, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
+                     uint8_t* sigs, uint8_t* status);
+BN_KERNEL k_hash_to_scalar_x(uint32_t xid, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len, uint8_t* out);
 BN_KERNEL k_g1_check(const uint8_t* g1, size_t n, uint8_t* bitmap);
 BN_KERNEL k_g2_check(const uint8_t* g2, size_t n, uint8_t* ok_bytes, uint8_t* bitmap);
 BN_KERNEL k_miller_1(const uint8_t* g1, const uint8_t* g2, size_t n, int32_t* f_ws, size_t f_stride, uint8_t* status);

@@ -10,6 +10,12 @@ disjoint, so SUM == OR and no carry can occur).  1 MiB at n = 8M: latency-bound,
 import numpy as np
 
 
+def rank_engine(engine_cls, device, expander=0):
+    """This rank's engine on its own GPU.  The message expander is a setting of each context, so every rank sets it on its
+    own engine (the constructor's keyword); all ranks of a job pass the same id."""
+    return engine_cls(device, expander=expander)
+
+
 def shard_range(n, rank, world):
     return (n * rank) // world, (n * (rank + 1)) // world
 

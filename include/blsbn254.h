@@ -115,6 +115,28 @@ int blsbn254_hash_to_g2_batch(blsbn254_ctx* ctx, const uint8_t* msgs, const uint
                               const uint8_t* dst, size_t dst_len, uint8_t* out);
 int blsbn254_encode_to_g2_batch(blsbn254_ctx* ctx, const uint8_t* msgs, const uint64_t* off, size_t n,
                                 const uint8_t* dst, size_t dst_len, uint8_t* out);
+/* The message expander: the type parameter X: ExpandMsg of Fp::hash<X> / Fp::encode<X> (fp.rs:433-458), Fp2::hash<X>
+ * (fp2.rs:463-487), G1Projective::hash<X> / encode<X> (g1.rs:910-928), G2Projective::hash<X> / encode<X> (g2.rs:919-936) and
+ * Scalar::hash<X> (scalar.rs:554-563), as a setting of the context.  XMD: RFC 9380 5.3.1 (Keccak-256 and SHA3-256 with
+ * s_in_bytes = 136); XOF: 5.3.2.  Keccak-256 is the hash of the EVM (domain byte 0x01), SHA3-256 the FIPS 202 one (0x06).
+ * EVERY call that hashes a message follows the setting, without an argument of its own: the hash / encode calls above, verify
+ * in all its forms (exact, RLC, compressed, prepared, _dev), aggregate verify with its batch and RLC forms, fast aggregate
+ * verify, the key-set and committee calls, the threshold share checks and the checked combine, sign_batch, pop_prove_batch /
+ * pop_verify_batch, keyset_create_checked and hash_to_scalar_batch.  blsbn254_keygen_batch does not: its HKDF-SHA-256 is fixed
+ * by the BLS draft and is no ExpandMsg.  No result changes under the default.  The rules:
+ *   - an id outside the table returns BLSBN254_E_ARG and changes nothing;
+ *   - the setter settles the context first: pending asynchronous verify calls are resolved (a failed guess re-run) under the
+ *     expander they were made with before the new one is stored;
+ *   - a DST longer than 255 bytes is replaced as RFC 9380 5.3.3 says, with the CONTEXT's hash: H("H2C-OVERSIZE-DST-" || dst),
+ *     32 bytes, for the XMD forms; H(..., 32) for the XOF forms (ceil(2 k / 8) with k = 128).
+ * The multi-GPU handle has no call of its own: blsbn254_set_expander(blsbn254_multi_ctx(m, i), id) for each device i. */
+#define BLSBN254_EXPAND_XMD_SHA256 0    /* ExpandMsgXmd<sha2::Sha256>, the default */
+#define BLSBN254_EXPAND_XMD_KECCAK256 1 /* ExpandMsgXmd<sha3::Keccak256> */
+#define BLSBN254_EXPAND_XMD_SHA3_256 2  /* ExpandMsgXmd<sha3::Sha3_256> */
+#define BLSBN254_EXPAND_XOF_SHAKE128 3  /* ExpandMsgXof<sha3::Shake128> */
+#define BLSBN254_EXPAND_XOF_SHAKE256 4  /* ExpandMsgXof<sha3::Shake256> */
+int blsbn254_set_expander(blsbn254_ctx* ctx, int id);
+int blsbn254_get_expander(const blsbn254_ctx* ctx); /* the id in force; BLSBN254_E_ARG for NULL */
 /* G1Affine::from_uncompressed + is_on_curve (g1.rs:339-360, :383-391); G1 has cofactor 1 */
 int blsbn254_g1_check_batch(blsbn254_ctx* ctx, const uint8_t* g1, size_t n, uint8_t* ok_bitmap);
 /* G2Affine::from_uncompressed + is_on_curve + is_torsion_free (g2.rs:350-414, :733-736) */
