@@ -1,5 +1,9 @@
-// host_aggregate.hip -- aggregate verify (pair by pair, per-key sums, sharded partial / finish), signature aggregation,
-// threshold combine and Lagrange coefficients.  Host side of include/blsbn254.h; see host_common.h.
+// host_aggregate.hip -- the aggregate family: aggregate verify (per-key sums, pair by pair, sharded partial / finish, over prepared
+// keys) and the Miller product over prepared keys; signature aggregation, threshold combine and Lagrange coefficients.  Host side of
+// include/blsbn254.h; see host_common.h.
+// What the calls that run Miller loops off the RAW line tables share is here, each written once: launch_miller_raw (THE size rule
+// of that loop; host_aggregate_rlc.hip's rounds take it too), agg_keys_stage / agg_keys_prepare (the call's keys and -G2gen as
+// tables beside the hashing), product_bytes / product_is_one over fp12_tree, and the verdict words (VW_*) the calls read back.
 #include "host_common.h"
 
 extern "C" {
@@ -16,6 +20,71 @@ int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res,
   *res = a; *rs = sa;
   return 0;
 }
+// the product of the cnt values at f (stride cnt) as 384 bytes: the copy into `out` is enqueued, the caller waits for the stream
+static int product_bytes(blsbn254_ctx* c, int32_t* f, size_t cnt, uint8_t out[384]) {
+  int32_t* res; size_t rs;
+  HIPCHK(c, c->out.reserve(384));
+  TRY(fp12_tree(c, f, cnt, cnt, &res, &rs));
+  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(1), k_fp12_to_bytes, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p));
+  HIPCHK(c, hipMemcpyAsync(out, c->out.p, 384, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+// ... or ONE final exponentiation of it: 1 into *d_is_one where the result is one (enqueued)
+static int product_is_one(blsbn254_ctx* c, int32_t* f, size_t cnt, int* d_is_one) {
+  int32_t* res; size_t rs;
+  TRY(fp12_tree(c, f, cnt, cnt, &res, &rs));
+  return run_final_exp(c, res, 1, rs, 3, nullptr, nullptr, nullptr, nullptr, d_is_one);
+}
+// The verdict words of a call, in c->misc: the first key index out of range (check_key_indices folds it into word 0: the calls over
+// a caller's indices), all keys valid (k_and_reduce), the signature's validity byte (k_g1_to_ws), the is-one word of product_is_one.
+// verdict_arm: {NO_INDEX, 1, 1} in ONE upload from a static source; verdict_read: all of them, synchronised.
+enum { VW_INDEX = 0, VW_KEYS = 1, VW_SIG = 2, VW_IS_ONE = 4, VW_WORDS = 5 };
+static int verdict_arm(blsbn254_ctx* c, int** d) {
+  static const int init[3] = {NO_INDEX, 1, 1};
+  HIPCHK(c, c->misc.reserve(64));
+  *d = (int*)c->misc.p;
+  return upload(c, c->misc, init, sizeof init);
+}
+static int verdict_read(blsbn254_ctx* c, int h[VW_WORDS]) { return download(c, h, c->misc.p, 4 * VW_WORDS); }
+
+// The table-only Miller loop over n pairs off the raw line tables: the rule is host_common.h's, written out here and nowhere else.
+int launch_miller_raw(blsbn254_ctx* c, const int32_t* h, size_t h_stride, const uint32_t* kid, RawTables kt, size_t n, const uint8_t* st, unsigned forms,
+                      size_t* left) {
+  const auto wide = [&](size_t m) { return (forms & MR_WIDE) && c->wide_fe && m <= c->wide_fe_max; };     // a handful of pairs: one WAVE per pair
+  const auto tri = [&](size_t m) { return (forms & MR_TRI) && c->tri_miller && m <= c->tri_max; };        // a few thousand pairs: a quad of lanes per pair
+  // few pairs: the launch is the latency of one wave, so one pair per lane (no shared f^2, shorter chain); else two per lane
+  const bool one = (forms & MR_ONE) && (n * 2 <= c->lanes_per_round || !(forms & MR_TWO) || n > c->chunk);
+  const bool two = !wide(n) && !tri(n) && !one;
+  *left = two ? (n + 1) / 2 : n;
+  HIPCHK(c, c->f_ws.reserve(*left * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
+  int32_t* f = (int32_t*)c->f_ws.p; uint8_t* flags = (uint8_t*)c->flags.p;
+  if (two) return launch(c, c->stream, "miller_hpk2p", grid_lanes(*left), k_miller_hpk2p, h, h_stride, kid, kt.raw, kt.ok, n, f, *left, flags, st);
+  return for_chunks(c, n, [&](size_t lo, size_t m) -> int {
+    const uint8_t* s = st ? st + lo : nullptr;
+    if (wide(m)) return launch(c, c->stream, "miller_wide_1p", grid_wide(m), k_miller_wide_1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
+    if (tri(m)) return launch(c, c->stream, "miller_tri_1p", grid_tri(m), k_miller_tri_1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
+    return launch(c, c->stream, "miller_hpk1p", grid_lanes(m), k_miller_hpk1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
+  });
+}
+int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u) {
+  HIPCHK(c, c->in_a.reserve(128 * (n + 1)));
+  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * n, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));   // "pair n": the key of the signatures' pairs
+  return dedup_keys(c, (const uint8_t*)c->in_a.p, n, u);
+}
+// the `keys` keys of c->in_a that kd_keys names become raw line tables on the second stream, ev_join behind them
+static int raw_tables_fork(blsbn254_ctx* c, size_t keys) {
+  HIPCHK(c, c->prep_ok.reserve(keys)); HIPCHK(c, c->prep_raw.reserve(keys * PREP_RAW_LIMBS * 4));
+  HIPCHK(c, fork_stream2(c));
+  TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, keys, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
+  HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+  return 0;
+}
+int agg_keys_prepare(blsbn254_ctx* c, size_t n, size_t u) {
+  c->last_key = (uint32_t)n;                            // context-owned: nothing waits for this copy (dedup_keys has waited for all before it)
+  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_keys.p + u, &c->last_key, 4, hipMemcpyHostToDevice, c->stream));
+  return raw_tables_fork(c, u + 1);
+}
 // prod_i ML(H(msg_i), pk_i) over the caller's n pairs, optionally times ML(extra_sig, -G2gen): the aggregate signature
 // then simply joins the batch as pair n (one more lane half among the million) instead of a latency-bound one-lane launch.
 // Two pairs per lane sharing one f^2 (k_miller_hpk2), then the pairwise product tree.
@@ -31,39 +100,30 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
   if (np == 0) { std::memset(ml_out, 0, 384); ml_out[31] = 1; return 0; }
   CHECK_LANES(c, np);
   ENTER(c);
-  uint32_t dl = 0; int rc;
+  uint32_t dl = 0;
   if (n) {
-    rc = stage_dst(c, dst, dst_len, &dl);                    // (a no-op when the tag is already resident)
-    if (rc) return rc;
-    if (!staged) {
-      rc = stage_msgs(c, msgs, off, n);
-      if (rc) return rc;
-    }
+    TRY(stage_dst(c, dst, dst_len, &dl));                    // (a no-op when the tag is already resident)
+    if (!staged) TRY(stage_msgs(c, msgs, off, n));
   }
-  const size_t n_lanes = (np + 1) / 2;
-  HIPCHK(c, c->in_a.reserve(128 * np)); HIPCHK(c, c->in_b.reserve(64)); HIPCHK(c, c->h_ws.reserve(np * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4));
-  HIPCHK(c, c->q_ws.reserve(n_lanes * 72 * 4));
-  HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->sub_ok.reserve(np)); HIPCHK(c, c->misc.reserve(64)); HIPCHK(c, c->out.reserve(384));
+  size_t left = (np + 1) / 2;                                // Fp12 values the loop leaves: one per lane
+  HIPCHK(c, c->in_a.reserve(128 * np)); HIPCHK(c, c->in_b.reserve(64)); HIPCHK(c, c->h_ws.reserve(np * 18 * 4)); HIPCHK(c, c->f_ws.reserve(left * 108 * 4));
+  HIPCHK(c, c->q_ws.reserve(left * 72 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->sub_ok.reserve(np)); HIPCHK(c, c->misc.reserve(64)); HIPCHK(c, c->out.reserve(384));
   if (n && !staged) HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
-  int32_t* f = (int32_t*)c->f_ws.p;
-  int* d_ok = (int*)c->misc.p;                               // [0] all keys valid, [1] (byte) signature valid
-  static const int ones[2] = {1, 1};
-  HIPCHK(c, hipMemcpyAsync(d_ok, ones, 8, hipMemcpyHostToDevice, c->stream));
+  int* d_ok;
+  TRY(verdict_arm(c, &d_ok));
   if (extra_sig && !staged) {
     HIPCHK(c, hipMemcpyAsync(c->in_b.p, extra_sig, 64, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * n, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));
   }
   // few distinct keys among the np pairs (the pair (sig, -G2gen) included)?  then prepare each once, beside the hashing
+  // (agg_keys_stage / agg_keys_prepare do not fit: -G2gen is one of the np keys here, not one more, and only where a signature came)
   bool prepared = false;
   if (c->auto_prepare && np >= 1024) {
     size_t u = 0;
-    rc = dedup_keys(c, (const uint8_t*)c->in_a.p, np, &u);
-    if (rc) return rc;
+    TRY(dedup_keys(c, (const uint8_t*)c->in_a.p, np, &u));
     if (u * 2 <= np && u <= PREP_MAX_KEYS) {
-      HIPCHK(c, c->prep_table.reserve(64)); HIPCHK(c, c->prep_ok.reserve(u)); HIPCHK(c, c->prep_raw.reserve(u * PREP_RAW_LIMBS * 4));
-      HIPCHK(c, fork_stream2(c));
-      TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, u, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
-      HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+      HIPCHK(c, c->prep_table.reserve(64));
+      TRY(raw_tables_fork(c, u));
       TRY(dedup_key_ids(c, np, u, false));   // no sorting here: no histogram
       prepared = true;
     }
@@ -74,28 +134,23 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
                np, (uint8_t*)nullptr, 0));
     if (!prepared) TRY(launch(c, c->stream, "g2_check", grid_lanes(n), k_g2_check, (const uint8_t*)c->in_a.p, n, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));
   }
-  if (extra_sig) TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 1)));
+  if (extra_sig) TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + VW_SIG)));
   if (prepared) {
     // few distinct keys: every key (and -G2gen, when the signature's pair is carried) was validated and turned into its line
     // table once, beside hash-to-G1; the pairs read their lines from those tables
     HIPCHK(c, join_stream2(c));
-    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)c->prep_raw.p,
-               (const uint8_t*)c->prep_ok.p, np, f, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)nullptr));
-    if (n) TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok));
+    TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, {(const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p}, np, nullptr,
+                          MR_TWO, &left));
   } else {
-    TRY(launch(c, c->stream, "miller_hpk2", grid_lanes(n_lanes), k_miller_hpk2, (const int32_t*)c->h_ws.p, (const uint8_t*)c->in_a.p, np, (int32_t*)c->q_ws.p, f, n_lanes,
-               (uint8_t*)c->flags.p));
-    if (n) TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p, n, d_ok));
+    TRY(launch(c, c->stream, "miller_hpk2", grid_lanes(left), k_miller_hpk2, (const int32_t*)c->h_ws.p, (const uint8_t*)c->in_a.p, np, (int32_t*)c->q_ws.p,
+               (int32_t*)c->f_ws.p, left, (uint8_t*)c->flags.p));
   }
-  int32_t* res; size_t rs;
-  rc = fp12_tree(c, f, n_lanes, n_lanes, &res, &rs);
-  if (rc) return rc;
-  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(1), k_fp12_to_bytes, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p));
-  int h_ok[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(ml_out, c->out.p, 384, hipMemcpyDeviceToHost, c->stream));
-  TRY(download(c, h_ok, d_ok, 8));
-  *all_pks_ok = h_ok[0];
-  if (sig_ok) *sig_ok = (h_ok[1] & 0xff) == 1;
+  if (n) TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)(prepared ? c->flags.p : c->sub_ok.p), n, d_ok + VW_KEYS));
+  TRY(product_bytes(c, (int32_t*)c->f_ws.p, left, ml_out));
+  int h[VW_WORDS];
+  TRY(verdict_read(c, h));
+  *all_pks_ok = h[VW_KEYS];
+  if (sig_ok) *sig_ok = (h[VW_SIG] & 0xff) == 1;
   return 0;
 }
 int blsbn254_aggregate_partial(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, size_t n,
@@ -129,20 +184,16 @@ int blsbn254_aggregate_finish(blsbn254_ctx* c, const uint8_t* partials, size_t k
     HIPCHK(c, hipMemcpyAsync(c->in_a.p, partials, 384 * k, hipMemcpyHostToDevice, c->stream));
     // partials arrive as bytes: decode into slots 0..k-1 of the stride-m array
     TRY(launch(c, c->stream, "fp12_from_bytes", grid_lanes(k), k_fp12_from_bytes, (const uint8_t*)c->in_a.p, k, f, m, (uint8_t*)c->status.p));
-    int bad; int rc = first_bad(c, (const uint8_t*)c->status.p, k, 1, 1, &bad);
-    if (rc) return rc;
+    int bad;
+    TRY(first_bad(c, (const uint8_t*)c->status.p, k, 1, 1, &bad));
     if (bad >= 0) return BLSBN254_ERR_GT;
   }
   if (with_sig) {
     TRY(launch(c, c->stream, "miller_1", grid_lanes(1), k_miller_1, (const uint8_t*)c->in_b.p, (const uint8_t*)c->in_b.p + 64, (size_t)1, f + k, m, (uint8_t*)c->status.p));
     TRY(launch(c, c->stream, "g1_check", grid_lanes(1), k_g1_check, (const uint8_t*)c->in_b.p, (size_t)1, (uint8_t*)c->bitmap.p));
   }
-  int32_t* res; size_t rs;
-  int rc = fp12_tree(c, f, m, m, &res, &rs);
-  if (rc) return rc;
-  int* d_one = (int*)c->misc.p;
-  rc = run_final_exp(c, res, 1, rs, 3, nullptr, nullptr, nullptr, nullptr, d_one);
-  if (rc) return rc;
+  int* d_one = (int*)c->misc.p + VW_IS_ONE;
+  TRY(product_is_one(c, f, m, d_one));
   int h_one = 0; uint8_t sig_st = 3, sig_on_curve = 1;
   HIPCHK(c, hipMemcpyAsync(&h_one, d_one, 4, hipMemcpyDeviceToHost, c->stream));
   if (with_sig) {
@@ -158,7 +209,7 @@ int blsbn254_aggregate_finish(blsbn254_ctx* c, const uint8_t* partials, size_t k
 //   prod_i e(H_i, pk_(k_i)) = prod_k e( sum_{i: k_i = k} H_i , pk_k )
 // so only one Miller loop per DISTINCT key (plus the signature's pair) runs, after n G1 additions: key de-duplication and
 // key-sorted order as in verify_batch, the sums by levels of chunks of KEY_SUM_GROUP points (key_sums, k_g1_seg_sum), the u + 1 pairs on the
-// prepared two-pairs-per-lane loop, product tree, ONE final exponentiation.  The boolean is aggregate_verify's; the Miller
+// table-only loop in the form that fits them (launch_miller_raw), product tree, ONE final exponentiation.  The boolean is aggregate_verify's; the Miller
 // value is not the product of the n per-pair values (blsbn254_aggregate_partial keeps that bit-exact form for the sharded API).
 // *took = false: keys do not repeat, nothing was done.
 static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t agg_sig[64],
@@ -167,32 +218,20 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   *took = false;
   ENTER(c);
   uint32_t dl = 0;
-  int rc = stage_dst(c, dst, dst_len, &dl);
-  if (rc) return rc;
-  rc = stage_msgs(c, msgs, off, n);
-  if (rc) return rc;
+  TRY(stage_dst(c, dst, dst_len, &dl));
+  TRY(stage_msgs(c, msgs, off, n));
   HIPCHK(c, c->in_a.reserve(128 * (n + 1)));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks, 128 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * n, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));   // "tuple n": the key of the signature's pair
   TRY(upload(c, c->in_b, agg_sig, 64));
   size_t u = 0;
-  rc = dedup_keys(c, (const uint8_t*)c->in_a.p, n, &u);
-  if (rc) return rc;
-  // few pairs: from tables, one wave per pair (or, up to tri_max pairs, a quad of lanes per pair: k_miller_tri_1p), whatever the keys
+  TRY(agg_keys_stage(c, pks, n, &u));
+  // few pairs: from tables, one wave per pair (or, up to tri_max pairs, a quad of lanes per pair), whatever the keys
   const bool small = small_for_prepared(c, n + 1, false);      // n + 1: the signature's pair joins the launch; one final exponentiation in all
   if (!((u * 2 <= n || small) && u + 1 <= PREP_MAX_KEYS)) return 0;
   *took = true;
-  const size_t np = u + 1, n_lanes = (np + 1) / 2;
-  // the u keys and -G2gen (key id u) become line tables on the second stream, beside the hashing
-  const uint32_t last_key = (uint32_t)n;
-  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_keys.p + u, &last_key, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));                                   // last_key and the staged copies are consumed
-  HIPCHK(c, c->prep_ok.reserve(np)); HIPCHK(c, c->prep_raw.reserve(np * PREP_RAW_LIMBS * 4));
-  HIPCHK(c, fork_stream2(c));
-  TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, np, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
-  HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+  const size_t np = u + 1;
+  TRY(agg_keys_prepare(c, n, u));                                               // the u keys and -G2gen (key id u), beside the hashing
   // key ids, key-sorted order
-  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->status.reserve(np + 8)); HIPCHK(c, c->misc.reserve(64));
+  HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve((np + 1) / 2 * 108 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->status.reserve(np + 8)); HIPCHK(c, c->misc.reserve(64));
   HIPCHK(c, c->rlc_b.reserve(np * 18 * 4)); HIPCHK(c, c->rlc_idx.reserve(4 * np));
   TRY(dedup_key_ids(c, n, u, true));
   TRY(key_sorted_order(c, (const uint32_t*)c->kd_kid.p, n, u));                 // cursor[k] is now the END of run k
@@ -201,46 +240,23 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
              (uint8_t*)nullptr, 3));
   // sums per key: the tuples in sorted order (columns perm[s] of h_ws) -> one sum per key (key_sums)
   const int32_t* pts = nullptr; size_t pts_stride = u;
-  rc = key_sums(c, (const int32_t*)c->h_ws.p, nullptr, n, perm, perm, kid, hist, cursor, n, u, &pts, nullptr);
-  if (rc) return rc;
+  TRY(key_sums(c, (const int32_t*)c->h_ws.p, nullptr, n, perm, perm, kid, hist, cursor, n, u, &pts, nullptr));
   // the u + 1 pairs: (sum_k, pk_k) for k < u and (agg_sig, -G2gen) as pair u with key id u
   int32_t* h2 = (int32_t*)c->rlc_b.p; uint8_t* st = (uint8_t*)c->status.p; uint32_t* kid2 = (uint32_t*)c->rlc_idx.p;
-  int* d_ok = (int*)c->misc.p;                                                  // [0] all keys valid, [1] (byte) signature valid, [4] is_one
-  static const int ones[2] = {1, 1};
-  HIPCHK(c, hipMemcpyAsync(d_ok, ones, 8, hipMemcpyHostToDevice, c->stream));
+  int* d_ok;
+  TRY(verdict_arm(c, &d_ok));
   TRY(launch(c, c->stream, "g1p_to_h", grid_lanes(u), k_g1p_to_h_affine, pts, pts_stride, u, h2, np, st));
   HIPCHK(c, hipMemsetAsync(st + u, 1, 1, c->stream));
-  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, h2, u, np, (uint8_t*)(d_ok + 1)));
+  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, h2, u, np, (uint8_t*)(d_ok + VW_SIG)));
   TRY(launch(c, c->stream, "iota", grid_lanes(np), k_iota_u32, kid2, (uint32_t)np));
   HIPCHK(c, join_stream2(c));
-  // few pairs: the launch is the latency of one wave, so one pair per lane (no shared f^2, shorter chain); else two per lane
-  const bool one_per_lane = np * 2 <= c->lanes_per_round;
-  const size_t f_cnt = one_per_lane ? np : n_lanes;
-  HIPCHK(c, c->f_ws.reserve(f_cnt * 108 * 4));
-  if (c->wide_fe && np <= c->wide_fe_max) {           // a handful of keys: one WAVE per pair
-    TRY(launch(c, c->stream, "miller_wide_1p", grid_wide(np), k_miller_wide_1p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p,
-               (const uint8_t*)c->prep_ok.p, np,
-               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st));
-  } else if (c->tri_miller && np <= c->tri_max) {     // a few thousand pairs: a quad of lanes per pair
-    TRY(launch(c, c->stream, "miller_tri_1p", grid_tri(np), k_miller_tri_1p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
-               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st));
-  } else if (one_per_lane) {
-    TRY(launch(c, c->stream, "miller_hpk1p", grid_lanes(np), k_miller_hpk1p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p, np,
-               (int32_t*)c->f_ws.p, np, (uint8_t*)c->flags.p, (const uint8_t*)st));
-  } else {
-    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)h2, np, (const uint32_t*)kid2, (const int32_t*)c->prep_raw.p,
-               (const uint8_t*)c->prep_ok.p, np,
-               (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)st));
-  }
-  TRY(launch(c, c->stream, "and_reduce", grid_lanes(u), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, u, d_ok));
-  int32_t* res; size_t rs;
-  rc = fp12_tree(c, (int32_t*)c->f_ws.p, f_cnt, f_cnt, &res, &rs);
-  if (rc) return rc;
-  rc = run_final_exp(c, res, 1, rs, 3, nullptr, nullptr, nullptr, nullptr, d_ok + 4);
-  if (rc) return rc;
-  int h[5] = {0, 0, 0, 0, 0};
-  TRY(download(c, h, d_ok, 20));
-  *valid = (h[0] == 1 && (h[1] & 0xff) == 1 && h[4] == 1) ? 1 : 0;
+  size_t left;
+  TRY(launch_miller_raw(c, h2, np, kid2, {(const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p}, np, st, MR_ALL, &left));
+  TRY(launch(c, c->stream, "and_reduce", grid_lanes(u), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, u, d_ok + VW_KEYS));
+  TRY(product_is_one(c, (int32_t*)c->f_ws.p, left, d_ok + VW_IS_ONE));
+  int h[VW_WORDS];
+  TRY(verdict_read(c, h));
+  *valid = (h[VW_KEYS] == 1 && (h[VW_SIG] & 0xff) == 1 && h[VW_IS_ONE] == 1) ? 1 : 0;
   ++c->stat_grouped_aggregates;
   return 0;
 }
@@ -251,20 +267,77 @@ int blsbn254_aggregate_verify(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   if (n == 0) return 0;
   if (n + 1 > MAX_LANES) { c->last_error = "more than 2^23 - 1 pairs in one aggregate_verify call"; return BLSBN254_E_ARG; }
   uint8_t ml[384]; int ok = 0, sig_ok = 0, v = 0;
-  int rc;
   bool staged = false;
   if (c->auto_prepare && (n >= 1024 || (c->wide_fe && n + 1 <= c->wide_fe_max))) {   // repeated keys (or few pairs): one pair per distinct key
     bool took = false;
-    rc = aggregate_verify_grouped(c, pks, msgs, off, n, agg_sig, dst, dst_len, valid, &took);
-    if (rc || took) return rc;
+    TRY(aggregate_verify_grouped(c, pks, msgs, off, n, agg_sig, dst, dst_len, valid, &took));
+    if (took) return 0;
     staged = true;
   }
   ++c->stat_pairwise_aggregates;
-  rc = aggregate_partial_impl(c, pks, msgs, off, n, dst, dst_len, agg_sig, ml, &ok, &sig_ok, staged);
-  if (rc) return rc;
-  rc = blsbn254_aggregate_finish(c, ml, 1, nullptr, &v);
-  if (rc) return rc;
+  TRY(aggregate_partial_impl(c, pks, msgs, off, n, dst, dst_len, agg_sig, ml, &ok, &sig_ok, staged));
+  TRY(blsbn254_aggregate_finish(c, ml, 1, nullptr, &v));
   *valid = (ok == 1 && sig_ok == 1 && v == 1) ? 1 : 0;
+  return 0;
+}
+// multi_miller_loop(&[(&G1Affine, &G2Prepared)]) (pairings.rs:808-857) over prepared keys named by index: the Fp12 product of
+// the n Miller values, one wave per pair or two pairs per lane sharing f^2, every line read from the keys' tables.  A pair whose G1 member is
+// the identity contributes 1 (the reference skips such terms); every referenced key must be valid (else InvalidG2Bytes).
+int blsbn254_multi_miller_loop_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* keys, const uint32_t* key_idx, const uint8_t* g1, size_t n,
+                                        uint8_t ml_out[384]) {
+  if (!c || !keys || keys->ctx != c || !ml_out || (n && (!key_idx || !g1))) return BLSBN254_E_ARG;
+  if (n == 0) { std::memset(ml_out, 0, 384); ml_out[31] = 1; return 0; }
+  CHECK_LANES(c, n);
+  ENTER(c);
+  HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 1)));
+  TRY(upload(c, c->in_a, g1, 64 * n));
+  TRY(upload(c, c->kd_kid, key_idx, 4 * n));
+  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", false));
+  int bad;
+  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(n), k_g1_to_ws_batch, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p));
+  TRY(first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad));
+  if (bad >= 0) return BLSBN254_ERR_G1;
+  size_t left;                                               // few pairs: one wave per pair, product of n values instead of n / 2
+  TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, {(const int32_t*)keys->raw.p, (const uint8_t*)keys->ok.p}, n,
+                        (const uint8_t*)c->status.p, MR_WIDE | MR_TWO, &left));
+  TRY(first_bad(c, (const uint8_t*)c->flags.p, n, 1, 1, &bad));
+  if (bad >= 0) return BLSBN254_ERR_G2;
+  TRY(product_bytes(c, (int32_t*)c->f_ws.p, left, ml_out));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+// CoreAggregateVerify with the public keys given as prepared keys by index: prod_i e(H(msg_i), pk_[key_idx_i]) * e(agg_sig, -G2gen) == 1.
+// The signature's pair uses the table's own -G2gen entry; two pairs per lane, every line from the tables, ONE final exponentiation.
+int blsbn254_aggregate_verify_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* keys, const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* off,
+                                       size_t n, const uint8_t agg_sig[64], const uint8_t* dst, size_t dst_len, int* valid) {
+  if (!c || !keys || keys->ctx != c || !valid || !agg_sig || !off || (n && !key_idx) || (dst_len && !dst)) return BLSBN254_E_ARG;
+  *valid = 0;
+  if (n == 0) return 0;
+  const size_t np = n + 1;
+  CHECK_LANES(c, np);
+  ENTER(c);
+  uint32_t dl;
+  TRY(stage_dst(c, dst, dst_len, &dl));
+  TRY(stage_msgs(c, msgs, off, n));
+  HIPCHK(c, c->in_b.reserve(64)); HIPCHK(c, c->kd_kid.reserve(4 * np)); HIPCHK(c, c->h_ws.reserve(np * 18 * 4)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 2)));
+  const uint32_t sig_key = (uint32_t)keys->u;
+  HIPCHK(c, hipMemcpyAsync(c->kd_kid.p, key_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_kid.p + n, &sig_key, 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sig, 64, hipMemcpyHostToDevice, c->stream));
+  int* d_ok;
+  TRY(verdict_arm(c, &d_ok));                           // the armed index shares its upload with the two validity words
+  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", true));   // its read-back also waits for the copy of sig_key (on the stack)
+  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, np,
+             (uint8_t*)nullptr, 0));
+  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + VW_SIG)));
+  size_t left;
+  TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, {(const int32_t*)keys->raw.p, (const uint8_t*)keys->ok.p}, np, nullptr,
+                        MR_TWO, &left));
+  TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok + VW_KEYS));
+  TRY(product_is_one(c, (int32_t*)c->f_ws.p, left, d_ok + VW_IS_ONE));
+  int h[VW_WORDS];
+  TRY(verdict_read(c, h));
+  *valid = (h[VW_KEYS] == 1 && (h[VW_SIG] & 0xff) == 1 && h[VW_IS_ONE] == 1) ? 1 : 0;
   return 0;
 }
 // n G1 points (limb-major projective, stride n) in c->h_ws -> their sum as 64 bytes

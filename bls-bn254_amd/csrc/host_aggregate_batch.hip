@@ -14,20 +14,27 @@
 
 extern "C" {
 
-int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
-                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+int agg_batch_args(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, const uint8_t* agg_sigs,
+                   size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* valid_bitmap, const char* call) {
   if (!c) return BLSBN254_E_ARG;
-  if (n_groups == 0) return 0;
+  if (n_groups == 0) return CK_NOTHING;
   if (!grp_off || !agg_sigs || !valid_bitmap || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (check_offsets(grp_off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
   const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
   if (N && (!pks || !off)) return BLSBN254_E_ARG;
   if (N > MAX_LANES || G > MAX_LANES || N + G > MAX_LANES) {
-    c->last_error = "more than 2^23 pairs (the signatures' pairs counted) in one aggregate_verify_batch call";
+    c->last_error = std::string("more than 2^23 pairs (the signatures' pairs counted) in one ") + call + " call";
     return BLSBN254_E_ARG;
   }
   if (N && check_offsets(off + base, N)) { c->last_error = "message offsets decrease"; return BLSBN254_E_ARG; }
   if (N && !msgs && off[base + N] != off[base]) return BLSBN254_E_ARG;
+  return 0;
+}
+int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+  const int args = agg_batch_args(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, "aggregate_verify_batch");
+  if (args) return args == CK_NOTHING ? 0 : args;
+  const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
   ENTER(c);                                             // settles pending asynchronous verify calls BEFORE the tag is staged
   if (N == 0) {                                         // every group is empty: invalid, as the single call's n == 0 (nothing to launch)
     std::memset(valid_bitmap, 0, (G + 7) / 8);

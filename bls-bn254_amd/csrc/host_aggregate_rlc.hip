@@ -3,12 +3,12 @@
 // repeat.  Host side of include/blsbn254.h; kernels in k_aggregate_rlc.hip, lane functions in aggregate_rlc.h, the plan in
 // aggregate_rlc_plan.h; see host_common.h and DESIGN.md 6s.
 //
-// A call: the keys de-duplicated (dedup_keys: u distinct keys; keys that do not repeat: the exact call, nothing else), their raw
-// line tables and -G2gen's (table u) on the second stream beside the hashing (launch_g2_prepare), the hash points homogeneous
+// A call: the keys de-duplicated (agg_keys_stage: u distinct keys; keys that do not repeat: the exact call, nothing else), their raw
+// line tables and -G2gen's (table u) on the second stream beside the hashing (agg_keys_prepare), the hash points homogeneous
 // (k_hash_to_g1 mode 3), then k_agr_group and k_agr_weigh leave r_g sig_g and r_g H_gi in ONE workspace that stays on the device
 // for both rounds.  A round over S segments (agr_round; S = 1: the whole call) gives every item the virtual key id
 // segment * u + key id (a signature: S u + segment), sums the items per virtual key (key_sorted_order, key_sums), and pairs the
-// S (u + 1) sums with their keys' tables in the form that fits the launch (the choice of aggregate_verify_grouped); the segments'
+// S (u + 1) sums with their keys' tables in the form that fits the launch (launch_miller_raw, host_aggregate.hip); the segments'
 // products (fp12_tree; k_fp12_seg_prod by levels and the signatures' values multiplied in) finish in ONE run_final_exp.  Whatever
 // the rounds do not decide goes to blsbn254_aggregate_verify_batch on contiguous group ranges: a pointer offset, not a repack.
 #include "host_common.h"
@@ -34,24 +34,12 @@ static int agr_round(blsbn254_ctx* c, size_t N, size_t G, size_t u, size_t S, si
   TRY(key_sums(c, (const int32_t*)w.w.p, nullptr, W, perm, perm, vkid, hist, cursor, items, V, &pts, nullptr));
   // the V pairs (sum, its key's table); a sum that is the identity contributes 1 (status bit 1: the loops' skip)
   HIPCHK(c, w.h2.reserve(V * 18 * 4)); HIPCHK(c, w.st.reserve(V)); HIPCHK(c, w.isone.reserve(S));
-  HIPCHK(c, c->f_ws.reserve(V * 108 * 4)); HIPCHK(c, c->flags.reserve(V));
-  const int32_t* h2 = (const int32_t*)w.h2.p; const uint8_t* st = (const uint8_t*)w.st.p; const uint32_t* mkid = (const uint32_t*)w.mkid.p;
-  const int32_t* raw = (const int32_t*)c->prep_raw.p; const uint8_t* key_ok = (const uint8_t*)c->prep_ok.p;
-  int32_t* f = (int32_t*)c->f_ws.p; uint8_t* flags = (uint8_t*)c->flags.p;
   TRY(launch(c, c->stream, "g1p_to_h", grid_lanes(V), k_g1p_to_h_affine, pts, V, V, (int32_t*)w.h2.p, V, (uint8_t*)w.st.p));
-  size_t f_cnt = V;
-  if (S == 1 && V * 2 > c->lanes_per_round && V <= c->chunk && !(c->wide_fe && V <= c->wide_fe_max) && !(c->tri_miller && V <= c->tri_max)) {   // many keys: two pairs per lane share f^2
-    f_cnt = (V + 1) / 2;
-    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(f_cnt), k_miller_hpk2p, h2, V, mkid, raw, key_ok, V, f, f_cnt, flags, st));
-  } else {
-    TRY(for_chunks(c, V, [&](size_t lo, size_t m) -> int {
-      if (c->wide_fe && m <= c->wide_fe_max)             // a handful of pairs: one WAVE per pair
-        return launch(c, c->stream, "miller_wide_1p", grid_wide(m), k_miller_wide_1p, h2 + lo, V, mkid + lo, raw, key_ok, m, f + lo, V, flags + lo, st + lo);
-      if (c->tri_miller && m <= c->tri_max)              // a few thousand pairs: a quad of lanes per pair
-        return launch(c, c->stream, "miller_tri_1p", grid_tri(m), k_miller_tri_1p, h2 + lo, V, mkid + lo, raw, key_ok, m, f + lo, V, flags + lo, st + lo);
-      return launch(c, c->stream, "miller_hpk1p", grid_lanes(m), k_miller_hpk1p, h2 + lo, V, mkid + lo, raw, key_ok, m, f + lo, V, flags + lo, st + lo);
-    }));
-  }
+  // S > 1: never two slots per lane, because a lane's value must belong to ONE segment slot
+  size_t f_cnt;
+  TRY(launch_miller_raw(c, (const int32_t*)w.h2.p, V, (const uint32_t*)w.mkid.p, {(const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p}, V, (const uint8_t*)w.st.p,
+                        S == 1 ? MR_ALL : MR_ALL & ~MR_TWO, &f_cnt));
+  int32_t* f = (int32_t*)c->f_ws.p;
   // (the loops' flags are not read: a key that is not valid belongs to ineligible groups only, so its sums are the identity)
   int32_t* prod; size_t ps;
   if (S == 1) {
@@ -93,18 +81,9 @@ static int agr_bits(blsbn254_ctx* c, size_t G, const uint32_t* d_seg_of, uint8_t
 int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
                                         const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t seed[32],
                                         uint8_t* valid_bitmap) {
-  if (!c) return BLSBN254_E_ARG;
-  if (n_groups == 0) return 0;
-  if (!grp_off || !agg_sigs || !valid_bitmap || (dst_len && !dst)) return BLSBN254_E_ARG;
-  if (check_offsets(grp_off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
+  const int args = agg_batch_args(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, "aggregate_verify_batch_rlc");
+  if (args) return args == CK_NOTHING ? 0 : args;
   const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
-  if (N && (!pks || !off)) return BLSBN254_E_ARG;
-  if (N > MAX_LANES || G > MAX_LANES || N + G > MAX_LANES) {
-    c->last_error = "more than 2^23 pairs (the signatures' pairs counted) in one aggregate_verify_batch_rlc call";
-    return BLSBN254_E_ARG;
-  }
-  if (N && check_offsets(off + base, N)) { c->last_error = "message offsets decrease"; return BLSBN254_E_ARG; }
-  if (N && !msgs && off[base + N] != off[base]) return BLSBN254_E_ARG;
   Stream2Guard s2_guard(c);
   ENTER(c);                                             // settles pending asynchronous verify calls BEFORE the tag is staged
   const size_t nb = (G + 7) / 8;
@@ -117,29 +96,16 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off + base, N));
   AgrWs& w = c->agr;
-  // the keys with -G2gen as "pair N" (the key of the signatures' slots), de-duplicated
-  HIPCHK(c, c->in_a.reserve(128 * (N + 1)));
-  HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks + 128 * base, 128 * N, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * N, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));
   size_t u = 0;
-  TRY(dedup_keys(c, (const uint8_t*)c->in_a.p, N, &u));
+  TRY(agg_keys_stage(c, pks + 128 * base, N, &u));     // the keys with -G2gen as "pair N" (the key of the signatures' slots), de-duplicated
   if (!agr_keys_repeat(N, u, PREP_MAX_KEYS)) {          // nothing to share per key: the call is the exact call
     TRY(blsbn254_aggregate_verify_batch(c, pks, msgs, off, grp_off, agg_sigs, G, dst, dst_len, valid_bitmap));
     ++c->stat_agr[0]; ++c->stat_agr[6]; c->stat_agr[3] += G;
     return 0;
   }
-  if (seed) std::memcpy(w.h_seed, seed, 32);
-  else TRY(draw_seed(c, w.h_seed));                     // drawn now: after the batch is fixed
-  TRY(upload(c, w.seed, w.h_seed, 32));
+  TRY(stage_seed(c, w.seed, seed));
   TRY(upload(c, c->in_b, agg_sigs, 64 * G));
-  // the u keys and -G2gen (key id u) become line tables on the second stream, beside the hashing
-  const uint32_t last_key = (uint32_t)N;
-  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_keys.p + u, &last_key, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));           // last_key is on the stack
-  HIPCHK(c, c->prep_ok.reserve(u + 1)); HIPCHK(c, c->prep_raw.reserve((u + 1) * PREP_RAW_LIMBS * 4));
-  HIPCHK(c, fork_stream2(c));
-  TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, u + 1, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
-  HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+  TRY(agg_keys_prepare(c, N, u));                      // the u keys and -G2gen (key id u): line tables beside the hashing
   // the plan: the segments of a second round are known before the first, so the workspace is reserved once
   size_t S2 = agr_segments(c->agr_segments, AGR_SMAX, N, u, G);
   if (S2 * (u + 1) > MAX_LANES) S2 = 1;                 // the slots of a round are one launch's stride
@@ -189,7 +155,7 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
       w.h_bits.assign((m + 7) / 8, 0);
       TRY(blsbn254_aggregate_verify_batch(c, pks, msgs, off, grp_off + a, agg_sigs + 64 * a, m, dst, dst_len, w.h_bits.data()));
       for (size_t j = 0; j < m; ++j)
-        if (w.h_elig[a + j] && bit_at(w.h_bits.data(), j)) valid_bitmap[(a + j) >> 3] |= (uint8_t)(1u << ((a + j) & 7));
+        if (w.h_elig[a + j] && bit_at(w.h_bits.data(), j)) set_bit(valid_bitmap, a + j);
     }
   }
   ++c->stat_agr[0]; c->stat_agr[1] += pass1 ? n_elig : 0; c->stat_agr[2] += by_round2; c->stat_agr[3] += n_exact;

@@ -1,5 +1,7 @@
 // host_common.h -- shared by the host-side translation units (host*.hip): the context, device buffers, the launch helper and the
-// internal helpers one pipeline borrows from another.  Nothing here is exported (BNH = hidden visibility); the C ABI is
+// internal helpers one pipeline borrows from another (the size rules of the two table-only Miller loops among them:
+// launch_miller_prepared, host_verify.hip, over the expanded pair tables; launch_miller_raw, host_aggregate.hip, over the raw line
+// tables).  Nothing here is exported (BNH = hidden visibility); the C ABI is
 // include/blsbn254.h.  There is no CPU fallback anywhere on the host side: every entry point launches kernels or fails.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -184,7 +186,6 @@ struct BNH KsrWs {
          moff, bits;
   SegWs seg;
   KsrPlan plan;
-  uint8_t h_seed[32];
   std::vector<uint8_t> h_elig, h_state, h_bits, h_msgs;
   std::vector<uint32_t> h_cstart, h_clen, h_list;
   std::vector<uint64_t> h_moff, h_rowoff;
@@ -199,7 +200,6 @@ struct BNH AgrWs {
   DevBuf seed, gidx, seg_of, sig_ok, elig, wt, w, vkid, mkid, h2, st, prod, isone, valid;
   GroupOff goff;
   SegWs seg;
-  uint8_t h_seed[32];
   std::vector<uint32_t> h_gidx, h_bound, h_seg_of;
   std::vector<uint8_t> h_elig, h_pass, h_bits;
   std::vector<std::pair<size_t, size_t>> ranges;
@@ -242,6 +242,8 @@ struct blsbn254_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool s2_pending = false;           // work was forked onto stream2 and the main stream has not waited for ev_join yet
   uint32_t kd_seed = 0;              // per-context random seed of the key hash table
+  uint32_t last_key = 0;             // the id of -G2gen among a call's keys, as agg_keys_prepare uploads it
+  uint8_t h_seed[32];                // the seed of the RLC call in flight, as stage_seed uploads it
   bool auto_prepare = true;          // verify_batch: de-duplicate the public keys and prepare each distinct key once (BLSBN254_AUTO_PREPARE=0 disables)
   uint64_t stat_prepared_chunks = 0, stat_exact_chunks = 0, stat_grouped_aggregates = 0, stat_pairwise_aggregates = 0;
   DevBuf q_ws;           // decoded public keys of the two-pairs-per-lane Miller kernel, 72 x lanes limbs
@@ -517,6 +519,27 @@ BNH int verify_prepared_dev(blsbn254_ctx* c, const KeyTables& kt, size_t u, cons
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
 BNH int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u, uint32_t* hist, const char* what, bool armed);   // host_verify.hip
 BNH int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, const KeyTables& kt, size_t n);   // host_verify.hip
+// Its twin over the RAW line tables (prep_raw / a G2Prepared's raw: the aggregate family): pair i = (H point i of the workspace h
+// at stride h_stride, table kid[i] of kt), st: the optional status bytes of the H points (bit 1: the identity, contributes 1).
+// Reserves and fills c->f_ws / c->flags; *left Fp12 values at stride *left remain: n, or (n + 1) / 2 from two pairs per lane.
+// THE rule, over the forms the site admits (MR_*): one wave per pair if wide_fe and n <= wide_fe_max; else a quad of lanes per
+// pair if tri_miller and n <= tri_max; else one pair per lane if 2 n <= lanes_per_round (the launch is the latency of one wave:
+// no shared f^2, the shorter chain), or two per lane is not admitted, or n > ctx->chunk; else two pairs per lane sharing f^2.
+// n > ctx->chunk: the per-pair forms run chunk by chunk at stride n, each chunk in the form that fits it.
+struct RawTables { const int32_t* raw; const uint8_t* ok; };
+enum : unsigned { MR_WIDE = 1, MR_TRI = 2, MR_ONE = 4, MR_TWO = 8, MR_ALL = 15 };
+BNH int launch_miller_raw(blsbn254_ctx* c, const int32_t* h, size_t h_stride, const uint32_t* kid, RawTables kt, size_t n, const uint8_t* st, unsigned forms,
+                          size_t* left);   // host_aggregate.hip
+// The key tables of an aggregate call, in two steps because the callers decide between them whether to go on at all.
+// agg_keys_stage: the caller's n keys into c->in_a with -G2gen as entry n, de-duplicated (dedup_keys: *u distinct among the n;
+// synchronises).  agg_keys_prepare: -G2gen appended as key u, the raw tables of the u + 1 keys enqueued on the second stream beside
+// whatever the caller enqueues next, ev_join recorded (raw_tables_fork: the same for the `keys` keys kd_keys names as it stands).
+BNH int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u);   // host_aggregate.hip
+BNH int agg_keys_prepare(blsbn254_ctx* c, size_t n, size_t u);   // host_aggregate.hip
+// what blsbn254_aggregate_verify_batch and ..._batch_rlc check alike (`call` names the one in the error text); CK_NOTHING: no
+// groups, the caller returns 0
+BNH int agg_batch_args(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, const uint8_t* agg_sigs,
+                       size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* valid_bitmap, const char* call);   // host_aggregate_batch.hip
 BNH int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out);   // host_verify.hip
 BNH int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
@@ -564,7 +587,9 @@ BNH int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t
 BNH void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches);   // host_keyset.hip
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
-BNH int draw_seed(blsbn254_ctx* c, uint8_t out[32]);   // host_rlc.hip
+// THE seed stage of the RLC pipelines: the caller's seed, or 32 bytes drawn from the OS now -- after the batch is fixed -- into
+// c->h_seed (context-owned: it outlives the copy) and from there into d.  Enqueued.
+BNH int stage_seed(blsbn254_ctx* c, DevBuf& d, const uint8_t* seed);   // host_rlc.hip
 BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const KeyTables& kt, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone);   // host_rlc.hip
 // The segmented reductions' device side.  seg_stage: w's ping-pong buffers for levels of at most items_max items of `limbs` limbs
 // (with `flags`, a byte per item too) and the upload of the descriptors planned into w.h_start / w.h_len.
@@ -601,6 +626,7 @@ BNH int td_verify_shares_enqueue(blsbn254_ctx* c, const uint8_t* commitments, co
 // (wire: 32 bytes per signature in and per sum out); CkOut: the caller's outputs (used: merge forms, else NULL).
 static const size_t CK_SUM_GROUP = 16;      // signatures per lane and level of the group sums
 static inline bool bit_at(const uint8_t* bm, size_t i) { return (bm[i >> 3] >> (i & 7)) & 1; }
+static inline void set_bit(uint8_t* bm, size_t i) { bm[i >> 3] |= (uint8_t)(1u << (i & 7)); }
 struct CkArgs {
   const uint8_t* sigs; const uint64_t* ent_off; const uint8_t* msgs; const uint64_t* msg_off;
   size_t n_groups;

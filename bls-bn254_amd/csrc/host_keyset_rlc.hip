@@ -37,14 +37,10 @@ static void ksr_push_msg(KsrWs& w, const uint8_t* msgs, const uint64_t* off, siz
   if (off[g + 1] > off[g]) w.h_msgs.insert(w.h_msgs.end(), msgs + off[g], msgs + off[g + 1]);
   w.h_moff.push_back(w.h_msgs.size());
 }
-static bool ksr_bit(const std::vector<uint8_t>& bits, size_t j) { return (bits[j >> 3] >> (j & 7)) & 1; }
 
 // the signatures into c->in_b and the seed (the caller's, or 32 bytes drawn now: after the batch is fixed) into c->ksr.seed
 static int ksr_stage(blsbn254_ctx* c, const uint8_t* sigs, const uint8_t* seed, size_t n) {
-  KsrWs& w = c->ksr;
-  if (seed) std::memcpy(w.h_seed, seed, 32);
-  else TRY(draw_seed(c, w.h_seed));
-  TRY(upload(c, w.seed, w.h_seed, 32));
+  TRY(stage_seed(c, c->ksr.seed, seed));
   return upload(c, c->in_b, sigs, 64 * n);
 }
 
@@ -120,7 +116,7 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
     if (checked) {
       w.h_msgs.push_back(0);
       TRY(ksr_subcall(c, (const int32_t*)w.sb.p, M, nullptr, (const uint8_t*)w.sa_bytes.p, 0, dl));
-      for (size_t j = 0; j < checked; ++j) w.h_state[w.h_list[j]] = ksr_bit(w.h_bits, j) ? PASSED : FAILED;
+      for (size_t j = 0; j < checked; ++j) w.h_state[w.h_list[j]] = bit_at(w.h_bits.data(), j) ? PASSED : FAILED;
     }
   }
   // every group's fate, in the caller's order
@@ -130,7 +126,7 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
   for (size_t g = 0; g < n; ++g) {
     const uint8_t st = w.h_state[P.chunk_of[g]];
     const bool e = w.h_elig[g] != 0;
-    if (st == PASSED && e) { bm[g >> 3] |= (uint8_t)(1u << (g & 7)); ++decided; continue; }
+    if (st == PASSED && e) { set_bit(bm, g); ++decided; continue; }
     if (st == FAILED && e) ++failed; else ++direct;
     w.h_list.push_back((uint32_t)g); ksr_push_msg(w, msgs, off, g);
   }
@@ -139,7 +135,7 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
     w.h_msgs.push_back(0);
     TRY(ksr_subcall(c, (const int32_t*)c->gs_sum.p, n, (const uint8_t*)c->gs_sum_ok.p, d_sigs, 1, dl));
     for (size_t j = 0; j < w.h_list.size(); ++j)
-      if (ksr_bit(w.h_bits, j)) { const size_t g = w.h_list[j]; bm[g >> 3] |= (uint8_t)(1u << (g & 7)); }
+      if (bit_at(w.h_bits.data(), j)) set_bit(bm, w.h_list[j]);
   } else HIPCHK(c, hipStreamSynchronize(c->stream));
   c->stat_ksr[0] += decided; c->stat_ksr[1] += checked; c->stat_ksr[2] += failed; c->stat_ksr[3] += direct; c->stat_ksr[4] += P.rep.size(); ++c->stat_ksr[5];
   return 0;

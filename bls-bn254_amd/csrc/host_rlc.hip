@@ -50,14 +50,14 @@ int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pt
 }
 
 // ---------------- random-linear-combination batch verification over repeated keys (k_rlc2.hip)
-int draw_seed(blsbn254_ctx* c, uint8_t out[32]) {
-  size_t got = 0;
-  while (got < 32) {
-    ssize_t k = getrandom(out + got, 32 - got, 0);
+int stage_seed(blsbn254_ctx* c, DevBuf& d, const uint8_t* seed) {
+  if (seed) std::memcpy(c->h_seed, seed, 32);
+  for (size_t got = 0; !seed && got < 32; ) {          // the normal case: 32 bytes from the OS, drawn now -- after the batch is fixed
+    ssize_t k = getrandom(c->h_seed + got, 32 - got, 0);
     if (k <= 0) { c->last_error = "getrandom failed"; return BLSBN254_E_HIP; }
     got += (size_t)k;
   }
-  return 0;
+  return upload(c, d, c->h_seed, 32);
 }
 // One table-only Miller loop + final exponentiation over `cnt` (virtual or real) tuples: is_one bytes to d_isone, flags in ctx->flags.
 // kid[perm[s]] names the key's entry in kt's tables: what miller_ids / key_miller_ids make of the batch key ids.
@@ -219,26 +219,14 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   }
   return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->r2_valid.p, n, d_bitmap);
 }
-static int stage_seed(blsbn254_ctx* c, const uint8_t* seed) {
-  uint8_t own[32];
-  if (!seed) {                                        // the normal case: 32 bytes from the OS, drawn now -- after the batch is fixed
-    int rc = draw_seed(c, own);
-    if (rc) return rc;
-    seed = own;
-  }
-  TRY(upload(c, c->r2_seed, seed, 32));
-  HIPCHK(c, hipStreamSynchronize(c->stream));         // `own` is on the stack
-  return 0;
-}
 int blsbn254_verify_batch_rlc_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n,
                                   const uint8_t* dst, size_t dst_len, const uint8_t seed[32], uint8_t* d_bitmap) {
   if (!c || (n && (!d_pks || !d_off || !d_sigs || !d_bitmap)) || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
-  uint32_t dl; int rc = stage_dst(c, dst, dst_len, &dl);
-  if (rc) return rc;
-  rc = stage_seed(c, seed);
-  if (rc) return rc;
+  uint32_t dl;
+  TRY(stage_dst(c, dst, dst_len, &dl));
+  TRY(stage_seed(c, c->r2_seed, seed));
   return for_chunks(c, n, [&](size_t lo, size_t m) -> int {
     bool took = false;
     TRY(rlc2_chunk_dev(c, d_pks + 128 * lo, d_msgs, d_off + lo, d_sigs + 64 * lo, m, dl, (const uint8_t*)c->r2_seed.p, d_bitmap + lo / 8, &took));
@@ -272,32 +260,26 @@ int blsbn254_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
 }
 int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, size_t n, const uint8_t* dst,
                           size_t dst_len, const uint8_t* seed, uint8_t* bm, bool compressed) {
-  uint32_t dl; int rc = stage_dst(c, dst, dst_len, &dl);
-  if (rc) return rc;
-  rc = stage_msgs(c, msgs, off, n);
-  if (rc) return rc;
+  uint32_t dl;
+  TRY(stage_dst(c, dst, dst_len, &dl));
+  TRY(stage_msgs(c, msgs, off, n));
   const size_t nb = (n + 7) / 8;
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   TRY(stage_g2(c, pks, n, compressed));
   TRY(stage_g1(c, sigs, n, compressed));
-  rc = stage_seed(c, seed);
-  if (rc) return rc;
   // Repeated keys: per-key chunks as virtual tuples on the prepared-key path (k_rlc2.hip).  Batches beyond one launch chunk
   // go chunk by chunk through the device entry point (which takes the exact path for a chunk of distinct keys).
   bool took = false;
   if (n <= c->chunk) {
-    rc = rlc2_chunk_dev(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n, dl,
-                        (const uint8_t*)c->r2_seed.p, (uint8_t*)c->bitmap.p, &took);
-    if (rc) return rc;
-  } else {
-    rc = blsbn254_verify_batch_rlc_dev(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n,
-                                       dst, dst_len, seed, (uint8_t*)c->bitmap.p);
-    if (rc) return rc;
+    TRY(stage_seed(c, c->r2_seed, seed));
+    TRY(rlc2_chunk_dev(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n, dl,
+                       (const uint8_t*)c->r2_seed.p, (uint8_t*)c->bitmap.p, &took));
+  } else {                                                               // (the device entry point stages the seed itself)
+    TRY(blsbn254_verify_batch_rlc_dev(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n,
+                                      dst, dst_len, seed, (uint8_t*)c->bitmap.p));
     took = true;
   }
-  if (took) {
-    return download(c, bm, c->bitmap.p, nb);
-  }
+  if (took) return download(c, bm, c->bitmap.p, nb);
   // Distinct keys: groups of RLC_GROUP tuples in the caller's order share the signature-side Miller loop and the final exponentiation.
   c->stat_rlc[3] += n;
   const size_t G = RLC_GROUP, n_pad = (n + G - 1) / G * G, ng = n_pad / G;
@@ -334,8 +316,7 @@ int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* ms
   TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)ga, st, ng, (uint8_t*)c->rlc_bytes.p));
   TRY(launch(c, c->stream, "miller_1", grid_lanes(ng), k_miller_1, (const uint8_t*)c->rlc_bytes.p, (const uint8_t*)c->rlc_neg.p, ng, (int32_t*)c->rlc_f2.p, ng, (uint8_t*)c->status.p));
   TRY(launch(c, c->stream, "fp12_mul_elem", grid_lanes(ng), k_fp12_mul_elem, pa, st, (const int32_t*)c->rlc_f2.p, ng, ng));
-  rc = run_final_exp(c, pa, ng, st, 4, nullptr, nullptr, nullptr, (uint8_t*)c->rlc_ok.p, nullptr);
-  if (rc) return rc;
+  TRY(run_final_exp(c, pa, ng, st, 4, nullptr, nullptr, nullptr, (uint8_t*)c->rlc_ok.p, nullptr));
   std::vector<uint8_t> h_ok(ng), h_elig(n_pad);
   HIPCHK(c, hipMemcpyAsync(h_ok.data(), c->rlc_ok.p, ng, hipMemcpyDeviceToHost, c->stream));
   TRY(download(c, h_elig.data(), c->rlc_elig.p, n_pad));
@@ -344,7 +325,7 @@ int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* ms
   for (size_t g = 0; g < ng; ++g) {
     for (size_t i = g * G; i < (g + 1) * G && i < n; ++i) {
       if (!h_elig[i]) continue;                                        // failed a precheck: invalid, not part of any product
-      if (h_ok[g]) bm[i >> 3] |= (uint8_t)(1u << (i & 7));
+      if (h_ok[g]) set_bit(bm, i);
       else idx.push_back((uint32_t)i);
     }
   }
@@ -358,11 +339,10 @@ int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* ms
                (uint8_t*)c->rlc_cpk.p, (uint8_t*)c->rlc_csig.p, (int32_t*)c->rlc_ch.p, (uint8_t*)c->rlc_csub.p));
     TRY(launch(c, c->stream, "miller_verify", grid_lanes(m), k_miller_verify, (const uint8_t*)c->rlc_cpk.p, (const uint8_t*)c->rlc_csig.p, (const int32_t*)c->rlc_ch.p, m,
                (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p));
-    rc = run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 0, (const uint8_t*)c->flags.p, (const uint8_t*)c->rlc_csub.p, (uint8_t*)c->rlc_cbm.p, nullptr, nullptr);
-    if (rc) return rc;
+    TRY(run_final_exp(c, (int32_t*)c->f_ws.p, m, m, 0, (const uint8_t*)c->flags.p, (const uint8_t*)c->rlc_csub.p, (uint8_t*)c->rlc_cbm.p, nullptr, nullptr));
     std::vector<uint8_t> cb(mb);
     TRY(download(c, cb.data(), c->rlc_cbm.p, mb));
-    for (size_t j = 0; j < m; ++j) if (cb[j >> 3] & (1u << (j & 7))) { size_t i = idx[j]; bm[i >> 3] |= (uint8_t)(1u << (i & 7)); }
+    for (size_t j = 0; j < m; ++j) if (bit_at(cb.data(), j)) set_bit(bm, idx[j]);
   }
   return 0;
 }

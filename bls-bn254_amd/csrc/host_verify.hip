@@ -415,86 +415,7 @@ int blsbn254_verify_batch_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* k
   }));
   return download(c, bm, c->bitmap.p, nb);
 }
-// multi_miller_loop(&[(&G1Affine, &G2Prepared)]) (pairings.rs:808-857) over prepared keys named by index: the Fp12 product of
-// the n Miller values, two pairs per lane sharing f^2, every line read from the keys' tables.  A pair whose G1 member is
-// the identity contributes 1 (the reference skips such terms); every referenced key must be valid (else InvalidG2Bytes).
-int blsbn254_multi_miller_loop_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* keys, const uint32_t* key_idx, const uint8_t* g1, size_t n,
-                                        uint8_t ml_out[384]) {
-  if (!c || !keys || keys->ctx != c || !ml_out || (n && (!key_idx || !g1))) return BLSBN254_E_ARG;
-  if (n == 0) { std::memset(ml_out, 0, 384); ml_out[31] = 1; return 0; }
-  CHECK_LANES(c, n);
-  ENTER(c);
-  const size_t n_lanes = (n + 1) / 2;
-  HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4));
-  HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->flags.reserve(n)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 1))); HIPCHK(c, c->out.reserve(384));
-  TRY(upload(c, c->in_a, g1, 64 * n));
-  TRY(upload(c, c->kd_kid, key_idx, 4 * n));
-  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", false));
-  int bad;
-  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(n), k_g1_to_ws_batch, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p));
-  int rc = first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad);
-  if (rc) return rc;
-  if (bad >= 0) return BLSBN254_ERR_G1;
-  const bool wide = c->wide_fe && n <= c->wide_fe_max;       // few pairs: one wave per pair, product of n values instead of n / 2
-  const size_t f_cnt = wide ? n : n_lanes;
-  if (wide) {
-    HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
-    TRY(launch(c, c->stream, "miller_wide_1p", grid_wide(n), k_miller_wide_1p, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
-               (const uint8_t*)keys->ok.p, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->flags.p, (const uint8_t*)c->status.p));
-  } else {
-    TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
-               (const uint8_t*)keys->ok.p, n, (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)c->status.p));
-  }
-  rc = first_bad(c, (const uint8_t*)c->flags.p, n, 1, 1, &bad);
-  if (rc) return rc;
-  if (bad >= 0) return BLSBN254_ERR_G2;
-  int32_t* res; size_t rs;
-  rc = fp12_tree(c, (int32_t*)c->f_ws.p, f_cnt, f_cnt, &res, &rs);
-  if (rc) return rc;
-  TRY(launch(c, c->stream, "fp12_to_bytes", grid_lanes(1), k_fp12_to_bytes, (const int32_t*)res, (size_t)1, rs, (uint8_t*)c->out.p));
-  return download(c, ml_out, c->out.p, 384);
-}
-// CoreAggregateVerify with the public keys given as prepared keys by index: prod_i e(H(msg_i), pk_[key_idx_i]) * e(agg_sig, -G2gen) == 1.
-// The signature's pair uses the table's own -G2gen entry; two pairs per lane, every line from the tables, ONE final exponentiation.
-int blsbn254_aggregate_verify_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* keys, const uint32_t* key_idx, const uint8_t* msgs, const uint64_t* off,
-                                       size_t n, const uint8_t agg_sig[64], const uint8_t* dst, size_t dst_len, int* valid) {
-  if (!c || !keys || keys->ctx != c || !valid || !agg_sig || !off || (n && !key_idx) || (dst_len && !dst)) return BLSBN254_E_ARG;
-  *valid = 0;
-  if (n == 0) return 0;
-  const size_t np = n + 1, n_lanes = (np + 1) / 2;
-  CHECK_LANES(c, np);
-  ENTER(c);
-  uint32_t dl; int rc = stage_dst(c, dst, dst_len, &dl);
-  if (rc) return rc;
-  rc = stage_msgs(c, msgs, off, n);
-  if (rc) return rc;
-  HIPCHK(c, c->in_b.reserve(64)); HIPCHK(c, c->kd_kid.reserve(4 * np)); HIPCHK(c, c->h_ws.reserve(np * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n_lanes * 108 * 4));
-  HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 2))); HIPCHK(c, c->misc.reserve(64));
-  const uint32_t sig_key = (uint32_t)keys->u;
-  HIPCHK(c, hipMemcpyAsync(c->kd_kid.p, key_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_kid.p + n, &sig_key, 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sig, 64, hipMemcpyHostToDevice, c->stream));
-  int* d_ok = (int*)c->misc.p;               // [0] first bad key index (kd_hist), [1] all keys valid, [2] (byte) signature valid
-  static const int init[3] = {NO_INDEX, 1, 1};         // the armed index shares its upload with the two validity words
-  HIPCHK(c, hipMemcpyAsync(d_ok, init, 12, hipMemcpyHostToDevice, c->stream));
-  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", true));   // its read-back also waits for the copy of sig_key (on the stack)
-  TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, np,
-             (uint8_t*)nullptr, 0));
-  TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + 2)));
-  TRY(launch(c, c->stream, "miller_hpk2p", grid_lanes(n_lanes), k_miller_hpk2p, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, (const int32_t*)keys->raw.p,
-             (const uint8_t*)keys->ok.p, np, (int32_t*)c->f_ws.p, n_lanes, (uint8_t*)c->flags.p, (const uint8_t*)nullptr));
-  TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok + 1));
-  int32_t* res; size_t rs;
-  rc = fp12_tree(c, (int32_t*)c->f_ws.p, n_lanes, n_lanes, &res, &rs);
-  if (rc) return rc;
-  int* d_one = d_ok + 4;
-  rc = run_final_exp(c, res, 1, rs, 3, nullptr, nullptr, nullptr, nullptr, d_one);
-  if (rc) return rc;
-  int h[5] = {0, 0, 0, 0, 0};
-  TRY(download(c, h, d_ok, 20));
-  *valid = (h[1] == 1 && (h[2] & 0xff) == 1 && h[4] == 1) ? 1 : 0;
-  return 0;
-}
+// (blsbn254_multi_miller_loop_prepared and blsbn254_aggregate_verify_prepared read the RAW tables: host_aggregate.hip)
 // how many verify chunks took the prepared-key path / the exact per-tuple path on this context (tests, bench)
 int blsbn254_path_stats(blsbn254_ctx* c, uint64_t out[2]) {
   if (!c || !out) return BLSBN254_E_ARG;

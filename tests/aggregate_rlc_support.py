@@ -1,6 +1,9 @@
 """What the tests of the aggregate verify over ragged groups by random linear combination share: the Python models of the weight
-derivation and of the plan (bls-bn254_amd/csrc/aggregate_rlc.h, aggregate_rlc_plan.h), and the names the feature adds."""
+derivation and of the plan (bls-bn254_amd/csrc/aggregate_rlc.h, aggregate_rlc_plan.h), the names the feature adds, and the
+groups of signed pairs the GPU tests run it on."""
 import hashlib
+
+from tests import synth
 
 AGR_KERNELS = ("k_agr_group", "k_agr_weigh", "k_agr_items", "k_agr_bits")
 AGR_SYMBOLS = ("blsbn254_aggregate_verify_batch_rlc", "blsbn254_set_aggregate_rlc_segments", "blsbn254_aggregate_rlc_stats")
@@ -66,3 +69,32 @@ def failed_ranges(bound, passed, elig, off=None, merge_gap=0):
                 out.append((a, b))
         s = e
     return sum(1 for a, b in out for g in range(a, b) if elig[g]), out
+
+
+SEED = bytes(range(1, 33))
+
+
+class Data:
+    """sizes[g] pairs per group: pair i of the call uses key i mod pool and a message of its own; every group's aggregate is the
+    engine's sum of its pairs' signatures (an empty group: the first pair's signature, a valid point)"""
+    def __init__(self, e, sizes, dst, pool=8, salt=0):
+        n = sum(sizes)
+        skb = [synth.sk_of(k).to_bytes(32, "big") for k in range(pool)]
+        pk_pool = e.sk_to_pk_batch(b"".join(skb), pool)
+        msgs = [synth.msg_of((salt << 20) + i) for i in range(n)]
+        sigs = e.sign_batch(b"".join(skb[i % pool] for i in range(n)), msgs, dst)
+        self.dst, self.sizes = dst, list(sizes)
+        self.keys, self.msgs, self.sigs = [], [], []
+        pos = 0
+        for k in sizes:
+            self.keys.append([pk_pool[128 * (i % pool):128 * (i % pool) + 128] for i in range(pos, pos + k)])
+            self.msgs.append(msgs[pos:pos + k])
+            self.sigs.append(e.aggregate_sigs(sigs[64 * pos:64 * (pos + k)], k) if k else sigs[:64])
+            pos += k
+
+    def flip_message(self, g, j=0):
+        m = self.msgs[g][j]
+        self.msgs[g][j] = bytes([m[0] ^ 1]) + m[1:]
+
+    def args(self):
+        return [b"".join(k) for k in self.keys], self.msgs, b"".join(self.sigs), self.dst

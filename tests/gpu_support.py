@@ -30,8 +30,8 @@ FE_FORM_KNOBS = ("BLSBN254_WIDE_FE", "BLSBN254_WIDE_FE_MAX", "BLSBN254_TRI_MAX",
 FE_KERNELS = ("fe_easy", "fe_easy_head", "fe_inv4", "fe_easy_tail", "fe_hard_wide", "fe_tri_hard", "fe_expx_h1", "fe_expx_h2", "fe_expx", "fe_h3")
 
 
-# ... and of the Miller loop and of the key preparation (miller_to_ws, host.hip; launch_g2_prepare, launch_miller_prepared,
-# verify_chunk_dev and blsbn254_multi_miller_loop_prepared, host_verify.hip): the same sizes, and three switches of their own
+# ... and of the Miller loop and of the key preparation (miller_to_ws, host.hip; launch_g2_prepare, launch_miller_prepared and
+# verify_chunk_dev, host_verify.hip; launch_miller_raw, host_aggregate.hip): the same sizes, and three switches of their own
 MILLER_FORM_KNOBS = FE_FORM_KNOBS + ("BLSBN254_TRI_MILLER", "BLSBN254_QUAD_PREP", "BLSBN254_AUTO_PREPARE")
 # every Miller-loop kernel the host code launches, under the name its launch is recorded by
 MILLER_KERNELS = ("miller_wide_1", "miller_tri_1", "miller_1", "miller_wide_1p", "miller_tri_1p", "miller_hpk1p", "miller_hpk2p", "miller_hpk2", "miller_hpk2r",
@@ -48,6 +48,28 @@ def fe_forms_set_by_environment():
 def miller_forms_set_by_environment():
     """the same for MILLER_FORM_KNOBS"""
     return [k for k in MILLER_FORM_KNOBS if k in os.environ]
+
+
+ENGINES = ("default", "tri", "lane")
+
+
+@pytest.fixture(scope="module")
+def engines(M, eng):
+    """default: the production choice by size; tri: no wave-per-pair kernels; lane: neither those nor the quad ones; serial_prep:
+    the key preparation on one lane per key"""
+    if miller_forms_set_by_environment():
+        pytest.skip("the environment sets %s: the forms do not run at their production sizes" % ", ".join(miller_forms_set_by_environment()))
+    mp = pytest.MonkeyPatch()
+    made = {"default": eng}
+    try:
+        made["tri"] = fresh_engine(M, mp, None, {"BLSBN254_WIDE_FE": "0"})
+        made["lane"] = fresh_engine(M, mp, None, {"BLSBN254_WIDE_FE": "0", "BLSBN254_TRI_MAX": "0"})
+        made["serial_prep"] = fresh_engine(M, mp, None, {"BLSBN254_QUAD_PREP": "0"})
+        yield made
+    finally:
+        for name in ("tri", "lane", "serial_prep"):
+            if name in made:
+                made[name].close()
 
 
 def launches(e, call, kernels):

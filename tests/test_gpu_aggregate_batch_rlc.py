@@ -8,41 +8,14 @@ import numpy as np
 import pytest
 
 from tests import point_cases, synth
-from tests.aggregate_rlc_support import AGR_STATS, cut
+from tests.aggregate_rlc_support import AGR_STATS, Data, SEED, cut
 from tests.gpu_support import MILLER_KERNELS, eng, fresh_engine, launches, M
 from tests.helpers import bits_of, IDENT1, IDENT2, offsets_u64
 
 pytestmark = pytest.mark.gpu
 R = synth.R
 E_ARG = -1
-SEED = bytes(range(1, 33))
 SEED_B = bytes(range(101, 133))
-
-
-class Data:
-    """sizes[g] pairs per group: pair i of the call uses key i mod pool and a message of its own; every group's aggregate is the
-    engine's sum of its pairs' signatures (an empty group: the first pair's signature, a valid point)"""
-    def __init__(self, e, sizes, dst, pool=8, salt=0):
-        n = sum(sizes)
-        skb = [synth.sk_of(k).to_bytes(32, "big") for k in range(pool)]
-        pk_pool = e.sk_to_pk_batch(b"".join(skb), pool)
-        msgs = [synth.msg_of((salt << 20) + i) for i in range(n)]
-        sigs = e.sign_batch(b"".join(skb[i % pool] for i in range(n)), msgs, dst)
-        self.dst, self.sizes = dst, list(sizes)
-        self.keys, self.msgs, self.sigs = [], [], []
-        pos = 0
-        for k in sizes:
-            self.keys.append([pk_pool[128 * (i % pool):128 * (i % pool) + 128] for i in range(pos, pos + k)])
-            self.msgs.append(msgs[pos:pos + k])
-            self.sigs.append(e.aggregate_sigs(sigs[64 * pos:64 * (pos + k)], k) if k else sigs[:64])
-            pos += k
-
-    def flip_message(self, g, j=0):
-        m = self.msgs[g][j]
-        self.msgs[g][j] = bytes([m[0] ^ 1]) + m[1:]
-
-    def args(self):
-        return [b"".join(k) for k in self.keys], self.msgs, b"".join(self.sigs), self.dst
 
 
 def run(e, D, seed=SEED):
@@ -204,23 +177,27 @@ def test_group_offsets_need_not_start_at_zero(eng, M, segments):
 
 # ---------------------------------------------------------------- 7. segment forms over several launches
 def test_segments_span_several_launches(M, monkeypatch):
-    e = fresh_engine(M, monkeypatch, "64")                               # 4 x (33 + 1) Miller slots: three launches of at most 64
-    try:
-        n_g = 24
-        D = Data(e, [3] * n_g, M.DEFAULT_DST, pool=33, salt=7)
-        e.set_aggregate_rlc_segments(4)
-        bits, delta = run(e, D)
-        assert bits == [True] * n_g and delta == stats(round1=n_g)
-        D.flip_message(n_g - 2, 2)                                       # in the last of the 4 segments of 6 groups
-        want = [g != n_g - 2 for g in range(n_g)]
-        (bits, delta), rec = launches(e, lambda: run(e, D), MILLER_KERNELS)
-        assert bits == want and delta == stats(round2=18, exact=6, equations=5, failed=1, pipeline=6)
-        assert rec.get("miller_wide_1p", 0) == 1 + 3, rec                 # round 1: 34 slots; round 2: 136 slots, 64 + 64 + 8
-        e.set_aggregate_rlc_segments(1)                                  # no second round: every eligible group to the exact pipeline
-        bits, delta = run(e, D)
-        assert bits == want and delta == stats(exact=n_g, pipeline=n_g)
-    finally:
-        e.close()
+    """... in the form that fits each launch: a wave per slot, and one slot per lane on an engine without the wave and quad
+    kernels -- never two slots per lane in a second round, where a lane's value must belong to one segment"""
+    for knobs, kernel in (({}, "miller_wide_1p"), ({"BLSBN254_WIDE_FE": "0", "BLSBN254_TRI_MAX": "0"}, "miller_hpk1p")):
+        e = fresh_engine(M, monkeypatch, "64", knobs)                    # 4 x (33 + 1) Miller slots: three launches of at most 64
+        try:
+            n_g = 24
+            D = Data(e, [3] * n_g, M.DEFAULT_DST, pool=33, salt=7)
+            e.set_aggregate_rlc_segments(4)
+            bits, delta = run(e, D)
+            assert bits == [True] * n_g and delta == stats(round1=n_g)
+            D.flip_message(n_g - 2, 2)                                   # in the last of the 4 segments of 6 groups
+            want = [g != n_g - 2 for g in range(n_g)]
+            (bits, delta), rec = launches(e, lambda: run(e, D), MILLER_KERNELS)
+            assert bits == want and delta == stats(round2=18, exact=6, equations=5, failed=1, pipeline=6)
+            assert rec.get(kernel, 0) == 1 + 3, rec                       # round 1: 34 slots; round 2: 136 slots, 64 + 64 + 8
+            assert set(rec) == {kernel, "miller_hpk2r"}, rec              # (the exact pipeline's own loop: the failed segment, and run()'s exact call)
+            e.set_aggregate_rlc_segments(1)                              # no second round: every eligible group to the exact pipeline
+            bits, delta = run(e, D)
+            assert bits == want and delta == stats(exact=n_g, pipeline=n_g)
+        finally:
+            e.close()
 
 
 # ---------------------------------------------------------------- 8. seed = None, argument errors

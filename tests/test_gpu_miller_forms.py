@@ -3,17 +3,17 @@
 identities by encoding, tiled without a period), byte for byte against the oracle, whose raw calls have the same domain: they
 decode their operands and check nothing else.  Every assertion about a form also asserts, from the engine's launch record, that
 this Miller kernel ran once and no other Miller kernel ran.  The sizes at which a form takes over are those of miller_to_ws
-(host.hip), launch_g2_prepare, launch_miller_prepared, verify_chunk_dev and blsbn254_multi_miller_loop_prepared (host_verify.hip)."""
+(host.hip), launch_g2_prepare, launch_miller_prepared and verify_chunk_dev (host_verify.hip) and, for
+blsbn254_multi_miller_loop_prepared, launch_miller_raw (host_aggregate.hip; the other callers: tests/test_gpu_aggregate_forms.py)."""
 import numpy as np
 import pytest
 
 from tests import point_cases as C
 from tests import synth
-from tests.gpu_support import MILLER_KERNELS, PREP_KERNELS, eng, fresh_engine, launches, miller_forms_set_by_environment, M
+from tests.gpu_support import ENGINES, MILLER_KERNELS, PREP_KERNELS, eng, engines, launches, M  # noqa: F401 (fixtures)
 from tests.helpers import b32, bits_of
 
 pytestmark = pytest.mark.gpu
-ENGINES = ("default", "tri", "lane")
 WIDE_MAX = 2048                                   # wide_fe_max of host_common.h: the prepared-key forms; variable points take half
 
 
@@ -21,25 +21,6 @@ WIDE_MAX = 2048                                   # wide_fe_max of host_common.h
 def cus():
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-@pytest.fixture(scope="module")
-def engines(M, eng):
-    """default: the production choice by size; tri: no wave-per-pair kernels; lane: neither those nor the quad ones; serial_prep:
-    the key preparation on one lane per key"""
-    if miller_forms_set_by_environment():
-        pytest.skip("the environment sets %s: the forms do not run at their production sizes" % ", ".join(miller_forms_set_by_environment()))
-    mp = pytest.MonkeyPatch()
-    made = {"default": eng}
-    try:
-        made["tri"] = fresh_engine(M, mp, None, {"BLSBN254_WIDE_FE": "0"})
-        made["lane"] = fresh_engine(M, mp, None, {"BLSBN254_WIDE_FE": "0", "BLSBN254_TRI_MAX": "0"})
-        made["serial_prep"] = fresh_engine(M, mp, None, {"BLSBN254_QUAD_PREP": "0"})
-        yield made
-    finally:
-        for name in ("tri", "lane", "serial_prep"):
-            if name in made:
-                made[name].close()
 
 
 @pytest.fixture(scope="module")
