@@ -12,4 +12,5 @@ Layout:
 """
 from .engine import (Bn254Error, Engine, MultiEngine, PreparedKeys, KeySet, InvalidG1Bytes, InvalidG2Bytes, InvalidGtBytes,  # noqa: F401
                      InvalidScalarBytes, DEFAULT_DST, POP_DST, ST_SHORT, library_path, load_library,
-                     EXPAND_XMD_SHA256, EXPAND_XMD_KECCAK256, EXPAND_XMD_SHA3_256, EXPAND_XOF_SHAKE128, EXPAND_XOF_SHAKE256)
+                     EXPAND_XMD_SHA256, EXPAND_XMD_KECCAK256, EXPAND_XMD_SHA3_256, EXPAND_XOF_SHAKE128, EXPAND_XOF_SHAKE256,
+                     G1MAP_SVDW, G1MAP_TAI_DIGEST, G1MAP_TAI_HASH)

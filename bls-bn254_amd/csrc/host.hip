@@ -4,6 +4,7 @@
 // (aggregate verify, sums, threshold), host_groupops.hip (group operations, FastAggregateVerify), host_pairing_check.hip
 // (pairing-product equations over groups of pairs), host_misc.hip.
 #include "host_common.h"
+#include "lane_hash_tai.h"   // the map ids (G1MAP_*) the header's are checked against
 
 extern "C" {
 
@@ -181,6 +182,19 @@ int blsbn254_set_expander(blsbn254_ctx* c, int id) {
   return 0;
 }
 int blsbn254_get_expander(const blsbn254_ctx* c) { return c ? (int)c->expander : BLSBN254_E_ARG; }
+
+// The map behind every message hashed to G1 (host_common.h launch_hash_to_g1 / launch_sign).  Settles the context FIRST, as
+// blsbn254_set_expander does and for the same reason: a pending asynchronous verify call whose guess fails is re-run by
+// resolve_pending, and that re-run must hash under the map the call was made with.  The resident tag stays: no map changes it.
+static_assert(BLSBN254_G1MAP_SVDW == G1MAP_SVDW && BLSBN254_G1MAP_TAI_DIGEST == G1MAP_TAI_DIGEST && BLSBN254_G1MAP_TAI_HASH == G1MAP_TAI_HASH,
+              "the header's ids are lane_hash_tai.h's");
+int blsbn254_set_g1_map(blsbn254_ctx* c, int id) {
+  if (!c || id < 0 || id >= (int)G1MAP_COUNT) return BLSBN254_E_ARG;
+  ENTER(c);
+  c->g1_map = (uint32_t)id;
+  return 0;
+}
+int blsbn254_get_g1_map(const blsbn254_ctx* c) { return c ? (int)c->g1_map : BLSBN254_E_ARG; }
 
 // DST handling: RFC 9380 5.3.3 (an oversize DST is pre-hashed with the context's expander, keccak.h oversize_dst); staged into
 // device memory once per call

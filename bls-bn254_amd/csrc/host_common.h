@@ -277,6 +277,7 @@ struct blsbn254_ctx {
   uint8_t dst_host[256];  // the (pre-hashed if oversize) DST currently resident in `dst`, and its length; -1 = none
   int dst_host_len = -1;
   uint32_t expander = BLSBN254_EXPAND_XMD_SHA256;   // the message expander every hashing launch runs under (blsbn254_set_expander; keccak.h EXPAND_*)
+  uint32_t g1_map = BLSBN254_G1MAP_SVDW;            // the map behind every MESSAGE hashed to G1 (blsbn254_set_g1_map; lane_hash_tai.h G1MAP_*)
   size_t chunk = (size_t)1 << 22;   // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
   MsmWs msm;
   PcWs pc;
@@ -353,9 +354,14 @@ static inline int launch(blsbn254_ctx* c, hipStream_t s, const char* name, Shape
 // THE launches of the four hashing kernels, on the tag resident in c->dst (stage_dst: dl): the XMD-SHA-256 kernel under the
 // default expander, its sibling of k_hash_keccak.hip under any other.  No host unit names those kernels but these four helpers,
 // so every call that hashes follows blsbn254_set_expander.  Counted under one name whatever the expander.
+// The two that hash a MESSAGE to G1 follow blsbn254_set_g1_map as well: under a try-and-increment map they launch the kernels of
+// k_hash_tai.hip (the tag is passed and ignored).  encode_to_g1 (mode 2) keeps the RFC map, and so does every launch inside a
+// RfcMapScope: the proofs of possession, whose tag is what separates them from messages.
 static inline int launch_hash_to_g1(blsbn254_ctx* c, hipStream_t s, const uint8_t* msgs, const uint64_t* off, size_t n, uint32_t dl, int32_t* ws, size_t stride,
                                     uint8_t* out, int mode) {
   const uint8_t* dst = (const uint8_t*)c->dst.p;
+  if (c->g1_map != BLSBN254_G1MAP_SVDW && mode != 2)
+    return launch(c, s, "hash_to_g1", grid_lanes(n), k_hash_to_g1_tai, c->g1_map, c->expander, msgs, off, n, dst, dl, ws, stride, out, mode);
   if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "hash_to_g1", grid_lanes(n), k_hash_to_g1, msgs, off, n, dst, dl, ws, stride, out, mode);
   return launch(c, s, "hash_to_g1", grid_lanes(n), k_hash_to_g1_x, c->expander, msgs, off, n, dst, dl, ws, stride, out, mode);
 }
@@ -367,6 +373,7 @@ static inline int launch_hash_to_g2(blsbn254_ctx* c, hipStream_t s, const uint8_
 static inline int launch_sign(blsbn254_ctx* c, hipStream_t s, const uint8_t* sks, const uint8_t* msgs, const uint64_t* off, size_t n, uint32_t dl, uint8_t* sigs,
                               uint8_t* status) {
   const uint8_t* dst = (const uint8_t*)c->dst.p;
+  if (c->g1_map != BLSBN254_G1MAP_SVDW) return launch(c, s, "sign", grid_lanes(n), k_sign_tai, c->g1_map, c->expander, sks, msgs, off, n, dst, dl, sigs, status);
   if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "sign", grid_lanes(n), k_sign, sks, msgs, off, n, dst, dl, sigs, status);
   return launch(c, s, "sign", grid_lanes(n), k_sign_x, c->expander, sks, msgs, off, n, dst, dl, sigs, status);
 }
@@ -375,6 +382,17 @@ static inline int launch_hash_to_scalar(blsbn254_ctx* c, hipStream_t s, const ui
   if (c->expander == BLSBN254_EXPAND_XMD_SHA256) return launch(c, s, "hash_to_scalar", grid_lanes(n), k_hash_to_scalar, msgs, off, n, dst, dl, out);
   return launch(c, s, "hash_to_scalar", grid_lanes(n), k_hash_to_scalar_x, c->expander, msgs, off, n, dst, dl, out);
 }
+// The RFC 9380 map for the launches of one call, whatever the context's setting: held by the calls that hash a PUBLIC KEY under
+// the proof-of-possession tag (pop_prove_batch, pop_verify_batch, the proof check of keyset_create_checked).  Taken AFTER ENTER
+// (pending verify calls are settled under the caller's map) by calls that end synchronised, so nothing enqueued under it is
+// re-run later.
+struct BNH RfcMapScope {
+  blsbn254_ctx* c; uint32_t was;
+  explicit RfcMapScope(blsbn254_ctx* c_) : c(c_), was(c_->g1_map) { c->g1_map = BLSBN254_G1MAP_SVDW; }
+  ~RfcMapScope() { c->g1_map = was; }
+  RfcMapScope(const RfcMapScope&) = delete;
+  RfcMapScope& operator=(const RfcMapScope&) = delete;
+};
 // reserve, then copy host -> device on the main stream (the source must outlive the copy: the caller's, or ctx-owned / static)
 static inline int upload(blsbn254_ctx* c, DevBuf& b, const void* src, size_t bytes) {
   HIPCHK(c, b.reserve(bytes));

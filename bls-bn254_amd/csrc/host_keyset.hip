@@ -41,6 +41,7 @@ int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t
     HIPCHK(c, k->pop.reserve(nb + 8)); HIPCHK(c, c->in_off.reserve(8 * (n_keys + 1))); HIPCHK(c, c->bitmap.reserve(nb + 8));
     TRY(stage_g1(c, proofs, n_keys, compressed));
     TRY(launch(c, c->stream, "iota_off", grid_lanes(n_keys + 1), k_iota_off, (uint64_t*)c->in_off.p, n_keys, (uint64_t)128));
+    RfcMapScope rfc(c);                                    // proofs of possession keep the RFC map and their tag (host_common.h)
     TRY(blsbn254_internal_verify_batch_dev_sync(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_a.p, (const uint64_t*)c->in_off.p,
                                                 (const uint8_t*)c->in_b.p, n_keys, pop_dst, pop_dst_len, (uint8_t*)c->bitmap.p));
     HIPCHK(c, hipMemcpyAsync(k->pop.p, c->bitmap.p, nb, hipMemcpyDeviceToDevice, c->stream));

@@ -137,6 +137,7 @@ int blsbn254_pop_prove_batch(blsbn254_ctx* c, const uint8_t* sks, size_t n, cons
   if (!c || (n && (!sks || !proofs_out)) || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
+  RfcMapScope rfc(c);                            // a proof hashes the key under its TAG: the RFC map whatever blsbn254_set_g1_map says
   uint32_t dl; int rc = stage_dst(c, dst, dst_len, &dl);
   if (rc) return rc;
   HIPCHK(c, c->in_c.reserve(128 * n)); HIPCHK(c, c->in_off.reserve(8 * (n + 1)));
@@ -158,6 +159,7 @@ int blsbn254_pop_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   if (!c || (n && (!pks || !proofs || !bm)) || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (n == 0) return 0;
   ENTER(c);
+  RfcMapScope rfc(c);
   size_t nb = (n + 7) / 8;
   HIPCHK(c, c->in_off.reserve(8 * (n + 1)));
   HIPCHK(c, c->bitmap.reserve(nb + 8));

@@ -35,6 +35,12 @@ BN_KERNEL_1 k_hash_to_g2_x(uint32_t xid, const uint8_t* msgs, const uint64_t* of
 BN_KERNEL_1 k_sign_x(uint32_t xid, const uint8_t* sks, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
                      uint8_t* sigs, uint8_t* status);
 BN_KERNEL k_hash_to_scalar_x(uint32_t xid, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len, uint8_t* out);
+// the G1 hashing kernels under the try-and-increment map (k_hash_tai.hip, lane_hash_tai.h G1MAP_*): k_hash_to_g1_x / k_sign_x with
+// the map id in front; dst is accepted and ignored
+BN_KERNEL k_hash_to_g1_tai(uint32_t map, uint32_t xid, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
+                           int32_t* h_ws, size_t h_stride, uint8_t* out_bytes, int mode);
+BN_KERNEL_1 k_sign_tai(uint32_t map, uint32_t xid, const uint8_t* sks, const uint8_t* msgs, const uint64_t* off, size_t n, const uint8_t* dst, uint32_t dst_len,
+                       uint8_t* sigs, uint8_t* status);
 BN_KERNEL k_g1_check(const uint8_t* g1, size_t n, uint8_t* bitmap);
 BN_KERNEL k_g2_check(const uint8_t* g2, size_t n, uint8_t* ok_bytes, uint8_t* bitmap);
 BN_KERNEL k_miller_1(const uint8_t* g1, const uint8_t* g2, size_t n, int32_t* f_ws, size_t f_stride, uint8_t* status);

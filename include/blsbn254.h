@@ -137,6 +137,32 @@ int blsbn254_encode_to_g2_batch(blsbn254_ctx* ctx, const uint8_t* msgs, const ui
 #define BLSBN254_EXPAND_XOF_SHAKE256 4  /* ExpandMsgXof<sha3::Shake256> */
 int blsbn254_set_expander(blsbn254_ctx* ctx, int id);
 int blsbn254_get_expander(const blsbn254_ctx* ctx); /* the id in force; BLSBN254_E_ARG for NULL */
+/* The map behind every MESSAGE hashed to G1, as a setting of the context.  SVDW is RFC 9380's hash_to_curve as above; the two
+ * others are the try-and-increment map of the BN254 BLS contracts deployed on the EVM (hashToG1(bytes32) and its kin), whose
+ * layout is this library's: signatures in G1, keys in G2, e(sig, -G2gen) * e(H(m), pk) == 1.  The map, exactly as they compute it:
+ *   x0     TAI_DIGEST: the message bytes read as ONE big-endian integer, reduced mod p; for 32 bytes uint256(h) % p.  Any other
+ *          length is reduced the same way: a total function, with NO security claim for anything but a 32-byte digest.
+ *          TAI_HASH: the 32-byte digest of the message, reduced mod p, under the plain hash of the context's expander: SHA-256
+ *          (id 0), Keccak-256 (1), SHA3-256 (2), the first 32 bytes of SHAKE-128 (3) / SHAKE-256 (4).  No tag, no padding block.
+ *   point  for k = 0, 1, 2, ...: x = x0 + k mod p, beta = x^3 + 3; the first x whose beta is a square gives (x, beta^((p+1)/4)):
+ *          exactly that root, no sign rule.  (beta == 0 cannot happen on a curve of prime order.)  The search is bounded: after
+ *          65 536 non-residues in a row (probability 2^-65536) the result is the off-curve point (0, 0), which no equation accepts.
+ * The dst argument is accepted and IGNORED under both TAI ids: the map has no tag.
+ * FOLLOW the setting: blsbn254_hash_to_g1_batch, verify in all its forms (exact, RLC, compressed, prepared, _dev, multi), aggregate
+ * verify with its batch and RLC forms, fast aggregate verify, the key-set and committee families, the threshold share checks and
+ * the checked combine, and blsbn254_sign_batch.
+ * DO NOT follow it and keep SVDW with their tag: blsbn254_encode_to_g1_batch, the G2 and scalar hashes, blsbn254_pop_prove_batch,
+ * blsbn254_pop_verify_batch and the proof check of blsbn254_keyset_create_checked.  Try-and-increment has no tag, so a proof of
+ * possession under it would share its domain with messages; an EVM-side registration proof is an ordinary blsbn254_verify_batch
+ * over the digest the application defines.
+ * The rules are the expander's: an id outside the table returns BLSBN254_E_ARG and changes nothing; the setter settles the
+ * context first (pending asynchronous verify calls are resolved under the old map before the new id is stored); the multi-GPU
+ * handle has no call of its own: blsbn254_set_g1_map(blsbn254_multi_ctx(m, i), id) for each device i. */
+#define BLSBN254_G1MAP_SVDW 0       /* RFC 9380 hash_to_curve, the default: nothing changes */
+#define BLSBN254_G1MAP_TAI_DIGEST 1 /* try-and-increment, the message IS the digest */
+#define BLSBN254_G1MAP_TAI_HASH 2   /* try-and-increment, digest = H(msg), H the plain hash of the context's expander */
+int blsbn254_set_g1_map(blsbn254_ctx* ctx, int id);
+int blsbn254_get_g1_map(const blsbn254_ctx* ctx); /* the id in force; BLSBN254_E_ARG for NULL */
 /* G1Affine::from_uncompressed + is_on_curve (g1.rs:339-360, :383-391); G1 has cofactor 1 */
 int blsbn254_g1_check_batch(blsbn254_ctx* ctx, const uint8_t* g1, size_t n, uint8_t* ok_bitmap);
 /* G2Affine::from_uncompressed + is_on_curve + is_torsion_free (g2.rs:350-414, :733-736) */
