@@ -53,9 +53,9 @@ int blsbn254_ctx_create(int device, blsbn254_ctx** out) {
       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return BLSBN254_E_HIP; }
   if (getrandom(&c->kd_seed, sizeof c->kd_seed, 0) != (ssize_t)sizeof c->kd_seed) c->kd_seed = 0x5bd1e995u;
   if (const char* e = std::getenv("BLSBN254_AUTO_PREPARE")) c->auto_prepare = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_RLC_GROUP")) { long v = std::atol(e); if (v >= 2 && v <= 4096) { c->rlc_group = (size_t)v; c->rlc_group_auto = false; } }
+  if (const char* e = std::getenv("BLSBN254_RLC_GROUP")) { long v = std::atol(e); if (v >= 2 && v <= (long)RLC_MAX_GROUP) { c->r2.group = (size_t)v; c->r2.group_auto = false; } }
   c->lanes_per_round = (size_t)prop.multiProcessorCount * 256;
-  if (const char* e = std::getenv("BLSBN254_RLC_KEY_ROUND")) c->rlc_key_round = std::atoi(e) != 0;
+  if (const char* e = std::getenv("BLSBN254_RLC_KEY_ROUND")) c->r2.key_round = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_WIDE_FE")) c->wide_fe = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_ASYNC_VERIFY")) c->async_verify = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_KEY_CACHE")) { long v = std::atol(e); if (v >= 0 && v <= (long)PREP_MAX_KEYS) c->kc.max = (size_t)v; }

@@ -232,7 +232,7 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(agg_keys_prepare(c, n, u));                                               // the u keys and -G2gen (key id u), beside the hashing
   // key ids, key-sorted order
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve((np + 1) / 2 * 108 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->status.reserve(np + 8)); HIPCHK(c, c->misc.reserve(64));
-  HIPCHK(c, c->rlc_b.reserve(np * 18 * 4)); HIPCHK(c, c->rlc_idx.reserve(4 * np));
+  HIPCHK(c, c->rlc.b.reserve(np * 18 * 4)); HIPCHK(c, c->rlc.idx.reserve(4 * np));
   TRY(dedup_key_ids(c, n, u, true));
   TRY(key_sorted_order(c, (const uint32_t*)c->kd_kid.p, n, u));                 // cursor[k] is now the END of run k
   const uint32_t *hist = (const uint32_t*)c->kd_hist.p, *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p, *kid = (const uint32_t*)c->kd_kid.p;
@@ -242,7 +242,7 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   const int32_t* pts = nullptr; size_t pts_stride = u;
   TRY(key_sums(c, (const int32_t*)c->h_ws.p, nullptr, n, perm, perm, kid, hist, cursor, n, u, &pts, nullptr));
   // the u + 1 pairs: (sum_k, pk_k) for k < u and (agg_sig, -G2gen) as pair u with key id u
-  int32_t* h2 = (int32_t*)c->rlc_b.p; uint8_t* st = (uint8_t*)c->status.p; uint32_t* kid2 = (uint32_t*)c->rlc_idx.p;
+  int32_t* h2 = (int32_t*)c->rlc.b.p; uint8_t* st = (uint8_t*)c->status.p; uint32_t* kid2 = (uint32_t*)c->rlc.idx.p;   // (RlcWs: the buffers of whichever call runs)
   int* d_ok;
   TRY(verdict_arm(c, &d_ok));
   TRY(launch(c, c->stream, "g1p_to_h", grid_lanes(u), k_g1p_to_h_affine, pts, pts_stride, u, h2, np, st));

@@ -1,8 +1,9 @@
-// host_common.h -- shared by the host-side translation units (host*.hip): the context, device buffers, the launch helper and the
-// internal helpers one pipeline borrows from another (the size rules of the two table-only Miller loops among them:
-// launch_miller_prepared, host_verify.hip, over the expanded pair tables; launch_miller_raw, host_aggregate.hip, over the raw line
-// tables).  Nothing here is exported (BNH = hidden visibility); the C ABI is
-// include/blsbn254.h.  There is no CPU fallback anywhere on the host side: every entry point launches kernels or fails.
+// host_common.h -- shared by the host-side translation units (host*.hip): the context, device buffers, one workspace struct per
+// pipeline (MsmWs ... AgrWs; the batch verification by random linear combination of host_rlc.hip: KeySumWs, Rlc2Ws, RlcWs, with
+// its host-only rules in rlc_plan.h), the launch helper and the internal helpers one pipeline borrows from another (the size
+// rules of the two table-only Miller loops among them: launch_miller_prepared, host_verify.hip, over the expanded pair tables;
+// launch_miller_raw, host_aggregate.hip, over the raw line tables).  Nothing here is exported (BNH = hidden visibility); the C
+// ABI is include/blsbn254.h.  There is no CPU fallback anywhere on the host side: every entry point launches kernels or fails.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/random.h>
@@ -28,6 +29,7 @@
 #include "keyset_committee_merge_plan.h" // KcmRepack, the argument walk of the checked merge per committee of a key set
 #include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
 #include "aggregate_rlc_plan.h" // the segments and exact ranges of the aggregate verify over groups by random linear combination
+#include "rlc_plan.h"          // the chunk size, the bounds and the key round's back-off of the batch verification by random linear combination
 #include "../../include/blsbn254.h"
 
 using namespace bn;
@@ -204,6 +206,51 @@ struct BNH AgrWs {
   std::vector<uint8_t> h_elig, h_pass, h_bits;
   std::vector<std::pair<size_t, size_t>> ranges;
 };
+// sums of G1 points per key, level by level (host_rlc.hip key_sums; its users: the key round of rlc2_chunk_dev there,
+// aggregate_verify_grouped of host_aggregate.hip and round 1 of host_aggregate_rlc.hip): per level (ping-pong) the keys' chunk
+// counts, their prefix, the chunks' key ids and the chunk sums of one or two point arrays (27 x M limbs each); the chunks' starts
+// and lengths and the items' chunk numbers of the level being summed; 0, 1, 2, ... as the item order of every level but the
+// first.  Host side: the chunk count a level reads back.
+struct BNH KeySumWs {
+  DevBuf cnt[2], base[2], kid[2], start, len, tchunk, iota, out[2], out2[2];
+  uint32_t h_m = 0;
+};
+// batch verification by random linear combination over repeated keys (host_rlc.hip rlc2_chunk_dev, k_rlc2.hip): the seed; the
+// weighted points r_i sig_i and r_i H_i in key-sorted order (27 x n limbs each) and the signatures' flags; per tuple its chunk;
+// per key its chunk count and the prefix of those; per chunk its key, start, length, sums (27 x m limbs each) and eligible count,
+// and as a virtual tuple its signature encoding, H point, state and is-one byte; 0, 1, 2, ... over the chunks; the tuples'
+// fallback marks with their block counts and prefix, the fallback list, the validity bytes.  The key round: per key its eligible
+// count and, as a virtual tuple, its signature encoding, H point, state, is-one byte and verdict; per chunk the verdict its key's
+// or its own check left, the mark "its key failed" with block counts and prefix, and the list of the marked chunks.  Host side,
+// context-owned because asynchronous copies write them: the chunk count, the key round's verdict, the length of the chunk list,
+// the fallback count; the seed of the call in flight (stage_seed uploads from it, for every RLC pipeline).  The settings, the
+// back-off of the key round (rlc_plan.h) and the counters.
+struct BNH Rlc2Ws {
+  DevBuf seed, a, b, sigok, tchunk, ccnt, cbase, ckid, cstart, clen, sa, sb, celig, csig, ch, cstate, cisone, iota, need, bcnt, bbase, list, valid;
+  DevBuf kelig, ksig, kh, kstate, kisone, kpass, cpass, cneed, cbcnt, cbbase, clist;
+  uint32_t h_m = 0, h_mc = 0, h_m2 = 0;
+  int h_all_pass = 0;
+  uint8_t h_seed[32];
+  size_t group = RLC_DEFAULT_GROUP;  // tuples per chunk (BLSBN254_RLC_GROUP / blsbn254_set_rlc_group)
+  bool group_auto = true;            // no explicit setting: 16, raised (to at most 32) when that saves a whole round of waves (rlc_chunk_size)
+  bool key_round = true;             // first check every key's whole run as ONE virtual tuple (BLSBN254_RLC_KEY_ROUND=0 disables)
+  RlcBackoff backoff;                // ... backing off while batches keep failing it (the next 2, 4, 8, 16 calls skip it)
+  // blsbn254_rlc_stats, in its order: tuples on the chunked path, chunks checked, tuples sent to the exact fallback, tuples on the
+  // exact path (distinct keys), key rounds taken, key rounds passed
+  uint64_t stat[6] = {0, 0, 0, 0, 0, 0};
+};
+// ... and its distinct-key variant (host_rlc.hip rlc_group_products / rlc_exact_failed, k_rlc.hip), groups of 16 tuples in the
+// caller's order: the weighted points r_i sig_i (27 x n limbs, and the levels of their pairwise sums) and r_i H_i (18 x n limbs),
+// the eligibility bytes; per group the Miller value of its signature sum, that sum's encoding, a -G2gen each, the is-one byte;
+// for the exact sub-call over the groups that failed the tuples' indices and their gathered keys, signatures, H points, subgroup
+// flags and bits.  Host side: the -G2gen tile the upload reads, what the two rounds download, the indices the upload reads.
+// aggregate_verify_grouped (host_aggregate.hip) keeps its u + 1 H points in `b` and their key ids in `idx`: the two buffers
+// serve whichever call runs, so the context's footprint is one of them, not two.
+struct BNH RlcWs {
+  DevBuf a2, a, b, elig, f2, bytes, neg, ok, idx, cpk, csig, ch, csub, cbm;
+  std::vector<uint8_t> h_neg, h_ok, h_elig, h_bits;
+  std::vector<uint32_t> h_idx;
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -221,19 +268,10 @@ struct blsbn254_ctx {
   DevBuf in_a, in_b, in_c, in_off, dst, h_ws, f_ws, f_ws2, flags, sub_ok, status, bitmap, out, scalars, misc;
   DevBuf wire_a, wire_b; // compressed keys / signatures as uploaded (host_compressed.hip): inflated into in_a / in_b, which the pipelines read
   DevBuf fe[6];          // final-exponentiation phase buffers (x, a, b, c, b2, d), 108 x n limbs each
-  DevBuf rlc_a2, rlc_a, rlc_b, rlc_elig, rlc_f2, rlc_bytes, rlc_neg, rlc_ok, rlc_idx, rlc_cpk, rlc_csig, rlc_ch, rlc_csub, rlc_cbm;   // RLC batch verification
-  // RLC over repeated keys (k_rlc2.hip): weighted points, chunk descriptions, virtual tuples, fallback list
-  DevBuf r2_seed, r2_a, r2_b, r2_sigok, r2_tchunk, r2_ccnt, r2_cbase, r2_ckid, r2_cstart, r2_clen, r2_csig, r2_ch, r2_cstate, r2_iota, r2_cisone,
-         r2_need, r2_bcnt, r2_bbase, r2_list, r2_valid;
-  DevBuf ks_cnt[2], ks_base[2], ks_kid[2], ks_start, ks_len, ks_tchunk, ks_iota, ks_out[2], ks_out2[2];   // key_sums scratch (levels of chunk sums)
-  DevBuf r2_sa, r2_sb, r2_celig, r2_kelig, r2_ksig, r2_kh, r2_kstate, r2_kisone, r2_kpass, r2_cpass, r2_clist, r2_cneed, r2_cbcnt, r2_cbbase;   // chunk sums, key round of the RLC path
-  bool rlc_key_round = true;         // RLC: first check every key's whole run as ONE virtual tuple (BLSBN254_RLC_KEY_ROUND=0 disables)
-  unsigned rlc_key_skip = 0, rlc_key_streak = 0;   // ... backing off while batches keep failing it (skip the next 2, 4, 8, 16 chunks of work)
-  size_t rlc_group = 16;             // tuples per chunk (BLSBN254_RLC_GROUP / blsbn254_set_rlc_group)
-  bool rlc_group_auto = true;        // no explicit setting: 16, raised (to at most 32) when that saves a whole round of waves
+  KeySumWs ks;                       // batch verification by random linear combination: the per-key sums,
+  Rlc2Ws r2;                         // ... the rounds over repeated keys with their settings and counters,
+  RlcWs rlc;                         // ... the distinct-key variant
   size_t lanes_per_round = 65536;    // CUs x 256: the lanes resident at one wave per SIMD (the big kernels' occupancy)
-  uint64_t stat_rlc_key_rounds = 0, stat_rlc_key_rounds_passed = 0;
-  uint64_t stat_rlc[4] = {0, 0, 0, 0};   // tuples on the chunked path, chunks checked, tuples sent to the exact fallback, tuples on the exact path (distinct keys)
   DevBuf status_all;     // per-element decode status of a chunked call, all chunks
   // prepared-key verify path (k_keyprep.hip, k_miller_prep.hip)
   DevBuf kd_slots, kd_rep, kd_kid, kd_keys, kd_hist, kd_cursor, kd_perm, kd_cnt, prep_table, prep_raw, prep_ok, prep_isone, prep_valid;
@@ -243,7 +281,6 @@ struct blsbn254_ctx {
   bool s2_pending = false;           // work was forked onto stream2 and the main stream has not waited for ev_join yet
   uint32_t kd_seed = 0;              // per-context random seed of the key hash table
   uint32_t last_key = 0;             // the id of -G2gen among a call's keys, as agg_keys_prepare uploads it
-  uint8_t h_seed[32];                // the seed of the RLC call in flight, as stage_seed uploads it
   bool auto_prepare = true;          // verify_batch: de-duplicate the public keys and prepare each distinct key once (BLSBN254_AUTO_PREPARE=0 disables)
   uint64_t stat_prepared_chunks = 0, stat_exact_chunks = 0, stat_grouped_aggregates = 0, stat_pairwise_aggregates = 0;
   DevBuf q_ws;           // decoded public keys of the two-pairs-per-lane Miller kernel, 72 x lanes limbs
@@ -606,7 +643,7 @@ BNH void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches);   // host_
 BNH int key_sums(blsbn254_ctx* c, const int32_t* pts, const int32_t* pts2, size_t pts_stride, const uint32_t* mark_perm, const uint32_t* pt_perm,
                     const uint32_t* kid, const uint32_t* hist, const uint32_t* run_end, size_t items, size_t u, const int32_t** out, const int32_t** out2);   // host_rlc.hip
 // THE seed stage of the RLC pipelines: the caller's seed, or 32 bytes drawn from the OS now -- after the batch is fixed -- into
-// c->h_seed (context-owned: it outlives the copy) and from there into d.  Enqueued.
+// c->r2.h_seed (context-owned: it outlives the copy) and from there into d.  Enqueued.
 BNH int stage_seed(blsbn254_ctx* c, DevBuf& d, const uint8_t* seed);   // host_rlc.hip
 BNH int prepared_round(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const KeyTables& kt, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, size_t cnt, uint8_t* d_isone);   // host_rlc.hip
 // The segmented reductions' device side.  seg_stage: w's ping-pong buffers for levels of at most items_max items of `limbs` limbs

@@ -18,9 +18,10 @@ FLAGS = {
     "pair_product_host.cpp": ["-DBN_CHECK"],
     "seg_plan_host.cpp": ["-Wall", "-Werror"],
     "key_cache_host.cpp": ["-Wall", "-Wextra", "-Werror"],
+    "rlc_plan_host.cpp": ["-Wall", "-Wextra", "-Werror"],
     "lazy_tower_host.cpp": [],
 }
-SANITIZED = ["-fsanitize=address,undefined", "-fno-sanitize-recover", "-g"]     # key_cache_host only, run as a program of its own
+SANITIZED = ["-fsanitize=address,undefined", "-fno-sanitize-recover", "-g"]     # key_cache_host and rlc_plan_host only, run as programs of their own
 
 
 def sources(main):
