@@ -14,14 +14,14 @@
 
 extern "C" {
 
-int agg_batch_args(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, const uint8_t* agg_sigs,
-                   size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* valid_bitmap, const char* call) {
+int agg_msg_args(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                 bool missing, bool pair_missing, const char* call) {
   if (!c) return BLSBN254_E_ARG;
   if (n_groups == 0) return CK_NOTHING;
-  if (!grp_off || !agg_sigs || !valid_bitmap || (dst_len && !dst)) return BLSBN254_E_ARG;
+  if (!grp_off || missing || (dst_len && !dst)) return BLSBN254_E_ARG;
   if (check_offsets(grp_off, n_groups)) { c->last_error = "group offsets decrease"; return BLSBN254_E_ARG; }
   const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
-  if (N && (!pks || !off)) return BLSBN254_E_ARG;
+  if (N && (pair_missing || !off)) return BLSBN254_E_ARG;
   if (N > MAX_LANES || G > MAX_LANES || N + G > MAX_LANES) {
     c->last_error = std::string("more than 2^23 pairs (the signatures' pairs counted) in one ") + call + " call";
     return BLSBN254_E_ARG;
@@ -30,15 +30,24 @@ int agg_batch_args(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, con
   if (N && !msgs && off[base + N] != off[base]) return BLSBN254_E_ARG;
   return 0;
 }
-int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
-                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
-  const int args = agg_batch_args(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, "aggregate_verify_batch");
+int agg_batch_args(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, const uint8_t* agg_sigs,
+                   size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* valid_bitmap, const char* call) {
+  return agg_msg_args(c, msgs, off, grp_off, n_groups, dst, dst_len, !agg_sigs || !valid_bitmap, !pks, call);
+}
+// The call behind its entry points.  want_dup (blsbn254_aggregate_verify_batch_distinct, and the RLC form's exact route): the
+// distinct-message stage runs on the hash points behind the hashing launch and leaves the groups' repeat bits in c->md.h_bits;
+// without it the launch sequence, the results and the counters are what they were before the stage existed.
+int aggregate_verify_batch_impl(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap, bool want_dup,
+                                const char* call) {
+  const int args = agg_batch_args(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, call);
   if (args) return args == CK_NOTHING ? 0 : args;
   const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
   ENTER(c);                                             // settles pending asynchronous verify calls BEFORE the tag is staged
   if (N == 0) {                                         // every group is empty: invalid, as the single call's n == 0 (nothing to launch)
     std::memset(valid_bitmap, 0, (G + 7) / 8);
     c->stat_agb[0] += G;
+    if (want_dup) { c->md.h_bits.assign((G + 7) / 8, 0); ++c->md.stat[0]; c->md.stat[3] = 0; }      // ... and none is repeated
     return 0;
   }
   uint32_t dl = 0;
@@ -84,6 +93,7 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const u
   int32_t* h = (int32_t*)c->h_ws.p;
   TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, dl, h, S,
              (uint8_t*)nullptr, 0));
+  if (want_dup) TRY(msg_distinct_stage(c, h, S, N, MD_AFFINE, (const uint32_t*)a.goff.d.p, G));      // slots 0 .. N - 1: the pairs' points, affine
   TRY(launch(c, c->stream, "agb_place_sigs", grid_lanes(G), k_agb_place_sigs, (const uint8_t*)c->in_b.p, G, h, N, S, (uint8_t*)a.sig_ok.p));
   TRY(launch(c, c->stream, "g2_check", grid_lanes(N), k_g2_check, d_pks, N, (uint8_t*)c->sub_ok.p, (uint8_t*)nullptr));   // the caller's keys only: never -G2gen
   const uint32_t *d_sa = (const uint32_t*)a.slot_a.p, *d_sb = (const uint32_t*)a.slot_b.p;
@@ -100,8 +110,13 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const u
     }));
   }
   TRY(pc_finish_bitmap(c, G, valid_bitmap));
+  if (want_dup) TRY(msg_distinct_bits(c, N, G, nullptr));
   c->stat_agb[0] += G; c->stat_agb[1] += lanes; c->stat_agb[3] += launches.size();      // counted once the call has succeeded
   return 0;
+}
+int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap) {
+  return aggregate_verify_batch_impl(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, false, "aggregate_verify_batch");
 }
 
 int blsbn254_aggregate_batch_stats(blsbn254_ctx* c, uint64_t out[4]) {

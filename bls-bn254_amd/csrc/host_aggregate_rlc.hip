@@ -78,10 +78,14 @@ static int agr_bits(blsbn254_ctx* c, size_t G, const uint32_t* d_seg_of, uint8_t
   return download(c, bm, c->bitmap.p, (G + 7) / 8);
 }
 
-int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
-                                        const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t seed[32],
-                                        uint8_t* valid_bitmap) {
-  const int args = agg_batch_args(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, "aggregate_verify_batch_rlc");
+// The call behind its entry points.  want_dup (blsbn254_aggregate_verify_batch_rlc_distinct): the distinct-message stage runs on
+// the homogeneous hash points behind the hashing launch -- once, for all groups, so the exact sub-calls of failed ranges run
+// without it -- and leaves the groups' repeat bits in c->md.h_bits; a call whose keys do not repeat hands the request to the exact call.
+// Without it the launch sequence, the results and the counters are what they were before the stage existed.
+int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* seed,
+                                    uint8_t* valid_bitmap, bool want_dup, const char* call) {
+  const int args = agg_batch_args(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, call);
   if (args) return args == CK_NOTHING ? 0 : args;
   const size_t G = n_groups, base = (size_t)grp_off[0], N = (size_t)(grp_off[G] - grp_off[0]);
   Stream2Guard s2_guard(c);
@@ -90,6 +94,7 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
   if (N == 0) {                                         // every group is empty: invalid, nothing to launch
     std::memset(valid_bitmap, 0, nb);
     ++c->stat_agr[0]; c->stat_agr[4] += G;
+    if (want_dup) { c->md.h_bits.assign(nb, 0); ++c->md.stat[0]; c->md.stat[3] = 0; }      // ... and none is repeated
     return 0;
   }
   uint32_t dl = 0;
@@ -99,7 +104,7 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
   size_t u = 0;
   TRY(agg_keys_stage(c, pks + 128 * base, N, &u));     // the keys with -G2gen as "pair N" (the key of the signatures' slots), de-duplicated
   if (!agr_keys_repeat(N, u, PREP_MAX_KEYS)) {          // nothing to share per key: the call is the exact call
-    TRY(blsbn254_aggregate_verify_batch(c, pks, msgs, off, grp_off, agg_sigs, G, dst, dst_len, valid_bitmap));
+    TRY(aggregate_verify_batch_impl(c, pks, msgs, off, grp_off, agg_sigs, G, dst, dst_len, valid_bitmap, want_dup, call));
     ++c->stat_agr[0]; ++c->stat_agr[6]; c->stat_agr[3] += G;
     return 0;
   }
@@ -118,6 +123,7 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
   TRY(dedup_key_ids(c, N, u, false));
   TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, N, dl, (int32_t*)c->h_ws.p, N,
              (uint8_t*)nullptr, 3));
+  if (want_dup) TRY(msg_distinct_stage(c, (const int32_t*)c->h_ws.p, N, N, MD_HOMOGENEOUS, (const uint32_t*)w.goff.d.p, G));
   HIPCHK(c, join_stream2(c));                           // the keys' validity bytes are final
   TRY(launch(c, c->stream, "agr_group", grid_lanes(G), k_agr_group, (const uint8_t*)c->in_b.p, (const uint32_t*)w.goff.d.p, (const uint32_t*)c->kd_kid.p, (const uint8_t*)c->prep_ok.p, (const uint8_t*)w.seed.p, G,
              (uint8_t*)w.sig_ok.p, (uint8_t*)w.elig.p, (uint2*)w.wt.p, (int32_t*)w.w.p, W, N));
@@ -158,9 +164,15 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, con
         if (w.h_elig[a + j] && bit_at(w.h_bits.data(), j)) set_bit(valid_bitmap, a + j);
     }
   }
+  if (want_dup) TRY(msg_distinct_bits(c, N, G, nullptr));
   ++c->stat_agr[0]; c->stat_agr[1] += pass1 ? n_elig : 0; c->stat_agr[2] += by_round2; c->stat_agr[3] += n_exact;
   c->stat_agr[4] += G - n_elig; c->stat_agr[5] += equations; c->stat_agr[7] += failed_segments;      // counted once the call has succeeded
   return 0;
+}
+int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                        const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t seed[32],
+                                        uint8_t* valid_bitmap) {
+  return aggregate_verify_batch_rlc_impl(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, seed, valid_bitmap, false, "aggregate_verify_batch_rlc");
 }
 
 int blsbn254_set_aggregate_rlc_segments(blsbn254_ctx* c, size_t segments) {

@@ -20,6 +20,7 @@
 #include "lane_ops.h"    // flag constants
 #include "kernels.h"
 #include "key_cache.h"   // the store of prepared keys: its state words and kernels
+#include "msg_distinct.h" // the distinct-message rule of the aggregate verify over groups: its forms, table size and kernels
 #include "seg_plan.h"    // SegLevel, SegLaunch, the planners of the segmented reductions
 #include "keyset_agg_plan.h"   // KaRepack, the argument walk of the checked aggregation over a key set
 #include "keyset_merge_plan.h" // KmRepack, the argument walk of the checked merge over a key set
@@ -206,6 +207,16 @@ struct BNH AgrWs {
   std::vector<uint8_t> h_elig, h_pass, h_bits;
   std::vector<std::pair<size_t, size_t>> ranges;
 };
+// the distinct-message rule of the aggregate verify over groups (host_msg_distinct.hip, k_msg_distinct.hip): per pair the canonical
+// (x, y) of its hash point (18 x N limbs), the slot table (M >= 2 N pair indices), the groups' repeat bytes and their bitmap; the
+// group offsets of blsbn254_hash_distinct_batch (the verify calls pass their own).  Host side: the bitmap as downloaded.
+// blsbn254_msg_distinct_stats, in its order: calls, pairs inserted, groups found repeated, slots of the last call
+struct BNH MdWs {
+  DevBuf key, slots, dup, bits;
+  GroupOff goff;
+  std::vector<uint8_t> h_bits;
+  uint64_t stat[4] = {0, 0, 0, 0};
+};
 // sums of G1 points per key, level by level (host_rlc.hip key_sums; its users: the key round of rlc2_chunk_dev there,
 // aggregate_verify_grouped of host_aggregate.hip and round 1 of host_aggregate_rlc.hip): per level (ping-pong) the keys' chunk
 // counts, their prefix, the chunks' key ids and the chunk sums of one or two point arrays (27 x M limbs each); the chunks' starts
@@ -346,6 +357,7 @@ struct blsbn254_ctx {
   uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
   uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
   AgrWs agr;
+  MdWs md;
   size_t agr_segments = 0;               // blsbn254_set_aggregate_rlc_segments: 0 = the default rule, 1 = no second round, else S
   // calls, groups decided by round 1, by round 2, groups sent to the exact pipeline, ineligible groups, equations checked, calls that
   // did not take round 1, segments that failed
@@ -593,8 +605,29 @@ BNH int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u)
 BNH int agg_keys_prepare(blsbn254_ctx* c, size_t n, size_t u);   // host_aggregate.hip
 // what blsbn254_aggregate_verify_batch and ..._batch_rlc check alike (`call` names the one in the error text); CK_NOTHING: no
 // groups, the caller returns 0
+// ... and the part of it that a call over ragged groups of MESSAGES alone shares (blsbn254_hash_distinct_batch): the context,
+// n_groups == 0, the group and message offsets, the tag, the limits.  missing: an argument of the form's own that every call
+// needs (its outputs, the signatures) is NULL; pair_missing: one that a call with pairs needs (the keys) is.  Neither is read.
+BNH int agg_msg_args(blsbn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                     bool missing, bool pair_missing, const char* call);   // host_aggregate_batch.hip
 BNH int agg_batch_args(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off, const uint8_t* agg_sigs,
                        size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* valid_bitmap, const char* call);   // host_aggregate_batch.hip
+// The distinct-message rule as ONE stage (host_msg_distinct.hip; enqueued): the N points at pts (limb-major, stride `stride`,
+// form MD_AFFINE: x, y / MD_HOMOGENEOUS: x, y, z) of the G groups whose rebased pair offsets lie at d_goff on the device; leaves
+// c->md.dup[g] = 1 for every group with two pairs of the same point.  The table and dup[] are cleared on the stream first.
+BNH int msg_distinct_stage(blsbn254_ctx* c, const int32_t* pts, size_t stride, size_t N, int form, const uint32_t* d_goff, size_t G);
+// ... and its result on the host: c->md.dup packed LSB-first into c->md.h_bits (ceil(G / 8) bytes; synchronises), copied to
+// dup_bitmap unless that is NULL; counts the call
+BNH int msg_distinct_bits(blsbn254_ctx* c, size_t N, size_t G, uint8_t* dup_bitmap);
+// the bodies of blsbn254_aggregate_verify_batch and ..._batch_rlc, argument checks included (`call` names the entry point in the
+// error text): want_dup runs the stage on the hash points of the pipeline and leaves the groups' repeat bits in c->md.h_bits
+// (valid_bitmap is NOT masked here: the _distinct entry points do that); without it they are the calls they were
+BNH int aggregate_verify_batch_impl(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                    const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap, bool want_dup,
+                                    const char* call);   // host_aggregate_batch.hip
+BNH int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
+                                        const uint8_t* agg_sigs, size_t n_groups, const uint8_t* dst, size_t dst_len, const uint8_t* seed,
+                                        uint8_t* valid_bitmap, bool want_dup, const char* call);   // host_aggregate_rlc.hip
 BNH int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out);   // host_verify.hip
 BNH int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip

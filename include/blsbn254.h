@@ -175,9 +175,13 @@ int blsbn254_verify_batch(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* 
                           const uint8_t* sigs, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* valid_bitmap);
 /* valid = prod_i e(H(msg_i), pk_i) * e(agg_sig, -G2gen) == 1, every pk_i valid, n >= 1.
  * PRECONDITION (rogue-key protection, IETF BLS section 3): this is CoreAggregateVerify -- the algebraic check only.  With a
- * basic-scheme tag (the suggested default DST ends in _NUL_) the CALLER must reject batches with repeated messages;
+ * basic-scheme tag (the suggested default DST ends in _NUL_) batches with repeated messages must be rejected;
  * alternatively use a proof-of-possession tag (_POP_) and only keys whose proof passed blsbn254_pop_verify_batch.
- * The library does not detect duplicate messages (the reference has no BLS layer to pin either behaviour). */
+ * THIS call does not detect repeated messages (the reference has no BLS layer to pin either behaviour).  The library checks
+ * the rule on the device, on the hash POINTS: blsbn254_hash_distinct_batch with one group (n_groups = 1, grp_off = {0, n})
+ * gives the rule's bit for the messages of this call, of blsbn254_aggregate_verify_prepared, of
+ * blsbn254_aggregate_partial and of blsbn254_aggregate_verify_multi; the batched calls have forms that apply it
+ * themselves (blsbn254_aggregate_verify_batch_distinct, blsbn254_aggregate_verify_batch_rlc_distinct). */
 int blsbn254_aggregate_verify(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, size_t n,
                               const uint8_t agg_sig[64], const uint8_t* dst, size_t dst_len, int* valid);
 /* blsbn254_aggregate_verify for many independent aggregates in one call: bit g (LSB-first) of valid_bitmap = *valid of
@@ -187,7 +191,8 @@ int blsbn254_aggregate_verify(blsbn254_ctx* ctx, const uint8_t* pks, const uint8
  * A group is valid when it has at least one pair (an empty group is INVALID, as the single call's n == 0), its signature decodes,
  * is not the identity and is on the curve, every key decodes, is not the identity, is on the curve and in the r-torsion, and
  * e(agg_sig, -G2gen) * prod_i e(H(msg_i), pk_i) == 1.  A bad point clears its group's bit and nothing else; it is never an
- * error of the call.  The PRECONDITION of blsbn254_aggregate_verify (rogue keys / repeated messages) holds per group, unchanged.
+ * error of the call.  The PRECONDITION of blsbn254_aggregate_verify (rogue keys / repeated messages) holds per group: this call
+ * does not apply the rule, blsbn254_aggregate_verify_batch_distinct does.
  * Two pairs per lane share one f^2 (the signature's pair, whose -G2gen is a constant and is never validated, included); the hash
  * points never leave the device.  BLSBN254_E_ARG: NULL arguments, decreasing offsets, pairs + n_groups > 2^23 (the signatures'
  * pairs count).  n_groups == 0 returns 0.  Launches span at most BLSBN254_CHUNK_LANES lanes.
@@ -225,7 +230,8 @@ int blsbn254_aggregate_batch_stats(blsbn254_ctx* ctx, uint64_t out[4]);
  * seed = NULL (the production setting): the library draws 32 bytes from the OS (getrandom) inside the call, i.e. after
  * the batch is fixed.  A caller-supplied seed exists for reproducible tests; soundness then rests on that seed being
  * fresh and secret -- never reuse one, never derive it from public data.
- * The PRECONDITION of blsbn254_aggregate_verify (rogue keys / repeated messages) holds per group, unchanged.
+ * The PRECONDITION of blsbn254_aggregate_verify (rogue keys / repeated messages) holds per group: this call does not apply the
+ * rule, blsbn254_aggregate_verify_batch_rlc_distinct does.
  * Pending asynchronous verify calls are settled on entry and none is left pending.
  * blsbn254_aggregate_rlc_stats, since the context was created: out[0] calls, out[1] groups decided by round 1, out[2] groups decided
  * by round 2, out[3] groups sent to the exact pipeline (the eligible groups inside the ranges of the sub-calls: those of failed
@@ -239,6 +245,46 @@ int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* ctx, const uint8_t* pks, c
                                         uint8_t* valid_bitmap /* ceil(n_groups/8) */);
 int blsbn254_set_aggregate_rlc_segments(blsbn254_ctx* ctx, size_t segments);
 int blsbn254_aggregate_rlc_stats(blsbn254_ctx* ctx, uint64_t out[8]);
+/* THE DISTINCT-MESSAGE RULE, checked on the device.  Group g is REPEATED when two of its pairs have the same hash point: equal
+ * affine (x, y) as field elements, under the context's expander and map.  A repeated group under a basic-scheme tag is open to a
+ * rogue key (pk2 = [a] G2gen - pk1, sig = [a] H(m) passes for {(pk1, m), (pk2, m)} with nobody having signed), so the calls below
+ * treat it as INVALID: never an error of the call, and it never touches its neighbours.
+ * POINTS, NOT BYTES: under the try-and-increment maps different messages can share a point (BLSBN254_G1MAP_TAI_DIGEST: the digests
+ * h and h + p; any map of the two: a start value x0 that is no x of the curve and x0 + 1), so comparing message bytes -- all a
+ * caller can do, because the hash points never leave the device -- misses repeats that this rule finds.  Under the RFC 9380 map
+ * the two notions agree up to collisions of the hash.
+ * Scope: the same point in two DIFFERENT groups is no repeat; pairs in front of grp_off[0] belong to no group; an empty group is
+ * not repeated (and stays invalid); key validity plays no part, a pair whose key does not decode still counts.
+ * How: one lane per pair puts (group, canonical x, canonical y) into an open-addressing table of 2^k >= 2 N slots, seeded per
+ * context, with a full comparison of group and point on every taken slot; the result does not depend on the order of arrival.
+ * Memory the stage reserves in the context: 72 bytes per pair for the canonical points, 8 .. 16 bytes per pair for the table,
+ * one byte and one bit per group.
+ *
+ * blsbn254_hash_distinct_batch: bit g (LSB-first) of dup_bitmap = group g is repeated.  Hashes as blsbn254_hash_to_g1_batch does;
+ * msgs / off / grp_off as blsbn254_aggregate_verify_batch takes them; nothing else is computed.  Argument errors, n_groups == 0
+ * (returns 0, nothing written), the all-empty case (all bits 0) and the size limits are those of blsbn254_aggregate_verify_batch.
+ * blsbn254_aggregate_verify_batch_distinct / blsbn254_aggregate_verify_batch_rlc_distinct: bit g of valid_bitmap = bit g of
+ * blsbn254_aggregate_verify_batch (of its _rlc form) on the same arguments AND NOT bit g of dup_bitmap; dup_bitmap may be NULL.
+ * The stage runs on the hash points the call's pipeline has produced anyway (affine in the exact call, homogeneous -- normalised
+ * by one inversion per pair -- in the RLC call): nothing is hashed twice and no point is downloaded.  Everything else, the
+ * counters of blsbn254_aggregate_batch_stats / blsbn254_aggregate_rlc_stats included, is the parent call's.
+ * blsbn254_msg_distinct_stats, since the context was created: out[0] calls that applied the rule, out[1] pairs inserted, out[2]
+ * groups found repeated, out[3] slots of the last call's table.  NULL out: BLSBN254_E_ARG. */
+int blsbn254_hash_distinct_batch(blsbn254_ctx* ctx, const uint8_t* msgs, const uint64_t* off,
+                                 const uint64_t* grp_off /* n_groups+1 */, size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                 uint8_t* dup_bitmap /* ceil(n_groups/8) */);
+int blsbn254_aggregate_verify_batch_distinct(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
+                                             const uint64_t* grp_off /* n_groups+1 */, const uint8_t* agg_sigs /* n_groups*64 */,
+                                             size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                             uint8_t* valid_bitmap /* ceil(n_groups/8) */,
+                                             uint8_t* dup_bitmap /* ceil(n_groups/8), or NULL */);
+int blsbn254_aggregate_verify_batch_rlc_distinct(blsbn254_ctx* ctx, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
+                                                 const uint64_t* grp_off /* n_groups+1 */, const uint8_t* agg_sigs /* n_groups*64 */,
+                                                 size_t n_groups, const uint8_t* dst, size_t dst_len,
+                                                 const uint8_t seed[32] /* NULL: getrandom inside the call */,
+                                                 uint8_t* valid_bitmap /* ceil(n_groups/8) */,
+                                                 uint8_t* dup_bitmap /* ceil(n_groups/8), or NULL */);
+int blsbn254_msg_distinct_stats(blsbn254_ctx* ctx, uint64_t out[4]);
 /* Repeated signers.  blsbn254_verify_batch (and _dev) de-duplicates the public keys of a batch on the GPU (hash table over
  * the 128-byte encodings, full comparison on every hit) and, when at most half of them are distinct (and at most 65536),
  * validates each DISTINCT key once and turns it into its table of 88 line-coefficient triples -- G2Prepared::from,
