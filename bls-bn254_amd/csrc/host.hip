@@ -51,21 +51,13 @@ int blsbn254_ctx_create(int device, blsbn254_ctx** out) {
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return BLSBN254_E_HIP; }
   if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return BLSBN254_E_HIP; }
-  if (getrandom(&c->kd_seed, sizeof c->kd_seed, 0) != (ssize_t)sizeof c->kd_seed) c->kd_seed = 0x5bd1e995u;
+  if (getrandom(&c->kd.seed, sizeof c->kd.seed, 0) != (ssize_t)sizeof c->kd.seed) c->kd.seed = 0x5bd1e995u;
+  c->forms = forms_from_env([](const char* name) -> const char* { return std::getenv(name); }, prop.multiProcessorCount);
   if (const char* e = std::getenv("BLSBN254_AUTO_PREPARE")) c->auto_prepare = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_RLC_GROUP")) { long v = std::atol(e); if (v >= 2 && v <= (long)RLC_MAX_GROUP) { c->r2.group = (size_t)v; c->r2.group_auto = false; } }
-  c->lanes_per_round = (size_t)prop.multiProcessorCount * 256;
   if (const char* e = std::getenv("BLSBN254_RLC_KEY_ROUND")) c->r2.key_round = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_WIDE_FE")) c->wide_fe = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_ASYNC_VERIFY")) c->async_verify = std::atoi(e) != 0;
+  if (const char* e = std::getenv("BLSBN254_ASYNC_VERIFY")) c->vq.async = std::atoi(e) != 0;
   if (const char* e = std::getenv("BLSBN254_KEY_CACHE")) { long v = std::atol(e); if (v >= 0 && v <= (long)PREP_MAX_KEYS) c->kc.max = (size_t)v; }
-  if (const char* e = std::getenv("BLSBN254_QUAD_PREP")) c->quad_prep = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_SPLIT_EASY")) c->split_easy = std::atoi(e) != 0;
-  c->tri_max = c->lanes_per_round / 4;        // four lanes per tuple: one round of waves
-  if (const char* e = std::getenv("BLSBN254_TRI_MILLER")) c->tri_miller = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_TRI_FE")) c->tri_fe = std::atoi(e) != 0;
-  if (const char* e = std::getenv("BLSBN254_TRI_MAX")) { long v = std::atol(e); if (v >= 0 && v <= (1 << 20)) c->tri_max = (size_t)v; }
-  if (const char* e = std::getenv("BLSBN254_WIDE_FE_MAX")) { long v = std::atol(e); if (v >= 0 && v <= (1 << 20)) c->wide_fe_max = (size_t)v; }
   *out = c;
   return 0;
 }
@@ -74,8 +66,8 @@ void blsbn254_ctx_destroy(blsbn254_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);               // nothing is freed while either stream may still run work that touches it
   (void)hipStreamSynchronize(c->stream2);
-  for (auto& pv : c->pend) if (pv.ev) (void)hipEventDestroy(pv.ev);       // pending checks are dropped: the caller did not ask for their results
-  if (c->pend_host) (void)hipHostFree(c->pend_host);
+  for (auto& pv : c->vq.pend) if (pv.ev) (void)hipEventDestroy(pv.ev);       // pending checks are dropped: the caller did not ask for their results
+  if (c->vq.host) (void)hipHostFree(c->vq.host);
   for (auto& kv : c->prof) for (auto& pr : kv.second.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join);
   (void)hipStreamDestroy(c->stream2);
@@ -247,36 +239,27 @@ int read_status(blsbn254_ctx* c, const uint8_t* d_status, int idx, uint8_t* st) 
 int run_final_exp(blsbn254_ctx* c, int32_t* f, size_t n, size_t stride, int mode, const uint8_t* flags, const uint8_t* sub_ok,
                          uint8_t* d_bitmap, uint8_t* d_gt, int* d_is_one) {
   CHECK_LANES(c, stride);
-  for (DevBuf& b : c->fe) HIPCHK(c, b.reserve(stride * 108 * 4));
-  HIPCHK(c, c->fe_slots.reserve(stride * 108 * 4 * 10));
-  int32_t* S = (int32_t*)c->fe_slots.p;
-  int32_t *X = (int32_t*)c->fe[0].p, *A = (int32_t*)c->fe[1].p, *B = (int32_t*)c->fe[2].p, *C = (int32_t*)c->fe[3].p,
-          *B2 = (int32_t*)c->fe[4].p, *D = (int32_t*)c->fe[5].p;
-  // t = f^((p^6-1)(p^2+1)), in place.  From a round of waves up, the ONE Fp inversion of the easy part is shared by four tuples
-  // per lane (head / inv4 / tail, k_fe_easy.hip; the pieces wait in the phase buffers A and B, which the hard part only fills later)
-  if (n >= c->lanes_per_round / 2 && c->split_easy) {
+  for (DevBuf& b : c->fe.ph) HIPCHK(c, b.reserve(stride * 108 * 4));
+  HIPCHK(c, c->fe.slots.reserve(stride * 108 * 4 * 10));
+  int32_t* S = (int32_t*)c->fe.slots.p;
+  int32_t *X = (int32_t*)c->fe.ph[0].p, *A = (int32_t*)c->fe.ph[1].p, *B = (int32_t*)c->fe.ph[2].p, *C = (int32_t*)c->fe.ph[3].p,
+          *B2 = (int32_t*)c->fe.ph[4].p, *D = (int32_t*)c->fe.ph[5].p;
+  // t = f^((p^6-1)(p^2+1)), in place (split: the pieces wait in the phase buffers A and B, which the hard part only fills later)
+  if (fe_easy_split(c->forms, n)) {
     TRY(launch(c, c->stream, "fe_easy_head", grid_lanes(n), k_fe_easy_head, (const int32_t*)f, n, stride, A, B));
     TRY(launch(c, c->stream, "fe_inv4", grid_lanes((n + 3) / 4), k_fe_inv4, B, n, stride));
     TRY(launch(c, c->stream, "fe_easy_tail", grid_lanes(n), k_fe_easy_tail, (const int32_t*)f, f, n, stride, (const int32_t*)A, (const int32_t*)B));
   } else {
     TRY(launch(c, c->stream, "fe_easy", grid_lanes(n), k_fe_easy, (const int32_t*)f, f, n, stride));
   }
-  // Few tuples: the lane-per-tuple kernels below would be the latency of one lane's chain (4.5 ms for any n <= 65536); the hard
-  // part runs with one WAVE per tuple instead (k_fe_wide.hip): ~0.6 ms per round of CUs x 16 tuples.  Same values.
-  if (c->wide_fe && n <= c->wide_fe_max) {
+  // the hard part: the wave and quad forms leave a validity byte per tuple (mode 0), packed behind them
+  const Form form = fe_hard_form(c->forms, n);
+  if (form != Form::LANE) {
     uint8_t* one = nullptr;
-    if (mode == 0) { HIPCHK(c, c->fe_wide_one.reserve(n)); one = (uint8_t*)c->fe_wide_one.p; }
-    TRY(launch(c, c->stream, "fe_hard_wide", grid_wide(n), k_fe_hard_wide, (const int32_t*)f, n, stride, flags, sub_ok, one, d_gt, d_is_one, mode));
-    if (mode == 0) TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)one, n, d_bitmap));
-    return 0;
-  }
-  // Between the wave-per-tuple limit and a quarter of a round of lanes: three lanes per tuple (k_tri.hip) -- the lane-per-tuple
-  // kernels below would cost one lane's whole chain (5.4 ms) however few tuples there are.  Same values.
-  if (n <= c->tri_max && c->tri_fe) {
-    HIPCHK(c, c->tri_vals.reserve(n * TRI_VALUE_LIMBS * 4));
-    uint8_t* one = nullptr;
-    if (mode == 0) { HIPCHK(c, c->fe_wide_one.reserve(n)); one = (uint8_t*)c->fe_wide_one.p; }
-    TRY(launch(c, c->stream, "fe_tri_hard", grid_tri(n), k_fe_tri_hard, (const int32_t*)f, n, stride, (int32_t*)c->tri_vals.p, flags, sub_ok, one, d_gt, d_is_one, mode));
+    if (form == Form::TRI) HIPCHK(c, c->fe.tri.reserve(n * TRI_VALUE_LIMBS * 4));
+    if (mode == 0) { HIPCHK(c, c->fe.one.reserve(n)); one = (uint8_t*)c->fe.one.p; }
+    if (form == Form::WIDE) TRY(launch(c, c->stream, "fe_hard_wide", grid_wide(n), k_fe_hard_wide, (const int32_t*)f, n, stride, flags, sub_ok, one, d_gt, d_is_one, mode));
+    else TRY(launch(c, c->stream, "fe_tri_hard", grid_tri(n), k_fe_tri_hard, (const int32_t*)f, n, stride, (int32_t*)c->fe.tri.p, flags, sub_ok, one, d_gt, d_is_one, mode));
     if (mode == 0) TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)one, n, d_bitmap));
     return 0;
   }
@@ -294,14 +277,13 @@ int miller_to_ws(blsbn254_ctx* c, const uint8_t* d_g1, const uint8_t* d_g2, size
   CHECK_LANES(c, n);
   HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
   HIPCHK(c, c->status.reserve(n));
-  if (c->wide_fe && n <= c->wide_fe_max / 2) {        // few pairs: one wave per pair (lane 0 runs the G2 point arithmetic); the serial part makes the chain ~2 x a prepared one
-    TRY(launch(c, c->stream, "miller_wide_1", grid_wide(n), k_miller_wide_1, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p));
-  } else if (n <= c->tri_max && c->tri_miller) {      // mid-size: a quad of lanes per pair (k_tri.hip: line steps four lanes per point, f three lanes per value)
-    TRY(launch(c, c->stream, "miller_tri_1", grid_tri(n), k_miller_tri_1, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p));
-  } else {
-    TRY(launch(c, c->stream, "miller_1", grid_lanes(n), k_miller_1, d_g1, d_g2, n, (int32_t*)c->f_ws.p, n, (uint8_t*)c->status.p));
+  int32_t* f = (int32_t*)c->f_ws.p; uint8_t* st = (uint8_t*)c->status.p;
+  switch (miller_form(c->forms, n)) {
+    case Form::WIDE: return launch(c, c->stream, "miller_wide_1", grid_wide(n), k_miller_wide_1, d_g1, d_g2, n, f, n, st);
+    case Form::TRI: return launch(c, c->stream, "miller_tri_1", grid_tri(n), k_miller_tri_1, d_g1, d_g2, n, f, n, st);
+    case Form::LANE: break;
   }
-  return 0;
+  return launch(c, c->stream, "miller_1", grid_lanes(n), k_miller_1, d_g1, d_g2, n, f, n, st);
 }
 int decode_status_rc(blsbn254_ctx* c, const uint8_t* d_status, size_t n) {
   int bad;

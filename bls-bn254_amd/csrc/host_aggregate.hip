@@ -47,22 +47,21 @@ static int verdict_arm(blsbn254_ctx* c, int** d) {
 }
 static int verdict_read(blsbn254_ctx* c, int h[VW_WORDS]) { return download(c, h, c->misc.p, 4 * VW_WORDS); }
 
-// The table-only Miller loop over n pairs off the raw line tables: the rule is host_common.h's, written out here and nowhere else.
+// The table-only Miller loop over n pairs off the raw line tables, in the form launch_forms.h names
 int launch_miller_raw(blsbn254_ctx* c, const int32_t* h, size_t h_stride, const uint32_t* kid, RawTables kt, size_t n, const uint8_t* st, unsigned forms,
                       size_t* left) {
-  const auto wide = [&](size_t m) { return (forms & MR_WIDE) && c->wide_fe && m <= c->wide_fe_max; };     // a handful of pairs: one WAVE per pair
-  const auto tri = [&](size_t m) { return (forms & MR_TRI) && c->tri_miller && m <= c->tri_max; };        // a few thousand pairs: a quad of lanes per pair
-  // few pairs: the launch is the latency of one wave, so one pair per lane (no shared f^2, shorter chain); else two per lane
-  const bool one = (forms & MR_ONE) && (n * 2 <= c->lanes_per_round || !(forms & MR_TWO) || n > c->chunk);
-  const bool two = !wide(n) && !tri(n) && !one;
+  const bool two = raw_two_per_lane(c->forms, n, forms, c->chunk);
   *left = two ? (n + 1) / 2 : n;
   HIPCHK(c, c->f_ws.reserve(*left * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
   int32_t* f = (int32_t*)c->f_ws.p; uint8_t* flags = (uint8_t*)c->flags.p;
   if (two) return launch(c, c->stream, "miller_hpk2p", grid_lanes(*left), k_miller_hpk2p, h, h_stride, kid, kt.raw, kt.ok, n, f, *left, flags, st);
   return for_chunks(c, n, [&](size_t lo, size_t m) -> int {
     const uint8_t* s = st ? st + lo : nullptr;
-    if (wide(m)) return launch(c, c->stream, "miller_wide_1p", grid_wide(m), k_miller_wide_1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
-    if (tri(m)) return launch(c, c->stream, "miller_tri_1p", grid_tri(m), k_miller_tri_1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
+    switch (table_miller_form(c->forms, m, forms)) {
+      case Form::WIDE: return launch(c, c->stream, "miller_wide_1p", grid_wide(m), k_miller_wide_1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
+      case Form::TRI: return launch(c, c->stream, "miller_tri_1p", grid_tri(m), k_miller_tri_1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
+      case Form::LANE: break;
+    }
     return launch(c, c->stream, "miller_hpk1p", grid_lanes(m), k_miller_hpk1p, h + lo, h_stride, kid + lo, kt.raw, kt.ok, m, f + lo, n, flags + lo, s);
   });
 }
@@ -72,17 +71,17 @@ int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u) {
   HIPCHK(c, hipMemcpyAsync((uint8_t*)c->in_a.p + 128 * n, NEG_G2_BYTES, 128, hipMemcpyHostToDevice, c->stream));   // "pair n": the key of the signatures' pairs
   return dedup_keys(c, (const uint8_t*)c->in_a.p, n, u);
 }
-// the `keys` keys of c->in_a that kd_keys names become raw line tables on the second stream, ev_join behind them
+// the `keys` keys of c->in_a that kd.keys names become raw line tables on the second stream, ev_join behind them
 static int raw_tables_fork(blsbn254_ctx* c, size_t keys) {
-  HIPCHK(c, c->prep_ok.reserve(keys)); HIPCHK(c, c->prep_raw.reserve(keys * PREP_RAW_LIMBS * 4));
+  HIPCHK(c, c->prep.ok.reserve(keys)); HIPCHK(c, c->prep.raw.reserve(keys * PREP_RAW_LIMBS * 4));
   HIPCHK(c, fork_stream2(c));
-  TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd_keys.p, keys, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, nullptr));
+  TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd.keys.p, keys, (int32_t*)c->prep.raw.p, (uint8_t*)c->prep.ok.p, nullptr));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   return 0;
 }
 int agg_keys_prepare(blsbn254_ctx* c, size_t n, size_t u) {
-  c->last_key = (uint32_t)n;                            // context-owned: nothing waits for this copy (dedup_keys has waited for all before it)
-  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_keys.p + u, &c->last_key, 4, hipMemcpyHostToDevice, c->stream));
+  c->kd.last_key = (uint32_t)n;                            // context-owned: nothing waits for this copy (dedup_keys has waited for all before it)
+  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd.keys.p + u, &c->kd.last_key, 4, hipMemcpyHostToDevice, c->stream));
   return raw_tables_fork(c, u + 1);
 }
 // prod_i ML(H(msg_i), pk_i) over the caller's n pairs, optionally times ML(extra_sig, -G2gen): the aggregate signature
@@ -122,7 +121,7 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
     size_t u = 0;
     TRY(dedup_keys(c, (const uint8_t*)c->in_a.p, np, &u));
     if (u * 2 <= np && u <= PREP_MAX_KEYS) {
-      HIPCHK(c, c->prep_table.reserve(64));
+      HIPCHK(c, c->prep.table.reserve(64));
       TRY(raw_tables_fork(c, u));
       TRY(dedup_key_ids(c, np, u, false));   // no sorting here: no histogram
       prepared = true;
@@ -139,7 +138,7 @@ static int aggregate_partial_impl(blsbn254_ctx* c, const uint8_t* pks, const uin
     // few distinct keys: every key (and -G2gen, when the signature's pair is carried) was validated and turned into its line
     // table once, beside hash-to-G1; the pairs read their lines from those tables
     HIPCHK(c, join_stream2(c));
-    TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, {(const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p}, np, nullptr,
+    TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd.kid.p, {(const int32_t*)c->prep.raw.p, (const uint8_t*)c->prep.ok.p}, np, nullptr,
                           MR_TWO, &left));
   } else {
     TRY(launch(c, c->stream, "miller_hpk2", grid_lanes(left), k_miller_hpk2, (const int32_t*)c->h_ws.p, (const uint8_t*)c->in_a.p, np, (int32_t*)c->q_ws.p,
@@ -224,8 +223,8 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(upload(c, c->in_b, agg_sig, 64));
   size_t u = 0;
   TRY(agg_keys_stage(c, pks, n, &u));
-  // few pairs: from tables, one wave per pair (or, up to tri_max pairs, a quad of lanes per pair), whatever the keys
-  const bool small = small_for_prepared(c, n + 1, false);      // n + 1: the signature's pair joins the launch; one final exponentiation in all
+  // few pairs: from tables, one wave or a quad of lanes per pair, whatever the keys
+  const bool small = small_for_prepared(c->forms, n + 1, false);      // n + 1: the signature's pair joins the launch; one final exponentiation in all
   if (!((u * 2 <= n || small) && u + 1 <= PREP_MAX_KEYS)) return 0;
   *took = true;
   const size_t np = u + 1;
@@ -234,8 +233,8 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve((np + 1) / 2 * 108 * 4)); HIPCHK(c, c->flags.reserve(np)); HIPCHK(c, c->status.reserve(np + 8)); HIPCHK(c, c->misc.reserve(64));
   HIPCHK(c, c->rlc.b.reserve(np * 18 * 4)); HIPCHK(c, c->rlc.idx.reserve(4 * np));
   TRY(dedup_key_ids(c, n, u, true));
-  TRY(key_sorted_order(c, (const uint32_t*)c->kd_kid.p, n, u));                 // cursor[k] is now the END of run k
-  const uint32_t *hist = (const uint32_t*)c->kd_hist.p, *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p, *kid = (const uint32_t*)c->kd_kid.p;
+  TRY(key_sorted_order(c, (const uint32_t*)c->kd.kid.p, n, u));                 // cursor[k] is now the END of run k
+  const uint32_t *hist = (const uint32_t*)c->kd.hist.p, *cursor = (const uint32_t*)c->kd.cursor.p, *perm = (const uint32_t*)c->kd.perm.p, *kid = (const uint32_t*)c->kd.kid.p;
   TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, n,
              (uint8_t*)nullptr, 3));
   // sums per key: the tuples in sorted order (columns perm[s] of h_ws) -> one sum per key (key_sums)
@@ -251,13 +250,13 @@ static int aggregate_verify_grouped(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(launch(c, c->stream, "iota", grid_lanes(np), k_iota_u32, kid2, (uint32_t)np));
   HIPCHK(c, join_stream2(c));
   size_t left;
-  TRY(launch_miller_raw(c, h2, np, kid2, {(const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p}, np, st, MR_ALL, &left));
+  TRY(launch_miller_raw(c, h2, np, kid2, {(const int32_t*)c->prep.raw.p, (const uint8_t*)c->prep.ok.p}, np, st, MR_ALL, &left));
   TRY(launch(c, c->stream, "and_reduce", grid_lanes(u), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, u, d_ok + VW_KEYS));
   TRY(product_is_one(c, (int32_t*)c->f_ws.p, left, d_ok + VW_IS_ONE));
   int h[VW_WORDS];
   TRY(verdict_read(c, h));
   *valid = (h[VW_KEYS] == 1 && (h[VW_SIG] & 0xff) == 1 && h[VW_IS_ONE] == 1) ? 1 : 0;
-  ++c->stat_grouped_aggregates;
+  ++c->agg_stat[0];
   return 0;
 }
 int blsbn254_aggregate_verify(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, size_t n,
@@ -268,13 +267,13 @@ int blsbn254_aggregate_verify(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
   if (n + 1 > MAX_LANES) { c->last_error = "more than 2^23 - 1 pairs in one aggregate_verify call"; return BLSBN254_E_ARG; }
   uint8_t ml[384]; int ok = 0, sig_ok = 0, v = 0;
   bool staged = false;
-  if (c->auto_prepare && (n >= 1024 || (c->wide_fe && n + 1 <= c->wide_fe_max))) {   // repeated keys (or few pairs): one pair per distinct key
+  if (c->auto_prepare && (n >= 1024 || grouped_whatever_keys(c->forms, n + 1))) {   // repeated keys (or few pairs): one pair per distinct key
     bool took = false;
     TRY(aggregate_verify_grouped(c, pks, msgs, off, n, agg_sig, dst, dst_len, valid, &took));
     if (took) return 0;
     staged = true;
   }
-  ++c->stat_pairwise_aggregates;
+  ++c->agg_stat[1];
   TRY(aggregate_partial_impl(c, pks, msgs, off, n, dst, dst_len, agg_sig, ml, &ok, &sig_ok, staged));
   TRY(blsbn254_aggregate_finish(c, ml, 1, nullptr, &v));
   *valid = (ok == 1 && sig_ok == 1 && v == 1) ? 1 : 0;
@@ -289,16 +288,16 @@ int blsbn254_multi_miller_loop_prepared(blsbn254_ctx* c, const blsbn254_g2prepar
   if (n == 0) { std::memset(ml_out, 0, 384); ml_out[31] = 1; return 0; }
   CHECK_LANES(c, n);
   ENTER(c);
-  HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 1)));
+  HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->status.reserve(n)); HIPCHK(c, c->kd.hist.reserve(4 * (keys->u + 1)));
   TRY(upload(c, c->in_a, g1, 64 * n));
-  TRY(upload(c, c->kd_kid, key_idx, 4 * n));
-  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", false));
+  TRY(upload(c, c->kd.kid, key_idx, 4 * n));
+  TRY(check_key_indices(c, (const uint32_t*)c->kd.kid.p, n, keys->u, (uint32_t*)c->kd.hist.p, "pair", false));
   int bad;
   TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(n), k_g1_to_ws_batch, (const uint8_t*)c->in_a.p, n, (int32_t*)c->h_ws.p, (uint8_t*)c->status.p));
   TRY(first_bad(c, (const uint8_t*)c->status.p, n, 1, 1, &bad));
   if (bad >= 0) return BLSBN254_ERR_G1;
   size_t left;                                               // few pairs: one wave per pair, product of n values instead of n / 2
-  TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd_kid.p, {(const int32_t*)keys->raw.p, (const uint8_t*)keys->ok.p}, n,
+  TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, n, (const uint32_t*)c->kd.kid.p, {(const int32_t*)keys->raw.p, (const uint8_t*)keys->ok.p}, n,
                         (const uint8_t*)c->status.p, MR_WIDE | MR_TWO, &left));
   TRY(first_bad(c, (const uint8_t*)c->flags.p, n, 1, 1, &bad));
   if (bad >= 0) return BLSBN254_ERR_G2;
@@ -319,19 +318,19 @@ int blsbn254_aggregate_verify_prepared(blsbn254_ctx* c, const blsbn254_g2prepare
   uint32_t dl;
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off, n));
-  HIPCHK(c, c->in_b.reserve(64)); HIPCHK(c, c->kd_kid.reserve(4 * np)); HIPCHK(c, c->h_ws.reserve(np * 18 * 4)); HIPCHK(c, c->kd_hist.reserve(4 * (keys->u + 2)));
+  HIPCHK(c, c->in_b.reserve(64)); HIPCHK(c, c->kd.kid.reserve(4 * np)); HIPCHK(c, c->h_ws.reserve(np * 18 * 4)); HIPCHK(c, c->kd.hist.reserve(4 * (keys->u + 2)));
   const uint32_t sig_key = (uint32_t)keys->u;
-  HIPCHK(c, hipMemcpyAsync(c->kd_kid.p, key_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd_kid.p + n, &sig_key, 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->kd.kid.p, key_idx, 4 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync((uint32_t*)c->kd.kid.p + n, &sig_key, 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->in_b.p, agg_sig, 64, hipMemcpyHostToDevice, c->stream));
   int* d_ok;
   TRY(verdict_arm(c, &d_ok));                           // the armed index shares its upload with the two validity words
-  TRY(check_key_indices(c, (const uint32_t*)c->kd_kid.p, n, keys->u, (uint32_t*)c->kd_hist.p, "pair", true));   // its read-back also waits for the copy of sig_key (on the stack)
+  TRY(check_key_indices(c, (const uint32_t*)c->kd.kid.p, n, keys->u, (uint32_t*)c->kd.hist.p, "pair", true));   // its read-back also waits for the copy of sig_key (on the stack)
   TRY(launch_hash_to_g1(c, c->stream, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, n, dl, (int32_t*)c->h_ws.p, np,
              (uint8_t*)nullptr, 0));
   TRY(launch(c, c->stream, "g1_to_ws", grid_lanes(1), k_g1_to_ws, (const uint8_t*)c->in_b.p, (int32_t*)c->h_ws.p, n, np, (uint8_t*)(d_ok + VW_SIG)));
   size_t left;
-  TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd_kid.p, {(const int32_t*)keys->raw.p, (const uint8_t*)keys->ok.p}, np, nullptr,
+  TRY(launch_miller_raw(c, (const int32_t*)c->h_ws.p, np, (const uint32_t*)c->kd.kid.p, {(const int32_t*)keys->raw.p, (const uint8_t*)keys->ok.p}, np, nullptr,
                         MR_TWO, &left));
   TRY(launch(c, c->stream, "and_reduce", grid_lanes(n), k_and_reduce, (const uint8_t*)c->flags.p, (const uint8_t*)c->flags.p, n, d_ok + VW_KEYS));
   TRY(product_is_one(c, (int32_t*)c->f_ws.p, left, d_ok + VW_IS_ONE));
@@ -366,7 +365,7 @@ int blsbn254_aggregate_sigs(blsbn254_ctx* c, const uint8_t* sigs, size_t n, uint
   return g1_sum_to_bytes(c, n, out);
 }
 // The first half of threshold_combine and lagrange_at_zero: t ids (32 bytes each, the caller's) -> their Lagrange coefficients at
-// zero in c->scalars (t x 32 bytes big-endian) and as GLV halves in c->th_glv, over t x S lanes (S ~ sqrt(t) slices: critical
+// zero in c->scalars (t x 32 bytes big-endian) and as GLV halves in c->th.glv, over t x S lanes (S ~ sqrt(t) slices: critical
 // path 2 (t / S + S) products).  Left for the caller: the ids' decode status in c->status[0 .. t) (room for t more bytes behind
 // them), their duplicate marks in c->flags, and two armed "first bad index" words at c->misc.
 static int lagrange_enqueue(blsbn254_ctx* c, const uint8_t* ids, size_t t) {
@@ -374,16 +373,16 @@ static int lagrange_enqueue(blsbn254_ctx* c, const uint8_t* ids, size_t t) {
   while (S < 64 && S * S < t) ++S;
   const size_t J = (t + S - 1) / S;
   HIPCHK(c, c->scalars.reserve(32 * t)); HIPCHK(c, c->status.reserve(2 * t)); HIPCHK(c, c->flags.reserve(t)); HIPCHK(c, c->misc.reserve(64));
-  HIPCHK(c, c->th_x.reserve(9 * t * 4)); HIPCHK(c, c->th_num.reserve(9 * t * S * 4)); HIPCHK(c, c->th_den.reserve(9 * t * S * 4)); HIPCHK(c, c->th_glv.reserve(9 * t * 4));
+  HIPCHK(c, c->th.x.reserve(9 * t * 4)); HIPCHK(c, c->th.num.reserve(9 * t * S * 4)); HIPCHK(c, c->th.den.reserve(9 * t * S * 4)); HIPCHK(c, c->th.glv.reserve(9 * t * 4));
   uint8_t* dup = (uint8_t*)c->flags.p;
   TRY(upload(c, c->in_b, ids, 32 * t));
   TRY(min_index_arm(c, (int*)c->misc.p, 2));
   HIPCHK(c, hipMemsetAsync(dup, 0, t, c->stream));
-  TRY(launch(c, c->stream, "fr_decode", grid_lanes(t), k_fr_decode, (const uint8_t*)c->in_b.p, t, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
-  TRY(launch(c, c->stream, "lagrange_partial", Shape{dim3(nblocks(t), (unsigned)S), dim3(256)}, k_lagrange_partial, (const int32_t*)c->th_x.p, t, J,
-             (int32_t*)c->th_num.p, (int32_t*)c->th_den.p, dup));
-  return launch(c, c->stream, "lagrange_finish", grid_lanes(t), k_lagrange_finish, (const int32_t*)c->th_num.p, (const int32_t*)c->th_den.p, t, S, (uint8_t*)c->scalars.p,
-                (uint32_t*)c->th_glv.p);
+  TRY(launch(c, c->stream, "fr_decode", grid_lanes(t), k_fr_decode, (const uint8_t*)c->in_b.p, t, (int32_t*)c->th.x.p, (uint8_t*)c->status.p));
+  TRY(launch(c, c->stream, "lagrange_partial", Shape{dim3(nblocks(t), (unsigned)S), dim3(256)}, k_lagrange_partial, (const int32_t*)c->th.x.p, t, J,
+             (int32_t*)c->th.num.p, (int32_t*)c->th.den.p, dup));
+  return launch(c, c->stream, "lagrange_finish", grid_lanes(t), k_lagrange_finish, (const int32_t*)c->th.num.p, (const int32_t*)c->th.den.p, t, S, (uint8_t*)c->scalars.p,
+                (uint32_t*)c->th.glv.p);
 }
 // ... and the ids' checks, folded into misc[0]: decoded, non-zero (status 1) and pairwise distinct (dup 0)
 static int lagrange_ids_reduce(blsbn254_ctx* c, size_t t) {
@@ -396,14 +395,14 @@ static int lagrange_ids_reduce(blsbn254_ctx* c, size_t t) {
 // large groups through it, host_threshold_batch.hip)
 int threshold_combine_one(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]) {
   size_t n_chunks = (2 * t + 255) / 256;
-  HIPCHK(c, c->out.reserve(64)); HIPCHK(c, c->th_part.reserve(27 * 32 * n_chunks * 4)); HIPCHK(c, c->th_part2.reserve(27 * 32 * ((n_chunks + 1) / 2) * 4));
+  HIPCHK(c, c->out.reserve(64)); HIPCHK(c, c->th.part.reserve(27 * 32 * n_chunks * 4)); HIPCHK(c, c->th.part2.reserve(27 * 32 * ((n_chunks + 1) / 2) * 4));
   TRY(upload(c, c->in_a, partial_sigs, 64 * t));
   TRY(lagrange_enqueue(c, ids, t));
   uint8_t* st_pts = (uint8_t*)c->status.p + t;
   int* d_bad = (int*)c->misc.p;
-  TRY(launch(c, c->stream, "msm_window", Shape{dim3((unsigned)n_chunks, 32), dim3(256)}, k_msm_window, (const uint8_t*)c->in_a.p, (const uint32_t*)c->th_glv.p, t,
-             (int32_t*)c->th_part.p, st_pts));
-  int32_t* pa = (int32_t*)c->th_part.p; int32_t* pb = (int32_t*)c->th_part2.p;
+  TRY(launch(c, c->stream, "msm_window", Shape{dim3((unsigned)n_chunks, 32), dim3(256)}, k_msm_window, (const uint8_t*)c->in_a.p, (const uint32_t*)c->th.glv.p, t,
+             (int32_t*)c->th.part.p, st_pts));
+  int32_t* pa = (int32_t*)c->th.part.p; int32_t* pb = (int32_t*)c->th.part2.p;
   while (n_chunks > 16) {                                  // large t only: fold the chunk axis pairwise
     const size_t no = (n_chunks + 1) / 2;
     TRY(launch(c, c->stream, "msm_fold", grid_lanes(no * 32), k_msm_fold, (const int32_t*)pa, n_chunks, pb));

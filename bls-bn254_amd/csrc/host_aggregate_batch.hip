@@ -46,7 +46,7 @@ int aggregate_verify_batch_impl(blsbn254_ctx* c, const uint8_t* pks, const uint8
   ENTER(c);                                             // settles pending asynchronous verify calls BEFORE the tag is staged
   if (N == 0) {                                         // every group is empty: invalid, as the single call's n == 0 (nothing to launch)
     std::memset(valid_bitmap, 0, (G + 7) / 8);
-    c->stat_agb[0] += G;
+    c->agb.stat[0] += G;
     if (want_dup) { c->md.h_bits.assign((G + 7) / 8, 0); ++c->md.stat[0]; c->md.stat[3] = 0; }      // ... and none is repeated
     return 0;
   }
@@ -111,7 +111,7 @@ int aggregate_verify_batch_impl(blsbn254_ctx* c, const uint8_t* pks, const uint8
   }
   TRY(pc_finish_bitmap(c, G, valid_bitmap));
   if (want_dup) TRY(msg_distinct_bits(c, N, G, nullptr));
-  c->stat_agb[0] += G; c->stat_agb[1] += lanes; c->stat_agb[3] += launches.size();      // counted once the call has succeeded
+  c->agb.stat[0] += G; c->agb.stat[1] += lanes; c->agb.stat[3] += launches.size();      // counted once the call has succeeded
   return 0;
 }
 int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
@@ -119,10 +119,6 @@ int blsbn254_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const u
   return aggregate_verify_batch_impl(c, pks, msgs, off, grp_off, agg_sigs, n_groups, dst, dst_len, valid_bitmap, false, "aggregate_verify_batch");
 }
 
-int blsbn254_aggregate_batch_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_agb[i];
-  return 0;
-}
+int blsbn254_aggregate_batch_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, agb.stat, 4, out); }
 
 }  // extern "C"

@@ -23,13 +23,13 @@ static int agr_round(blsbn254_ctx* c, size_t N, size_t G, size_t u, size_t S, si
   const uint32_t u32 = (uint32_t)u, S32 = (uint32_t)S;
   uint32_t* vkid = (uint32_t*)w.vkid.p;
   HIPCHK(c, w.mkid.reserve(4 * V));
-  TRY(launch(c, c->stream, "agr_items", grid_lanes(items), k_agr_items, (const uint32_t*)w.gidx.p, (const uint32_t*)c->kd_kid.p, d_seg_of, N, G, u32, S32, (int32_t*)w.w.p, W,
+  TRY(launch(c, c->stream, "agr_items", grid_lanes(items), k_agr_items, (const uint32_t*)w.gidx.p, (const uint32_t*)c->kd.kid.p, d_seg_of, N, G, u32, S32, (int32_t*)w.w.p, W,
              vkid, (uint32_t*)w.mkid.p));
   // the items' histogram over the virtual keys (every id is below V by construction: the check cannot fail), the sorted order, the sums
-  HIPCHK(c, c->kd_hist.reserve(4 * (V + 2)));
-  TRY(check_key_indices(c, vkid, items, V, (uint32_t*)c->kd_hist.p, "pair", false));
+  HIPCHK(c, c->kd.hist.reserve(4 * (V + 2)));
+  TRY(check_key_indices(c, vkid, items, V, (uint32_t*)c->kd.hist.p, "pair", false));
   TRY(key_sorted_order(c, vkid, items, V));
-  const uint32_t *hist = (const uint32_t*)c->kd_hist.p, *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p;
+  const uint32_t *hist = (const uint32_t*)c->kd.hist.p, *cursor = (const uint32_t*)c->kd.cursor.p, *perm = (const uint32_t*)c->kd.perm.p;
   const int32_t* pts = nullptr;
   TRY(key_sums(c, (const int32_t*)w.w.p, nullptr, W, perm, perm, vkid, hist, cursor, items, V, &pts, nullptr));
   // the V pairs (sum, its key's table); a sum that is the identity contributes 1 (status bit 1: the loops' skip)
@@ -37,7 +37,7 @@ static int agr_round(blsbn254_ctx* c, size_t N, size_t G, size_t u, size_t S, si
   TRY(launch(c, c->stream, "g1p_to_h", grid_lanes(V), k_g1p_to_h_affine, pts, V, V, (int32_t*)w.h2.p, V, (uint8_t*)w.st.p));
   // S > 1: never two slots per lane, because a lane's value must belong to ONE segment slot
   size_t f_cnt;
-  TRY(launch_miller_raw(c, (const int32_t*)w.h2.p, V, (const uint32_t*)w.mkid.p, {(const int32_t*)c->prep_raw.p, (const uint8_t*)c->prep_ok.p}, V, (const uint8_t*)w.st.p,
+  TRY(launch_miller_raw(c, (const int32_t*)w.h2.p, V, (const uint32_t*)w.mkid.p, {(const int32_t*)c->prep.raw.p, (const uint8_t*)c->prep.ok.p}, V, (const uint8_t*)w.st.p,
                         S == 1 ? MR_ALL : MR_ALL & ~MR_TWO, &f_cnt));
   int32_t* f = (int32_t*)c->f_ws.p;
   // (the loops' flags are not read: a key that is not valid belongs to ineligible groups only, so its sums are the identity)
@@ -93,7 +93,7 @@ int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const u
   const size_t nb = (G + 7) / 8;
   if (N == 0) {                                         // every group is empty: invalid, nothing to launch
     std::memset(valid_bitmap, 0, nb);
-    ++c->stat_agr[0]; c->stat_agr[4] += G;
+    ++c->agr.stat[0]; c->agr.stat[4] += G;
     if (want_dup) { c->md.h_bits.assign(nb, 0); ++c->md.stat[0]; c->md.stat[3] = 0; }      // ... and none is repeated
     return 0;
   }
@@ -105,7 +105,7 @@ int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const u
   TRY(agg_keys_stage(c, pks + 128 * base, N, &u));     // the keys with -G2gen as "pair N" (the key of the signatures' slots), de-duplicated
   if (!agr_keys_repeat(N, u, PREP_MAX_KEYS)) {          // nothing to share per key: the call is the exact call
     TRY(aggregate_verify_batch_impl(c, pks, msgs, off, grp_off, agg_sigs, G, dst, dst_len, valid_bitmap, want_dup, call));
-    ++c->stat_agr[0]; ++c->stat_agr[6]; c->stat_agr[3] += G;
+    ++c->agr.stat[0]; ++c->agr.stat[6]; c->agr.stat[3] += G;
     return 0;
   }
   TRY(stage_seed(c, w.seed, seed));
@@ -125,7 +125,7 @@ int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const u
              (uint8_t*)nullptr, 3));
   if (want_dup) TRY(msg_distinct_stage(c, (const int32_t*)c->h_ws.p, N, N, MD_HOMOGENEOUS, (const uint32_t*)w.goff.d.p, G));
   HIPCHK(c, join_stream2(c));                           // the keys' validity bytes are final
-  TRY(launch(c, c->stream, "agr_group", grid_lanes(G), k_agr_group, (const uint8_t*)c->in_b.p, (const uint32_t*)w.goff.d.p, (const uint32_t*)c->kd_kid.p, (const uint8_t*)c->prep_ok.p, (const uint8_t*)w.seed.p, G,
+  TRY(launch(c, c->stream, "agr_group", grid_lanes(G), k_agr_group, (const uint8_t*)c->in_b.p, (const uint32_t*)w.goff.d.p, (const uint32_t*)c->kd.kid.p, (const uint8_t*)c->prep.ok.p, (const uint8_t*)w.seed.p, G,
              (uint8_t*)w.sig_ok.p, (uint8_t*)w.elig.p, (uint2*)w.wt.p, (int32_t*)w.w.p, W, N));
   TRY(launch(c, c->stream, "agr_weigh", grid_lanes((N + 1) / 2), k_agr_weigh, (const int32_t*)c->h_ws.p, N, (const uint32_t*)w.gidx.p, (const uint8_t*)w.elig.p,
              (const uint2*)w.wt.p, (int32_t*)w.w.p, W));
@@ -165,8 +165,8 @@ int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const u
     }
   }
   if (want_dup) TRY(msg_distinct_bits(c, N, G, nullptr));
-  ++c->stat_agr[0]; c->stat_agr[1] += pass1 ? n_elig : 0; c->stat_agr[2] += by_round2; c->stat_agr[3] += n_exact;
-  c->stat_agr[4] += G - n_elig; c->stat_agr[5] += equations; c->stat_agr[7] += failed_segments;      // counted once the call has succeeded
+  ++c->agr.stat[0]; c->agr.stat[1] += pass1 ? n_elig : 0; c->agr.stat[2] += by_round2; c->agr.stat[3] += n_exact;
+  c->agr.stat[4] += G - n_elig; c->agr.stat[5] += equations; c->agr.stat[7] += failed_segments;      // counted once the call has succeeded
   return 0;
 }
 int blsbn254_aggregate_verify_batch_rlc(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint64_t* grp_off,
@@ -180,10 +180,6 @@ int blsbn254_set_aggregate_rlc_segments(blsbn254_ctx* c, size_t segments) {
   c->agr_segments = segments;
   return 0;
 }
-int blsbn254_aggregate_rlc_stats(blsbn254_ctx* c, uint64_t out[8]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 8; ++i) out[i] = c->stat_agr[i];
-  return 0;
-}
+int blsbn254_aggregate_rlc_stats(blsbn254_ctx* c, uint64_t out[8]) { return COPY_STATS(c, agr.stat, 8, out); }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
-// host_common.h -- shared by the host-side translation units (host*.hip): the context, device buffers, one workspace struct per
-// pipeline (MsmWs ... AgrWs; the batch verification by random linear combination of host_rlc.hip: KeySumWs, Rlc2Ws, RlcWs, with
-// its host-only rules in rlc_plan.h), the launch helper and the internal helpers one pipeline borrows from another (the size
-// rules of the two table-only Miller loops among them: launch_miller_prepared, host_verify.hip, over the expanded pair tables;
-// launch_miller_raw, host_aggregate.hip, over the raw line tables).  Nothing here is exported (BNH = hidden visibility); the C
-// ABI is include/blsbn254.h.  There is no CPU fallback anywhere on the host side: every entry point launches kernels or fails.
+// host_common.h -- shared by the host-side translation units (host*.hip): device buffers, ONE workspace struct per pipeline
+// holding its buffers, the host copies its uploads read, its settings and its counters (MsmWs ... MdWs; the verify path: FeWs,
+// KeyDedupWs, PrepWs, KeyStore, VerifyQueue; the batch verification by random linear combination: KeySumWs, Rlc2Ws, RlcWs), the
+// context that holds one of each beside the staging buffers all pipelines share, the launch helper and the internal helpers one
+// pipeline borrows from another.  The host-only rules live in plan headers without HIP: launch_forms.h (which device form runs at
+// which size: the context's `forms`, asked by every launcher), rlc_plan.h, seg_plan.h and the keyset / aggregate plans.  Nothing
+// here is exported (BNH = hidden visibility); the C ABI is include/blsbn254.h.  There is no CPU fallback anywhere on the host
+// side: every entry point launches kernels or fails.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/random.h>
@@ -30,6 +32,7 @@
 #include "keyset_committee_merge_plan.h" // KcmRepack, the argument walk of the checked merge per committee of a key set
 #include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
 #include "aggregate_rlc_plan.h" // the segments and exact ranges of the aggregate verify over groups by random linear combination
+#include "launch_forms.h"      // LaunchForms and THE rule of every launcher: which device form runs at which size
 #include "rlc_plan.h"          // the chunk size, the bounds and the key round's back-off of the batch verification by random linear combination
 #include "../../include/blsbn254.h"
 
@@ -58,7 +61,8 @@ struct BNH DevBuf {
 };
 // multi-scalar multiplication (host_msm.hip, k_msm_bucket.hip): point rows, bucket entries, sorted entries, bucket counts and ends,
 // the levels' partial sums (ping-pong), the bucket sums, the window segments, the device-side counters; reserved for the largest call
-struct BNH MsmWs { DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, stat; };
+// blsbn254_msm_stats, in its order: bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
+struct BNH MsmWs { DevBuf pts, key, val, sorted, hist, end, part[2], bsum, seg, dstat; uint64_t stat[4] = {0, 0, 0, 0}; };
 // A segmented reduction over ragged groups (seg_plan.h, seg_stage / seg_run_levels below): the levels between the first and the
 // last (ping-pong) with their flags, and the run descriptors of every level of every launch of a call, on the device and as the
 // host copies they are uploaded from.  The rule for every host copy an upload reads (these, GroupOff::h, the h_* / s_* vectors
@@ -75,13 +79,15 @@ struct BNH GroupOff { DevBuf d; std::vector<uint32_t> h; };
 struct BNH PcWs { DevBuf prod, ok, pair_ok; SegWs seg; };
 // threshold combine over groups (host_threshold_batch.hip, k_threshold_batch.hip): the groups' offsets, per-share group words,
 // the products, the levels of the group sums, the sums, the per-group marks, the encodings and statuses
-struct BNH ThbWs { GroupOff goff; DevBuf gid, pts, gsum, gstat, out, st; SegWs seg; };
+// blsbn254_threshold_batch_stats: groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
+struct BNH ThbWs { GroupOff goff; DevBuf gid, pts, gsum, gstat, out, st; SegWs seg; uint64_t stat[3] = {0, 0, 0}; };
 // aggregate verify over groups (host_aggregate_batch.hip, k_aggregate_batch.hip): the lanes' slot descriptors (device buffers and
 // the host copies they are uploaded from), the groups' pair offsets, the signatures' flags.  The products and their levels are PcWs's.
 struct BNH AgbWs {
   DevBuf slot_a, slot_b, sig_ok;
   GroupOff goff;
   std::vector<uint32_t> h_slot_a, h_slot_b;
+  uint64_t stat[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
 };
 // key shares and their public keys over groups (host_threshold_deal.hip, k_threshold_deal.hip): the staged coefficients /
 // commitments and ids, the decoded coefficients (9 x T limbs) / loaded commitments (54 x T limbs) with their validity bytes, the
@@ -93,6 +99,7 @@ struct BNH TdlWs {
   GroupOff goff, coff;
   std::vector<uint8_t> h_msgs;
   std::vector<uint64_t> h_moff;
+  uint64_t stat[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
 };
 // checked threshold combine over groups (host_threshold_checked.hip, k_threshold_checked.hip): the staged ids and partial
 // signatures, the candidate and used bitmaps over the call's shares, the compacted ids / partial signatures (t_g slots per group),
@@ -106,10 +113,12 @@ struct BNH TcWs {
   std::vector<uint8_t> h_gbits, s_commit, s_ids, s_sigs, s_msgs, s_out, s_used;
   std::vector<uint64_t> s_coff, s_goff, s_moff;
   std::vector<size_t> fail;
+  uint64_t stat[4] = {0, 0, 0, 0};   // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
 };
 // sums over a registered key set selected by bitmaps (host_keyset.hip, k_keyset.hip): the call's rows, the groups' flip / ok bytes,
 // the word-major partials of a launch and of its reduction passes (ping-pong); the host copy the flip bytes are downloaded to
-struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; };
+// blsbn254_keyset_stats: groups served, groups summed through the complement, launches of the word kernel, key sets created
+struct BNH KsetWs { DevBuf sel, flip, ok, part[2]; std::vector<uint8_t> h_flip; uint64_t stat[4] = {0, 0, 0, 0}; };
 // What the four checked calls over a registered key set hold alike (host_keyset_checked.hip; aggregation and merge, full-width and
 // per committee: DESIGN.md 6i, 6j, 6o, 6p, 6q).  An "entry" is a signature of the aggregation forms, a contribution of the merge
 // forms.  On the device: the entries' signatures as 64-byte encodings (sigs) and, wire-format forms, as the 32 bytes uploaded
@@ -126,6 +135,8 @@ struct BNH CkWs {
   std::vector<uint8_t> h_gbits, h_used, h_cand, s_msgs, s_emsgs, s_out, s_rows;
   std::vector<uint64_t> s_moff, s_emoff, even_off;
   std::vector<size_t> fail;
+  // each form's ..._stats: groups settled by the optimistic attempt, groups sent to the per-entry fallback, entries verified individually, short groups
+  uint64_t stat[4] = {0, 0, 0, 0};
 };
 // ... and each form's own (KcaWs, KcmWs: behind KcWs).  Aggregation (host_keyset_agg.hip): the staged indices, the keys the
 // fallback gathers, the sub-call (keyset_agg_plan.h KaRepack) and its signatures
@@ -143,6 +154,7 @@ struct BNH KwWs {
   std::vector<uint64_t> h_tab;
   std::vector<uint8_t> h_ones, h_bits;
   std::vector<size_t> reach;
+  uint64_t stat[4] = {0, 0, 0, 0};   // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
 };
 // committees over a registered key set (host_keyset_committee.hip, k_keyset_committee.hip): the call's rows; per sorted group its
 // committee, row offset, partial base and caller's group; the items; the flip / ok bytes; the group-major partials of a launch
@@ -156,6 +168,7 @@ struct BNH KcWs {
   std::vector<uint8_t> h_flip, h_ones;
   std::vector<uint64_t> h_off;
   std::vector<uint32_t> h_com;
+  uint64_t stat[4] = {0, 0, 0, 0};   // groups served, groups summed through the complement, launches of the word kernel, committee tables set
 };
 // aggregation per committee (host_keyset_committee_agg.hip; the key sums run in KcWs): positions in place of indices; the
 // groups' committees, the prefix of their row words and the byte offsets of their rows (device buffers and the host copies they
@@ -192,6 +205,8 @@ struct BNH KsrWs {
   std::vector<uint8_t> h_elig, h_state, h_bits, h_msgs;
   std::vector<uint32_t> h_cstart, h_clen, h_list;
   std::vector<uint64_t> h_moff, h_rowoff;
+  // groups decided by a passed chunk, chunks checked, groups sent to the exact path after their chunk failed, groups sent there directly, message classes, calls
+  uint64_t stat[6] = {0, 0, 0, 0, 0, 0};
 };
 // aggregate verify over groups by random linear combination (host_aggregate_rlc.hip, k_aggregate_rlc.hip): the seed; per pair its
 // group; the groups' pair offsets, segments, signature flags, eligibility bytes and weights; the weighted points
@@ -206,6 +221,9 @@ struct BNH AgrWs {
   std::vector<uint32_t> h_gidx, h_bound, h_seg_of;
   std::vector<uint8_t> h_elig, h_pass, h_bits;
   std::vector<std::pair<size_t, size_t>> ranges;
+  // calls, groups decided by round 1, by round 2, groups sent to the exact pipeline, ineligible groups, equations checked, calls that
+  // did not take round 1, segments that failed
+  uint64_t stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 // the distinct-message rule of the aggregate verify over groups (host_msg_distinct.hip, k_msg_distinct.hip): per pair the canonical
 // (x, y) of its hash point (18 x N limbs), the slot table (M >= 2 N pair indices), the groups' repeat bytes and their bitmap; the
@@ -262,6 +280,26 @@ struct BNH RlcWs {
   std::vector<uint8_t> h_neg, h_ok, h_elig, h_bits;
   std::vector<uint32_t> h_idx;
 };
+// The final exponentiation (host.hip run_final_exp): the phase buffers (x, a, b, c, b2, d; 108 x n limbs each), the ten named
+// powers of the t -> t^x addition chain (10 x 108 x n limbs), the validity bytes of the wave and quad hard parts (mode 0), the
+// named values of the quad hard part (TRI_VALUES x 108 x n limbs)
+struct BNH FeWs { DevBuf ph[6], slots, one, tri; };
+// Key de-duplication of a chunk (host_verify.hip dedup_enqueue and what follows it): the hash table's slots, per tuple its
+// representative and its key id, per distinct key its representative tuple, the keys' tuple counts, the run cursors (ends, after
+// the scatter) and the key-sorted order, the key count.  Host side: the per-context random seed of the table's hash, and the id
+// of -G2gen among a call's keys -- the one host copy an upload reads here (agg_keys_prepare), context-owned so nothing waits for it
+struct BNH KeyDedupWs {
+  DevBuf slots, rep, kid, keys, hist, cursor, perm, cnt;
+  uint32_t seed = 0, last_key = 0;
+};
+// The prepared keys of a call (k_keyprep.hip, k_miller_prep.hip; prepare_keys, raw_tables_fork): the expanded pair tables, the raw
+// line triples and the validity bytes of the keys prepared for this call; per tuple the is-one byte and the verdict byte of
+// verify_prepared_dev.  No host copies.  blsbn254_path_stats, in its order: verify chunks that took the prepared-key path, the
+// exact per-tuple path
+struct BNH PrepWs {
+  DevBuf table, raw, ok, isone, valid;
+  uint64_t stat[2] = {0, 0};
+};
 // The store of prepared keys (key_cache.h, k_keycache.hip; host_verify.hip prepare_keys): the keys' encodings, pair tables and
 // validity bytes, the slot table, the state words and running totals; per call the distinct keys' store indices, the miss list,
 // and the store indices per tuple / per chunk of the RLC path, with the validity bytes in batch key order for that path
@@ -271,67 +309,82 @@ struct BNH KeyStore {
   size_t cap = 0;                    // keys the store has room for: max(max, the largest key capacity a call was enqueued with); 0: not set up
   uint32_t mask = 0;                 // slot-table entries - 1
 };
-struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
-
-struct blsbn254_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  DevBuf in_a, in_b, in_c, in_off, dst, h_ws, f_ws, f_ws2, flags, sub_ok, status, bitmap, out, scalars, misc;
-  DevBuf wire_a, wire_b; // compressed keys / signatures as uploaded (host_compressed.hip): inflated into in_a / in_b, which the pipelines read
-  DevBuf fe[6];          // final-exponentiation phase buffers (x, a, b, c, b2, d), 108 x n limbs each
-  KeySumWs ks;                       // batch verification by random linear combination: the per-key sums,
-  Rlc2Ws r2;                         // ... the rounds over repeated keys with their settings and counters,
-  RlcWs rlc;                         // ... the distinct-key variant
-  size_t lanes_per_round = 65536;    // CUs x 256: the lanes resident at one wave per SIMD (the big kernels' occupancy)
-  DevBuf status_all;     // per-element decode status of a chunked call, all chunks
-  // prepared-key verify path (k_keyprep.hip, k_miller_prep.hip)
-  DevBuf kd_slots, kd_rep, kd_kid, kd_keys, kd_hist, kd_cursor, kd_perm, kd_cnt, prep_table, prep_raw, prep_ok, prep_isone, prep_valid;
-  KeyStore kc;                       // the store of prepared keys
-  hipStream_t stream2 = nullptr;     // the per-key preparation runs beside hash-to-G1
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool s2_pending = false;           // work was forked onto stream2 and the main stream has not waited for ev_join yet
-  uint32_t kd_seed = 0;              // per-context random seed of the key hash table
-  uint32_t last_key = 0;             // the id of -G2gen among a call's keys, as agg_keys_prepare uploads it
-  bool auto_prepare = true;          // verify_batch: de-duplicate the public keys and prepare each distinct key once (BLSBN254_AUTO_PREPARE=0 disables)
-  uint64_t stat_prepared_chunks = 0, stat_exact_chunks = 0, stat_grouped_aggregates = 0, stat_pairwise_aggregates = 0;
-  DevBuf q_ws;           // decoded public keys of the two-pairs-per-lane Miller kernel, 72 x lanes limbs
-  DevBuf th_x, th_num, th_den, th_glv, th_part, th_part2;   // threshold combine: ids, partial products, GLV halves, window sums
-  DevBuf fe_wide_one;    // validity bytes of the wave-per-tuple final exponentiation (mode 0)
-  bool wide_fe = true;               // BLSBN254_WIDE_FE=0 disables the wave-per-tuple hard part
-  size_t tri_max = 16384;            // launches of wide_fe_max < n <= tri_max tuples run three lanes per tuple (k_tri.hip); BLSBN254_TRI_MAX, 0 = off
-  bool tri_miller = true, tri_fe = true;   // BLSBN254_TRI_MILLER=0 / BLSBN254_TRI_FE=0: keep one of the two on the lane-per-tuple kernels (A/B runs)
-  DevBuf tri_vals;                   // the named values of the tri hard part, TRI_VALUES x 108 x n limbs
-  // Asynchronous blsbn254_verify_batch_dev (host_verify.hip): calls whose pipeline was enqueued on the previous call's key count and
-  // whose check (res[1]) has not been read back yet, oldest first
-  struct PendingVerify {
-    bool active = false; const uint8_t *d_pks = nullptr, *d_msgs = nullptr, *d_sigs = nullptr; const uint64_t* d_off = nullptr;
-    size_t n = 0; uint8_t* d_bitmap = nullptr; uint8_t dst[256]; size_t dst_len = 0; hipEvent_t ev = nullptr;
-  } pend[4];
-  int pend_head = 0, pend_count = 0;
-  uint32_t* pend_host = nullptr;     // pinned, 4 slots x (u, ok)
-  DevBuf pend_dev;                   // the same on the device
+// A blsbn254_verify_batch_dev call whose pipeline was enqueued on the previous call's key count and whose check has not been read
+// back yet: the caller's device pointers, its tag (a copy: a re-run stages it again) and the event behind the check's copy
+struct PendingVerify {
+  const uint8_t *d_pks = nullptr, *d_msgs = nullptr, *d_sigs = nullptr; const uint64_t* d_off = nullptr;
+  size_t n = 0; uint8_t* d_bitmap = nullptr; uint8_t dst[256]; size_t dst_len = 0; hipEvent_t ev = nullptr;
+};
+// The asynchronous verify queue (host_verify.hip verify_chunk_async / resolve_pending): up to four such calls, oldest first; their
+// checks (u, ok) on the device and in the pinned host buffer the copies land in.  The events and the pinned buffer are created by
+// the first asynchronous call and released by blsbn254_ctx_destroy.  The hints the capacity of the next call is chosen from, the
+// switch, and blsbn254_async_stats in its order: chunks enqueued without a read-back, chunks re-run on the counting path
+struct BNH VerifyQueue {
+  PendingVerify pend[4];
+  int head = 0, count = 0;
+  uint32_t* host = nullptr;          // pinned, 4 slots x (u, ok)
+  DevBuf dev;                        // the same on the device
   size_t u_hint = 0;                 // distinct keys of the last chunk that took the prepared path (0: none yet)
   size_t u_max_seen = 0;             // the largest key count a prepared chunk had on this context: the capacity never drops below it (a caller
                                      // alternating between a small and a large key set would otherwise re-run every large batch)
-  bool async_verify = true;          // BLSBN254_ASYNC_VERIFY=0: every call reads the key count back before it enqueues the pipeline
-  uint64_t stat_async_chunks = 0, stat_async_reruns = 0;
-  bool quad_prep = true;             // per-key preparation with four lanes per key while that fits one round of waves (BLSBN254_QUAD_PREP=0: off)
-  bool split_easy = true;            // BLSBN254_SPLIT_EASY=0: the one-launch easy part at every size
-  size_t wide_fe_max = 2048;         // ... used for launches of at most this many tuples (BLSBN254_WIDE_FE_MAX): two rounds of a wave per tuple
-                                     // cost what the three-lanes-per-tuple kernels cost for anything up to 16384 (r03: 4096 wide = 7.8 ms, 4100 on quads = 5.6 ms)
-  DevBuf gs_items, gs_items_ok, gs_sum, gs_sum_ok, gs_pk;   // segmented G2 sums (host_groupops.hip): the loaded points and the groups' sums with their flags, the sums' encodings
-  SegWs gs;                                                 // ... and the levels between them
-  DevBuf fe_slots;       // the ten named powers of the t -> t^x addition chain, 10 x 108 x n limbs
+  bool async = true;                 // BLSBN254_ASYNC_VERIFY=0: every call reads the key count back before it enqueues the pipeline
+  uint64_t stat[2] = {0, 0};
+};
+// Threshold combine of one group (host_aggregate.hip lagrange_enqueue / threshold_combine_one, k_threshold.hip): the decoded
+// ids, the partial products of the Lagrange numerators and denominators, the coefficients as GLV halves, the window sums of the
+// MSM and the buffer they are folded into
+struct BNH ThWs { DevBuf x, num, den, glv, part, part2; };
+// Segmented G2 sums (host_groupops.hip g2_group_sums; the key-set calls leave their sums here too): the loaded points and the
+// groups' sums with their flags, the sums' encodings, the levels between points and sums
+struct BNH G2SumWs { DevBuf items, items_ok, sum, sum_ok, pk; SegWs seg; };
+// The check of dealt key shares (host_threshold_deal.hip, threshold_keycheck.h): the generator's multiples, built at the first
+// check -- no workspace aliases them.  blsbn254_threshold_key_check_stats: launches of the check kernel, shares checked, builds of
+// the table (0: not built yet)
+struct BNH KeyCheckWs { DevBuf tab; uint64_t stat[3] = {0, 0, 0}; };
+struct ProfEntry { uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; };
+
+// The context: two streams, the staging buffers every pipeline shares, one workspace per pipeline, the settings no single
+// workspace owns, the profile.
+struct blsbn254_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t stream2 = nullptr;     // the per-key preparation runs beside hash-to-G1
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool s2_pending = false;           // work was forked onto stream2 and the main stream has not waited for ev_join yet
+  // Shared BY DESIGN, the property of whichever call runs: the call's inputs as uploaded (in_a keys / points, in_b signatures,
+  // in_c messages, in_off their offsets; wire_a / wire_b: compressed keys / signatures, inflated into in_a / in_b by
+  // host_compressed.hip), the tag, the H points (h_ws), the Miller values and their product levels (f_ws, f_ws2), the decoded keys
+  // of the two-pairs-per-lane kernel (q_ws, 72 x lanes limbs), per-element flags, subgroup bytes and decode statuses (status_all:
+  // of every chunk of a chunked call), the result bitmap, other outputs, scalars, and a few words of verdicts (misc)
+  DevBuf in_a, in_b, in_c, in_off, dst, h_ws, f_ws, f_ws2, q_ws, flags, sub_ok, status, status_all, bitmap, out, scalars, misc;
+  DevBuf wire_a, wire_b;
   uint8_t dst_host[256];  // the (pre-hashed if oversize) DST currently resident in `dst`, and its length; -1 = none
   int dst_host_len = -1;
+  LaunchForms forms;                 // which device form runs at which size (launch_forms.h)
   uint32_t expander = BLSBN254_EXPAND_XMD_SHA256;   // the message expander every hashing launch runs under (blsbn254_set_expander; keccak.h EXPAND_*)
   uint32_t g1_map = BLSBN254_G1MAP_SVDW;            // the map behind every MESSAGE hashed to G1 (blsbn254_set_g1_map; lane_hash_tai.h G1MAP_*)
-  size_t chunk = (size_t)1 << 22;   // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
+  size_t chunk = (size_t)1 << 22;    // tuples per launch of the chunked entry points (BLSBN254_CHUNK_LANES overrides: tests)
+  bool auto_prepare = true;          // verify_batch / aggregate_verify: de-duplicate the public keys and prepare each distinct key once (BLSBN254_AUTO_PREPARE=0 disables)
+  uint64_t agg_stat[2] = {0, 0};     // blsbn254_aggregate_path_stats: aggregate verifies served per distinct key, pair by pair
+  size_t ksr_group = KSR_DEFAULT_GROUP;  // groups per chunk of the key-set RLC calls (blsbn254_set_keyset_rlc_group)
+  size_t agr_segments = 0;           // blsbn254_set_aggregate_rlc_segments: 0 = the default rule, 1 = no second round, else S
+  int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
+  FeWs fe;
+  KeyDedupWs kd;                     // the verify path: key de-duplication,
+  PrepWs prep;                       // ... the prepared keys of a call,
+  KeyStore kc;                       // ... the store of prepared keys,
+  VerifyQueue vq;                    // ... the asynchronous queue
+  KeySumWs ks;                       // batch verification by random linear combination: the per-key sums,
+  Rlc2Ws r2;                         // ... the rounds over repeated keys with their settings and counters,
+  RlcWs rlc;                         // ... the distinct-key variant
+  ThWs th;
+  G2SumWs gs;
   MsmWs msm;
   PcWs pc;
   ThbWs thb;
   AgbWs agb;
   TdlWs tdl;
+  KeyCheckWs kchk;
   TcWs tc;
   KsetWs kset;
   KaggWs kagg;
@@ -341,33 +394,15 @@ struct blsbn254_ctx {
   KcaWs kcagg;
   KcmWs kcmrg;
   KsrWs ksr;
-  uint64_t stat_kset[4] = {0, 0, 0, 0};  // groups served, groups summed through the complement, launches of the word kernel, key sets created
-  uint64_t stat_kw[4] = {0, 0, 0, 0};    // groups weighed, groups below quorum (not paired), launches of k_ks_weight for them, weight tables set
-  uint64_t stat_kc[4] = {0, 0, 0, 0};    // committee calls: groups served, groups summed through the complement, launches of the word kernel, committee tables set
-  size_t ksr_group = KSR_DEFAULT_GROUP;  // groups per chunk of the key-set RLC calls (blsbn254_set_keyset_rlc_group)
-  uint64_t stat_ksr[6] = {0, 0, 0, 0, 0, 0};   // groups decided by a passed chunk, chunks checked, groups sent to the exact path after their chunk failed, groups sent there directly, message classes, calls
-  uint64_t stat_kagg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-signature fallback, signatures verified individually, short groups
-  uint64_t stat_kcagg[4] = {0, 0, 0, 0}; // the same four counts of the checked aggregation per committee
-  uint64_t stat_kmrg[4] = {0, 0, 0, 0};  // groups settled by the optimistic attempt, groups sent to the per-contribution fallback, contributions verified individually, short groups
-  uint64_t stat_kcmrg[4] = {0, 0, 0, 0}; // the same four counts of the checked merge per committee
-  uint64_t stat_tc[4] = {0, 0, 0, 0};    // groups settled by the optimistic attempt, groups sent to the per-share fallback, shares verified individually, short groups
-  uint64_t stat_tdl[4] = {0, 0, 0, 0};   // launches of the G2 evaluation, shares evaluated in G2, shares evaluated in Fr, bits of the last G2 launch
-  DevBuf kc_tab;                         // the generator's multiples (threshold_keycheck.h): built at the first key-share check, no workspace aliases it
-  uint64_t stat_kchk[3] = {0, 0, 0};     // launches of the key-share check kernel, shares checked, builds of kc_tab (0: not built yet)
-  uint64_t stat_agb[4] = {0, 0, 0, 0};   // groups served, lanes run by the two-pair kernel, calls served by the small forms, launches
-  uint64_t stat_thb[3] = {0, 0, 0};      // groups served by the lane-per-share kernels, groups handed to the single-group pipeline, launches
   AgrWs agr;
   MdWs md;
-  size_t agr_segments = 0;               // blsbn254_set_aggregate_rlc_segments: 0 = the default rule, 1 = no second round, else S
-  // calls, groups decided by round 1, by round 2, groups sent to the exact pipeline, ineligible groups, equations checked, calls that
-  // did not take round 1, segments that failed
-  uint64_t stat_agr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
-  uint64_t stat_msm[4] = {0, 0, 0, 0};   // bucket-path calls, small-n calls, bucket entries accumulated, level-0 chunks summed
   bool profiling = false;
   std::map<std::string, ProfEntry> prof;
   std::string last_error;
 };
+
+// THE body of a plain counter getter: the null checks, then the first n counters of the context's `stat` (kset.stat, ...) into out
+#define COPY_STATS(c, stat, n, out) (!(c) || !(out) ? (int)BLSBN254_E_ARG : (std::copy_n((c)->stat, n, out), 0))
 
 #define HIPCHK(ctx, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { (ctx)->last_error = std::string(#x) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? BLSBN254_E_NOMEM : BLSBN254_E_HIP; } } while (0)
@@ -487,7 +522,7 @@ static inline void g1_identity_out(uint8_t* o, bool wire) { if (wire) g1_identit
 
 // Work forked onto stream2 must never outlive a failing call: a function that forks holds one of these, and an early
 // error return (before the main stream has waited for ev_join) then waits for stream2 on the way out, so nothing is
-// still writing prep_raw / prep_table when the caller sees the error code.
+// still writing prep.raw / prep.table when the caller sees the error code.
 struct Stream2Guard {
   blsbn254_ctx* c;
   explicit Stream2Guard(blsbn254_ctx* c_) : c(c_) {}
@@ -511,7 +546,7 @@ extern "C" {
 BNH int resolve_pending(blsbn254_ctx* c, bool blocking);   // host_verify.hip
 BNH int blsbn254_internal_verify_batch_dev_sync(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                                                 const uint8_t* d_sigs, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap);   // host_verify.hip
-#define ENTER(c) do { HIPCHK(c, hipSetDevice((c)->device)); if ((c)->pend_count) TRY(resolve_pending(c, true)); } while (0)
+#define ENTER(c) do { HIPCHK(c, hipSetDevice((c)->device)); if ((c)->vq.count) TRY(resolve_pending(c, true)); } while (0)
 extern BNH const uint8_t NEG_G2_BYTES[128];     // -G2gen = (x, p - y) of the generator fp2.rs:305-333, as bytes (host.hip)
 
 // The kernels address limb-major workspaces through a buffer descriptor with a 32-bit scalar byte offset
@@ -579,28 +614,25 @@ static inline const uint32_t* key_miller_ids(const KeyTables& kt, const uint32_t
 BNH int prepare_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap, const uint32_t* d_u, KeyTables* kt);   // host_verify.hip
 BNH int miller_ids(blsbn254_ctx* c, const KeyTables& kt, const uint32_t* ids, size_t n, DevBuf& buf, const uint32_t** out);   // host_verify.hip
 BNH int keys_valid(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint8_t** out);   // host_verify.hip
-// behind dedup_keys / dedup_enqueue: key ids (kd_kid; hist: their counts, kd_hist), then the key-sorted order of d_kid (kd_perm, kd_cursor)
+// behind dedup_keys / dedup_enqueue: key ids (kd.kid; hist: their counts, kd.hist), then the key-sorted order of d_kid (kd.perm, kd.cursor)
 BNH int dedup_key_ids(blsbn254_ctx* c, size_t n, size_t u, bool hist);   // host_verify.hip
 BNH int key_sorted_order(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u);   // host_verify.hip
 BNH int verify_prepared_dev(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint32_t* d_kid, bool deduped, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
 BNH int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u, uint32_t* hist, const char* what, bool armed);   // host_verify.hip
 BNH int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, const KeyTables& kt, size_t n);   // host_verify.hip
-// Its twin over the RAW line tables (prep_raw / a G2Prepared's raw: the aggregate family): pair i = (H point i of the workspace h
+// Its twin over the RAW line tables (prep.raw / a G2Prepared's raw: the aggregate family): pair i = (H point i of the workspace h
 // at stride h_stride, table kid[i] of kt), st: the optional status bytes of the H points (bit 1: the identity, contributes 1).
 // Reserves and fills c->f_ws / c->flags; *left Fp12 values at stride *left remain: n, or (n + 1) / 2 from two pairs per lane.
-// THE rule, over the forms the site admits (MR_*): one wave per pair if wide_fe and n <= wide_fe_max; else a quad of lanes per
-// pair if tri_miller and n <= tri_max; else one pair per lane if 2 n <= lanes_per_round (the launch is the latency of one wave:
-// no shared f^2, the shorter chain), or two per lane is not admitted, or n > ctx->chunk; else two pairs per lane sharing f^2.
-// n > ctx->chunk: the per-pair forms run chunk by chunk at stride n, each chunk in the form that fits it.
+// The form is launch_forms.h's (table_miller_form / raw_two_per_lane) over the forms the site admits (MR_*); n > ctx->chunk: the
+// per-pair forms run chunk by chunk at stride n, each chunk in the form that fits it.
 struct RawTables { const int32_t* raw; const uint8_t* ok; };
-enum : unsigned { MR_WIDE = 1, MR_TRI = 2, MR_ONE = 4, MR_TWO = 8, MR_ALL = 15 };
 BNH int launch_miller_raw(blsbn254_ctx* c, const int32_t* h, size_t h_stride, const uint32_t* kid, RawTables kt, size_t n, const uint8_t* st, unsigned forms,
                           size_t* left);   // host_aggregate.hip
 // The key tables of an aggregate call, in two steps because the callers decide between them whether to go on at all.
 // agg_keys_stage: the caller's n keys into c->in_a with -G2gen as entry n, de-duplicated (dedup_keys: *u distinct among the n;
 // synchronises).  agg_keys_prepare: -G2gen appended as key u, the raw tables of the u + 1 keys enqueued on the second stream beside
-// whatever the caller enqueues next, ev_join recorded (raw_tables_fork: the same for the `keys` keys kd_keys names as it stands).
+// whatever the caller enqueues next, ev_join recorded (raw_tables_fork: the same for the `keys` keys kd.keys names as it stands).
 BNH int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u);   // host_aggregate.hip
 BNH int agg_keys_prepare(blsbn254_ctx* c, size_t n, size_t u);   // host_aggregate.hip
 // what blsbn254_aggregate_verify_batch and ..._batch_rlc check alike (`call` names the one in the error text); CK_NOTHING: no
@@ -633,9 +665,9 @@ BNH int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
 BNH int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap);   // host_verify.hip
-// segmented sums of n G2 encodings staged at d_pks over the groups goff (host offsets) into c->gs_sum / c->gs_sum_ok
+// segmented sums of n G2 encodings staged at d_pks over the groups goff (host offsets) into c->gs.sum / c->gs.sum_ok
 BNH int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups);   // host_groupops.hip
-// the sums of n_groups rows ALREADY ON THE DEVICE (ceil(k->n / 8) bytes each) over the key set k into c->gs_sum / c->gs_sum_ok,
+// the sums of n_groups rows ALREADY ON THE DEVICE (ceil(k->n / 8) bytes each) over the key set k into c->gs.sum / c->gs.sum_ok,
 // the flip bytes into c->kset.h_flip (enqueued); *launches: launches of the word kernel
 BNH int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* d_rows, size_t n_groups, size_t* launches);   // host_keyset.hip
 // the argument checks the calls over rows share (n_groups > 0): the limit, and no row may set a bit that names no key
@@ -660,11 +692,11 @@ BNH int verify_batch_rlc_host(blsbn254_ctx* c, const uint8_t* pks, const uint8_t
 // the registration of a key set, arguments checked in here; proofs == nullptr: without proofs of possession
 BNH int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t n_keys, const uint8_t* pop_dst, size_t pop_dst_len,
                   blsbn254_keyset** out, bool compressed);   // host_keyset.hip
-// the tail of ks_verify_rows: the sums in c->gs_sum / c->gs_sum_ok (enqueued) encoded and paired with the staged messages and
+// the tail of ks_verify_rows: the sums in c->gs.sum / c->gs.sum_ok (enqueued) encoded and paired with the staged messages and
 // signatures (stage_msgs, c->in_b), the bits downloaded
 BNH int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid_bitmap);   // host_keyset.hip
-// the committee form's sums: the arguments checked (n_groups > 0), then the rows staged in c->kcom.sel, the sums into c->gs_sum /
-// c->gs_sum_ok in the caller's order (enqueued); kc_tally counts the call once it has succeeded and synchronised
+// the committee form's sums: the arguments checked (n_groups > 0), then the rows staged in c->kcom.sel, the sums into c->gs.sum /
+// c->gs.sum_ok in the caller's order (enqueued); kc_tally counts the call once it has succeeded and synchronised
 BNH int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
 BNH int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups);   // host_keyset_committee.hip
 BNH void kc_tally(blsbn254_ctx* c, size_t n_groups);   // host_keyset_committee.hip
@@ -733,13 +765,13 @@ BNH int ck_args(blsbn254_ctx* c, const blsbn254_keyset* k, const CkArgs& A, bool
 // the call's N signatures into w.sigs, through w.wire and g1_inflate_dev when compressed; inflate = false: compressed entries stay
 // in w.wire, where the caller's scan reads them, and no 64 N buffer is reserved
 BNH int ck_stage_sigs(blsbn254_ctx* c, CkWs& w, const CkArgs& A, size_t N, bool inflate);
-// c->gs_pk / gs_sum / gs_sum_ok for n key sums: a call that uses them twice reserves for the larger use BEFORE the first kernel
+// c->gs.pk / gs.sum / gs.sum_ok for n key sums: a call that uses them twice reserves for the larger use BEFORE the first kernel
 // that touches them is enqueued (a later reserve that grows them would free what that kernel still reads)
 BNH int ck_reserve_key_sums(blsbn254_ctx* c, size_t n);
 // the group's message once per entry of w.goff into w.s_emsgs / w.s_emoff (ctx-owned: they outlive the upload)
 BNH void ck_expand_msgs(CkWs& w, const CkArgs& A);
 // the tail of an attempt, behind the kernels that left the entries' points in w.pts and the rows in w.orows: the signature sums by
-// levels, their encodings into w.out (wire: w.wout too), the key sums by key_sums() into c->gs_sum / c->gs_sum_ok, then ONE
+// levels, their encodings into w.out (wire: w.wout too), the key sums by key_sums() into c->gs.sum / c->gs.sum_ok, then ONE
 // verification per group of (key sum, message, signature sum), its bits into w.gbits.  Enqueued.
 BNH int ck_tail(blsbn254_ctx* c, CkWs& w, const CkArgs& A, uint32_t dl, const std::function<int()>& key_sums);
 // The two attempts of a call: attempt(false) over the caller's groups, the download, the groups marked; for those that had a
@@ -759,13 +791,5 @@ BNH int ck_select(blsbn254_ctx* c, KmStage& w, size_t n_groups, size_t N, const 
 // the bits into w.vbits; settle: wait for each launch before the next is planned
 BNH int ck_verify_contributions(blsbn254_ctx* c, KmStage& w, const CkArgs& A, size_t N, uint32_t dl, bool settle,
                                 const std::function<int(size_t, size_t)>& key_sums);
-
-// A launch of n tuples is small enough that the prepared-key path wins whatever its keys: with line tables the Miller loop (and
-// the final exponentiation) can run one WAVE per tuple (wide.h) or, up to tri_max, three lanes per tuple (k_tri.hip) instead of
-// at the latency of one lane.  per_tuple_fe: the launch also runs a final exponentiation per tuple, so the three-lane form only
-// pays when that half is enabled too (the grouped aggregate verify runs ONE final exponentiation and passes false).
-static inline bool small_for_prepared(const blsbn254_ctx* c, size_t n, bool per_tuple_fe) {
-  return (c->wide_fe && n <= c->wide_fe_max) || (c->tri_miller && (c->tri_fe || !per_tuple_fe) && n <= c->tri_max);
-}
 
 }  // extern "C"

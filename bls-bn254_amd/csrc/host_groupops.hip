@@ -35,21 +35,21 @@ int blsbn254_g2_mul_batch(blsbn254_ctx* c, const uint8_t* g2, const uint8_t* sca
 // cut into chunks of at most G2_SUM_GROUP items, one lane sums a chunk, and the chunk sums (group-major order) are the next
 // level's items, until every group is ONE item (plan_seg_levels, seg_plan.h; seg_run_levels with k_g2_seg_sum).  The chunk
 // descriptors of all levels come from the host (the offsets are the caller's host array) in one copy: nothing synchronises
-// between the levels or behind them.  The sums end up in c->gs_sum (limb-major, stride n_groups), their flags in c->gs_sum_ok.
+// between the levels or behind them.  The sums end up in c->gs.sum (limb-major, stride n_groups), their flags in c->gs.sum_ok.
 static const size_t G2_SUM_GROUP = 16;
 int g2_group_sums(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, const uint64_t* goff, size_t n_groups) {
-  SegWs& w = c->gs;
+  SegWs& w = c->gs.seg;
   std::vector<SegRange> seg(n_groups);
   for (size_t g = 0; g < n_groups; ++g) seg[g] = {goff[g] - goff[0], goff[g + 1] - goff[0]};
   w.h_start.clear(); w.h_len.clear();
   std::vector<SegLevel> levels;
   size_t items_max = 1;
   if (!plan_seg_levels(seg, G2_SUM_GROUP, w.h_start, w.h_len, levels, &items_max)) { c->last_error = "internal: group sums do not converge"; return BLSBN254_E_HIP; }
-  HIPCHK(c, c->gs_items.reserve((n ? n : 1) * 54 * 4)); HIPCHK(c, c->gs_items_ok.reserve(n ? n : 1));
-  HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
+  HIPCHK(c, c->gs.items.reserve((n ? n : 1) * 54 * 4)); HIPCHK(c, c->gs.items_ok.reserve(n ? n : 1));
+  HIPCHK(c, c->gs.sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs.sum_ok.reserve(n_groups));
   TRY(seg_stage(c, w, items_max, 54, true));
-  if (n) TRY(launch(c, c->stream, "g2_load", grid_lanes(n), k_g2_load, d_pks, n, (int32_t*)c->gs_items.p, (uint8_t*)c->gs_items_ok.p));
-  return seg_run_levels(w, levels, {(const int32_t*)c->gs_items.p, n ? n : 1, (const uint8_t*)c->gs_items_ok.p}, {(int32_t*)c->gs_sum.p, n_groups, (uint8_t*)c->gs_sum_ok.p},
+  if (n) TRY(launch(c, c->stream, "g2_load", grid_lanes(n), k_g2_load, d_pks, n, (int32_t*)c->gs.items.p, (uint8_t*)c->gs.items_ok.p));
+  return seg_run_levels(w, levels, {(const int32_t*)c->gs.items.p, n ? n : 1, (const uint8_t*)c->gs.items_ok.p}, {(int32_t*)c->gs.sum.p, n_groups, (uint8_t*)c->gs.sum_ok.p},
                         [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
     return launch(c, c->stream, "g2_seg_sum", grid_lanes(runs), k_g2_seg_sum, in.v, in.stride, in.ok, start, len, runs, out.v, out.stride, out.ok);
   });
@@ -66,10 +66,10 @@ int blsbn254_aggregate_pks(blsbn254_ctx* c, const uint8_t* pks, size_t n, uint8_
   const uint64_t goff[2] = {0, (uint64_t)n};
   TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n, goff, 1));
   uint8_t good = 0;
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(1), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, (size_t)1, (const uint8_t*)c->gs_sum_ok.p, (size_t)1,
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(1), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, (size_t)1, (const uint8_t*)c->gs.sum_ok.p, (size_t)1,
              (uint8_t*)c->out.p, 0));
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, 128, hipMemcpyDeviceToHost, c->stream));
-  TRY(download(c, &good, c->gs_sum_ok.p, 1));
+  TRY(download(c, &good, c->gs.sum_ok.p, 1));
   if (!good) { c->last_error = "a point does not decode or is off the curve"; return BLSBN254_ERR_G2; }
   return 0;
 }
@@ -92,14 +92,14 @@ int blsbn254_fast_aggregate_verify_batch(blsbn254_ctx* c, const uint8_t* pks, co
   rc = stage_msgs(c, msgs, off, n_groups);
   if (rc) return rc;
   const size_t nb = (n_groups + 7) / 8;
-  HIPCHK(c, c->in_a.reserve(128 * (n_keys ? n_keys : 1))); HIPCHK(c, c->gs_pk.reserve(128 * n_groups));
+  HIPCHK(c, c->in_a.reserve(128 * (n_keys ? n_keys : 1))); HIPCHK(c, c->gs.pk.reserve(128 * n_groups));
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   if (n_keys) HIPCHK(c, hipMemcpyAsync(c->in_a.p, pks + 128 * (size_t)key_off[0], 128 * n_keys, hipMemcpyHostToDevice, c->stream));
   TRY(upload(c, c->in_b, sigs, 64 * n_groups));
   TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, key_off, n_groups));
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
-             (uint8_t*)c->gs_pk.p, 1));
-  rc = verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, n_groups, (const uint8_t*)c->gs.sum_ok.p, n_groups,
+             (uint8_t*)c->gs.pk.p, 1));
+  rc = verify_chunk_dev(c, (const uint8_t*)c->gs.pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
                         (uint8_t*)c->bitmap.p);
   if (rc) return rc;
   return download(c, valid_bitmap, c->bitmap.p, nb);

@@ -57,7 +57,7 @@ int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t
   // encodings is the sum of the non-skipped keys (the flag of that sum is not looked at)
   const uint64_t goff[2] = {0, (uint64_t)n_keys};
   TRY(g2_group_sums(c, (const uint8_t*)c->in_a.p, n_keys, goff, 1));
-  HIPCHK(c, hipMemcpyAsync(k->total.p, c->gs_sum.p, 54 * 4, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k->total.p, c->gs.sum.p, 54 * 4, hipMemcpyDeviceToDevice, c->stream));
   // the KeyValidate bits by words, for the selection of the checked merge: packed once, here
   HIPCHK(c, k->vwords.reserve(W * 4));
   HIPCHK(c, hipMemsetAsync(k->vwords.p, 0, W * 4, c->stream));
@@ -65,7 +65,7 @@ int ks_create(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* proofs, size_t
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) { (void)hipDeviceSynchronize(); }       // nothing may still be writing the buffers the owner frees
   HIPCHK(c, es);
-  ++c->stat_kset[3];
+  ++c->kset.stat[3];
   own.p = nullptr;
   *out = k;
   return 0;
@@ -107,7 +107,7 @@ int ks_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel, size_
   }
   return 0;
 }
-// The sums of every row (d_rows: on the device) into c->gs_sum / c->gs_sum_ok (enqueued), the flip bytes into c->kset.h_flip
+// The sums of every row (d_rows: on the device) into c->gs.sum / c->gs.sum_ok (enqueued), the flip bytes into c->kset.h_flip
 // (enqueued: read after the caller's synchronising download).  A launch covers as many groups as keep groups x W within
 // KS_LAUNCH_ITEMS partials (within ctx->chunk when that is smaller); launch starts are multiples of 8 groups.
 int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* d_rows, size_t n_groups, size_t* launches) {
@@ -117,7 +117,7 @@ int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t
   const size_t runs0 = (W + KS_RUN_ITEMS - 1) / KS_RUN_ITEMS;
   HIPCHK(c, w.flip.reserve(n_groups)); HIPCHK(c, w.ok.reserve(n_groups));
   HIPCHK(c, w.part[0].reserve(54 * 4 * W * Gmax)); HIPCHK(c, w.part[1].reserve(54 * 4 * runs0 * Gmax));
-  HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
+  HIPCHK(c, c->gs.sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs.sum_ok.reserve(n_groups));
   *launches = 0;
   for (size_t lo = 0; lo < n_groups; lo += Gl, ++*launches) {
     const size_t m = std::min(Gl, n_groups - lo);
@@ -130,8 +130,8 @@ int ks_enqueue_sums_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t
       const size_t runs = (cnt + KS_RUN_ITEMS - 1) / KS_RUN_ITEMS;
       const bool last = runs == 1;
       TRY(launch(c, c->stream, "ks_group_sum", grid_lanes(runs * m), k_ks_group_sum, (const int32_t*)w.part[src].p, cnt * m, (uint32_t)cnt, m, flip, ok,
-                 (const int32_t*)k->total.p, last ? 1 : 0, last ? (int32_t*)c->gs_sum.p + lo : (int32_t*)w.part[src ^ 1].p, last ? n_groups : runs * m,
-                 last ? (uint8_t*)c->gs_sum_ok.p + lo : (uint8_t*)nullptr));
+                 (const int32_t*)k->total.p, last ? 1 : 0, last ? (int32_t*)c->gs.sum.p + lo : (int32_t*)w.part[src ^ 1].p, last ? n_groups : runs * m,
+                 last ? (uint8_t*)c->gs.sum_ok.p + lo : (uint8_t*)nullptr));
       if (last) break;
       src ^= 1; cnt = runs;
     }
@@ -147,8 +147,8 @@ int ks_enqueue_sums(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* se
 }
 // counted once the call has succeeded (and synchronised: the flip bytes are on the host)
 void ks_tally(blsbn254_ctx* c, size_t n_groups, size_t launches) {
-  c->stat_kset[0] += n_groups; c->stat_kset[2] += launches;
-  for (size_t g = 0; g < n_groups; ++g) c->stat_kset[1] += c->kset.h_flip[g] ? 1 : 0;
+  c->kset.stat[0] += n_groups; c->kset.stat[2] += launches;
+  for (size_t g = 0; g < n_groups; ++g) c->kset.stat[1] += c->kset.h_flip[g] ? 1 : 0;
 }
 
 // row g: out = blsbn254_aggregate_pks on the selected keys in index order, status 1; a row that selects a key that does not
@@ -161,20 +161,20 @@ int blsbn254_keyset_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const u
   size_t launches;
   TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
   HIPCHK(c, c->out.reserve(128 * n_groups));
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, n_groups, (const uint8_t*)c->gs.sum_ok.p, n_groups,
              (uint8_t*)c->out.p, 0));
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, 128 * n_groups, hipMemcpyDeviceToHost, c->stream));
-  TRY(download(c, status, c->gs_sum_ok.p, n_groups));
+  TRY(download(c, status, c->gs.sum_ok.p, n_groups));
   ks_tally(c, n_groups, launches);
   return 0;
 }
 
-// from the groups' sums on (c->gs_sum / c->gs_sum_ok, enqueued; c->gs_pk and c->bitmap reserved by the caller): the pipeline of
+// from the groups' sums on (c->gs.sum / c->gs.sum_ok, enqueued; c->gs.pk and c->bitmap reserved by the caller): the pipeline of
 // blsbn254_fast_aggregate_verify_batch.  Shared with the committee form (host_keyset_committee.hip).
 int ks_verify_sums(blsbn254_ctx* c, size_t n_groups, uint32_t dl, uint8_t* valid_bitmap) {
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
-             (uint8_t*)c->gs_pk.p, 1));
-  TRY(verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, n_groups, (const uint8_t*)c->gs.sum_ok.p, n_groups,
+             (uint8_t*)c->gs.pk.p, 1));
+  TRY(verify_chunk_dev(c, (const uint8_t*)c->gs.pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)c->in_b.p, n_groups, dl,
                        (uint8_t*)c->bitmap.p));
   return download(c, valid_bitmap, c->bitmap.p, (n_groups + 7) / 8);
 }
@@ -186,7 +186,7 @@ int ks_verify_rows(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* sel
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off, n_groups));
   const size_t nb = (n_groups + 7) / 8;
-  HIPCHK(c, c->gs_pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve(nb + 8));
+  HIPCHK(c, c->gs.pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve(nb + 8));
   TRY(stage_g1(c, sigs, n_groups, compressed));
   size_t launches;
   if (sel) TRY(ks_enqueue_sums(c, k, sel, n_groups, &launches));
@@ -204,10 +204,6 @@ int blsbn254_keyset_fast_aggregate_verify_batch(blsbn254_ctx* c, const blsbn254_
   return ks_verify_rows(c, k, sel, msgs, off, sigs, n_groups, dst, dst_len, valid_bitmap);
 }
 
-int blsbn254_keyset_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kset[i];
-  return 0;
-}
+int blsbn254_keyset_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kset.stat, 4, out); }
 
 }  // extern "C"

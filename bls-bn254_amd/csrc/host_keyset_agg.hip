@@ -68,7 +68,7 @@ static int ka_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t*
   KaggWs& w = c->kagg;
   const size_t rb = (k->n + 7) / 8, sb = wire ? 32 : 64;
   KaCall B{};                                                          // the sub-call, once the repack has run
-  return ck_two_attempts(c, w, A.a, ck_even_rows(w, n_groups, rb), {out_sigs, out_sel, nullptr, status}, c->stat_kagg,
+  return ck_two_attempts(c, w, A.a, ck_even_rows(w, n_groups, rb), {out_sigs, out_sel, nullptr, status}, c->kagg.stat,
     [&](bool fallback) { return ka_attempt(c, k, fallback ? B : A, fallback); },
     [&](const std::vector<size_t>& fail) {
       ka_repack(fail, idx, sig_off, out_sel, rb, w.sub);               // (the candidates read off the downloaded rows; s_msgs / s_moff are final)
@@ -91,10 +91,6 @@ int blsbn254_keyset_aggregate_checked_batch_compressed(blsbn254_ctx* c, const bl
   return ka_checked(c, k, idx, sigs, sig_off, msgs, msg_off, n_groups, dst, dst_len, out_sigs, out_sel, status, true);
 }
 
-int blsbn254_keyset_aggregate_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kagg[i];
-  return 0;
-}
+int blsbn254_keyset_aggregate_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kagg.stat, 4, out); }
 
 }  // extern "C"

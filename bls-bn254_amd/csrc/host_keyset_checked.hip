@@ -44,7 +44,7 @@ int ck_stage_sigs(blsbn254_ctx* c, CkWs& w, const CkArgs& A, size_t N, bool infl
 }
 
 int ck_reserve_key_sums(blsbn254_ctx* c, size_t n) {
-  HIPCHK(c, c->gs_pk.reserve(128 * n)); HIPCHK(c, c->gs_sum.reserve(n * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n));
+  HIPCHK(c, c->gs.pk.reserve(128 * n)); HIPCHK(c, c->gs.sum.reserve(n * 54 * 4)); HIPCHK(c, c->gs.sum_ok.reserve(n));
   return 0;
 }
 
@@ -79,9 +79,9 @@ int ck_tail(blsbn254_ctx* c, CkWs& w, const CkArgs& A, uint32_t dl, const std::f
   else TRY(launch(c, c->stream, "g1p_to_bytes", grid_lanes(ng), k_g1p_to_bytes, (const int32_t*)w.gsum.p, ng, ng, (uint8_t*)w.out.p));
   // the key sums from the rows where they are, then the equation of the fast aggregate verify over rows
   TRY(key_sums());
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(ng), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, ng, (const uint8_t*)c->gs_sum_ok.p, ng, (uint8_t*)c->gs_pk.p, 1));
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(ng), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, ng, (const uint8_t*)c->gs.sum_ok.p, ng, (uint8_t*)c->gs.pk.p, 1));
   TRY(stage_msgs(c, A.msgs, A.msg_off, ng));               // ONE message per group
-  return verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)w.out.p, ng, dl, (uint8_t*)w.gbits.p);
+  return verify_chunk_dev(c, (const uint8_t*)c->gs.pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)w.out.p, ng, dl, (uint8_t*)w.gbits.p);
 }
 
 const uint64_t* ck_even_rows(CkWs& w, size_t n_groups, size_t row_bytes) {
@@ -202,9 +202,9 @@ int ck_verify_contributions(blsbn254_ctx* c, KmStage& w, const CkArgs& A, size_t
   ck_expand_msgs(w, A);
   return for_chunks(c, N, [&](size_t lo, size_t m) {
     TRY(key_sums(lo, m));
-    TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(m), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, m, (const uint8_t*)c->gs_sum_ok.p, m, (uint8_t*)c->gs_pk.p, 1));
+    TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(m), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, m, (const uint8_t*)c->gs.sum_ok.p, m, (uint8_t*)c->gs.pk.p, 1));
     TRY(stage_msgs(c, w.s_emsgs.data(), w.s_emoff.data() + lo, m));
-    TRY(verify_chunk_dev(c, (const uint8_t*)c->gs_pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)w.sigs.p + 64 * lo, m, dl,
+    TRY(verify_chunk_dev(c, (const uint8_t*)c->gs.pk.p, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p, (const uint8_t*)w.sigs.p + 64 * lo, m, dl,
                          (uint8_t*)w.vbits.p + (lo >> 3)));
     if (settle) HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;

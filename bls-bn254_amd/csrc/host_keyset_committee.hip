@@ -76,7 +76,7 @@ int blsbn254_keyset_set_committees(blsbn254_ctx* c, blsbn254_keyset* k, const ui
   int rc = kc_enqueue_sums(c, k, (const uint8_t*)w.sel.p, n_com, true, {(int32_t*)k->cm.totals.p, n_com, (uint8_t*)w.u_ok.p});
   if (!rc) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) { c->last_error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); rc = BLSBN254_E_HIP; } }
   if (rc) { (void)hipStreamSynchronize(c->stream); k->cm.swap(nw); return rc; }     // the handle keeps the table it had
-  ++c->stat_kc[3];
+  ++c->kcom.stat[3];
   return 0;
 }
 
@@ -88,7 +88,7 @@ int kc_args(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, cons
   if (n_groups > c->chunk) { c->last_error = "more groups than one launch chunk"; return BLSBN254_E_ARG; }
   return kc_check_rows(k->cm.tab, com, sel, sel_off, n_groups, c->last_error) ? 0 : BLSBN254_E_ARG;
 }
-// the call's rows staged (uploaded to c->kcom.sel), its plan made, its sums into c->gs_sum / c->gs_sum_ok in the caller's order (enqueued); the flip bytes
+// the call's rows staged (uploaded to c->kcom.sel), its plan made, its sums into c->gs.sum / c->gs.sum_ok in the caller's order (enqueued); the flip bytes
 // into c->kcom.h_flip (enqueued: read after the caller's synchronising download)
 int kc_enqueue_call(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups) {
   KcWs& w = c->kcom;
@@ -100,18 +100,18 @@ int kc_enqueue_call_dev(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_
   KcWs& w = c->kcom;
   if (!kc_plan(k->cm.tab, com, sel_off, n_groups, c->chunk, w.plan, w.seg.h_start, w.seg.h_len)) { c->last_error = "internal: committee sums do not converge"; return BLSBN254_E_HIP; }
   HIPCHK(c, w.u.reserve(54 * 4 * n_groups)); HIPCHK(c, w.u_ok.reserve(n_groups));
-  HIPCHK(c, c->gs_sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs_sum_ok.reserve(n_groups));
+  HIPCHK(c, c->gs.sum.reserve(n_groups * 54 * 4)); HIPCHK(c, c->gs.sum_ok.reserve(n_groups));
   TRY(kc_enqueue_sums(c, k, d_rows, n_groups, false, {(int32_t*)w.u.p, n_groups, (uint8_t*)w.u_ok.p}));
   TRY(launch(c, c->stream, "kc_finish", grid_lanes(n_groups), k_kc_finish, (const int32_t*)w.u.p, n_groups, n_groups, (const uint32_t*)w.scom.p, (const uint32_t*)w.order.p,
-             (const int32_t*)k->cm.totals.p, k->cm.tab.com.size(), (const uint8_t*)w.flip.p, (const uint8_t*)w.ok.p, (int32_t*)c->gs_sum.p, n_groups, (uint8_t*)c->gs_sum_ok.p));
+             (const int32_t*)k->cm.totals.p, k->cm.tab.com.size(), (const uint8_t*)w.flip.p, (const uint8_t*)w.ok.p, (int32_t*)c->gs.sum.p, n_groups, (uint8_t*)c->gs.sum_ok.p));
   w.h_flip.resize(n_groups);
   HIPCHK(c, hipMemcpyAsync(w.h_flip.data(), w.flip.p, n_groups, hipMemcpyDeviceToHost, c->stream));
   return 0;
 }
 // counted once the call has succeeded (and synchronised: the flip bytes are on the host)
 void kc_tally(blsbn254_ctx* c, size_t n_groups) {
-  c->stat_kc[0] += n_groups; c->stat_kc[2] += c->kcom.plan.launches.size();
-  for (size_t i = 0; i < n_groups; ++i) c->stat_kc[1] += c->kcom.h_flip[i] ? 1 : 0;
+  c->kcom.stat[0] += n_groups; c->kcom.stat[2] += c->kcom.plan.launches.size();
+  for (size_t i = 0; i < n_groups; ++i) c->kcom.stat[1] += c->kcom.h_flip[i] ? 1 : 0;
 }
 
 int blsbn254_keyset_committee_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint8_t* sel, const uint64_t* sel_off, size_t n_groups,
@@ -122,10 +122,10 @@ int blsbn254_keyset_committee_sum_batch(blsbn254_ctx* c, const blsbn254_keyset* 
   ENTER(c);
   TRY(kc_enqueue_call(c, k, com, sel, sel_off, n_groups));
   HIPCHK(c, c->out.reserve(128 * n_groups));
-  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs_sum.p, n_groups, (const uint8_t*)c->gs_sum_ok.p, n_groups,
+  TRY(launch(c, c->stream, "g2p_to_bytes", grid_lanes(n_groups), k_g2p_to_bytes, (const int32_t*)c->gs.sum.p, n_groups, (const uint8_t*)c->gs.sum_ok.p, n_groups,
              (uint8_t*)c->out.p, 0));
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, 128 * n_groups, hipMemcpyDeviceToHost, c->stream));
-  TRY(download(c, status, c->gs_sum_ok.p, n_groups));
+  TRY(download(c, status, c->gs.sum_ok.p, n_groups));
   kc_tally(c, n_groups);
   return 0;
 }
@@ -140,7 +140,7 @@ static int kc_verify(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* 
   uint32_t dl;
   TRY(stage_dst(c, dst, dst_len, &dl));
   TRY(stage_msgs(c, msgs, off, n_groups));
-  HIPCHK(c, c->gs_pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve((n_groups + 7) / 8 + 8));
+  HIPCHK(c, c->gs.pk.reserve(128 * n_groups)); HIPCHK(c, c->bitmap.reserve((n_groups + 7) / 8 + 8));
   TRY(stage_g1(c, sigs, n_groups, compressed));
   TRY(kc_enqueue_call(c, k, com, sel, sel_off, n_groups));
   TRY(ks_verify_sums(c, n_groups, dl, valid_bitmap));
@@ -180,14 +180,10 @@ int blsbn254_keyset_committee_weight_batch(blsbn254_ctx* c, const blsbn254_keyse
                (uint64_t*)w.wout.p));
   }
   TRY(download(c, out, w.wout.p, 8 * k->n_cols * n_groups));
-  c->stat_kc[0] += n_groups;
+  c->kcom.stat[0] += n_groups;
   return 0;
 }
 
-int blsbn254_keyset_committee_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kc[i];
-  return 0;
-}
+int blsbn254_keyset_committee_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kcom.stat, 4, out); }
 
 }  // extern "C"

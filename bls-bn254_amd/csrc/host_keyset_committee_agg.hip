@@ -86,7 +86,7 @@ static int kca_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t
   KcaWs& w = c->kcagg;
   const size_t sb = wire ? 32 : 64;
   KcaCall B{};                                                         // the sub-call, once the repack has run
-  return ck_two_attempts(c, w, A.a, sel_off, {out_sigs, out_sel, nullptr, status}, c->stat_kcagg,
+  return ck_two_attempts(c, w, A.a, sel_off, {out_sigs, out_sel, nullptr, status}, c->kcagg.stat,
     [&](bool fallback) { return kca_attempt(c, k, fallback ? B : A, fallback); },
     [&](const std::vector<size_t>& fail) {
       kca_repack(fail, com, pos, sig_off, sel_off, out_sel, w.sub);    // (the candidates read off the downloaded rows)
@@ -111,10 +111,6 @@ int blsbn254_keyset_committee_aggregate_checked_batch_compressed(blsbn254_ctx* c
   return kca_checked(c, k, com, pos, sigs, sig_off, msgs, msg_off, sel_off, n_groups, dst, dst_len, out_sigs, out_sel, status, true);
 }
 
-int blsbn254_keyset_committee_aggregate_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kcagg[i];
-  return 0;
-}
+int blsbn254_keyset_committee_aggregate_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kcagg.stat, 4, out); }
 
 }  // extern "C"

@@ -78,7 +78,7 @@ static int kcm_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t
   ENTER(c);
   KcmWs& w = c->kcmrg;
   KcmCall B{};                                                         // the sub-call, once the repack has run
-  return ck_two_attempts(c, w, A.a, sel_off, {out_sigs, out_sel, used, status}, c->stat_kcmrg,
+  return ck_two_attempts(c, w, A.a, sel_off, {out_sigs, out_sel, used, status}, c->kcmrg.stat,
     [&](bool fallback) { return kcm_attempt(c, k, fallback ? B : A, fallback); },
     [&](const std::vector<size_t>& fail) {
       kcm_repack(T, fail, com, rows, row_off, sigs, con_off, w.h_cand.data(), w.sub, wire ? 32 : 64);
@@ -101,10 +101,6 @@ int blsbn254_keyset_committee_merge_checked_batch_compressed(blsbn254_ctx* c, co
   return kcm_checked(c, k, com, rows, row_off, sigs, con_off, msgs, msg_off, sel_off, n_groups, dst, dst_len, out_sigs, out_sel, used, status, true);
 }
 
-int blsbn254_keyset_committee_merge_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kcmrg[i];
-  return 0;
-}
+int blsbn254_keyset_committee_merge_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kcmrg.stat, 4, out); }
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 // candidates in the order given, a wave per group, and leaves the merged rows (k_km_select); the caller gets used bits; the key
 // sums come from the merged rows by ks_enqueue_sums_dev.  The fallback repacks EVERY candidate of a failing group and verifies each
 // by the key sum of ITS row where the sub-call's rows already are on the device (ck_verify_contributions); those bits are the
-// selection's mask.  c->gs_sum / c->gs_pk serve that verification first and the groups' equation after it: stream order keeps
+// selection's mask.  c->gs.sum / c->gs.pk serve that verification first and the groups' equation after it: stream order keeps
 // the two uses apart, and both are reserved for the larger use before the first kernel is enqueued.
 #include "host_common.h"
 
@@ -66,7 +66,7 @@ static int km_checked(blsbn254_ctx* c, const blsbn254_keyset* k, const uint8_t* 
   KmWs& w = c->kmrg;
   const size_t rb = (k->n + 7) / 8;
   KmCall B{};                                                          // the sub-call, once the repack has run
-  return ck_two_attempts(c, w, A.a, ck_even_rows(w, n_groups, rb), {out_sigs, out_sel, used, status}, c->stat_kmrg,
+  return ck_two_attempts(c, w, A.a, ck_even_rows(w, n_groups, rb), {out_sigs, out_sel, used, status}, c->kmrg.stat,
     [&](bool fallback) { return km_attempt(c, k, fallback ? B : A, fallback); },
     [&](const std::vector<size_t>& fail) {
       km_repack(fail, rows, sigs, con_off, w.h_cand.data(), rb, w.sub, wire ? 32 : 64);
@@ -86,10 +86,6 @@ int blsbn254_keyset_merge_checked_batch_compressed(blsbn254_ctx* c, const blsbn2
   return km_checked(c, k, rows, sigs, con_off, msgs, msg_off, n_groups, dst, dst_len, out_sigs, out_sel, used, status, true);
 }
 
-int blsbn254_keyset_merge_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kmrg[i];
-  return 0;
-}
+int blsbn254_keyset_merge_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kmrg.stat, 4, out); }
 
 }  // extern "C"

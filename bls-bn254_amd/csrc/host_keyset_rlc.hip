@@ -4,7 +4,7 @@
 // one pairing equation for up to C aggregates.  Host side of include/blsbn254.h; kernels in k_keyset_rlc.hip, lane functions in
 // keyset_rlc.h, the plan in keyset_rlc_plan.h; see host_common.h and DESIGN.md 6m.
 //
-// A call: the key sums exactly as the exact calls make them (ks_enqueue_sums / kc_enqueue_call, into c->gs_sum / c->gs_sum_ok); the
+// A call: the key sums exactly as the exact calls make them (ks_enqueue_sums / kc_enqueue_call, into c->gs.sum / c->gs.sum_ok); the
 // plan (ksr_plan: classes by message bytes, the stable order, chunks, the runs of the sums); k_ksr_elig, the two weight kernels,
 // the segmented sums of the weighted points over the chunks (k_g1_seg_sum, k_g2_seg_sum by seg_run_levels), k_ksr_chunks; the
 // chunks worth checking go through verify_chunk_dev as virtual tuples (sum B, the class's message, sum A).  An eligible group of a
@@ -44,7 +44,7 @@ static int ksr_stage(blsbn254_ctx* c, const uint8_t* sigs, const uint8_t* seed, 
   return upload(c, c->in_b, sigs, 64 * n);
 }
 
-// From the sums on (c->gs_sum / c->gs_sum_ok enqueued, the signatures and the seed staged, the tag resident).  com != nullptr: the
+// From the sums on (c->gs.sum / c->gs.sum_ok enqueued, the signatures and the seed staged, the tag resident).  com != nullptr: the
 // committee form, rows in c->kcom.sel at sel_off[g] - sel_off[0]; else the rows are in c->kset.sel.
 static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* com, const uint64_t* sel_off, const uint8_t* msgs, const uint64_t* off,
                    size_t n, uint32_t dl, uint8_t* bm) {
@@ -56,9 +56,9 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
   const uint8_t* d_sigs = (const uint8_t*)c->in_b.p;
   if (!P.n_multi) {                                          // no two groups share a message: the exact call's own tail, nothing to gather
     TRY(stage_msgs(c, msgs, off, n));
-    HIPCHK(c, c->gs_pk.reserve(128 * n)); HIPCHK(c, c->bitmap.reserve((n + 7) / 8 + 8));
+    HIPCHK(c, c->gs.pk.reserve(128 * n)); HIPCHK(c, c->bitmap.reserve((n + 7) / 8 + 8));
     TRY(ks_verify_sums(c, n, dl, bm));
-    c->stat_ksr[3] += n; c->stat_ksr[4] += P.rep.size(); ++c->stat_ksr[5];
+    c->ksr.stat[3] += n; c->ksr.stat[4] += P.rep.size(); ++c->ksr.stat[5];
     return 0;
   }
   size_t checked = 0;
@@ -78,11 +78,11 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
       for (size_t g = 0; g < n; ++g) w.h_rowoff[g] = sel_off[g] - sel_off[0];
       TRY(upload(c, w.com, com, 4 * n)); TRY(upload(c, w.row_off, w.h_rowoff.data(), 8 * n));
       TRY(launch(c, c->stream, "ksr_elig", grid_lanes(n), k_ksr_elig, (const uint8_t*)c->kcom.sel.p, (const uint64_t*)w.row_off.p, (uint32_t)k->n, (const uint32_t*)w.com.p,
-                 (const uint4*)k->cm.coms.p, (const uint32_t*)k->cm.cskip.p, (const uint32_t*)k->cm.cvalid.p, (const int32_t*)c->gs_sum.p, (const uint8_t*)c->gs_sum_ok.p, n,
+                 (const uint4*)k->cm.coms.p, (const uint32_t*)k->cm.cskip.p, (const uint32_t*)k->cm.cvalid.p, (const int32_t*)c->gs.sum.p, (const uint8_t*)c->gs.sum_ok.p, n,
                  d_sigs, (const uint8_t*)w.seed.p, (const uint8_t*)w.multi.p, (uint8_t*)w.elig.p, (uint64_t*)w.wt.p));
     } else {
       TRY(launch(c, c->stream, "ksr_elig", grid_lanes(n), k_ksr_elig, (const uint8_t*)c->kset.sel.p, (const uint64_t*)nullptr, (uint32_t)k->n, (const uint32_t*)nullptr,
-                 (const uint4*)nullptr, (const uint32_t*)k->skip.p, (const uint32_t*)k->vwords.p, (const int32_t*)c->gs_sum.p, (const uint8_t*)c->gs_sum_ok.p, n, d_sigs,
+                 (const uint4*)nullptr, (const uint32_t*)k->skip.p, (const uint32_t*)k->vwords.p, (const int32_t*)c->gs.sum.p, (const uint8_t*)c->gs.sum_ok.p, n, d_sigs,
                  (const uint8_t*)w.seed.p, (const uint8_t*)w.multi.p, (uint8_t*)w.elig.p, (uint64_t*)w.wt.p));
     }
     // A lane per group fills a fraction of the device and runs at the latency of its 64 steps: the G1 weights run on the second
@@ -91,7 +91,7 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
     TRY(launch(c, c->stream2, "ksr_weigh_g1", grid_lanes(n), k_ksr_weigh_g1, d_sigs, (const uint8_t*)w.elig.p, (const uint64_t*)w.wt.p, (const uint32_t*)w.pos.p, n,
                (int32_t*)w.a.p));
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-    TRY(launch(c, c->stream, "ksr_weigh_g2", grid_lanes(n), k_ksr_weigh_g2, (const int32_t*)c->gs_sum.p, (const uint8_t*)w.elig.p, (const uint64_t*)w.wt.p,
+    TRY(launch(c, c->stream, "ksr_weigh_g2", grid_lanes(n), k_ksr_weigh_g2, (const int32_t*)c->gs.sum.p, (const uint8_t*)w.elig.p, (const uint64_t*)w.wt.p,
                (const uint32_t*)w.pos.p, n, (int32_t*)w.b.p));
     // the chunks' sums: the same runs for both sides, one after the other on the main stream (they share the ping-pong buffers)
     TRY(seg_run_levels(w.seg, P.levels, {(const int32_t*)w.b.p, n, (const uint8_t*)w.ones.p}, {(int32_t*)w.sb.p, M, (uint8_t*)w.sb_ok.p},
@@ -133,11 +133,11 @@ static int ksr_run(blsbn254_ctx* c, const blsbn254_keyset* k, const uint32_t* co
   // ... and everything the chunks did not decide: the exact pipeline on the gathered sums, one sub-call
   if (!w.h_list.empty()) {
     w.h_msgs.push_back(0);
-    TRY(ksr_subcall(c, (const int32_t*)c->gs_sum.p, n, (const uint8_t*)c->gs_sum_ok.p, d_sigs, 1, dl));
+    TRY(ksr_subcall(c, (const int32_t*)c->gs.sum.p, n, (const uint8_t*)c->gs.sum_ok.p, d_sigs, 1, dl));
     for (size_t j = 0; j < w.h_list.size(); ++j)
       if (bit_at(w.h_bits.data(), j)) set_bit(bm, w.h_list[j]);
   } else HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->stat_ksr[0] += decided; c->stat_ksr[1] += checked; c->stat_ksr[2] += failed; c->stat_ksr[3] += direct; c->stat_ksr[4] += P.rep.size(); ++c->stat_ksr[5];
+  c->ksr.stat[0] += decided; c->ksr.stat[1] += checked; c->ksr.stat[2] += failed; c->ksr.stat[3] += direct; c->ksr.stat[4] += P.rep.size(); ++c->ksr.stat[5];
   return 0;
 }
 // the arguments about messages that the host reads here (the exact calls leave them to the staging copy)
@@ -186,10 +186,6 @@ int blsbn254_set_keyset_rlc_group(blsbn254_ctx* c, size_t group) {
   c->ksr_group = group ? group : KSR_DEFAULT_GROUP;
   return 0;
 }
-int blsbn254_keyset_rlc_stats(blsbn254_ctx* c, uint64_t out[6]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 6; ++i) out[i] = c->stat_ksr[i];
-  return 0;
-}
+int blsbn254_keyset_rlc_stats(blsbn254_ctx* c, uint64_t out[6]) { return COPY_STATS(c, ksr.stat, 6, out); }
 
 }  // extern "C"

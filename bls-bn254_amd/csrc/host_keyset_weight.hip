@@ -53,7 +53,7 @@ int blsbn254_keyset_set_weights(blsbn254_ctx* c, blsbn254_keyset* k, const uint6
   int rc = kw_enqueue(c, k, (const uint8_t*)c->kset.sel.p, 1, (uint64_t*)w.out.p, &launches);
   if (!rc) rc = download(c, k->wtotal, w.out.p, 8 * n_cols);
   if (rc) { (void)hipStreamSynchronize(c->stream); k->n_cols = 0; return rc; }
-  ++c->stat_kw[3];
+  ++c->kw.stat[3];
   return 0;
 }
 
@@ -76,7 +76,7 @@ int blsbn254_keyset_weight_batch(blsbn254_ctx* c, const blsbn254_keyset* k, cons
   size_t launches;
   TRY(kw_enqueue(c, k, (const uint8_t*)c->kset.sel.p, n_groups, (uint64_t*)w.out.p, &launches));
   TRY(download(c, out, w.out.p, 8 * k->n_cols * n_groups));
-  c->stat_kw[0] += n_groups; c->stat_kw[2] += launches;
+  c->kw.stat[0] += n_groups; c->kw.stat[2] += launches;
   return 0;
 }
 
@@ -99,7 +99,7 @@ int blsbn254_keyset_quorum_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* 
   TRY(download(c, weights_out, w.out.p, 8 * nc * n_groups));
   kw_reaching(weights_out, min_weight, n_groups, nc, w.reach);
   const size_t nr = w.reach.size();
-  c->stat_kw[0] += n_groups; c->stat_kw[1] += n_groups - nr; c->stat_kw[2] += launches;
+  c->kw.stat[0] += n_groups; c->kw.stat[1] += n_groups - nr; c->kw.stat[2] += launches;
   if (nr == n_groups) return ks_verify_rows(c, k, nullptr, msgs, off, sigs, n_groups, dst, dst_len, valid_bitmap);
   std::memset(valid_bitmap, 0, nb);
   if (nr == 0) return 0;
@@ -111,10 +111,6 @@ int blsbn254_keyset_quorum_verify_batch(blsbn254_ctx* c, const blsbn254_keyset* 
   return 0;
 }
 
-int blsbn254_keyset_weight_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->stat_kw[i];
-  return 0;
-}
+int blsbn254_keyset_weight_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, kw.stat, 4, out); }
 
 }  // extern "C"

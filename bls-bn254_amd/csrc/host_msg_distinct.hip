@@ -19,7 +19,7 @@ int msg_distinct_stage(blsbn254_ctx* c, const int32_t* pts, size_t stride, size_
   HIPCHK(c, hipMemsetAsync(w.slots.p, 0xff, 4 * (size_t)M, c->stream));          // ... KC_EMPTY in every slot
   if (N == 0) return 0;
   TRY(launch(c, c->stream, "md_keys", grid_lanes(N), k_md_keys, pts, stride, (uint32_t)N, form, (int32_t*)w.key.p));
-  TRY(launch(c, c->stream, "md_insert", grid_lanes(N), k_md_insert, (uint32_t)N, d_goff, (uint32_t)G, (const int32_t*)w.key.p, (uint32_t*)w.slots.p, M - 1, c->kd_seed,
+  TRY(launch(c, c->stream, "md_insert", grid_lanes(N), k_md_insert, (uint32_t)N, d_goff, (uint32_t)G, (const int32_t*)w.key.p, (uint32_t*)w.slots.p, M - 1, c->kd.seed,
              (uint8_t*)w.dup.p));
   return 0;
 }
@@ -85,10 +85,6 @@ int blsbn254_aggregate_verify_batch_rlc_distinct(blsbn254_ctx* c, const uint8_t*
   return 0;
 }
 
-int blsbn254_msg_distinct_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int i = 0; i < 4; ++i) out[i] = c->md.stat[i];
-  return 0;
-}
+int blsbn254_msg_distinct_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, md.stat, 4, out); }
 
 }  // extern "C"

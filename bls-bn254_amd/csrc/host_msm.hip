@@ -50,7 +50,7 @@ int msm_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalars, size
   HIPCHK(c, m.pts.reserve(S * 2 * K * 4)); HIPCHK(c, m.key.reserve(E * 4)); HIPCHK(c, m.val.reserve(E * 4)); HIPCHK(c, m.sorted.reserve(E * 4));
   HIPCHK(c, m.hist.reserve((size_t)u * 4)); HIPCHK(c, m.end.reserve((size_t)u * 4));
   HIPCHK(c, m.part[0].reserve(slots0 * 3 * K * 4)); HIPCHK(c, m.part[1].reserve(slots0 * 3 * K * 4));
-  HIPCHK(c, m.bsum.reserve((size_t)u * 3 * K * 4)); HIPCHK(c, m.seg.reserve((size_t)W * G * 3 * K * 4)); HIPCHK(c, m.stat.reserve(8));
+  HIPCHK(c, m.bsum.reserve((size_t)u * 3 * K * 4)); HIPCHK(c, m.seg.reserve((size_t)W * G * 3 * K * 4)); HIPCHK(c, m.dstat.reserve(8));
   TRY(upload(c, c->in_a, pts, psz * n));
   TRY(upload(c, c->scalars, scalars, 32 * n));
   const uint8_t* d_pts = (const uint8_t*)c->in_a.p; const uint8_t* d_sc = (const uint8_t*)c->scalars.p;
@@ -80,8 +80,8 @@ int msm_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalars, size
   const size_t lanes = (size_t)W * G;
   if (g2) TRY(launch(c, c->stream, "msm_reduce", grid_lanes(lanes), k_msm_g2_reduce, W, B, G, cw, (const int32_t*)m.bsum.p, (size_t)u, (int32_t*)m.seg.p));
   else TRY(launch(c, c->stream, "msm_reduce", grid_lanes(lanes), k_msm_g1_reduce, W, B, G, cw, (const int32_t*)m.bsum.p, (size_t)u, (int32_t*)m.seg.p));
-  if (g2) TRY(launch(c, c->stream, "msm_final", grid_lanes(1), k_msm_g2_final, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.stat.p));
-  else TRY(launch(c, c->stream, "msm_final", grid_lanes(1), k_msm_g1_final, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.stat.p));
+  if (g2) TRY(launch(c, c->stream, "msm_final", grid_lanes(1), k_msm_g2_final, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.dstat.p));
+  else TRY(launch(c, c->stream, "msm_final", grid_lanes(1), k_msm_g1_final, (const int32_t*)m.seg.p, W, G, cw, (const uint32_t*)hist, u, (uint8_t*)c->out.p, (uint32_t*)m.dstat.p));
   // the validity of every term (first bad index, as blsbn254_g1_mul_batch)
   int bad;
   int rc = first_bad(c, status, n, 3, 3, &bad);
@@ -95,8 +95,8 @@ int msm_common(blsbn254_ctx* c, const uint8_t* pts, const uint8_t* scalars, size
   }
   uint32_t cnt[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(out, c->out.p, psz, hipMemcpyDeviceToHost, c->stream));
-  TRY(download(c, cnt, m.stat.p, 8));
-  c->stat_msm[0] += 1; c->stat_msm[2] += cnt[0]; c->stat_msm[3] += cnt[1];
+  TRY(download(c, cnt, m.dstat.p, 8));
+  c->msm.stat[0] += 1; c->msm.stat[2] += cnt[0]; c->msm.stat[3] += cnt[1];
   return 0;
 }
 }  // namespace
@@ -110,10 +110,6 @@ int blsbn254_set_msm_window(blsbn254_ctx* c, int cw) {
   c->msm_window = cw;
   return 0;
 }
-int blsbn254_msm_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int k = 0; k < 4; ++k) out[k] = c->stat_msm[k];
-  return 0;
-}
+int blsbn254_msm_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, msm.stat, 4, out); }
 
 }  // extern "C"

@@ -94,14 +94,14 @@ static int rlc2_weigh(blsbn254_ctx* c, Rlc2Call& q, const uint8_t* d_pks, const 
   HIPCHK(c, w.tchunk.reserve(4 * n)); HIPCHK(c, w.ccnt.reserve(4 * (u + 2))); HIPCHK(c, w.cbase.reserve(4 * (u + 2)));
   HIPCHK(c, w.need.reserve(n)); HIPCHK(c, w.bcnt.reserve(4 * (nblk + 2))); HIPCHK(c, w.bbase.reserve(4 * (nblk + 2)));
   HIPCHK(c, w.list.reserve(4 * n)); HIPCHK(c, w.valid.reserve(n));
-  const uint32_t *hist = (const uint32_t*)c->kd_hist.p, *kid = (const uint32_t*)c->kd_kid.p;
+  const uint32_t *hist = (const uint32_t*)c->kd.hist.p, *kid = (const uint32_t*)c->kd.kid.p;
   uint32_t *ccnt = (uint32_t*)w.ccnt.p, *cbase = (uint32_t*)w.cbase.p, *tchunk = (uint32_t*)w.tchunk.p;
   int32_t *h = (int32_t*)c->h_ws.p, *wa = (int32_t*)w.a.p, *wb = (int32_t*)w.b.p;
   uint8_t* sigok = (uint8_t*)w.sigok.p;
   // key ids, key-sorted order, chunk numbering
   TRY(dedup_key_ids(c, n, u, true));
   TRY(key_sorted_order(c, kid, n, u));                 // cursor[k] is now the END of run k
-  const uint32_t *cursor = (const uint32_t*)c->kd_cursor.p, *perm = (const uint32_t*)c->kd_perm.p;
+  const uint32_t *cursor = (const uint32_t*)c->kd.cursor.p, *perm = (const uint32_t*)c->kd.perm.p;
   TRY(launch(c, c->stream, "rlc2_counts", grid_lanes(u + 1), k_rlc2_chunk_counts, hist, u32, G32, ccnt));
   TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, ccnt, u32 + 1, cbase));
   w.h_m = 0;
@@ -203,8 +203,8 @@ static int rlc2_fallback(blsbn254_ctx* c, const Rlc2Call& q, const uint8_t* d_si
   if (!rlc_fallback_in_range(m2, n)) { c->last_error = "internal: fallback count out of range"; return BLSBN254_E_HIP; }
   w.stat[1] += q.mc; w.stat[2] += m2;
   if (!m2) return 0;
-  HIPCHK(c, c->prep_isone.reserve(m2));
-  uint8_t* isone = (uint8_t*)c->prep_isone.p;
+  HIPCHK(c, c->prep.isone.reserve(m2));
+  uint8_t* isone = (uint8_t*)c->prep.isone.p;
   TRY(launch(c, c->stream, "rlc2_compact", grid_lanes(n), k_rlc2_compact, (const uint8_t*)w.need.p, q.perm, (uint32_t)n, bbase, list));
   TRY(prepared_round(c, list, q.tuple_slot, q.kt, d_sigs, (const int32_t*)c->h_ws.p, n, m2, isone));
   return launch(c, c->stream, "prep_unsort", grid_lanes(m2), k_prep_unsort, isone, (const uint8_t*)c->flags.p, list, m2, (uint8_t*)w.valid.p);
@@ -222,7 +222,7 @@ static int rlc2_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* 
   TRY(dedup_keys(c, d_pks, n, &q.u));
   if (!rlc_keys_repeat(n, q.u, PREP_MAX_KEYS)) return 0;
   *took = true;
-  q.G = rlc_chunk_size(n, q.u, w.group, w.group_auto, c->lanes_per_round, c->tri_miller && c->tri_fe, c->tri_max, c->wide_fe_max);
+  q.G = rlc_chunk_size(n, q.u, w.group, w.group_auto, c->forms);
   TRY(rlc2_weigh(c, q, d_pks, d_msgs, d_off, d_sigs, dl, d_seed));
   bool decided = false;
   if (w.backoff.take(w.key_round)) TRY(rlc2_key_round(c, q, &decided));
@@ -255,11 +255,7 @@ int blsbn254_set_rlc_group(blsbn254_ctx* c, size_t group) {
   c->r2.group_auto = group == 0;
   return 0;
 }
-int blsbn254_rlc_stats(blsbn254_ctx* c, uint64_t out[6]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int k = 0; k < 6; ++k) out[k] = c->r2.stat[k];
-  return 0;
-}
+int blsbn254_rlc_stats(blsbn254_ctx* c, uint64_t out[6]) { return COPY_STATS(c, r2.stat, 6, out); }
 int blsbn254_set_rlc_key_round(blsbn254_ctx* c, int on) { if (!c) return BLSBN254_E_ARG; c->r2.key_round = on != 0; c->r2.backoff.reset(); return 0; }
 
 // ---------------- random-linear-combination batch verification: the distinct-key variant (k_rlc.hip)

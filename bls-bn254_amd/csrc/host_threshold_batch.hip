@@ -47,7 +47,7 @@ int th_enqueue_dev(blsbn254_ctx* c, const uint8_t* d_ids, const uint8_t* d_sigs,
     return BLSBN254_E_HIP;
   }
   const size_t m1 = m_max ? m_max : 1, N1 = N ? N : 1;
-  HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->th_glv.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
+  HIPCHK(c, c->th.x.reserve(9 * m1 * 4)); HIPCHK(c, c->th.glv.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
   HIPCHK(c, w.gid.reserve(4 * m1)); HIPCHK(c, w.gstat.reserve(4 * n_groups)); HIPCHK(c, w.st.reserve(n_groups));
   if (sigs) {
     HIPCHK(c, w.pts.reserve(27 * m1 * 4)); HIPCHK(c, w.gsum.reserve(27 * n_groups * 4)); HIPCHK(c, w.out.reserve(64 * n_groups));
@@ -58,15 +58,15 @@ int th_enqueue_dev(blsbn254_ctx* c, const uint8_t* d_ids, const uint8_t* d_sigs,
   uint32_t* gstat = (uint32_t*)w.gstat.p;
   for (const SegLaunch& L : launches) {
     const size_t m = L.hi - L.lo;
-    ++c->stat_thb[2];
+    ++c->thb.stat[2];
     if (m) {
-      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, d_ids + 32 * L.lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
-      TRY(launch(c, c->stream, "lagrange_seg", grid_lanes(m), k_lagrange_seg, (const int32_t*)c->th_x.p, (const uint8_t*)c->status.p, m, (uint32_t)L.lo, goff + L.ga,
-                 (uint32_t)(L.gb - L.ga), (uint32_t)TH_BATCH_TBIG, sigs ? (uint8_t*)nullptr : (uint8_t*)c->scalars.p + 32 * L.lo, (uint32_t*)c->th_glv.p, (uint32_t*)w.gid.p,
+      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, d_ids + 32 * L.lo, m, (int32_t*)c->th.x.p, (uint8_t*)c->status.p));
+      TRY(launch(c, c->stream, "lagrange_seg", grid_lanes(m), k_lagrange_seg, (const int32_t*)c->th.x.p, (const uint8_t*)c->status.p, m, (uint32_t)L.lo, goff + L.ga,
+                 (uint32_t)(L.gb - L.ga), (uint32_t)TH_BATCH_TBIG, sigs ? (uint8_t*)nullptr : (uint8_t*)c->scalars.p + 32 * L.lo, (uint32_t*)c->th.glv.p, (uint32_t*)w.gid.p,
                  gstat + L.ga));
     }
     if (!sigs) continue;
-    if (m) TRY(launch(c, c->stream, "g1_smul_glv", grid_lanes(m), k_g1_smul_glv, d_sigs + 64 * L.lo, (const uint32_t*)c->th_glv.p, (const uint32_t*)w.gid.p, m,
+    if (m) TRY(launch(c, c->stream, "g1_smul_glv", grid_lanes(m), k_g1_smul_glv, d_sigs + 64 * L.lo, (const uint32_t*)c->th.glv.p, (const uint32_t*)w.gid.p, m,
                       (int32_t*)w.pts.p, gstat + L.ga));
     TRY(seg_run_levels(w.seg, L.levels, {(const int32_t*)w.pts.p, m ? m : 1, nullptr}, {(int32_t*)w.gsum.p + L.ga, n_groups, nullptr},
                        [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
@@ -114,8 +114,8 @@ int blsbn254_threshold_combine_batch(blsbn254_ctx* c, const uint8_t* ids, const 
   // the large groups, one after the other through the single-group pipeline; their point check came from the lanes above
   for (size_t g = 0; g < n_groups; ++g) {
     const size_t t = (size_t)(off[g + 1] - off[g]);
-    if (t <= TH_BATCH_TBIG) { ++c->stat_thb[0]; continue; }
-    ++c->stat_thb[1];
+    if (t <= TH_BATCH_TBIG) { ++c->thb.stat[0]; continue; }
+    ++c->thb.stat[1];
     uint8_t* o = out_sigs + 64 * g;
     rc = threshold_combine_one(c, ids + 32 * off[g], partial_sigs + 64 * off[g], t, o);
     if (rc < 0) return rc;
@@ -140,9 +140,9 @@ int blsbn254_lagrange_at_zero_batch(blsbn254_ctx* c, const uint8_t* ids, const u
   for (size_t g = 0; g < n_groups; ++g) {
     const size_t t = (size_t)(off[g + 1] - off[g]);
     uint8_t* o = out + 32 * (off[g] - off[0]);
-    if (t <= TH_BATCH_TBIG) ++c->stat_thb[0];
+    if (t <= TH_BATCH_TBIG) ++c->thb.stat[0];
     else {
-      ++c->stat_thb[1];
+      ++c->thb.stat[1];
       rc = lagrange_one(c, ids + 32 * off[g], t, o);
       if (rc < 0) return rc;
       status[g] = rc == BLSBN254_ERR_SCALAR ? BLSBN254_ERR_SCALAR : 0;
@@ -153,8 +153,7 @@ int blsbn254_lagrange_at_zero_batch(blsbn254_ctx* c, const uint8_t* ids, const u
 }
 
 int blsbn254_threshold_batch_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int k = 0; k < 3; ++k) out[k] = c->stat_thb[k];
+  TRY(COPY_STATS(c, thb.stat, 3, out));
   out[3] = TH_BATCH_TBIG;
   return 0;
 }

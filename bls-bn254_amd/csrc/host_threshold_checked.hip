@@ -51,11 +51,11 @@ static int tc_attempt(blsbn254_ctx* c, const TcCall& A, bool fallback) {
   if (!fallback) TRY(td_stage_commitments(c, A.commitments, A.coef_off, ng));
   if (N) {
     const size_t m1 = std::min(N, c->chunk);
-    HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
+    HIPCHK(c, c->th.x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1));
     TRY(upload(c, w.ids, A.ids + 32 * A.id_off[0], 32 * N));
     TRY(upload(c, w.sigs, A.sigs + 64 * A.id_off[0], 64 * N));
     TRY(for_chunks(c, N, [&](size_t lo, size_t m) {
-      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)w.ids.p + 32 * lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
+      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)w.ids.p + 32 * lo, m, (int32_t*)c->th.x.p, (uint8_t*)c->status.p));
       return launch(c, c->stream, "tc_scan", grid_lanes(m), k_tc_scan, (const uint8_t*)w.ids.p, (const uint8_t*)w.sigs.p, (const uint8_t*)c->status.p, m, (uint32_t)lo, goff,
                     (uint32_t)ng, gstat, (uint8_t*)w.cand.p);
     }));
@@ -104,8 +104,8 @@ int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* c, const uint8_t* com
     const uint8_t code = tc_code(w.h_gstat[g]);
     const bool good = (w.h_gbits[g >> 3] >> (g & 7)) & 1;
     status[g] = code;
-    if (!code && good) { ++c->stat_tc[0]; continue; }
-    if (code == BLSBN254_ST_SHORT) ++c->stat_tc[3];
+    if (!code && good) { ++c->tc.stat[0]; continue; }
+    if (code == BLSBN254_ST_SHORT) ++c->tc.stat[3];
     if (!code) w.fail.push_back(g);
     g1_identity_bytes(out_sigs + 64 * g);
     for (uint64_t s = id_off[g] - id_off[0]; s < id_off[g + 1] - id_off[0]; ++s) used_bitmap[s >> 3] &= (uint8_t)~(1u << (s & 7));
@@ -123,7 +123,7 @@ int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* c, const uint8_t* com
     w.s_coff.push_back(w.s_commit.size() / 128); w.s_goff.push_back(w.s_ids.size() / 32); w.s_moff.push_back(w.s_msgs.size());
   }
   const size_t Ns = (size_t)w.s_goff[k];
-  c->stat_tc[1] += k; c->stat_tc[2] += Ns;
+  c->tc.stat[1] += k; c->tc.stat[2] += Ns;
   const TcCall B{w.s_commit.data(), w.s_ids.data(), w.s_sigs.data(), w.s_msgs.data(), w.s_coff.data(), w.s_goff.data(), w.s_moff.data(), k, dst, dst_len};
   TRY(tc_attempt(c, B, true));
   w.s_out.resize(64 * k); w.s_used.resize((Ns + 7) / 8); w.h_gstat.resize(k);
@@ -134,7 +134,7 @@ int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* c, const uint8_t* com
     const size_t g = w.fail[j];
     const uint8_t code = tc_code(w.h_gstat[j]);
     status[g] = code;
-    if (code) { ++c->stat_tc[3]; continue; }
+    if (code) { ++c->tc.stat[3]; continue; }
     std::memcpy(out_sigs + 64 * g, w.s_out.data() + 64 * j, 64);
     const uint64_t base = id_off[g] - id_off[0];
     for (uint64_t i = 0; i < id_off[g + 1] - id_off[g]; ++i) {
@@ -145,10 +145,6 @@ int blsbn254_threshold_combine_checked_batch(blsbn254_ctx* c, const uint8_t* com
   return 0;
 }
 
-int blsbn254_threshold_checked_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int k = 0; k < 4; ++k) out[k] = c->stat_tc[k];
-  return 0;
-}
+int blsbn254_threshold_checked_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, tc.stat, 4, out); }
 
 }  // extern "C"

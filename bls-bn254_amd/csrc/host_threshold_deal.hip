@@ -73,13 +73,13 @@ static int td_g2_eval_enqueue(blsbn254_ctx* c, const uint8_t* commitments, const
   TRY(td_stage_commitments(c, commitments, coef_off, n_groups));
   if (N) {
     const size_t m1 = std::min(N, c->chunk);
-    HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1)); HIPCHK(c, w.r_ws.reserve(54 * N * 4));
+    HIPCHK(c, c->th.x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1)); HIPCHK(c, w.r_ws.reserve(54 * N * 4));
     TRY(upload(c, w.ids, ids + 32 * id_off[0], 32 * N));
     TRY(for_chunks(c, N, [&](size_t lo, size_t m) {
       const int nbits = td_id_bits(ids + 32 * (id_off[0] + lo), m);
-      ++c->stat_tdl[0]; c->stat_tdl[1] += m; c->stat_tdl[3] = (uint64_t)nbits;
-      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)w.ids.p + 32 * lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
-      return launch(c, c->stream, "g2_poly_eval", grid_lanes(m), k_g2_poly_eval, (const int32_t*)c->th_x.p, (const uint8_t*)c->status.p, m, (uint32_t)lo, goff, coff,
+      ++c->tdl.stat[0]; c->tdl.stat[1] += m; c->tdl.stat[3] = (uint64_t)nbits;
+      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)w.ids.p + 32 * lo, m, (int32_t*)c->th.x.p, (uint8_t*)c->status.p));
+      return launch(c, c->stream, "g2_poly_eval", grid_lanes(m), k_g2_poly_eval, (const int32_t*)c->th.x.p, (const uint8_t*)c->status.p, m, (uint32_t)lo, goff, coff,
                     (uint32_t)n_groups, (const int32_t*)w.c_ws.p, T, nbits, (int32_t*)w.r_ws.p, N, gstat);
     }));
   }
@@ -119,12 +119,12 @@ int blsbn254_fr_poly_eval_batch(blsbn254_ctx* c, const uint8_t* coeffs, const ui
   }
   if (N) {
     const size_t m1 = std::min(N, c->chunk);
-    HIPCHK(c, c->th_x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1)); HIPCHK(c, w.r_ws.reserve(9 * N * 4)); HIPCHK(c, c->out.reserve(32 * N));
+    HIPCHK(c, c->th.x.reserve(9 * m1 * 4)); HIPCHK(c, c->status.reserve(m1)); HIPCHK(c, w.r_ws.reserve(9 * N * 4)); HIPCHK(c, c->out.reserve(32 * N));
     TRY(upload(c, w.ids, ids + 32 * id_off[0], 32 * N));
     TRY(for_chunks(c, N, [&](size_t lo, size_t m) {
-      c->stat_tdl[2] += m;
-      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)w.ids.p + 32 * lo, m, (int32_t*)c->th_x.p, (uint8_t*)c->status.p));
-      return launch(c, c->stream, "fr_poly_eval", grid_lanes(m), k_fr_poly_eval, (const int32_t*)c->th_x.p, (const uint8_t*)c->status.p, m, (uint32_t)lo, goff, coff,
+      c->tdl.stat[2] += m;
+      TRY(launch(c, c->stream, "fr_decode", grid_lanes(m), k_fr_decode, (const uint8_t*)w.ids.p + 32 * lo, m, (int32_t*)c->th.x.p, (uint8_t*)c->status.p));
+      return launch(c, c->stream, "fr_poly_eval", grid_lanes(m), k_fr_poly_eval, (const int32_t*)c->th.x.p, (const uint8_t*)c->status.p, m, (uint32_t)lo, goff, coff,
                     (uint32_t)n_groups, (const int32_t*)w.cf_ws.p, T, (int32_t*)w.r_ws.p, N, gstat);
     }));
   }
@@ -205,10 +205,10 @@ int blsbn254_threshold_verify_shares_batch(blsbn254_ctx* c, const uint8_t* commi
 
 // the table of the generator's multiples, built on the device at the first call that needs it and kept for the context's life
 static int kc_table(blsbn254_ctx* c) {
-  if (c->stat_kchk[2]) return 0;
-  HIPCHK(c, c->kc_tab.reserve(KC_TABLE_LIMBS * 4));
-  TRY(launch(c, c->stream, "g2gen_table", Shape{dim3((KC_WINDOWS + 63) / 64), dim3(64)}, k_g2gen_table, (int32_t*)c->kc_tab.p));
-  ++c->stat_kchk[2];
+  if (c->kchk.stat[2]) return 0;
+  HIPCHK(c, c->kchk.tab.reserve(KC_TABLE_LIMBS * 4));
+  TRY(launch(c, c->stream, "g2gen_table", Shape{dim3((KC_WINDOWS + 63) / 64), dim3(64)}, k_g2gen_table, (int32_t*)c->kchk.tab.p));
+  ++c->kchk.stat[2];
   return 0;
 }
 
@@ -230,8 +230,8 @@ int blsbn254_threshold_verify_key_shares_batch(blsbn254_ctx* c, const uint8_t* c
   TRY(td_g2_eval_enqueue(c, commitments, coef_off, ids, id_off, n_groups));
   if (N) {
     TRY(for_chunks(c, N, [&](size_t lo, size_t m) {
-      ++c->stat_kchk[0]; c->stat_kchk[1] += m;
-      return launch(c, c->stream, "td_key_check", grid_lanes(m), k_td_key_check, (const uint8_t*)w.shares.p, m, (uint32_t)lo, (const int32_t*)c->kc_tab.p,
+      ++c->kchk.stat[0]; c->kchk.stat[1] += m;
+      return launch(c, c->stream, "td_key_check", grid_lanes(m), k_td_key_check, (const uint8_t*)w.shares.p, m, (uint32_t)lo, (const int32_t*)c->kchk.tab.p,
                     (const int32_t*)w.r_ws.p, N, (uint8_t*)w.share_ok.p);
     }));
     // a share's bit needs its group's marks, complete only behind the last launch and k_td_finish
@@ -244,16 +244,11 @@ int blsbn254_threshold_verify_key_shares_batch(blsbn254_ctx* c, const uint8_t* c
 }
 
 int blsbn254_threshold_key_check_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int k = 0; k < 3; ++k) out[k] = c->stat_kchk[k];
+  TRY(COPY_STATS(c, kchk.stat, 3, out));
   out[3] = (uint64_t)KC_WINDOW_BITS;
   return 0;
 }
 
-int blsbn254_threshold_deal_stats(blsbn254_ctx* c, uint64_t out[4]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  for (int k = 0; k < 4; ++k) out[k] = c->stat_tdl[k];
-  return 0;
-}
+int blsbn254_threshold_deal_stats(blsbn254_ctx* c, uint64_t out[4]) { return COPY_STATS(c, tdl.stat, 4, out); }
 
 }  // extern "C"

@@ -5,22 +5,18 @@
 extern "C" {
 
 // ---------------- verify
-// Workspace is ~7.4 KB per tuple (H, f, six final-exponentiation phase buffers, ten chain slots); batches
-// larger than ctx->chunk (4 Mi) tuples are processed chunk by chunk so that any n fits the 288 GB of HBM.
-
-// G2Prepared::from for u keys (decode, on-curve, psi subgroup test, 88 line triples) on stream s: four lanes per key
-// (k_keyprep_quad.hip, half the latency) while the 8 u lanes fit one round of waves, else one lane per key (k_keyprep.hip).
+// G2Prepared::from for u keys (decode, on-curve, psi subgroup test, 88 line triples) on stream s, four lanes per key or one
 int launch_g2_prepare(blsbn254_ctx* c, hipStream_t s, const uint8_t* pks, const uint32_t* keys, size_t u, int32_t* raw, uint8_t* ok, const uint32_t* d_u) {
-  if (c->quad_prep && 8 * u <= c->lanes_per_round)
+  if (prepare_on_quads(c->forms, u))
     return launch(c, s, "g2_prepare", grid_lanes(2 * 256 * (size_t)nblocks(4 * u)), k_g2_prepare_quad, pks, keys, (uint32_t)u, raw, ok, d_u);
   return launch(c, s, "g2_prepare", grid_lanes(2 * 256 * (size_t)nblocks(u)), k_g2_prepare, pks, keys, (uint32_t)u, raw, ok, d_u);
 }
 // G2Prepared::from for at most u of the tuples `keys` names (u a capacity when d_u gives the count on the device), dense into
-// prep_raw / prep_table / prep_ok, on the second stream
+// prep.raw / prep.table / prep.ok, on the second stream
 static int prepare_dense(blsbn254_ctx* c, const uint8_t* d_pks, const uint32_t* keys, size_t u, const uint32_t* d_u) {
-  TRY(launch_g2_prepare(c, c->stream2, d_pks, keys, u, (int32_t*)c->prep_raw.p, (uint8_t*)c->prep_ok.p, d_u));
-  return launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep_raw.p, (uint32_t)u, (int32_t*)c->prep_table.p, d_u,
-                (uint8_t*)c->prep_ok.p);
+  TRY(launch_g2_prepare(c, c->stream2, d_pks, keys, u, (int32_t*)c->prep.raw.p, (uint8_t*)c->prep.ok.p, d_u));
+  return launch(c, c->stream2, "g2_expand", grid_lanes(u * (size_t)BN_NEG_G2_LINES), k_g2_expand, (const int32_t*)c->prep.raw.p, (uint32_t)u, (int32_t*)c->prep.table.p, d_u,
+                (uint8_t*)c->prep.ok.p);
 }
 // ---- the store of prepared keys (key_cache.h, k_keycache.hip).  In real use a validator set's keys stay the same from batch to
 // batch: a key whose 128 bytes an earlier call on this context prepared keeps its table in the store, and only the keys that
@@ -54,16 +50,16 @@ static int prepare_into_store(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap)
   uint32_t* st = (uint32_t*)s.state.p;
   unsigned long long* stats = (unsigned long long*)((uint8_t*)s.state.p + 32);
   const uint32_t key_words = (uint32_t)(PREP_KEY_LIMBS / 4);
-  TRY(launch(c, c->stream2, "kd_cache_begin", Shape{dim3(1), dim3(1)}, k_kd_cache_begin, (const uint32_t*)c->kd_cnt.p, (uint32_t)cap, (uint32_t)s.max, (uint32_t)s.cap, st, stats));
+  TRY(launch(c, c->stream2, "kd_cache_begin", Shape{dim3(1), dim3(1)}, k_kd_cache_begin, (const uint32_t*)c->kd.cnt.p, (uint32_t)cap, (uint32_t)s.max, (uint32_t)s.cap, st, stats));
   TRY(launch(c, c->stream2, "kd_cache_clear", grid_lanes((size_t)s.mask + 1), k_kd_cache_clear, (const uint32_t*)st, (uint32_t*)s.slots.p, s.mask + 1));
-  TRY(launch(c, c->stream2, "kd_cache_lookup", grid_lanes(cap), k_kd_cache_lookup, d_pks, (const uint32_t*)c->kd_keys.p, st, (uint32_t*)s.slots.p, s.mask, c->kd_seed,
+  TRY(launch(c, c->stream2, "kd_cache_lookup", grid_lanes(cap), k_kd_cache_lookup, d_pks, (const uint32_t*)c->kd.keys.p, st, (uint32_t*)s.slots.p, s.mask, c->kd.seed,
              (uint8_t*)s.keys.p, (uint32_t*)s.slot_of.p, (uint32_t*)s.miss_rep.p, (uint32_t*)s.miss_slot.p));
   TRY(prepare_dense(c, d_pks, (const uint32_t*)s.miss_rep.p, cap, st + KC_MISS));
   const size_t copy_blocks = std::min<size_t>(nblocks(cap * (size_t)key_words), 2048);
-  return launch(c, c->stream2, "kd_cache_scatter", Shape{dim3((unsigned)copy_blocks), dim3(256)}, k_kd_cache_scatter, (const int4*)c->prep_table.p, (const uint8_t*)c->prep_ok.p,
+  return launch(c, c->stream2, "kd_cache_scatter", Shape{dim3((unsigned)copy_blocks), dim3(256)}, k_kd_cache_scatter, (const int4*)c->prep.table.p, (const uint8_t*)c->prep.ok.p,
                 (const uint32_t*)s.miss_slot.p, key_words, st, stats, (int4*)s.table.p, (uint8_t*)s.valid.p);
 }
-// The prepared keys of the batch behind dedup_enqueue (kd_keys[j] = the representative tuple of the batch's distinct key j, kd_cnt
+// The prepared keys of the batch behind dedup_enqueue (kd.keys[j] = the representative tuple of the batch's distinct key j, kd.cnt
 // of them on the device): see KeyTables in host_common.h.  THE place that chooses between the store and tables of this call:
 // it reserves what the branch needs, forks, and records ev_join behind the branch's launches.  d_u bounds the work without a
 // store, the miss count with one (a count beyond the capacity: the first `cap` keys are prepared or looked up, and
@@ -75,12 +71,12 @@ int prepare_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t cap, const uint32
     TRY(kc_reserve(c, cap));
     HIPCHK(c, s.slot_of.reserve(4 * cap)); HIPCHK(c, s.miss_rep.reserve(4 * cap)); HIPCHK(c, s.miss_slot.reserve(4 * cap));
   }
-  HIPCHK(c, c->prep_raw.reserve(cap * PREP_RAW_LIMBS * 4)); HIPCHK(c, c->prep_table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep_ok.reserve(cap));
+  HIPCHK(c, c->prep.raw.reserve(cap * PREP_RAW_LIMBS * 4)); HIPCHK(c, c->prep.table.reserve(cap * PREP_KEY_LIMBS * 4)); HIPCHK(c, c->prep.ok.reserve(cap));
   HIPCHK(c, fork_stream2(c));
-  TRY(store ? prepare_into_store(c, d_pks, cap) : prepare_dense(c, d_pks, (const uint32_t*)c->kd_keys.p, cap, d_u));
+  TRY(store ? prepare_into_store(c, d_pks, cap) : prepare_dense(c, d_pks, (const uint32_t*)c->kd.keys.p, cap, d_u));
   HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
   *kt = store ? KeyTables{(const int32_t*)s.table.p, (const uint8_t*)s.valid.p, (const uint32_t*)s.slot_of.p}
-              : KeyTables{(const int32_t*)c->prep_table.p, (const uint8_t*)c->prep_ok.p, nullptr};
+              : KeyTables{(const int32_t*)c->prep.table.p, (const uint8_t*)c->prep.ok.p, nullptr};
   return 0;
 }
 // *out = the ids the Miller loops take for n elements given by batch key id: the ids themselves, or with a store its indices,
@@ -100,18 +96,18 @@ int keys_valid(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint8_t** o
   *out = (const uint8_t*)c->kc.batch_ok.p;
   return launch(c, c->stream, "kd_cache_ok", grid_lanes(u), k_kd_cache_ok, kt.slot_of, (uint32_t)u, kt.ok, (uint8_t*)c->kc.batch_ok.p);
 }
-// Behind dedup_enqueue, on the main stream: every tuple's key id (kd_kid; ids beyond u clamped) and, hist: how many tuples each
-// key has (kd_hist).  Then, from that histogram: the key-sorted order of the n tuples d_kid (kd_perm; kd_cursor[k] ends as the END
+// Behind dedup_enqueue, on the main stream: every tuple's key id (kd.kid; ids beyond u clamped) and, hist: how many tuples each
+// key has (kd.hist).  Then, from that histogram: the key-sorted order of the n tuples d_kid (kd.perm; kd.cursor[k] ends as the END
 // of run k).  Two steps: verify_prepared_dev enqueues hash-to-G1 (and checks the explicit API's indices) between them.
 int dedup_key_ids(blsbn254_ctx* c, size_t n, size_t u, bool hist) {
-  if (hist) HIPCHK(c, hipMemsetAsync(c->kd_hist.p, 0, 4 * u, c->stream));
-  return launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_kid.p,
-                hist ? (uint32_t*)c->kd_hist.p : nullptr);
+  if (hist) HIPCHK(c, hipMemsetAsync(c->kd.hist.p, 0, 4 * u, c->stream));
+  return launch(c, c->stream, "kd_propagate", grid_lanes(n), k_kd_propagate, (const uint32_t*)c->kd.rep.p, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd.kid.p,
+                hist ? (uint32_t*)c->kd.hist.p : nullptr);
 }
 int key_sorted_order(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u) {
-  HIPCHK(c, c->kd_cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd_perm.reserve(4 * n));
-  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)c->kd_hist.p, (uint32_t)u, (uint32_t*)c->kd_cursor.p));
-  return launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, d_kid, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd_cursor.p, (uint32_t*)c->kd_perm.p);
+  HIPCHK(c, c->kd.cursor.reserve(4 * (u + 1))); HIPCHK(c, c->kd.perm.reserve(4 * n));
+  TRY(launch(c, c->stream, "kd_scan", Shape{dim3(1), dim3(1024)}, k_scan_excl, (const uint32_t*)c->kd.hist.p, (uint32_t)u, (uint32_t*)c->kd.cursor.p));
+  return launch(c, c->stream, "kd_scatter", grid_lanes(n), k_kd_scatter, d_kid, (uint32_t)n, (uint32_t)u, (uint32_t*)c->kd.cursor.p, (uint32_t*)c->kd.perm.p);
 }
 // Are all n key indices at d_kid below u?  k_kd_hist counts the keys into hist (zeroed here) and folds the first index out of
 // range into misc[0]; read back (one 4-byte copy and a stream synchronisation).  armed: the caller has already put NO_INDEX there,
@@ -129,10 +125,11 @@ int check_key_indices(blsbn254_ctx* c, const uint32_t* d_kid, size_t n, size_t u
 // The table-only Miller loop over n tuples (f_ws, flags) in the form that fits n; the three forms give the same values.
 int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t* kid, const uint8_t* sigs, const int32_t* h_ws, size_t h_stride, const KeyTables& kt, size_t n) {
   int32_t* f = (int32_t*)c->f_ws.p; uint8_t* flags = (uint8_t*)c->flags.p;
-  if (c->wide_fe && n <= c->wide_fe_max)               // few tuples: one wave per tuple (k_miller_wide.hip)
-    return launch(c, c->stream, "miller_wide_prepared", grid_wide(n), k_miller_wide_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
-  if (n <= c->tri_max && c->tri_miller)                // mid-size launches: three lanes per tuple (k_tri.hip)
-    return launch(c, c->stream, "miller_tri_prepared", grid_tri(n), k_miller_tri_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
+  switch (table_miller_form(c->forms, n)) {
+    case Form::WIDE: return launch(c, c->stream, "miller_wide_prepared", grid_wide(n), k_miller_wide_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
+    case Form::TRI: return launch(c, c->stream, "miller_tri_prepared", grid_tri(n), k_miller_tri_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
+    case Form::LANE: break;
+  }
   return launch(c, c->stream, "miller_prepared", grid_lanes(n), k_miller_prepared, perm, kid, sigs, h_ws, h_stride, kt.table, kt.ok, n, f, flags);
 }
 // Verify n tuples whose keys are given by index into prepared tables (d_kid[i] < u), everything device-resident.
@@ -142,38 +139,38 @@ int launch_miller_prepared(blsbn254_ctx* c, const uint32_t* perm, const uint32_t
 int verify_prepared_dev(blsbn254_ctx* c, const KeyTables& kt, size_t u, const uint32_t* d_kid, bool deduped, const uint8_t* d_msgs, const uint64_t* d_off,
                         const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap) {
   HIPCHK(c, c->h_ws.reserve(n * 27 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4)); HIPCHK(c, c->flags.reserve(n));
-  HIPCHK(c, c->kd_hist.reserve(4 * (u + 1))); HIPCHK(c, c->prep_isone.reserve(n)); HIPCHK(c, c->prep_valid.reserve(n));
+  HIPCHK(c, c->kd.hist.reserve(4 * (u + 1))); HIPCHK(c, c->prep.isone.reserve(n)); HIPCHK(c, c->prep.valid.reserve(n));
   TRY(launch_hash_to_g1(c, c->stream, d_msgs, d_off, n, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr,
              3));   // homogeneous H: no inversion
-  if (!deduped) TRY(check_key_indices(c, d_kid, n, u, (uint32_t*)c->kd_hist.p, "tuple", false));
+  if (!deduped) TRY(check_key_indices(c, d_kid, n, u, (uint32_t*)c->kd.hist.p, "tuple", false));
   TRY(key_sorted_order(c, d_kid, n, u));
   if (deduped) HIPCHK(c, join_stream2(c));
-  const uint32_t *perm = (const uint32_t*)c->kd_perm.p, *ids;
+  const uint32_t *perm = (const uint32_t*)c->kd.perm.p, *ids;
   TRY(miller_ids(c, kt, d_kid, n, c->kc.tslot, &ids));
   TRY(launch_miller_prepared(c, perm, ids, d_sigs, (const int32_t*)c->h_ws.p, n, kt, n));
-  TRY(run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 4, nullptr, nullptr, nullptr, (uint8_t*)c->prep_isone.p, nullptr));
-  TRY(launch(c, c->stream, "prep_unsort", grid_lanes(n), k_prep_unsort, (const uint8_t*)c->prep_isone.p, (const uint8_t*)c->flags.p, perm, (uint32_t)n,
-             (uint8_t*)c->prep_valid.p));
-  return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->prep_valid.p, n, d_bitmap);
+  TRY(run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 4, nullptr, nullptr, nullptr, (uint8_t*)c->prep.isone.p, nullptr));
+  TRY(launch(c, c->stream, "prep_unsort", grid_lanes(n), k_prep_unsort, (const uint8_t*)c->prep.isone.p, (const uint8_t*)c->flags.p, perm, (uint32_t)n,
+             (uint8_t*)c->prep.valid.p));
+  return launch(c, c->stream, "pack_bitmap", grid_lanes(n), k_pack_bitmap, (const uint8_t*)c->prep.valid.p, n, d_bitmap);
 }
-// De-duplicate the public keys of a chunk: kd_rep / kd_kid / kd_keys and the count (kd_cnt) are filled on the device.
+// De-duplicate the public keys of a chunk: kd.rep / kd.kid / kd.keys and the count (kd.cnt) are filled on the device.
 static int dedup_enqueue(blsbn254_ctx* c, const uint8_t* d_pks, size_t n) {
   size_t m = 1;
   while (m < 2 * n) m <<= 1;
   // n + 1 entries: aggregate_verify_grouped appends the key of the signature's pair (-G2gen) as entry u, and u can be n
-  HIPCHK(c, c->kd_slots.reserve(4 * m)); HIPCHK(c, c->kd_rep.reserve(4 * (n + 1))); HIPCHK(c, c->kd_kid.reserve(4 * (n + 1))); HIPCHK(c, c->kd_keys.reserve(4 * (n + 1)));
-  HIPCHK(c, c->kd_hist.reserve(4 * (n + 2))); HIPCHK(c, c->kd_cnt.reserve(64));
-  HIPCHK(c, hipMemsetAsync(c->kd_slots.p, 0xff, 4 * m, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->kd_cnt.p, 0, 4, c->stream));
-  TRY(launch(c, c->stream, "kd_insert", grid_lanes(n), k_kd_insert, d_pks, (uint32_t)n, (uint32_t*)c->kd_slots.p, (uint32_t)(m - 1), c->kd_seed, (uint32_t*)c->kd_rep.p));
-  return launch(c, c->stream, "kd_assign", grid_lanes(n), k_kd_assign, (const uint32_t*)c->kd_rep.p, (uint32_t)n, (uint32_t*)c->kd_kid.p, (uint32_t*)c->kd_cnt.p, (uint32_t*)c->kd_keys.p);
+  HIPCHK(c, c->kd.slots.reserve(4 * m)); HIPCHK(c, c->kd.rep.reserve(4 * (n + 1))); HIPCHK(c, c->kd.kid.reserve(4 * (n + 1))); HIPCHK(c, c->kd.keys.reserve(4 * (n + 1)));
+  HIPCHK(c, c->kd.hist.reserve(4 * (n + 2))); HIPCHK(c, c->kd.cnt.reserve(64));
+  HIPCHK(c, hipMemsetAsync(c->kd.slots.p, 0xff, 4 * m, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->kd.cnt.p, 0, 4, c->stream));
+  TRY(launch(c, c->stream, "kd_insert", grid_lanes(n), k_kd_insert, d_pks, (uint32_t)n, (uint32_t*)c->kd.slots.p, (uint32_t)(m - 1), c->kd.seed, (uint32_t*)c->kd.rep.p));
+  return launch(c, c->stream, "kd_assign", grid_lanes(n), k_kd_assign, (const uint32_t*)c->kd.rep.p, (uint32_t)n, (uint32_t*)c->kd.kid.p, (uint32_t*)c->kd.cnt.p, (uint32_t*)c->kd.keys.p);
 }
 // ... and *u_out = the number of distinct keys, read back (one 4-byte copy and a stream synchronisation)
 int dedup_keys(blsbn254_ctx* c, const uint8_t* d_pks, size_t n, size_t* u_out) {
   int rc = dedup_enqueue(c, d_pks, n);
   if (rc) return rc;
   uint32_t u = 0;
-  TRY(download(c, &u, c->kd_cnt.p, 4));
+  TRY(download(c, &u, c->kd.cnt.p, 4));
   *u_out = u;
   return 0;
 }
@@ -183,12 +180,12 @@ static int verify_deduped_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8
   KeyTables kt;
   TRY(prepare_keys(c, d_pks, cap, d_u, &kt));
   TRY(dedup_key_ids(c, n, cap, true));
-  return verify_prepared_dev(c, kt, cap, (const uint32_t*)c->kd_kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap);
+  return verify_prepared_dev(c, kt, cap, (const uint32_t*)c->kd.kid.p, true, d_msgs, d_off, d_sigs, n, dl, d_bitmap);
 }
 // the exact per-tuple path: every tuple validates its own key and runs the two-pair Miller loop with a variable-Q pair
 int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap) {
-  ++c->stat_exact_chunks;
+  ++c->prep.stat[1];
   HIPCHK(c, c->h_ws.reserve(n * 18 * 4)); HIPCHK(c, c->f_ws.reserve(n * 108 * 4));
   HIPCHK(c, c->flags.reserve(n)); HIPCHK(c, c->sub_ok.reserve(n));
   TRY(launch_hash_to_g1(c, c->stream, d_msgs, d_off, n, dl, (int32_t*)c->h_ws.p, n, (uint8_t*)nullptr, 0));
@@ -196,7 +193,7 @@ int verify_exact_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
   TRY(launch(c, c->stream, "miller_verify", grid_lanes(n), k_miller_verify, d_pks, d_sigs, (const int32_t*)c->h_ws.p, n, (int32_t*)c->f_ws.p, (uint8_t*)c->flags.p));
   return run_final_exp(c, (int32_t*)c->f_ws.p, n, n, 0, (const uint8_t*)c->flags.p, (const uint8_t*)c->sub_ok.p, d_bitmap, nullptr, nullptr);
 }
-// Workspace is ~7.4 KB per tuple (H, f, six final-exponentiation phase buffers, ten chain slots); batches
+// One launch chunk.  Workspace is ~7.4 KB per tuple (H, f, six final-exponentiation phase buffers, ten chain slots); batches
 // larger than ctx->chunk (4 Mi) tuples are processed chunk by chunk so that any n fits the 288 GB of HBM.
 int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
                             const uint8_t* d_sigs, size_t n, uint32_t dl, uint8_t* d_bitmap) {
@@ -204,32 +201,29 @@ int verify_chunk_dev(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msg
   // Few distinct keys (a validator set signing many messages): every distinct key is validated and turned into its line
   // table ONCE (G2Prepared), beside hash-to-G1, and the tuples run the table-only Miller loop in key-sorted order.
   // Same bitmap as the exact per-tuple path below, which batches of mostly distinct keys keep taking.
-  // Small chunks (at most wide_fe_max tuples) take it whatever their keys: with tables, the Miller loop and the final
-  // exponentiation can run one WAVE per tuple (k_miller_wide.hip, k_fe_wide.hip) instead of at the latency of one lane.
-  // ... and mid-size chunks (up to tri_max tuples) likewise: three lanes per tuple (k_tri.hip) need the tables too, and a launch of
-  // that size is bound by latency, not by the table work (16 384 distinct keys: ~2 ms of preparation against 4 ms saved).
-  const bool small = small_for_prepared(c, n, true);
+  // Small chunks take it whatever their keys: the wave and quad forms need the tables too (launch_forms.h small_for_prepared).
+  const bool small = small_for_prepared(c->forms, n, true);
   if (c->auto_prepare && (n >= 1024 || small)) {
     size_t u = 0;
     int rc = dedup_keys(c, d_pks, n, &u);
     if (rc) return rc;
     if ((u * 2 <= n || small) && u <= PREP_MAX_KEYS) {
-      ++c->stat_prepared_chunks;
-      c->u_hint = u ? u : 1;
-      if (u > c->u_max_seen) c->u_max_seen = u;
+      ++c->prep.stat[0];
+      c->vq.u_hint = u ? u : 1;
+      if (u > c->vq.u_max_seen) c->vq.u_max_seen = u;
       return verify_deduped_dev(c, d_pks, d_msgs, d_off, d_sigs, n, u, nullptr, dl, d_bitmap);
     }
   }
-  c->u_hint = 0;                                      // keys did not repeat: the next call counts them first again
+  c->vq.u_hint = 0;                                      // keys did not repeat: the next call counts them first again
   return verify_exact_dev(c, d_pks, d_msgs, d_off, d_sigs, n, dl, d_bitmap);
 }
 // The key capacity a chunk of n tuples would be enqueued with, or 0 when it has to take the counting path.  Host state only: the
 // caller decides with it BEFORE it stages its tag (see verify_batch_dev_impl).
 static size_t async_capacity(const blsbn254_ctx* c, size_t n, size_t dst_len) {
-  const bool small = small_for_prepared(c, n, true);
-  if (!c->async_verify || !c->auto_prepare || c->u_hint == 0 || !(n >= 1024 || small) || dst_len > 255) return 0;
-  size_t cap = 2 * c->u_hint < 1024 ? 1024 : 2 * c->u_hint;
-  if (cap < c->u_max_seen) cap = c->u_max_seen;
+  const bool small = small_for_prepared(c->forms, n, true);
+  if (!c->vq.async || !c->auto_prepare || c->vq.u_hint == 0 || !(n >= 1024 || small) || dst_len > 255) return 0;
+  size_t cap = 2 * c->vq.u_hint < 1024 ? 1024 : 2 * c->vq.u_hint;
+  if (cap < c->vq.u_max_seen) cap = c->vq.u_max_seen;
   if (cap > PREP_MAX_KEYS) cap = PREP_MAX_KEYS;
   if (cap > n) cap = n;
   if (!small && cap > n / 2) cap = n / 2;
@@ -248,43 +242,42 @@ static size_t async_capacity(const blsbn254_ctx* c, size_t n, size_t dst_len) {
 // The caller has made room in the queue (fewer than four calls pending) and staged the tag; nothing in here settles a pending call.
 static int verify_chunk_async(blsbn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, size_t n,
                               size_t cap, uint32_t dl, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap) {
-  const bool small = small_for_prepared(c, n, true);
-  if (cap == 0 || c->pend_count >= 4) { c->last_error = "verify_chunk_async: not eligible or queue full"; return BLSBN254_E_ARG; }
-  if (!c->pend_host) {
-    HIPCHK(c, hipHostMalloc((void**)&c->pend_host, 4 * 2 * sizeof(uint32_t), hipHostMallocDefault));
-    HIPCHK(c, c->pend_dev.reserve(4 * 2 * sizeof(uint32_t)));
-    for (auto& pv : c->pend) HIPCHK(c, hipEventCreateWithFlags(&pv.ev, hipEventDisableTiming));
+  const bool small = small_for_prepared(c->forms, n, true);
+  if (cap == 0 || c->vq.count >= 4) { c->last_error = "verify_chunk_async: not eligible or queue full"; return BLSBN254_E_ARG; }
+  if (!c->vq.host) {
+    HIPCHK(c, hipHostMalloc((void**)&c->vq.host, 4 * 2 * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(c, c->vq.dev.reserve(4 * 2 * sizeof(uint32_t)));
+    for (auto& pv : c->vq.pend) HIPCHK(c, hipEventCreateWithFlags(&pv.ev, hipEventDisableTiming));
   }
   Stream2Guard s2_guard(c);
-  const int slot = (c->pend_head + c->pend_count) & 3;
-  uint32_t* d_res = (uint32_t*)c->pend_dev.p + 2 * slot;
+  const int slot = (c->vq.head + c->vq.count) & 3;
+  uint32_t* d_res = (uint32_t*)c->vq.dev.p + 2 * slot;
   TRY(dedup_enqueue(c, d_pks, n));
-  TRY(launch(c, c->stream, nullptr, Shape{dim3(1), dim3(1)}, k_kd_decide, (const uint32_t*)c->kd_cnt.p, (uint32_t)n, (uint32_t)cap, small ? 1 : 0, d_res));
+  TRY(launch(c, c->stream, nullptr, Shape{dim3(1), dim3(1)}, k_kd_decide, (const uint32_t*)c->kd.cnt.p, (uint32_t)n, (uint32_t)cap, small ? 1 : 0, d_res));
   TRY(verify_deduped_dev(c, d_pks, d_msgs, d_off, d_sigs, n, cap, d_res, dl, d_bitmap));   // (d_res[0]: the key count k_kd_decide left)
-  blsbn254_ctx::PendingVerify& pv = c->pend[slot];
-  HIPCHK(c, hipMemcpyAsync(c->pend_host + 2 * slot, d_res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  PendingVerify& pv = c->vq.pend[slot];
+  HIPCHK(c, hipMemcpyAsync(c->vq.host + 2 * slot, d_res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(pv.ev, c->stream));
-  pv.active = true; pv.d_pks = d_pks; pv.d_msgs = d_msgs; pv.d_off = d_off; pv.d_sigs = d_sigs; pv.n = n; pv.d_bitmap = d_bitmap;
+  pv.d_pks = d_pks; pv.d_msgs = d_msgs; pv.d_off = d_off; pv.d_sigs = d_sigs; pv.n = n; pv.d_bitmap = d_bitmap;
   pv.dst_len = dst_len;
   if (dst_len) std::memcpy(pv.dst, dst, dst_len);
-  ++c->pend_count;
-  ++c->stat_async_chunks;
+  ++c->vq.count;
+  ++c->vq.stat[0];
   return 0;
 }
 // Read back the checks of the asynchronously enqueued chunks, oldest first (blocking: all of them; else only those whose event has
 // fired); a chunk whose optimistic choice did not hold is re-run on the counting path.
 int resolve_pending(blsbn254_ctx* c, bool blocking) {
-  while (c->pend_count) {
-    blsbn254_ctx::PendingVerify& pv = c->pend[c->pend_head];
+  while (c->vq.count) {
+    PendingVerify& pv = c->vq.pend[c->vq.head];
     if (!blocking && hipEventQuery(pv.ev) != hipSuccess) { (void)hipGetLastError(); break; }
     HIPCHK(c, hipEventSynchronize(pv.ev));
-    const uint32_t u = c->pend_host[2 * c->pend_head], ok = c->pend_host[2 * c->pend_head + 1];
-    const blsbn254_ctx::PendingVerify done = pv;
-    pv.active = false;
-    c->pend_head = (c->pend_head + 1) & 3; --c->pend_count;
-    if (ok) { c->u_hint = u ? u : 1; if (u > c->u_max_seen) c->u_max_seen = u; ++c->stat_prepared_chunks; continue; }
-    ++c->stat_async_reruns;
-    c->u_hint = 0;
+    const uint32_t u = c->vq.host[2 * c->vq.head], ok = c->vq.host[2 * c->vq.head + 1];
+    const PendingVerify done = pv;
+    c->vq.head = (c->vq.head + 1) & 3; --c->vq.count;
+    if (ok) { c->vq.u_hint = u ? u : 1; if (u > c->vq.u_max_seen) c->vq.u_max_seen = u; ++c->prep.stat[0]; continue; }
+    ++c->vq.stat[1];
+    c->vq.u_hint = 0;
     uint32_t dl; int rc = stage_dst(c, done.dst, done.dst_len, &dl);
     if (rc) return rc;
     rc = verify_chunk_dev(c, done.d_pks, done.d_msgs, done.d_off, done.d_sigs, done.n, dl, done.d_bitmap);
@@ -304,7 +297,7 @@ static int verify_batch_dev_impl(blsbn254_ctx* c, const uint8_t* d_pks, const ui
   // path is chosen from host state alone (no read-back); the queue is drained when it is full or when this call takes the
   // counting path, which reads back anyway.
   const size_t cap = (allow_async && n <= c->chunk) ? async_capacity(c, n, dst_len) : 0;
-  if (c->pend_count && (cap == 0 || c->pend_count == 4)) { rc = resolve_pending(c, true); if (rc) return rc; }
+  if (c->vq.count && (cap == 0 || c->vq.count == 4)) { rc = resolve_pending(c, true); if (rc) return rc; }
   uint32_t dl; rc = stage_dst(c, dst, dst_len, &dl);   // (a new tag waits for the kernels that still read the old one)
   if (rc) return rc;
   if (cap) return verify_chunk_async(c, d_pks, d_msgs, d_off, d_sigs, n, cap, dl, dst, dst_len, d_bitmap);
@@ -322,11 +315,7 @@ int blsbn254_internal_verify_batch_dev_sync(blsbn254_ctx* c, const uint8_t* d_pk
                                             const uint8_t* d_sigs, size_t n, const uint8_t* dst, size_t dst_len, uint8_t* d_bitmap) {
   return verify_batch_dev_impl(c, d_pks, d_msgs, d_off, d_sigs, n, dst, dst_len, d_bitmap, false);
 }
-int blsbn254_async_stats(blsbn254_ctx* c, uint64_t out[2]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  out[0] = c->stat_async_chunks; out[1] = c->stat_async_reruns;
-  return 0;
-}
+int blsbn254_async_stats(blsbn254_ctx* c, uint64_t out[2]) { return COPY_STATS(c, vq.stat, 2, out); }
 // The store's size in keys (0: no store -- every call prepares its keys, the kernels and arguments of a build without one).
 // Settles what is pending, waits for the device and empties the store; its memory is taken by the next call that uses it.
 int blsbn254_set_key_cache(blsbn254_ctx* c, size_t max_keys) {
@@ -352,7 +341,7 @@ int blsbn254_key_cache_stats(blsbn254_ctx* c, uint64_t out[4]) {
 int blsbn254_set_async_verify(blsbn254_ctx* c, int on) {
   if (!c) return BLSBN254_E_ARG;
   ENTER(c);
-  c->async_verify = on != 0;
+  c->vq.async = on != 0;
   return 0;
 }
 // ---------------- G2Prepared: explicit API
@@ -407,26 +396,18 @@ int blsbn254_verify_batch_prepared(blsbn254_ctx* c, const blsbn254_g2prepared* k
   const size_t nb = (n + 7) / 8;
   HIPCHK(c, c->bitmap.reserve(nb + 8));
   TRY(upload(c, c->in_b, sigs, 64 * n));
-  TRY(upload(c, c->kd_kid, key_idx, 4 * n));
+  TRY(upload(c, c->kd.kid, key_idx, 4 * n));
   const KeyTables kt{(const int32_t*)keys->table.p, (const uint8_t*)keys->ok.p, nullptr};
   TRY(for_chunks(c, n, [&](size_t lo, size_t m) {
-    return verify_prepared_dev(c, kt, keys->u, (const uint32_t*)c->kd_kid.p + lo, false, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo,
+    return verify_prepared_dev(c, kt, keys->u, (const uint32_t*)c->kd.kid.p + lo, false, (const uint8_t*)c->in_c.p, (const uint64_t*)c->in_off.p + lo,
                                (const uint8_t*)c->in_b.p + 64 * lo, m, dl, (uint8_t*)c->bitmap.p + lo / 8);
   }));
   return download(c, bm, c->bitmap.p, nb);
 }
 // (blsbn254_multi_miller_loop_prepared and blsbn254_aggregate_verify_prepared read the RAW tables: host_aggregate.hip)
 // how many verify chunks took the prepared-key path / the exact per-tuple path on this context (tests, bench)
-int blsbn254_path_stats(blsbn254_ctx* c, uint64_t out[2]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  out[0] = c->stat_prepared_chunks; out[1] = c->stat_exact_chunks;
-  return 0;
-}
-int blsbn254_aggregate_path_stats(blsbn254_ctx* c, uint64_t out[2]) {
-  if (!c || !out) return BLSBN254_E_ARG;
-  out[0] = c->stat_grouped_aggregates; out[1] = c->stat_pairwise_aggregates;
-  return 0;
-}
+int blsbn254_path_stats(blsbn254_ctx* c, uint64_t out[2]) { return COPY_STATS(c, prep.stat, 2, out); }
+int blsbn254_aggregate_path_stats(blsbn254_ctx* c, uint64_t out[2]) { return COPY_STATS(c, agg_stat, 2, out); }
 int blsbn254_set_auto_prepare(blsbn254_ctx* c, int on) { if (!c) return BLSBN254_E_ARG; c->auto_prepare = on != 0; return 0; }
 
 int blsbn254_verify_batch(blsbn254_ctx* c, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs,

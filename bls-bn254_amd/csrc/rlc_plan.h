@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "launch_forms.h"    // LaunchForms: the lanes of a round and the limits of the quad and wave forms
+
 static const size_t RLC_DEFAULT_GROUP = 16;    // tuples per chunk unless blsbn254_set_rlc_group / BLSBN254_RLC_GROUP says otherwise
 static const size_t RLC_MAX_GROUP = 4096;      // the largest chunk either of them takes
 static const unsigned RLC_MAX_STREAK = 4;      // the back-off doubles up to 2^4 = 16 skipped calls
@@ -23,20 +25,24 @@ static inline size_t rlc_chunk_bound(size_t items, size_t G, size_t u) { return 
 //      over a multiple of that pays a whole extra round: if the bound n / G + u needs more than one round, take the first g in
 //      G + 1 .. 2 G whose bound needs a round less;
 //   2. up to tri_max virtual tuples a round runs three lanes per tuple (k_tri.hip: less than half the latency of the
-//      lane-per-tuple kernels): if those kernels are enabled (tri, and tri_max above the wave-per-tuple limit wide_fe_max) and
+//      lane-per-tuple kernels): if those kernels are enabled (both quad halves, and tri_max above the wave-per-tuple limit) and
 //      the bound of the G chosen so far is above tri_max, take the first g in G + 1 .. 2 G whose bound is not (262144 tuples
 //      over 1024 keys: G = 18 -> at most 15587 chunks instead of 17408).
-static inline size_t rlc_chunk_size(size_t n, size_t u, size_t group, bool group_auto, size_t lanes_per_round, bool tri, size_t tri_max, size_t wide_fe_max) {
+// The numbers are LaunchForms' (launch_forms.h): R = lanes_per_round, tri = both quad halves on, the two limits.  Written over the
+// numbers so that the host program drives exactly this body; host_rlc.hip calls the overload below with the context's forms.
+static inline size_t rlc_chunk_size(size_t n, size_t u, size_t group, bool group_auto, size_t R, bool tri, size_t tri_max, size_t wide_max) {
   size_t G = group;
   if (!group_auto) return G;
-  const size_t R = lanes_per_round;
   const size_t r0 = (rlc_chunk_bound(n, G, u) + R - 1) / R;
   for (size_t g = G + 1; r0 > 1 && g <= 2 * G; ++g)
     if ((rlc_chunk_bound(n, g, u) + R - 1) / R < r0) { G = g; break; }
-  if (tri && tri_max > wide_fe_max && rlc_chunk_bound(n, G, u) > tri_max)
+  if (tri && tri_max > wide_max && rlc_chunk_bound(n, G, u) > tri_max)
     for (size_t g = G + 1; g <= 2 * G; ++g)
       if (rlc_chunk_bound(n, g, u) <= tri_max) { G = g; break; }
   return G;
+}
+static inline size_t rlc_chunk_size(size_t n, size_t u, size_t group, bool group_auto, const LaunchForms& F) {
+  return rlc_chunk_size(n, u, group, group_auto, F.lanes_per_round, F.tri_miller && F.tri_fe, F.tri_max, F.wide_max);
 }
 
 // What comes back from the device is checked before anything is sized by it.  The chunks of n tuples: at least one, and no more

@@ -19,9 +19,10 @@ FLAGS = {
     "seg_plan_host.cpp": ["-Wall", "-Werror"],
     "key_cache_host.cpp": ["-Wall", "-Wextra", "-Werror"],
     "rlc_plan_host.cpp": ["-Wall", "-Wextra", "-Werror"],
+    "launch_forms_host.cpp": ["-Wall", "-Wextra", "-Werror"],
     "lazy_tower_host.cpp": [],
 }
-SANITIZED = ["-fsanitize=address,undefined", "-fno-sanitize-recover", "-g"]     # key_cache_host and rlc_plan_host only, run as programs of their own
+SANITIZED = ["-fsanitize=address,undefined", "-fno-sanitize-recover", "-g"]     # key_cache_host, rlc_plan_host and launch_forms_host only, run as programs of their own
 
 
 def sources(main):
