@@ -72,7 +72,7 @@ int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u) {
   return dedup_keys(c, (const uint8_t*)c->in_a.p, n, u);
 }
 // the `keys` keys of c->in_a that kd.keys names become raw line tables on the second stream, ev_join behind them
-static int raw_tables_fork(blsbn254_ctx* c, size_t keys) {
+int raw_tables_fork(blsbn254_ctx* c, size_t keys) {
   HIPCHK(c, c->prep.ok.reserve(keys)); HIPCHK(c, c->prep.raw.reserve(keys * PREP_RAW_LIMBS * 4));
   HIPCHK(c, fork_stream2(c));
   TRY(launch_g2_prepare(c, c->stream2, (const uint8_t*)c->in_a.p, (const uint32_t*)c->kd.keys.p, keys, (int32_t*)c->prep.raw.p, (uint8_t*)c->prep.ok.p, nullptr));

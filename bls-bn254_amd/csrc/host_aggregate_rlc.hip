@@ -15,16 +15,22 @@
 
 extern "C" {
 
-// One round: the is-one byte of every segment into c->agr.h_pass (synchronised).  d_seg_of: the groups' segments on the device,
-// nullptr for S == 1.  W: the stride of the workspace c->agr.w, whose columns N + G .. N + G + S (u + 1) this round pads.
-static int agr_round(blsbn254_ctx* c, size_t N, size_t G, size_t u, size_t S, size_t W, const uint32_t* d_seg_of) {
-  AgrWs& w = c->agr;
-  const size_t V = S * (u + 1), items = N + G + V;
+// One round: the is-one byte of every segment into w.h_pass (synchronised).  d_seg_of: the groups' segments on the device,
+// nullptr for S == 1.  W: the stride of the workspace w.w, whose columns behind the items (N + G .. N + G + S (u + 1); without
+// signature slots N .. N + S u) this round pads.  The pairing-product checks (host_pairing_check_rlc.hip) run the same round
+// without signature slots: their items kernel, no signature value multiplied in, everything else launch for launch.
+int agr_round(blsbn254_ctx* c, AgrWs& w, size_t N, size_t G, size_t u, size_t S, size_t W, const uint32_t* d_seg_of, bool sig_slots) {
+  if (!sig_slots) G = 0;
+  const size_t V = S * (u + (sig_slots ? 1 : 0)), items = N + G + V;
   const uint32_t u32 = (uint32_t)u, S32 = (uint32_t)S;
   uint32_t* vkid = (uint32_t*)w.vkid.p;
   HIPCHK(c, w.mkid.reserve(4 * V));
-  TRY(launch(c, c->stream, "agr_items", grid_lanes(items), k_agr_items, (const uint32_t*)w.gidx.p, (const uint32_t*)c->kd.kid.p, d_seg_of, N, G, u32, S32, (int32_t*)w.w.p, W,
-             vkid, (uint32_t*)w.mkid.p));
+  if (sig_slots)
+    TRY(launch(c, c->stream, "agr_items", grid_lanes(items), k_agr_items, (const uint32_t*)w.gidx.p, (const uint32_t*)c->kd.kid.p, d_seg_of, N, G, u32, S32, (int32_t*)w.w.p, W,
+               vkid, (uint32_t*)w.mkid.p));
+  else
+    TRY(launch(c, c->stream, "pcr_items", grid_lanes(items), k_pcr_items, (const uint32_t*)w.gidx.p, (const uint32_t*)c->kd.kid.p, d_seg_of, N, u32, S32, (int32_t*)w.w.p, W,
+               vkid, (uint32_t*)w.mkid.p));
   // the items' histogram over the virtual keys (every id is below V by construction: the check cannot fail), the sorted order, the sums
   HIPCHK(c, c->kd.hist.reserve(4 * (V + 2)));
   TRY(check_key_indices(c, vkid, items, V, (uint32_t*)c->kd.hist.p, "pair", false));
@@ -62,7 +68,7 @@ static int agr_round(blsbn254_ctx* c, size_t N, size_t G, size_t u, size_t S, si
                        [&](SegSrc in, const uint32_t* start, const uint32_t* len, size_t runs, SegDst out, bool) {
       return launch(c, c->stream, "fp12_seg_prod", grid_lanes(runs), k_fp12_seg_prod, in.v, in.stride, in.ok, start, len, runs, out.v, out.stride, out.ok, 0);
     }));
-    TRY(launch(c, c->stream, "fp12_mul_elem", grid_lanes(S), k_fp12_mul_elem, prod, S, (const int32_t*)f + S * u, V, S));
+    if (sig_slots) TRY(launch(c, c->stream, "fp12_mul_elem", grid_lanes(S), k_fp12_mul_elem, prod, S, (const int32_t*)f + S * u, V, S));
   }
   TRY(run_final_exp(c, prod, S, ps, 4, nullptr, nullptr, nullptr, (uint8_t*)w.isone.p, nullptr));
   w.h_pass.resize(S);
@@ -70,8 +76,7 @@ static int agr_round(blsbn254_ctx* c, size_t N, size_t G, size_t u, size_t S, si
 }
 
 // valid = eligible and the segment's equation held, packed into c->bitmap and downloaded
-static int agr_bits(blsbn254_ctx* c, size_t G, const uint32_t* d_seg_of, uint8_t* bm) {
-  AgrWs& w = c->agr;
+int agr_bits(blsbn254_ctx* c, AgrWs& w, size_t G, const uint32_t* d_seg_of, uint8_t* bm) {
   HIPCHK(c, w.valid.reserve(G)); HIPCHK(c, c->bitmap.reserve((G + 7) / 8 + 8));
   TRY(launch(c, c->stream, "agr_bits", grid_lanes(G), k_agr_bits, (const uint8_t*)w.elig.p, d_seg_of, (const uint8_t*)w.isone.p, G, (uint8_t*)w.valid.p));
   TRY(launch(c, c->stream, "pack_bitmap", grid_lanes(G), k_pack_bitmap, (const uint8_t*)w.valid.p, G, (uint8_t*)c->bitmap.p));
@@ -132,21 +137,21 @@ int aggregate_verify_batch_rlc_impl(blsbn254_ctx* c, const uint8_t* pks, const u
   w.h_elig.resize(G);
   HIPCHK(c, hipMemcpyAsync(w.h_elig.data(), w.elig.p, G, hipMemcpyDeviceToHost, c->stream));
   // round 1: all eligible groups as ONE virtual aggregate
-  TRY(agr_round(c, N, G, u, 1, W, nullptr));
+  TRY(agr_round(c, w, N, G, u, 1, W, nullptr, true));
   size_t n_elig = 0;
   for (size_t g = 0; g < G; ++g) n_elig += w.h_elig[g] ? 1 : 0;
   uint64_t equations = 1, by_round2 = 0, failed_segments = 0;
   size_t n_exact = 0;
   const bool pass1 = w.h_pass[0] != 0;
   if (pass1) {
-    TRY(agr_bits(c, G, nullptr, valid_bitmap));
+    TRY(agr_bits(c, w, G, nullptr, valid_bitmap));
   } else {
     // round 2: S2 segments of consecutive groups in one batched pass over the same weighted points
     if (S2 >= 2) {
       agr_cut(G, S2, w.h_bound, w.h_seg_of);
       TRY(upload(c, w.seg_of, w.h_seg_of.data(), 4 * G));
-      TRY(agr_round(c, N, G, u, S2, W, (const uint32_t*)w.seg_of.p));
-      TRY(agr_bits(c, G, (const uint32_t*)w.seg_of.p, valid_bitmap));
+      TRY(agr_round(c, w, N, G, u, S2, W, (const uint32_t*)w.seg_of.p, true));
+      TRY(agr_bits(c, w, G, (const uint32_t*)w.seg_of.p, valid_bitmap));
       equations += S2;
       for (size_t s = 0; s < S2; ++s) failed_segments += w.h_pass[s] ? 0 : 1;
       for (size_t g = 0; g < G; ++g) by_round2 += (w.h_elig[g] && w.h_pass[w.h_seg_of[g]]) ? 1 : 0;

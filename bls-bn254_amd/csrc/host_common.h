@@ -32,6 +32,7 @@
 #include "keyset_committee_merge_plan.h" // KcmRepack, the argument walk of the checked merge per committee of a key set
 #include "keyset_rlc_plan.h"   // KsrPlan: classes, chunks and runs of the key-set verify by random linear combination
 #include "aggregate_rlc_plan.h" // the segments and exact ranges of the aggregate verify over groups by random linear combination
+#include "pairing_check_rlc_plan.h" // the round-1 rule, the cap on S and the merge gap of the pairing-product checks by random linear combination
 #include "launch_forms.h"      // LaunchForms and THE rule of every launcher: which device form runs at which size
 #include "rlc_plan.h"          // the chunk size, the bounds and the key round's back-off of the batch verification by random linear combination
 #include "../../include/blsbn254.h"
@@ -225,6 +226,11 @@ struct BNH AgrWs {
   // did not take round 1, segments that failed
   uint64_t stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+// pairing-product checks over groups by random linear combination (host_pairing_check_rlc.hip, k_pairing_check_rlc.hip): what a
+// round needs is AgrWs's, an equation in place of a group and no signature items (gidx: per pair its equation; goff: the
+// equations' pair offsets; sig_ok unused); on top of it the pairs' decoded P as affine limbs (18 x N) and the pairs' bytes.
+// blsbn254_pairing_check_rlc_stats: AgrWs's counters index for index, with "equations of the call" for "groups"
+struct BNH PcrWs : AgrWs { DevBuf pts, flag; };
 // the distinct-message rule of the aggregate verify over groups (host_msg_distinct.hip, k_msg_distinct.hip): per pair the canonical
 // (x, y) of its hash point (18 x N limbs), the slot table (M >= 2 N pair indices), the groups' repeat bytes and their bitmap; the
 // group offsets of blsbn254_hash_distinct_batch (the verify calls pass their own).  Host side: the bitmap as downloaded.
@@ -368,6 +374,7 @@ struct blsbn254_ctx {
   uint64_t agg_stat[2] = {0, 0};     // blsbn254_aggregate_path_stats: aggregate verifies served per distinct key, pair by pair
   size_t ksr_group = KSR_DEFAULT_GROUP;  // groups per chunk of the key-set RLC calls (blsbn254_set_keyset_rlc_group)
   size_t agr_segments = 0;           // blsbn254_set_aggregate_rlc_segments: 0 = the default rule, 1 = no second round, else S
+  size_t pcr_segments = 0;           // blsbn254_set_pairing_check_rlc_segments: the same for blsbn254_pairing_check_batch_rlc
   int msm_window = 0;                // blsbn254_set_msm_window: 0 = chosen from n, 2..16 = forced (and the bucket path forced)
   FeWs fe;
   KeyDedupWs kd;                     // the verify path: key de-duplication,
@@ -395,6 +402,7 @@ struct blsbn254_ctx {
   KcmWs kcmrg;
   KsrWs ksr;
   AgrWs agr;
+  PcrWs pcr;
   MdWs md;
   bool profiling = false;
   std::map<std::string, ProfEntry> prof;
@@ -635,6 +643,15 @@ BNH int launch_miller_raw(blsbn254_ctx* c, const int32_t* h, size_t h_stride, co
 // whatever the caller enqueues next, ev_join recorded (raw_tables_fork: the same for the `keys` keys kd.keys names as it stands).
 BNH int agg_keys_stage(blsbn254_ctx* c, const uint8_t* pks, size_t n, size_t* u);   // host_aggregate.hip
 BNH int agg_keys_prepare(blsbn254_ctx* c, size_t n, size_t u);   // host_aggregate.hip
+BNH int raw_tables_fork(blsbn254_ctx* c, size_t keys);   // host_aggregate.hip
+// One round of a verify by random linear combination over the weighted points of w.w (stride W; host_aggregate_rlc.hip): the N
+// pairs' items (and, sig_slots: the G signatures') get the virtual key id segment * u + key id, are summed per virtual key and
+// paired with their keys' raw tables; the is-one byte of every segment's product into w.h_pass (synchronised).  d_seg_of: the
+// groups' segments on the device, nullptr for S == 1.  sig_slots: blsbn254_aggregate_verify_batch_rlc's round (V = S (u + 1): a
+// signature slot per segment on table u); without them (G is not read) blsbn254_pairing_check_batch_rlc's, V = S u.
+BNH int agr_round(blsbn254_ctx* c, AgrWs& w, size_t N, size_t G, size_t u, size_t S, size_t W, const uint32_t* d_seg_of, bool sig_slots);
+// valid = eligible (w.elig) and the segment's equation held (w.isone), packed into c->bitmap and downloaded
+BNH int agr_bits(blsbn254_ctx* c, AgrWs& w, size_t G, const uint32_t* d_seg_of, uint8_t* bm);
 // what blsbn254_aggregate_verify_batch and ..._batch_rlc check alike (`call` names the one in the error text); CK_NOTHING: no
 // groups, the caller returns 0
 // ... and the part of it that a call over ragged groups of MESSAGES alone shares (blsbn254_hash_distinct_batch): the context,
@@ -722,6 +739,8 @@ BNH int stage_group_offsets(blsbn254_ctx* c, GroupOff& o, const uint64_t* off, s
 static const size_t FP12_SEG_GROUP = 8;     // Miller values per lane of the segmented product
 BNH int pc_reserve_products(blsbn254_ctx* c, size_t n_eq, size_t items_max);
 BNH int pc_finish_bitmap(blsbn254_ctx* c, size_t n_eq, uint8_t* valid_bitmap);
+// the argument checks of the calls over ragged groups of pairs (n_eq > 0, c not NULL; `out`: the call's output)
+BNH int pc_args(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint64_t* off, size_t n_eq, const void* out);
 BNH int fp12_tree(blsbn254_ctx* c, int32_t* a, size_t cnt, size_t sa, int32_t** res, size_t* rs);   // host_aggregate.hip
 BNH int g1_sum_to_bytes(blsbn254_ctx* c, size_t n, uint8_t out[64]);   // host_aggregate.hip
 BNH int threshold_combine_one(blsbn254_ctx* c, const uint8_t* ids, const uint8_t* partial_sigs, size_t t, uint8_t out_sig[64]);   // host_aggregate.hip

@@ -72,7 +72,7 @@ static int pc_products(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, co
   return 0;
 }
 
-static int pc_args(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint64_t* off, size_t n_eq, const void* out) {
+int pc_args(blsbn254_ctx* c, const uint8_t* g1, const uint8_t* g2, const uint64_t* off, size_t n_eq, const void* out) {
   if (!off || !out) return BLSBN254_E_ARG;
   if (check_offsets(off, n_eq)) { c->last_error = "equation offsets decrease"; return BLSBN254_E_ARG; }
   const size_t N = (size_t)(off[n_eq] - off[0]);

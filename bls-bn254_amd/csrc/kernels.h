@@ -248,6 +248,12 @@ BN_KERNEL k_agr_weigh(const int32_t* h_ws, size_t N, const uint32_t* gidx, const
 __global__ void __launch_bounds__(256) k_agr_items(const uint32_t* gidx, const uint32_t* kid, const uint32_t* seg_of, size_t N, size_t G, uint32_t u, uint32_t S,
                                                   int32_t* w_ws, size_t W, uint32_t* vkid, uint32_t* mkid);
 __global__ void __launch_bounds__(256) k_agr_bits(const uint8_t* elig, const uint32_t* seg_of, const uint8_t* isone, size_t G, uint8_t* valid);
+// pairing-product checks over ragged groups by random linear combination (k_pairing_check_rlc.hip)
+BN_KERNEL k_pcr_pairs(const uint8_t* g1, const uint8_t* g2, const uint32_t* kid, const uint8_t* key_ok, size_t N, int32_t* p_ws, uint8_t* flag);
+BN_KERNEL k_pcr_eq(const uint32_t* goff, const uint8_t* flag, const uint8_t* seed, size_t G, uint8_t* elig, uint2* wt);
+BN_KERNEL k_pcr_weigh(const int32_t* p_ws, size_t N, const uint32_t* gidx, const uint8_t* flag, const uint8_t* elig, const uint2* wt, int32_t* w_ws, size_t W);
+__global__ void __launch_bounds__(256) k_pcr_items(const uint32_t* gidx, const uint32_t* kid, const uint32_t* seg_of, size_t N, uint32_t u, uint32_t S,
+                                                  int32_t* w_ws, size_t W, uint32_t* vkid, uint32_t* mkid);
 __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed, int iters, int kind, uint64_t* stamps);
 __global__ void k_status_reduce(const uint8_t* status, size_t n, uint8_t want_mask, uint8_t want_val, int* first_bad);
 __global__ void k_and_reduce(const uint8_t* flags, const uint8_t* sub_ok, size_t n, int* all_ok);

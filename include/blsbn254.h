@@ -94,6 +94,47 @@ int blsbn254_multi_miller_loop_batch(blsbn254_ctx* ctx, const uint8_t* g1, const
  * clears its equation's bit; it is never an error.  An empty group holds.  Same size limits. */
 int blsbn254_pairing_check_batch(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint64_t* off,
                                  size_t n_eq, uint8_t* valid_bitmap /* ceil(n_eq/8) */);
+/* blsbn254_pairing_check_batch by RANDOM LINEAR COMBINATION ACROSS EQUATIONS: the same arguments plus a seed, the same bitmap
+ * (the check prod_j e(P_j, Q_j) == 1 of multi_miller_loop(..).final_exponentiation() == Gt::identity, pairings.rs:706-713 with
+ * :698-704 and :808-857, per equation).  Arguments, layout, argument errors, size limits and the n_eq == 0 case are exactly those
+ * of blsbn254_pairing_check_batch.  For a range R of equations with secret weights r_g
+ *   prod_{g in R} [ prod_j e(P_gj, Q_gj) ]^(r_g)  =  prod_{distinct Q} e( sum_{(g,j): Q_gj = Q} r_g P_gj , Q )
+ * so a call over u distinct G2 members (distinct by their 128 bytes) is decided by u table-only Miller loops and ONE final
+ * exponentiation, after N weighted G1 points and N G1 additions, where the exact call runs a variable-Q Miller slot and a torsion
+ * test per pair and a final exponentiation per equation.  Weighing P is the r_g-th power of e(P, Q) only for a Q in the r-torsion;
+ * that is why only equations whose every Q is the identity or in the r-torsion take part, and each DISTINCT Q is tested once.
+ * A pair is OK when P decodes and is on the curve (identity allowed) and Q decodes and is the identity or is on the curve and in
+ * the r-torsion: the exact call's predicate.  A pair with a member that is the identity by its encoding (x = 0) is SKIPPED: it
+ * contributes nothing.  An equation is ELIGIBLE when all its pairs are OK; an empty equation, or one whose pairs are all skipped,
+ * is eligible and holds.  An ineligible equation has bit 0 -- the exact call's bit -- and costs no equation and no exact sub-call;
+ * a bad point is never an error.
+ * Round 1: when the G2 members repeat (N > 0, 2 u <= N and u <= 65536) all eligible equations of the call form one combined
+ * equation; if it holds, every eligible equation has its bit set.  Otherwise the call IS the exact call (counted in out[6]).
+ * Round 2, only when round 1 fails: the equations are cut into S segments of consecutive equations, each checked as its own
+ * combined equation in one batched pass over the weighted points of round 1 (nothing is decoded or weighed twice);
+ * S = min(256, N / (2 u)) unless blsbn254_set_pairing_check_rlc_segments fixes it (0 restores that rule, 1 = no second round,
+ * 2 .. 4096 = S, never more segments than equations; anything else is BLSBN254_E_ARG), and the round is skipped when S < 2.  The
+ * eligible equations of a segment that passes have their bits set.  The eligible equations of the segments that FAILED (all of
+ * them when round 2 is skipped) are decided by blsbn254_pairing_check_batch itself on their contiguous equation ranges, adjacent
+ * failed segments merged, and ranges with fewer than 2^15 pairs and equations between them made one; only the bits of eligible
+ * equations are taken from it.  So bit g is bit g of the exact call on the same arguments, and can differ only where an invalid
+ * range passed its equation: probability at most 2^-64 per equation checked, given a fresh secret seed.
+ * Weights: r_g = a_g + b_g lambda (lambda the eigenvalue of phi(x, y) = (beta x, y) on G1) with the 32-bit a_g = the first 4 bytes
+ * and b_g = the next 4 bytes, each big-endian, of SHA-256(seed || "PCRLC" || g as 8 bytes little-endian), g the equation's index
+ * within the call; (0, 0) becomes (1, 0).  The 2^64 pairs give 2^64 distinct weights mod r, as for blsbn254_verify_batch_rlc.
+ * seed = NULL (the production setting): the library draws 32 bytes from the OS (getrandom) inside the call, i.e. after
+ * the batch is fixed.  A caller-supplied seed exists for reproducible tests; soundness then rests on that seed being
+ * fresh and secret -- never reuse one, never derive it from public data.
+ * Pending asynchronous verify calls are settled on entry and none is left pending.
+ * blsbn254_pairing_check_rlc_stats, since the context was created: out[0] calls, out[1] equations decided by round 1, out[2]
+ * equations decided by round 2, out[3] equations sent to the exact pipeline (the eligible equations inside the ranges of the
+ * sub-calls; every equation of a call that did not take round 1), out[4] ineligible equations, out[5] combined equations checked,
+ * out[6] calls that did not take round 1, out[7] segments that failed.  NULL out: BLSBN254_E_ARG. */
+int blsbn254_pairing_check_batch_rlc(blsbn254_ctx* ctx, const uint8_t* g1, const uint8_t* g2, const uint64_t* off,
+                                     size_t n_eq, const uint8_t seed[32] /* NULL: getrandom inside the call */,
+                                     uint8_t* valid_bitmap /* ceil(n_eq/8) */);
+int blsbn254_set_pairing_check_rlc_segments(blsbn254_ctx* ctx, size_t segments);
+int blsbn254_pairing_check_rlc_stats(blsbn254_ctx* ctx, uint64_t out[8]);
 /* per-pair Miller loops (no product): n outputs of 384 B.  The operands are decoded, not checked, as for
  * blsbn254_pairing_batch: any canonical coordinates are accepted, every size runs the same function whichever device form it
  * takes, and a pair with a member that is the identity by its encoding (x = 0) gives Fp12::ONE.  Pinned by
